@@ -7,27 +7,43 @@ A "step" is one pass of the hot path over one batch: `--batch` 4096x4096 RGBA
 frames (randtile, q=50; BASELINE.json configs[1]) that are ALREADY RESIDENT IN
 HBM are encoded to .himg streams and decoded back, all through the C ABI
 (hand-written HIP kernels).  value = pixels through encode+decode per second,
-i.e. N*batch*W*H*K / wall time, whole job.  EVERY frame of every rank is a
-golden input (randtile seeds 0..255): its stream and its decoded pixels are
-checked against the table recorded from the real reference before anything is
-timed, so a fast-but-wrong run cannot report a number.
+i.e. N*batch*W*H*K / wall time, whole job; ms_per_step = that wall time / K.
+
+A plain run does only what that figure needs: set up, warm up, time the K
+steps, write the last step's outputs when --dump-outputs DIR is given, print
+the line.  Everything else is behind --full:
+  * the golden gate: EVERY frame of every rank is a golden input (randtile
+    seeds 0..255), its stream and its decoded pixels are checked against the
+    table recorded from the real reference before anything is timed;
+  * the per-step spread, encode-only / decode-only rates and the dominant
+    kernel timed alone (`roofline.isolated`);
+  * `extras` (copy ceilings, single-frame latency, host API incl. PCIe) and
+    `cpu_baseline`: the REAL reference (oracle/_ref, built by oracle/Makefile)
+    or, if that library is absent, our C port (oracle/), timed on this node's
+    host cores on a bounded sample of the same workload;
+  * the `rows` object: BASELINE config 4, ONE 16384x16384 frame whose block
+    rows are sharded over the N ranks with the RCCL exchanges of
+    himg_amd/sharded.py, golden-checked (strong scaling).
 
 For N > 1 there is one rank per GPU (torch.distributed, backend "nccl" = RCCL):
 either the driver launches the ranks (torch.distributed.run) or, run as a plain
 `python bench.py --gpus N`, this script spawns them itself BEFORE it touches the
 GPU and waits for them.  Frames are independent objects, so they are sharded
 over the ranks with no data-path collective (weak scaling: fixed per-GPU batch);
-only the barrier and the max-over-ranks timing use the process group.  The same
-line carries a `rows` object: BASELINE config 4, ONE 16384x16384 frame whose
-block rows are sharded over the N ranks with the RCCL exchanges of
-himg_amd/sharded.py, golden-checked (strong scaling).
+only the barrier and the max-over-ranks timing use the process group.
 
-Extra objects on the JSON line:
-  roofline     dominant kernel, algorithmic bytes per launch / its mean duration
-               measured with HIP events on the launch stream, vs 8 TB/s HBM.
-  cpu_baseline the REAL reference (oracle/_ref, compiled from /root/reference)
-               or, if that library is absent, our C port (oracle/), timed on this
-               node's host cores on a bounded sample of the same workload.
+`roofline` (both runs): dominant kernel, algorithmic bytes per launch / its mean
+duration measured with HIP events on the launch stream during the timed steps,
+vs 8 TB/s HBM.
+
+--dump-outputs DIR (rank 0's frames; the inputs are seeded, so two builds can be
+compared file for file) writes what the last timed step returned to its caller:
+  encoded_sizes, encode_status, decode_status   one value per frame
+  encoded_checksum, decoded_checksum            per frame, sum of byte * weight(position)
+                                                mod 2^31-1 over the whole stream / all pixels
+  encoded_sample, decoded_sample                bytes at fixed seeded positions (all bytes when
+                                                there are fewer than DUMP_SAMPLES)
+all float64 / float32 .npy files, 40 MB at most.
 """
 import argparse
 import json
@@ -70,21 +86,99 @@ def parse_args():
                     help="frames: independent frames sharded over ranks (default, the headline "
                          "metric); rows: ONE frame (default 16384x16384, BASELINE config 4) sharded by "
                          "block rows with RCCL all-reduce / all-gather / gather (encode only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the golden gate over every frame, the "
+                         "per-step spread, encode-only / decode-only rates, the isolated dominant kernel, the extras, "
+                         "the CPU baseline and the row-sharded `rows` leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (sizes, statuses, checksums, seeded byte samples) "
+                         "as DIR/<name>.npy (frames mode, rank 0)")
     ap.add_argument("--rows-timeout", type=int, default=240,
                     help="seconds the config-4 rows leg may take before the frames line is printed without it")
     ap.add_argument("--no-rows", action="store_true",
-                    help="skip the row-sharded 16384x16384 leg (the `rows` object of the frames line)")
+                    help="with --full: skip the row-sharded 16384x16384 leg (the `rows` object of the frames line)")
     ap.add_argument("--rows-size", default=None,
                     help="TEST ONLY: WxH of the frame of the `rows` object of a frames line (default: config 4, "
                          "16384x16384 -- anything else is checked against the oracle instead of the golden table)")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="TEST ONLY (1-GPU box): every rank uses cuda:0 and the collectives run over gloo with "
                          "CPU staging, to exercise the launcher and the N > 1 orchestration; not a measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements (copy ceiling, latency, host API): profile runs")
+                    help="with --full: skip the side measurements (copy ceiling, latency, host API): profile runs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="CPU baseline time budget")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and args.mode != "frames":
+        ap.error("--dump-outputs writes the frames mode's outputs; --mode rows has none to write")
+    return args
+
+
+def _host_threads(world):
+    """Threads for host work of one rank: the CPUs this process may run on (not the whole
+    machine's count), no more than OMP_NUM_THREADS when that is set, at most 32."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "0")) or n)
+    except ValueError:
+        pass
+    return max(1, min(32, n // max(1, world)))
+
+
+DUMP_SEED = 20240607
+DUMP_SAMPLES = 1 << 22         # bytes sampled per output: 2 x 16 MiB of float32
+CHECKSUM_MOD = (1 << 31) - 1   # prime: one changed byte always changes its frame's checksum
+
+
+def _checksums(torch, x, lengths):
+    """Per row of the (rows, cap) uint8 tensor x: sum over j < lengths[row] of
+    x[row, j] * w(j) mod CHECKSUM_MOD, w(j) = (j + 1) * 2654435761 mod CHECKSUM_MOD
+    (int64 on the GPU, in column chunks: a chunk's sum stays below 2^63)."""
+    rows, cap = x.shape
+    lens = lengths.to(device=x.device, dtype=torch.int64).view(rows, 1)
+    acc = torch.zeros(rows, dtype=torch.int64, device=x.device)
+    step = max(1, min(1 << 23, (1 << 27) // max(1, rows)))
+    for c0 in range(0, cap, step):
+        c1 = min(cap, c0 + step)
+        j = torch.arange(c0, c1, dtype=torch.int64, device=x.device)
+        w = (j + 1) * 2654435761 % CHECKSUM_MOD
+        v = x[:, c0:c1].to(torch.int64) * w * (j.view(1, -1) < lens)
+        acc = (acc + v.sum(dim=1)) % CHECKSUM_MOD
+    return acc.cpu().numpy().astype(np.float64)
+
+
+def dump_outputs(torch, path, d_out, d_sizes, d_st_e, d_pix, d_st_d):
+    """What the last timed step handed its caller, written as float .npy files (module docstring)."""
+    os.makedirs(path, exist_ok=True)
+    B = d_pix.shape[0]
+    sizes = d_sizes.cpu().numpy().astype(np.int64)
+    assert ((sizes >= 0) & (sizes <= d_out.shape[1])).all(), "packed sizes outside the output buffer: %s" % sizes
+    pix = d_pix.reshape(B, -1)
+    rng = np.random.default_rng(DUMP_SEED)
+    # decoded pixels: positions in the batch's pixel bytes, drawn before anything that depends on the outputs
+    total = pix.numel()
+    idx = np.arange(total) if total <= DUMP_SAMPLES else np.sort(rng.integers(0, total, DUMP_SAMPLES))
+    dec_sample = pix.view(-1)[torch.from_numpy(idx).to(pix.device)].cpu().numpy()
+    # encoded streams: positions in the concatenation of the B streams (each stream's own bytes only)
+    starts = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(starts[-1])
+    v = np.arange(total) if total <= DUMP_SAMPLES else np.sort(rng.integers(0, total, DUMP_SAMPLES))
+    f = np.searchsorted(starts, v, side="right") - 1
+    flat = f * d_out.shape[1] + (v - starts[f])
+    enc_sample = d_out.reshape(-1)[torch.from_numpy(flat).to(d_out.device)].cpu().numpy()
+    arrays = {
+        "encoded_sizes": sizes.astype(np.float64),
+        "encode_status": d_st_e.cpu().numpy().astype(np.float64),
+        "decode_status": d_st_d.cpu().numpy().astype(np.float64),
+        "encoded_checksum": _checksums(torch, d_out, d_sizes),
+        "decoded_checksum": _checksums(torch, pix, torch.full((B,), pix.shape[1], dtype=torch.int64)),
+        "encoded_sample": enc_sample.astype(np.float32),
+        "decoded_sample": dec_sample.astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _mem_available_bytes():
@@ -500,7 +594,7 @@ def main():
     # library, which drops the GIL: a pool of threads over the frames keeps the run's wall
     # time near its GPU time instead of 128 x (0.15 + 0.1) s of one core.
     from concurrent.futures import ThreadPoolExecutor
-    pool = ThreadPoolExecutor(max(1, min(32, (os.cpu_count() or 1) // max(1, world))))
+    pool = ThreadPoolExecutor(_host_threads(world))
     for i, fr in enumerate(pool.map(lambda sd: himg_amd.synth(args.kind, sd, W, H), seeds)):
         d_frames[i].copy_(torch.from_numpy(fr))
         if i == 0:
@@ -555,33 +649,38 @@ def main():
     torch.cuda.synchronize()
     assert not d_st_d.cpu().numpy().any(), "decode failed: %s" % d_st_d.cpu().numpy()
 
-    # Parity gate before any timing counts: EVERY frame of this rank's batch, stream
+    # --full: parity gate before any timing counts: EVERY frame of this rank's batch, stream
     # and decoded pixels, against the table recorded from the real reference
-    # (tests/golden/batch_4096x4096_q50.json, seeds 0..255).
-    verified = "n/a"
-    table = None
-    tpath = os.path.join(ROOT, "tests", "golden", "batch_%dx%d_q%d.json" % (W, H, Q))
-    if args.kind == "randtile" and os.path.exists(tpath):
-        table = json.load(open(tpath))["seeds"]
-    if table is not None and len(table) >= 256:
-        def check(i):
-            want_size, want_s, want_p = table[seeds[i]]
-            assert int(h_sizes[i]) == want_size, (rank, i, int(h_sizes[i]), want_size)
-            assert himg_amd.fnv1a64(d_out[i, :want_size].cpu().numpy()) == want_s, \
-                "stream of frame %d (rank %d) differs from the reference" % (i, rank)
-            assert himg_amd.fnv1a64(d_pix[i].cpu().numpy()) == want_p, \
-                "pixels of frame %d (rank %d) differ from the reference" % (i, rank)
-        list(pool.map(check, range(B)))   # (re-raises the first failure)
-        verified = "golden, all %d frames of every rank (stream + pixels)" % B
-    elif rank == 0:
-        # Other geometries / qualities: frame 0 against the oracle (CPU seconds per frame).
-        sys.path.insert(0, os.path.join(ROOT, "tests"))
-        import oracle_lib as ol
-        want = ol.oracle_encode(frames[0], Q, True)
-        assert np.array_equal(d_out[0, : int(h_sizes[0])].cpu().numpy(), want), "stream differs from the oracle"
-        rc, ref = ol.oracle_decode(want)
-        assert rc == 0 and np.array_equal(d_pix[0].cpu().numpy().ravel(), ref.ravel()), "pixels differ from the oracle"
-        verified = "oracle, frame 0 (stream + pixels)"
+    # (tests/golden/batch_4096x4096_q50.json, seeds 0..255).  A plain run leaves the
+    # comparison to --dump-outputs.
+    verified = "not checked (plain run: --full checks the frames before timing)"
+    if args.full:
+        verified = "n/a"
+        table = None
+        tpath = os.path.join(ROOT, "tests", "golden", "batch_%dx%d_q%d.json" % (W, H, Q))
+        if args.kind == "randtile" and os.path.exists(tpath):
+            table = json.load(open(tpath))["seeds"]
+        if table is not None and len(table) >= 256:
+            def check(i):
+                want_size, want_s, want_p = table[seeds[i]]
+                assert int(h_sizes[i]) == want_size, (rank, i, int(h_sizes[i]), want_size)
+                assert himg_amd.fnv1a64(d_out[i, :want_size].cpu().numpy()) == want_s, \
+                    "stream of frame %d (rank %d) differs from the reference" % (i, rank)
+                assert himg_amd.fnv1a64(d_pix[i].cpu().numpy()) == want_p, \
+                    "pixels of frame %d (rank %d) differ from the reference" % (i, rank)
+            list(pool.map(check, range(B)))   # (re-raises the first failure)
+            verified = "golden, all %d frames of every rank (stream + pixels)" % B
+        elif rank == 0:
+            # Other geometries / qualities: frame 0 against the oracle (CPU seconds per frame).
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import oracle_lib as ol
+            want = ol.oracle_encode(frames[0], Q, True)
+            assert np.array_equal(d_out[0, : int(h_sizes[0])].cpu().numpy(), want), "stream differs from the oracle"
+            rc, ref = ol.oracle_decode(want)
+            assert rc == 0 and np.array_equal(d_pix[0].cpu().numpy().ravel(), ref.ravel()), \
+                "pixels differ from the oracle"
+            verified = "oracle, frame 0 (stream + pixels)"
+    pool.shutdown()
 
     def barrier():
         if world > 1:
@@ -606,52 +705,59 @@ def main():
             a = prof.get(k, (0.0, 0))
             prof[k] = (a[0] + v[0], a[1] + v[1])
 
-    # Per-step spread (benchmark.cpp:151-154 reports Min / Max / Average over 30
-    # iterations): the same step, synchronised after each one, >= 30 times.
-    per_step = []
-    for _ in range(max(30, args.steps)):
-        barrier()
-        t = time.perf_counter()
-        step()
-        barrier()
-        per_step.append(time.perf_counter() - t)
+    # What the last timed step returned, before anything else runs on these buffers.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, args.dump_outputs, d_out, d_sizes, d_st_e, d_pix, d_st_d)
 
-    # Encode-only and decode-only rates (same protocol, not part of `value`).
-    def timed(fn, n):
-        barrier()
-        t = time.perf_counter()
-        for _ in range(n):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t) / n
-    n_side = max(3, args.steps // 2)
-    t_enc = timed(encode, n_side)
-    t_dec = timed(decode, n_side)
+    per_step, t_enc, t_dec, iso = [], None, None, {}
+    if args.full:
+        # Per-step spread (benchmark.cpp:151-154 reports Min / Max / Average over 30
+        # iterations): the same step, synchronised after each one, >= 30 times.
+        for _ in range(max(30, args.steps)):
+            barrier()
+            t = time.perf_counter()
+            step()
+            barrier()
+            per_step.append(time.perf_counter() - t)
 
-    # The same kernels with nothing else on the GPU (group 0 on its stream only):
-    # under the multi-stream schedule above a kernel's event duration includes the
-    # time it shares the CUs with the other groups' kernels.
-    iso = {}
-    if rank == 0:
-        e0, st0, sl0 = engines[0], streams[0], slice(0, G)
-        barrier_local = torch.cuda.synchronize
-        barrier_local()
-        e0.profile_reset()
-        e0.profile(True)
-        for _ in range(3):
-            e0.encode_device(d_frames[sl0], G, W, H, 4, 4, Q, True, d_out[sl0], cap, d_sizes[sl0],
-                             d_st_e[sl0], st0.cuda_stream)
-            e0.decode_device(d_out[sl0], cap, h_sizes[sl0], G, W, H, 4, d_pix[sl0], d_st_d[sl0],
-                             st0.cuda_stream)
-        barrier_local()
-        e0.profile(False)
-        iso = {k: v[0] / max(v[1], 1) for k, v in e0.profile_read().items()}
+        # Encode-only and decode-only rates (same protocol, not part of `value`).
+        def timed(fn, n):
+            barrier()
+            t = time.perf_counter()
+            for _ in range(n):
+                fn()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t) / n
+        n_side = max(3, args.steps // 2)
+        t_enc = timed(encode, n_side)
+        t_dec = timed(decode, n_side)
+
+        # The same kernels with nothing else on the GPU (group 0 on its stream only):
+        # under the multi-stream schedule above a kernel's event duration includes the
+        # time it shares the CUs with the other groups' kernels.
+        if rank == 0:
+            e0, st0, sl0 = engines[0], streams[0], slice(0, G)
+            barrier_local = torch.cuda.synchronize
+            barrier_local()
+            e0.profile_reset()
+            e0.profile(True)
+            for _ in range(3):
+                e0.encode_device(d_frames[sl0], G, W, H, 4, 4, Q, True, d_out[sl0], cap, d_sizes[sl0],
+                                 d_st_e[sl0], st0.cuda_stream)
+                e0.decode_device(d_out[sl0], cap, h_sizes[sl0], G, W, H, 4, d_pix[sl0], d_st_d[sl0],
+                                 st0.cuda_stream)
+            barrier_local()
+            e0.profile(False)
+            iso = {k: v[0] / max(v[1], 1) for k, v in e0.profile_read().items()}
 
     if world > 1:
-        t = torch.tensor([dt, t_enc, t_dec] + per_step, dtype=torch.float64, device="cpu" if args.oversubscribe else dev)
+        t = torch.tensor([dt] + ([t_enc, t_dec] + per_step if args.full else []), dtype=torch.float64,
+                         device="cpu" if args.oversubscribe else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         t = [float(x) for x in t.cpu()]
-        dt, t_enc, t_dec, per_step = t[0], t[1], t[2], t[3:]
+        dt = t[0]
+        if args.full:
+            t_enc, t_dec, per_step = t[1], t[2], t[3:]
 
     out = None
     if rank == 0:
@@ -731,23 +837,32 @@ def main():
             "metric": "Mpixels/s encode+decode, 4K RGBA q=50", "value": round(value, 2),
             "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(ms_step, 3),
-            "step_ms": {"n": len(per_step), "min": round(min(per_step) * 1e3, 3),
-                        "mean": round(sum(per_step) / len(per_step) * 1e3, 3), "max": round(max(per_step) * 1e3, 3),
-                        "note": "each step synchronised on its own (not the timed region of `value`)"},
+        }
+        if args.full:
+            out["step_ms"] = {"n": len(per_step), "min": round(min(per_step) * 1e3, 3),
+                              "mean": round(sum(per_step) / len(per_step) * 1e3, 3),
+                              "max": round(max(per_step) * 1e3, 3),
+                              "note": "each step synchronised on its own (not the timed region of `value`)"}
+        out.update({
             "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "u8/i16/i32 integer", "data": "synthetic",
             "config": {"workload": "%dx%d RGBA %s q=%d, encode+decode, batch %d frames/GPU resident in HBM, "
                                    "%d stream(s) x %d frames per launch" % (W, H, args.kind, Q, B, S, G),
                        "parallelism": "independent frames sharded over %d rank(s), no data-path collective" % world,
                        "bit_exact": verified},
-            "encode_mpx_s": round(world * B * W * H / t_enc / 1e6, 2),
-            "decode_mpx_s": round(world * B * W * H / t_dec / 1e6, 2),
-            "encode_read_roofline_frac": round(B * W * H * 4.0 / t_enc / 1e9 / HBM_PEAK_GBS, 4),
-            "pipeline_roofline": {
-                "encode_GBs": round(alg_bytes_side / t_enc / 1e9, 1),
-                "decode_GBs": round(alg_bytes_side / t_dec / 1e9, 1),
-                "encode_frac": round(alg_bytes_side / t_enc / 1e9 / HBM_PEAK_GBS, 4),
-                "decode_frac": round(alg_bytes_side / t_dec / 1e9 / HBM_PEAK_GBS, 4)},
+        })
+        if args.full:
+            out.update({
+                "encode_mpx_s": round(world * B * W * H / t_enc / 1e6, 2),
+                "decode_mpx_s": round(world * B * W * H / t_dec / 1e6, 2),
+                "encode_read_roofline_frac": round(B * W * H * 4.0 / t_enc / 1e9 / HBM_PEAK_GBS, 4),
+                "pipeline_roofline": {
+                    "encode_GBs": round(alg_bytes_side / t_enc / 1e9, 1),
+                    "decode_GBs": round(alg_bytes_side / t_dec / 1e9, 1),
+                    "encode_frac": round(alg_bytes_side / t_enc / 1e9 / HBM_PEAK_GBS, 4),
+                    "decode_frac": round(alg_bytes_side / t_dec / 1e9 / HBM_PEAK_GBS, 4)},
+            })
+        out.update({
             "roofline": roofline,
             "roofline_valu": ({"note": "per kernel: SQ_INSTS_VALU per symbol and the fraction of its duration the "
                                        "1024 SIMDs need to ISSUE that count -- at the guide's 2 cycles per wave64 "
@@ -759,17 +874,17 @@ def main():
                                        "hot path, `dynamic_mix_source`) instead of by the static mix",
                                "source": traffic_src, "dynamic_mix_source": dyn_src, "kernels": pmc} if pmc else None),
             "stages_ms": {k: round(v["ms"], 4) for k, v in sorted(stages.items(), key=lambda kv: -kv[1]["ms"])},
-        }
-        if world == 1 and not args.no_extras:
+        })
+        if args.full and world == 1 and not args.no_extras:
             out["extras"] = measure_extras(torch, himg_amd, eng, dev, d_frames, d_out, d_sizes, d_st_e,
                                            d_st_d, d_pix, h_sizes, frames[0], W, H, Q, cap)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(frames[0], Q, args.cpu_seconds)
     for e in engines:
         e.close()
-    # BASELINE config 4 on the same ranks: one 16384x16384 frame, block rows sharded
+    # --full: BASELINE config 4 on the same ranks: one 16384x16384 frame, block rows sharded
     # over them, the RCCL exchanges of himg_amd/sharded.py (every rank takes part).
-    if not args.no_rows:
+    if args.full and not args.no_rows:
         del d_frames, d_out, d_pix, frames
         torch.cuda.empty_cache()
         # The frames line must come out whatever happens to the rows leg (its RCCL

@@ -100,31 +100,19 @@ def build_cli(verbose=False):
     return out
 
 
-REF_SRC = "/root/reference/src"
-
-
 def build_ref_benchmark(verbose=False):
     """The reference's OWN benchmark main (src/benchmark.cpp), compiled where it lies and
     unchanged, linked against this library -- FreeImage, which that main only needs for
-    non-HIMG files, is a test-only link stub whose loaders fail (tests/cpp/fi_stub).  Built
-    in the container that has /root/reference; the binary (git-ignored, like the .so)
-    travels to the GPU box, where tests/test_reference_benchmark.py runs it.  Returns the
-    path, or None when neither the sources nor a prebuilt binary are there."""
-    exe = os.path.join(BINDIR, "ref_benchmark")
-    src = os.path.join(REF_SRC, "benchmark.cpp")
-    if not os.path.exists(src):
-        return exe if os.path.exists(exe) else None
-    lib = build_lib(verbose=verbose)
-    os.makedirs(BINDIR, exist_ok=True)
-    stub_dir = os.path.join(ROOT, "tests", "cpp", "fi_stub")
-    stub = os.path.join(stub_dir, "freeimage_link_stub.cpp")
-    if _stale(exe, [src, stub, os.path.join(stub_dir, "FreeImage.h"), lib]):
-        cmd = ["g++", "-std=c++11", "-O2", "-I" + os.path.join(ROOT, "include"), "-I" + stub_dir, src, stub,
-               "-L" + LIBDIR, "-lhimg_hip", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,$ORIGIN/../lib", "-o", exe]
-        if verbose:
-            print(" ".join(cmd), file=sys.stderr)
-        subprocess.run(cmd, check=True)
-    return exe
+    non-HIMG files, is a test-only link stub whose loaders fail (tests/cpp/fi_stub).  The
+    recipe is oracle/Makefile's `ref_benchmark`: the binary goes to oracle/_ref/ with the
+    other builds of the reference and is kept where the sources are absent, so it can
+    travel with the tree to the GPU machine, where tests/test_reference_benchmark.py runs
+    it.  Returns the path, or None when neither the sources nor a prebuilt binary are there."""
+    build_lib(verbose=verbose)
+    subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref_benchmark"] + ([] if verbose else ["-s"]),
+                   check=True, stdout=None if verbose else subprocess.DEVNULL)
+    exe = os.path.join(ROOT, "oracle", "_ref", "ref_benchmark")
+    return exe if os.path.exists(exe) else None
 
 
 def build_unit_checks(verbose=False):

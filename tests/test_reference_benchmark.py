@@ -1,12 +1,12 @@
 """The reference's own `benchmark` main RUNS against the engine ("missing" #3).
 
-himg_amd/bin/ref_benchmark is /root/reference/src/benchmark.cpp, compiled where it lies
-and unchanged by himg_amd.build.build_ref_benchmark() in the build container, linked
+oracle/_ref/ref_benchmark is the reference's src/benchmark.cpp, compiled where it lies
+and unchanged by oracle/Makefile (himg_amd.build.build_ref_benchmark()) at build time, linked
 against libhimg_hip.so (himg::Decoder) and a test-only FreeImage link stub whose loaders
 fail -- so the only branch of that main that can work is the one a .himg file takes:
 IsHimg -> himg::Decoder::Decode, 30 iterations (src/benchmark.cpp:21,108-126), then the
-Min / Max / Average lines (src/benchmark.cpp:150-154).  The binary travels to the GPU box
-like the other built files; /root/reference does not, and nothing here reads it."""
+Min / Max / Average lines (src/benchmark.cpp:150-154).  The binary travels to the GPU
+machine with the rest of oracle/_ref/; the reference sources do not, and nothing here reads them."""
 import os
 import re
 import subprocess
@@ -23,7 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def _exe():
     exe = hb.build_ref_benchmark()
     if not exe or not os.path.exists(exe):
-        pytest.skip("ref_benchmark not built (no /root/reference at build time)")
+        pytest.skip("ref_benchmark not built (no reference sources at build time)")
     return exe
 
 

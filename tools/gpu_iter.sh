@@ -9,7 +9,7 @@ if [ "${2:-}" != "notest" ]; then
   tail -3 $OUT/pytest.txt
 fi
 python3 tools/dec_stats_batch.py 4096 4096 64 > $OUT/dec_stats.txt 2>&1
-python3 bench.py --no-cpu-baseline --no-extras --no-rows > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --full --no-cpu-baseline --no-extras --no-rows > $OUT/bench.json 2> $OUT/bench.err
 python3 - <<PY
 import json
 l=[x for x in open('$OUT/bench.json') if x.startswith('{')]
