@@ -95,6 +95,10 @@ def lib():
     L.himg_hip_decode_walk_ranges_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, C.POINTER(C.c_int), i32, vp, vp, vp, vp]
     L.himg_hip_decode_walk_wait_range.argtypes = [vp, i32]
     L.himg_hip_index_host.argtypes = [vp, sz, i32, P(i32), P(i32), P(i32), vp, sz, P(C.c_uint32)]
+    L.himg_hip_preview_peek.argtypes = [vp, sz, sz, P(i32), P(i32), P(i32), P(sz)]
+    L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
+    L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_create_multi.argtypes = [vp, i32, P(vp)]
     L.himg_hip_destroy_multi.argtypes = [vp]
     L.himg_hip_destroy_multi.restype = None
@@ -278,6 +282,67 @@ class Engine:
         rc = lib().himg_hip_decode_batch(self._ctx, src, szs, n, dst, caps, ws, hs, cs)
         self._check(rc, "decode_batch")
         return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+    def preview(self, packed, out=None, packed_size=None):
+        """1/8-scale preview (himg_hip_preview_to): the low-res picture at the front of the
+        stream as a (ceil(H/8), ceil(W/8), C) uint8 array.  `packed` may hold only the head of
+        the stream (preview_peek's head_bytes); packed_size is then the whole stream's size."""
+        packed = _as_u8(packed)
+        size = packed.nbytes if packed_size is None else int(packed_size)
+        pw, ph, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        hb = C.c_size_t()
+        rc = lib().himg_hip_preview_peek(packed.ctypes.data, packed.nbytes, size, C.byref(pw), C.byref(ph), C.byref(c),
+                                         C.byref(hb))
+        if rc == HIMG_OK:
+            n = pw.value * ph.value * c.value
+            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
+                out = np.empty(n, np.uint8)
+            dst, cap = out.ctypes.data, out.nbytes
+        elif rc != HIMG_ERR_FORMAT:
+            # himg_hip_preview_to reads head_bytes from `packed` (its precondition): an array that
+            # ends before the head (HIMG_ERR_CAPACITY) never reaches it.  (HIMG_ERR_FORMAT: the same
+            # walk stops at the same place inside the array, and preview_to words the stage.)
+            e = HimgError(rc, "preview: %s" % ("the array ends before the end of the LRES chunk (%d bytes)" % hb.value
+                                               if rc == HIMG_ERR_CAPACITY else "unsupported stream"))
+            e.head_bytes = hb.value
+            raise e
+        rc = lib().himg_hip_preview_to(self._ctx, packed.ctypes.data, size, dst, cap,
+                                       C.byref(pw), C.byref(ph), C.byref(c))
+        self._check(rc, "preview")
+        return out.reshape(ph.value, pw.value, c.value)
+
+    def preview_batch(self, streams, outs=None):
+        """himg_hip_preview_batch: the previews of several streams (frames of one geometry
+        share device launches of up to 256 frames); `outs` (optional) are reusable uint8 buffers."""
+        streams = [_as_u8(s_) for s_ in streams]
+        n = len(streams)
+        if outs is None:
+            outs = []
+            for s_ in streams:
+                try:
+                    pw, ph, c, _ = preview_peek(s_)
+                    outs.append(np.empty(pw * ph * c, np.uint8))
+                except HimgError:
+                    outs.append(np.empty(1, np.uint8))
+        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
+        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        rc = lib().himg_hip_preview_batch(self._ctx, src, szs, n, dst, caps, ws, hs, cs)
+        self._check(rc, "preview_batch")
+        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+    def preview_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_out,
+                       d_status, stream=0):
+        """himg_hip_preview_device: the contract of decode_device; d_out holds
+        batch x ceil(H/8) x ceil(W/8) x C bytes."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_preview_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data,
+                                           batch, width, height, channels, _ptr(d_out),
+                                           _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "preview_device")
 
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""
@@ -530,6 +595,28 @@ class MultiEngine:
         rc = lib().himg_hip_multi_decode_batch(self._m, src, szs, n, dst, caps, ws, hs, cs)
         self._check(rc, "multi_decode_batch")
         return [o[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+
+def preview_peek(packed, avail=None, packed_size=None):
+    """himg_hip_preview_peek (no GPU): (preview width, preview height, channels, head_bytes)
+    of a stream of which `avail` bytes (default: all of `packed`) are present; packed_size is
+    the whole stream's size (default: len(packed)).  Raises HimgError (code HIMG_ERR_FORMAT /
+    HIMG_ERR_CAPACITY / HIMG_ERR_UNSUPPORTED); on HIMG_ERR_CAPACITY its `head_bytes` is set
+    (0 when the LRES header was not reached)."""
+    a = _as_u8(packed)
+    avail = a.nbytes if avail is None else min(int(avail), a.nbytes)
+    size = a.nbytes if packed_size is None else int(packed_size)
+    pw, ph, c, hb = C.c_int(), C.c_int(), C.c_int(), C.c_size_t()
+    rc = lib().himg_hip_preview_peek(a.ctypes.data, avail, size, C.byref(pw), C.byref(ph), C.byref(c), C.byref(hb))
+    if rc != 0:
+        e = HimgError(rc, "preview_peek")
+        e.head_bytes = hb.value
+        raise e
+    return pw.value, ph.value, c.value, hb.value
+
+
+def _as_u8(x):
+    return np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, np.uint8)
 
 
 def index_host(packed, fix_t2=False):

@@ -219,6 +219,14 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
+// The 1/8-scale preview: the zeroing of the LRES symbols, the container parse up to the end of
+// the LRES chunk (k_dec_parse_head, which writes where that chunk ends to d_head_sizes[f]), the
+// LRES chain bounded there, the predictor inverse, then k_lres_preview: batch x ceil(H/8) x
+// ceil(W/8) x C interleaved bytes at d_out; the verdict per frame to d_status.  Needs of the
+// workspace only frames, the LRES stream's tables, lres_sym, low, stats and the spec_* scratch.
+void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                    const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
+                    hipStream_t stream, Profiler *prof);
 // The row-header walk of one frame alone (row-sharded decode: beside the head phase).
 void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
                          const uint32_t *d_sizes, hipStream_t stream);

@@ -527,13 +527,25 @@ static int wide_q_hint(const Geom &g, uint32_t max_packed_size) {
   return bits_per_quarter <= 272.0 ? 1 : 0;   // kStageSubBits = 320: rows up to 17 % above the mean
 }
 
-static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch) {
+// head_only (the 1/8-scale preview): what the head phase touches and nothing of the FRES rows --
+// no row index, lane records or FRES symbol plane (a 16384^2 frame's would be hundreds of MB),
+// the LRES stream's tables only; d_sizes holds the packed sizes, then where each LRES chunk ends.
+static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_only = false) {
   DecWs &w = ctx->dec_ws;
   ctx->head.valid = false;   // whatever decode this is, it overwrites what a head phase left
   const size_t plane = round_up((size_t)g.C * g.rows * g.cols, 256);
   const size_t lres = round_up((size_t)g.lres_size + 16, 256);
   const size_t fres = round_up((size_t)g.fres_size + 16, 256);
-  if (!ctx->d_frames.reserve(sizeof(DecFrame) * batch) ||
+  if (head_only) {
+    // The tables keep their [frame][stream] layout: frame f's LRES tables at 2 f, the last one at 2 batch - 2.
+    const size_t nst = 2 * (size_t)batch - 1;
+    if (!ctx->d_frames.reserve(sizeof(DecFrame) * batch) || !ctx->d_nodes.reserve(nst * (2 * kNumSym) * 4) ||
+        !ctx->d_grp.reserve(nst * (1u << kLutBits) * 8) || !ctx->d_gyc.reserve(nst * (1u << kLutBits) * 4) ||
+        !ctx->d_sub.reserve(nst * kSubEntries * 8) || !ctx->d_lres.reserve(lres * batch) ||
+        !ctx->d_planes.reserve(plane * batch) || !ctx->d_sizes.reserve((size_t)batch * 8) ||
+        !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4) * 4))
+      return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
+  } else if (!ctx->d_frames.reserve(sizeof(DecFrame) * batch) ||
       !ctx->d_nodes.reserve((size_t)batch * 2 * (2 * kNumSym) * 4) ||
       !ctx->d_grp.reserve((size_t)batch * 2 * (1u << kLutBits) * 8) ||
       !ctx->d_gyc.reserve((size_t)batch * 2 * (1u << kLutBits) * 4) ||
@@ -549,17 +561,17 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch) {
   w.grp = (uint2 *)ctx->d_grp.p;
   w.gyc = (uint32_t *)ctx->d_gyc.p;
   w.sub = (uint2 *)ctx->d_sub.p;
-  w.lane_start = (uint32_t *)ctx->d_lane.p;
-  w.lane_off = w.lane_start + (size_t)batch * g.rows * kDecThreads;
-  w.lane_q = himg_dev::dec_rows_fit_lds(g) ? nullptr : w.lane_off + (size_t)batch * g.rows * (kDecThreads + himg_dev::kRecHdr);
-  w.row_off = (uint32_t *)ctx->d_rows.p;
-  w.row_len = w.row_off + (size_t)batch * g.rows;
+  w.lane_start = head_only ? nullptr : (uint32_t *)ctx->d_lane.p;
+  w.lane_off = head_only ? nullptr : w.lane_start + (size_t)batch * g.rows * kDecThreads;
+  w.lane_q = (head_only || himg_dev::dec_rows_fit_lds(g)) ? nullptr : w.lane_off + (size_t)batch * g.rows * (kDecThreads + himg_dev::kRecHdr);
+  w.row_off = head_only ? nullptr : (uint32_t *)ctx->d_rows.p;
+  w.row_len = head_only ? nullptr : w.row_off + (size_t)batch * g.rows;
   w.lres_sym = (uint8_t *)ctx->d_lres.p; w.lres_stride = lres;
-  w.fres_sym = (uint8_t *)ctx->d_fres.p; w.fres_stride = fres;
+  w.fres_sym = head_only ? nullptr : (uint8_t *)ctx->d_fres.p; w.fres_stride = head_only ? 0 : fres;
   w.low = (uint8_t *)ctx->d_planes.p; w.plane_stride = plane;
   w.stats = (uint32_t *)ctx->d_stats.p;
   w.parse_stats = w.stats + (size_t)batch * (g.rows + 1) * 8;
-  w.rc_stats = w.parse_stats + (size_t)batch * 4;
+  w.rc_stats = head_only ? nullptr : w.parse_stats + (size_t)batch * 4;
   {
     // LRES payload <= lres_size + tree bytes (huffman_enc.cpp:242-244).
     const size_t max_bits = 8ull * ((size_t)g.lres_size + kTreeStride);
@@ -1420,6 +1432,221 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
 }
 
 // ---------------------------------------------------------------------------
+// 1/8-scale preview: the LRES chunk's plane as a picture (kernels_dec.hip, launch_preview).
+// ---------------------------------------------------------------------------
+// The reference's first four stages on the host, headers only (decoder.cpp:144-212,428-461):
+// RIFF, FRMT, the LMAP body (mapper.cpp:127-157, with the engine's size limit of k_dec_parse),
+// and the forward search for LRES.  Nothing at or beyond `avail` is read.  Returns HIMG_OK with
+// *head = the end of the LRES chunk, HIMG_ERR_FORMAT (and the reference's message for the stage)
+// where the reference rejects the head, HIMG_ERR_CAPACITY where `avail` ends first (*head set
+// when the LRES header was reached), HIMG_ERR_UNSUPPORTED for a geometry beyond the engine's.
+static int preview_walk(const uint8_t *p, size_t avail, size_t packed_size, int *W, int *H, int *C, size_t *head,
+                        const char **msg) {
+  static const char *kMsg[] = {"Not a RIFF HIMG file.\n", "Error decoding header.\n",
+                               "Error decoding low-res mapping function.\n", "Error decoding low-res data.\n"};
+  *head = 0;
+  *msg = nullptr;
+  if (packed_size < 12 || packed_size > 0x7fffffffu) return *msg = kMsg[0], HIMG_ERR_FORMAT;
+  if (avail < 12) return HIMG_ERR_CAPACITY;
+  uint32_t riff;
+  memcpy(&riff, p + 4, 4);
+  if (memcmp(p, "RIFF", 4) != 0 || (size_t)riff + 8 != packed_size || memcmp(p + 8, "HIMG", 4) != 0)
+    return *msg = kMsg[0], HIMG_ERR_FORMAT;
+  static const char *kTag[3] = {"FRMT", "LMAP", "LRES"};
+  size_t idx = 12;
+  for (int t = 0; t < 3; ++t) {
+    uint32_t sz = 0;
+    for (;;) {   // host_find_chunk, with the bytes present checked first
+      if (idx + 8 > packed_size) return *msg = kMsg[t + 1], HIMG_ERR_FORMAT;
+      if (idx + 8 > avail) return HIMG_ERR_CAPACITY;
+      memcpy(&sz, p + idx + 4, 4);
+      const bool hit = memcmp(p + idx, kTag[t], 4) == 0;
+      idx += 8;
+      if (sz > 0x7fffffffu || idx + sz > packed_size) return *msg = kMsg[t + 1], HIMG_ERR_FORMAT;
+      if (hit) break;
+      idx += sz;
+    }
+    if (t == 2) {
+      *head = idx + sz;
+      return idx + sz > avail ? HIMG_ERR_CAPACITY : HIMG_OK;
+    }
+    if (idx + sz > avail) return HIMG_ERR_CAPACITY;
+    const uint8_t *b = p + idx;
+    if (t == 0) {
+      if (sz < 11 || b[0] != 1) return *msg = kMsg[1], HIMG_ERR_FORMAT;
+      uint32_t w, h;
+      memcpy(&w, b + 1, 4);
+      memcpy(&h, b + 5, 4);
+      *W = (int)w; *H = (int)h; *C = b[9];
+      Geom g;
+      if (!make_geom(*W, *H, *C, *C, 1, &g)) return HIMG_ERR_UNSUPPORTED;
+    } else if (!(sz >= 1 && sz <= (uint32_t)kTreeStride && b[0] <= 127 && 1u + b[0] + 2u * (127u - b[0]) == sz)) {
+      return *msg = kMsg[2], HIMG_ERR_FORMAT;
+    }
+    idx += sz;
+  }
+  return HIMG_ERR_FORMAT;   // (not reached)
+}
+
+extern "C" int himg_hip_preview_peek(const uint8_t *packed, size_t avail, size_t packed_size, int *pw, int *ph,
+                                     int *channels, size_t *head_bytes) {
+  if (!packed || !pw || !ph || !channels || !head_bytes) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  size_t head = 0;
+  const char *msg = nullptr;
+  const int rc = preview_walk(packed, avail, packed_size, &W, &H, &C, &head, &msg);
+  *head_bytes = head;
+  if (rc == HIMG_OK) { *pw = (W + 7) / 8; *ph = (H + 7) / 8; *channels = C; }
+  return rc;
+}
+
+// The device launch behind every preview entry point; d_packed holds the streams at in_stride,
+// each readable up to its head rounded up to 4 bytes.
+static int preview_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes,
+                          int batch, int width, int height, int num_channels, void *d_out, int32_t *d_status,
+                          void *stream) {
+  Geom g;
+  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  g.fix_t2 = ctx->fix_t2;
+  g.max_sub = ctx->max_sub;
+  g.lead_bits = ctx->lead_bits;
+  g.lres_serial = ctx->lres_serial;
+  if (g.mrows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
+    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_dec_ws(ctx, g, batch, true);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ctx->last_stream = s;
+  rc = stage_sizes(ctx, h_sizes, batch, s);
+  if (rc) return rc;
+  launch_preview(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
+                 (uint32_t *)ctx->d_sizes.p + batch, (uint8_t *)d_out, d_status, s, &ctx->prof);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                       const uint32_t *h_sizes, int batch, int width, int height, int num_channels,
+                                       void *d_out, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  for (int i = 0; i < batch; ++i)
+    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
+      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
+  return preview_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream);
+}
+
+// Host streams -> staging (their heads only, zero-padded to the stride) -> one device launch.
+static int preview_staged(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *heads, const uint32_t *sizes,
+                          int n, int W, int H, int C, int32_t *h_status) {
+  size_t stride = 0;
+  for (int i = 0; i < n; ++i) stride = heads[i] > stride ? heads[i] : stride;
+  stride = round_up(stride + 16, 256);
+  const size_t out_bytes = (size_t)((W + 7) / 8) * ((H + 7) / 8) * C;
+  if (!ctx->h_in.reserve(stride * n) || !ctx->h_out.reserve(round_up(out_bytes * n, 256)) ||
+      !ctx->h_status.reserve(round_up((size_t)n * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  uint8_t *in = (uint8_t *)ctx->h_in.p;
+  for (int i = 0; i < n; ++i) {
+    const size_t lo = heads[i] & ~(size_t)15;
+    HIP_TRY(ctx, hipMemsetAsync(in + (size_t)i * stride + lo, 0, stride - lo, nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(in + (size_t)i * stride, packed[i], heads[i], hipMemcpyHostToDevice, nullptr));
+  }
+  int rc = preview_launch(ctx, in, stride, sizes, n, W, H, C, ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
+  if (rc) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's buffers
+    return rc;
+  }
+  HIP_TRY(ctx, hipMemcpy(h_status, ctx->h_status.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+static int status_error(himg_hip_ctx *ctx, int32_t st) {
+  const int code = status_to_code(st);
+  if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
+  else fail(ctx, code, "device preview reported an error");
+  return code;
+}
+
+extern "C" int himg_hip_preview_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
+                                   size_t dst_cap, int *pw, int *ph, int *channels) {
+  if (!ctx || !packed || !pw || !ph || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  size_t head = 0;
+  const char *msg = nullptr;
+  // (avail = packed_size: the walk stops at the end of LRES, so the caller's bytes behind it are never read)
+  int rc = preview_walk(packed, packed_size, packed_size, &W, &H, &C, &head, &msg);
+  if (rc == HIMG_ERR_FORMAT) return fail(ctx, rc, msg ? msg : "Error decoding low-res data.\n");
+  if (rc == HIMG_ERR_UNSUPPORTED) return fail(ctx, rc, "unsupported geometry");
+  if (rc) return fail(ctx, rc, "bad stream");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  int32_t st = 0;
+  rc = preview_staged(ctx, &packed, &head, &sz32, 1, W, H, C, &st);
+  if (rc) return rc;
+  if (st) return status_error(ctx, st);
+  *pw = (W + 7) / 8; *ph = (H + 7) / 8; *channels = C;
+  ctx->host_bytes = (size_t)*pw * *ph * C;
+  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_preview_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                                      int n, uint8_t *const *dst, const size_t *dst_cap, int *pw, int *ph,
+                                      int *channels) {
+  if (!ctx || !packed || !packed_sizes || !dst || !dst_cap || !pw || !ph || !channels || n < 0) return HIMG_ERR_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  int first_err = HIMG_OK;
+  std::vector<int> W(n), H(n), Cc(n), done(n, 0);
+  std::vector<size_t> head(n);
+  for (int i = 0; i < n; ++i) {
+    pw[i] = ph[i] = channels[i] = 0;
+    const char *msg = nullptr;
+    const int rc = packed[i] ? preview_walk(packed[i], packed_sizes[i], packed_sizes[i], &W[i], &H[i], &Cc[i], &head[i], &msg)
+                             : (msg = "Not a RIFF HIMG file.\n", HIMG_ERR_FORMAT);
+    if (rc) {
+      done[i] = 1;
+      if (!first_err) first_err = fail(ctx, rc, msg ? msg : rc == HIMG_ERR_UNSUPPORTED ? "unsupported geometry" : "bad stream");
+    }
+  }
+  // Frames that share a geometry: one launch (in the order of their first frame) of at most
+  // kPreviewLaunch frames -- the grids of the LRES kernels take batch x C <= 65535, and the staging
+  // holds one launch's heads and previews.
+  constexpr int kPreviewLaunch = 256;
+  for (int i0 = 0; i0 < n; ++i0) {
+    if (done[i0]) continue;
+    std::vector<int> grp;
+    const int lim = kPreviewLaunch < 65535 / Cc[i0] ? kPreviewLaunch : 65535 / Cc[i0];
+    for (int i = i0; i < n && (int)grp.size() < lim; ++i)
+      if (!done[i] && W[i] == W[i0] && H[i] == H[i0] && Cc[i] == Cc[i0]) { grp.push_back(i); done[i] = 1; }
+    const int m = (int)grp.size();
+    std::vector<const uint8_t *> src(m);
+    std::vector<size_t> hd(m);
+    std::vector<uint32_t> sz(m);
+    std::vector<int32_t> st(m);
+    for (int k = 0; k < m; ++k) { src[k] = packed[grp[k]]; hd[k] = head[grp[k]]; sz[k] = (uint32_t)packed_sizes[grp[k]]; }
+    const int rc = preview_staged(ctx, src.data(), hd.data(), sz.data(), m, W[i0], H[i0], Cc[i0], st.data());
+    if (rc) return rc;
+    const size_t bytes = (size_t)((W[i0] + 7) / 8) * ((H[i0] + 7) / 8) * Cc[i0];
+    for (int k = 0; k < m; ++k) {
+      const int i = grp[k];
+      int err = HIMG_OK;
+      if (st[k]) err = status_error(ctx, st[k]);
+      else if (!dst[i] || dst_cap[i] < bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+      if (err) { if (!first_err) first_err = err; continue; }
+      HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * bytes, bytes, hipMemcpyDeviceToHost, nullptr));
+      pw[i] = (W[i0] + 7) / 8; ph[i] = (H[i0] + 7) / 8; channels[i] = Cc[i0];
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+  }
+  return first_err;
+}
+
+// ---------------------------------------------------------------------------
 // Row-sharded encode of one frame over several GPUs (one context per rank).
 // ---------------------------------------------------------------------------
 extern "C" int himg_hip_shard_stats(himg_hip_ctx *ctx, const void *d_frame_base, int width,
@@ -1602,12 +1829,13 @@ extern "C" int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void 
     switch (what) {
       case HIMG_DBG_LOWRES: src = w.low + frame * w.plane_stride; n = (size_t)g.C * g.rows * g.cols; break;
       case HIMG_DBG_LRES_SYM: src = w.lres_sym + frame * w.lres_stride; n = (size_t)g.lres_size; break;
-      case HIMG_DBG_FRES_SYM: src = w.fres_sym + frame * w.fres_stride; n = (size_t)g.fres_size; break;
+      case HIMG_DBG_FRES_SYM: src = w.fres_sym ? w.fres_sym + frame * w.fres_stride : nullptr; n = (size_t)g.fres_size; break;
       case HIMG_DBG_DEC_STATS: src = w.stats + (size_t)frame * (g.rows + 1) * 8; n = (size_t)(g.rows + 1) * 32; break;
       case HIMG_DBG_PARSE_STATS: src = w.parse_stats + (size_t)frame * 4; n = 16; break;
-      case HIMG_DBG_ROWCOUNT_STATS: src = w.rc_stats + (size_t)frame * g.rows * 8; n = (size_t)g.rows * 32; break;
+      case HIMG_DBG_ROWCOUNT_STATS: src = w.rc_stats ? w.rc_stats + (size_t)frame * g.rows * 8 : nullptr; n = (size_t)g.rows * 32; break;
       default: return HIMG_ERR_ARG;
     }
+    if (!src) return HIMG_ERR_ARG;   // (after a preview: the workspace holds no FRES side)
   }
   if (dst_bytes < n) return HIMG_ERR_CAPACITY;
   HIP_TRY(ctx, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));

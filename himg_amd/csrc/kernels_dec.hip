@@ -151,12 +151,17 @@ __device__ __forceinline__ uint32_t sub_leaf(int sym, uint32_t rest_bits) {
 //   4. the verdict is the FIRST failure in the reference's order of checks;
 //   5. the decode tables of BOTH streams are built side by side, 512 lanes each.
 // ---------------------------------------------------------------------------
+// HEAD (k_dec_parse_head, the 1/8-scale preview): only what the reference checks in front of
+// QCFG (decoder.cpp:95-118) -- the headers RIFF .. LRES, the LMAP body, the LRES tree and its
+// decode tables; head_sizes[f] receives the byte offset of the end of the LRES chunk (the
+// packed size where it was not found), the bound the LRES kernels' readers are given.
 constexpr int kParseThreads = 1024;
 constexpr int kParseHalf = kParseThreads / 2;   // lanes per stream in step 5
 __device__ __forceinline__ void identity_test_words(const DecFrame *df, int l, uint32_t *dst);
 
-__global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, const uint8_t *packed,
-                                                             size_t in_stride, const uint32_t *sizes) {
+template <bool HEAD>
+__device__ __forceinline__ void dec_parse_body(Geom g, DecWs ws, const uint8_t *packed,
+                                               size_t in_stride, const uint32_t *sizes, uint32_t *head_sizes) {
   __shared__ TreeAux aux[2][kMaxNodes + 1];
   __shared__ uint32_t s_nd[2][kMaxNodes + 1];
   __shared__ __attribute__((aligned(16))) uint32_t s_lut[2][1 << kLutBits];
@@ -188,6 +193,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
 
   if (lane == 0) {   // ---- 1: chunk headers, in file order
     uint32_t idx = 12, sz = 0;
+    if (HEAD) df->walk_status = 0;   // (no row walk: k_dec_status reads the parse's verdict alone)
     do {
       if (n < 12 || rd32(p) != 0x46464952u /*RIFF*/ || rd32(p + 4) + 8u != n ||
           rd32(p + 8) != 0x474d4948u /*HIMG*/) { s_chk[cHead] = fmt_err(1, 0); break; }
@@ -203,6 +209,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
       if (!find_chunk(p, n, &idx, 0x5345524cu /*LRES*/, &sz)) { s_chk[cLresFind] = fmt_err(4, 0); break; }
       df->s[0].chunk_end = idx + sz;
       s_off[1] = idx; s_sz[1] = sz;
+      if (HEAD) break;
       idx += sz;
       if (!find_chunk(p, n, &idx, 0x47464351u /*QCFG*/, &sz) || sz != (df->ycbcr ? 64u : 32u)) { s_chk[cQcfg] = fmt_err(5, 0); break; }
       s_off[2] = idx; s_sz[2] = sz;
@@ -218,11 +225,13 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
       if (!g.fix_t2 && !((uint32_t)g.row_block < sz)) { s_chk[cFresFind] = fmt_err(7, 1); break; }
       s_off[4] = idx; s_sz[4] = sz;
     } while (0);
+    if (HEAD) head_sizes[f] = s_off[1] ? df->s[0].chunk_end : n;
   }
   __syncthreads();
 
   // ---- 2: stage the bodies (a dependent global load costs ~1 us, an LDS read ~50 ns)
-  for (int k = lane; k < 5 * kBodyBytes; k += kParseThreads) {
+  // (HEAD: LMAP and the LRES tree; the FRES side below finds no tree and recovers nothing.)
+  for (int k = lane; k < (HEAD ? 2 : 5) * kBodyBytes; k += kParseThreads) {
     const int b = k / kBodyBytes, j = k - b * kBodyBytes;
     const uint32_t cnt = s_sz[b] < (uint32_t)kTreeStride ? s_sz[b] : (uint32_t)kTreeStride;
     reinterpret_cast<uint8_t *>(s_buf[b])[j] = (uint32_t)j < cnt ? p[s_off[b] + j] : (uint8_t)0;
@@ -432,7 +441,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
   if (s_status) return;
   // The row kernels' tables (DecFrame::row_tabs).  df->fmap / df->shift were written by other
   // lanes of this workgroup in front of the two barriers above.
-  {
+  if (!HEAD) {
     int16_t *um = reinterpret_cast<int16_t *>(df->row_tabs);
     uint8_t *sh = reinterpret_cast<uint8_t *>(df->row_tabs + 128);
     uint32_t *sp = df->row_tabs + 160;
@@ -451,9 +460,11 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
   }
   const long long c_serial = clock64();
 
-  // ---- 5: both streams side by side
+  // ---- 5: both streams side by side (HEAD: the LRES stream's; the other half of the
+  // workgroup only keeps the barriers)
   const int s = lane / kParseHalf, l = lane - s * kParseHalf;
   const int nn = s_nn[s];
+  const int lut_n = (HEAD && s) ? 0 : (1 << kLutBits), sub_n = (HEAD && s) ? 0 : kSubEntries;
   // The packed nodes, for the tree walks of the row kernels (codes longer than both tables).
   {
     uint32_t *nodes = ws.nodes + ((size_t)f * 2 + s) * (kMaxNodes + 1);
@@ -476,7 +487,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
     s_symd[s][k] = (uint16_t)(sym >= 0 ? sym : 0x8000);
   }
   __syncthreads();
-  for (uint32_t idx = l; idx < (1u << kLutBits); idx += kParseHalf) {
+  for (uint32_t idx = l; idx < (uint32_t)lut_n; idx += kParseHalf) {
     uint32_t e = 0;
     // depth 0: a tree that is one leaf (rejected above, kept consistent anyway)
     uint32_t h = s_heap[s][1];
@@ -489,14 +500,14 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
     s_lut[s][idx] = e;
   }
   if (l == 0) s_nslow[s] = 0;
-  for (int k = l; k < kSubEntries; k += kParseHalf) s_sub[s][k] = 0;
+  for (int k = l; k < sub_n; k += kParseHalf) s_sub[s][k] = 0;
   __syncthreads();
   const long long c_lut = clock64();
   // Second-level tables for codes longer than kLutBits.  Few kLutBits-bit prefixes
   // lead to such codes; each gets a sub-table indexed by the next m bits (m = the
   // deepest leaf below it, at most kSubMaxBits; deeper leaves continue from a
   // branch node).  The flagged first-level entry keeps its slot in bits [8:0].
-  for (uint32_t idx = l; idx < (1u << kLutBits); idx += kParseHalf) {
+  for (uint32_t idx = l; idx < (uint32_t)lut_n; idx += kParseHalf) {
     const uint32_t e = s_lut[s][idx];
     if (e & 512u) {
       const uint32_t slot = atomicAdd(&s_nslow[s], 1u);
@@ -550,7 +561,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
     // token (code bits = what is left of the code after the kLutBits-bit prefix); a node
     // reference as .x = node | depth << 16, .y = 0 (also "nothing there": 0, 0).
     uint2 *sub = ws.sub + ((size_t)f * 2 + s) * kSubEntries;
-    for (int k = l; k < kSubEntries; k += kParseHalf) {
+    for (int k = l; k < sub_n; k += kParseHalf) {
       const uint32_t e = s_sub[s][k];
       uint2 o;
       if (e & 31u) {
@@ -573,7 +584,7 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
     // optionally closed by ONE zero-run token (its zeros need no explicit bytes;
     // its extra bits are read from the stream at decode time).
     uint2 *grp = ws.grp + ((size_t)f * 2 + s) * (1u << kLutBits);
-    for (uint32_t idx = l; idx < (1u << kLutBits); idx += kParseHalf) {
+    for (uint32_t idx = l; idx < (uint32_t)lut_n; idx += kParseHalf) {
       uint32_t used = 0, nout = 0, bytes = 0, g_eb = 0, s_tb = 0, s_class = 0, ntok = 0;
       const uint32_t e0 = s_lut[s][idx];
       for (;;) {
@@ -635,11 +646,22 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, c
       ws.gyc[((size_t)f * 2 + s) * (1u << kLutBits) + idx] = yc;
     }
   }
-  if (lane == 0) {   // phase cycles / 16 for tools/dec_stats.py (after the memset of stats)
+  if (!HEAD && lane == 0) {   // phase cycles / 16 for tools/dec_stats.py (after the memset of stats)
     uint32_t *st = ws.parse_stats + (size_t)f * 4;
     st[0] = (uint32_t)((c_serial - c_in) >> 4); st[1] = (uint32_t)((c_lut - c_serial) >> 4);
     st[2] = (uint32_t)((c_sub - c_lut) >> 4); st[3] = (uint32_t)((clock64() - c_sub) >> 4);
   }
+}
+
+__global__ __launch_bounds__(kParseThreads) void k_dec_parse(Geom g, DecWs ws, const uint8_t *packed,
+                                                             size_t in_stride, const uint32_t *sizes) {
+  dec_parse_body<false>(g, ws, packed, in_stride, sizes, nullptr);
+}
+
+__global__ __launch_bounds__(kParseThreads) void k_dec_parse_head(Geom g, DecWs ws, const uint8_t *packed,
+                                                                  size_t in_stride, const uint32_t *sizes,
+                                                                  uint32_t *head_sizes) {
+  dec_parse_body<true>(g, ws, packed, in_stride, sizes, head_sizes);
 }
 
 // ---------------------------------------------------------------------------
@@ -4051,6 +4073,63 @@ __global__ void k_dec_status(DecWs ws, int32_t *status, int batch) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// k_lres_preview: the 1/8-scale preview.  The low-res plane [C][rows][cols] of a frame is
+// its preview with the channels apart: pixel p = v * cols + u of the preview is byte p of
+// every channel plane, so the kernel interleaves C planes of rows * cols bytes -- four
+// pixels per lane, ragged widths need nothing -- and applies the colour inverse
+// (ycbcr.cpp:54-82: int16 arithmetic, clamp; channels 3.. as they are) where the frame's
+// FRMT asks for it.  RGBA: one 16-byte store per lane (four dwords where the frame's
+// output does not start on 16 bytes).  Frames with a verdict are skipped.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void ycc_to_rgb(uint32_t &c0, uint32_t &c1, uint32_t &c2) {
+  const int y = (int)c0, cb = ((int)c1 << 1) - 255, cr = ((int)c2 << 1) - 255;
+  const int gg = y - ((cb + cr + 2) >> 2), b = gg + cb, r = gg + cr;   // (no int16 overflow: |b|, |r| < 640)
+  c0 = (uint32_t)clamp255d(r); c1 = (uint32_t)clamp255d(gg); c2 = (uint32_t)clamp255d(b);
+}
+
+__global__ __launch_bounds__(256) void k_lres_preview(Geom g, DecWs ws, uint8_t *out) {
+  const int f = blockIdx.y;
+  const DecFrame *df = ws.frames + f;
+  if (df->status) return;
+  const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
+  const uint32_t p0 = 4u * (blockIdx.x * 256u + threadIdx.x);
+  if (p0 >= npix) return;
+  const int C = g.C, ycc = df->ycbcr;
+  const uint8_t *plane = ws.low + (size_t)f * ws.plane_stride;
+  uint8_t *dst = out + (size_t)f * npix * (uint32_t)C;
+  const uint32_t np = npix - p0 < 4u ? npix - p0 : 4u;
+  uint32_t v[4][4];   // [pixel][channel]
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      v[k][c] = (c < C && (uint32_t)k < np) ? plane[(size_t)c * npix + p0 + k] : 0u;
+  if (ycc) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) ycc_to_rgb(v[k][0], v[k][1], v[k][2]);
+  }
+  if (C == 4 && np == 4) {
+    uint4 q;
+    q.x = v[0][0] | (v[0][1] << 8) | (v[0][2] << 16) | (v[0][3] << 24);
+    q.y = v[1][0] | (v[1][1] << 8) | (v[1][2] << 16) | (v[1][3] << 24);
+    q.z = v[2][0] | (v[2][1] << 8) | (v[2][2] << 16) | (v[2][3] << 24);
+    q.w = v[3][0] | (v[3][1] << 8) | (v[3][2] << 16) | (v[3][3] << 24);
+    uint32_t *d = reinterpret_cast<uint32_t *>(dst + 4u * p0);   // (4 * npix per frame: dword aligned)
+    if (((uintptr_t)d & 15u) == 0) {
+      *reinterpret_cast<uint4 *>(d) = q;
+    } else {
+      d[0] = q.x; d[1] = q.y; d[2] = q.z; d[3] = q.w;
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if ((uint32_t)k < np && c < C) dst[(size_t)(p0 + k) * C + c] = (uint8_t)v[k][c];
+}
+
 #define HIMG_LAUNCH(name, grid, block, ...)                    \
   do {                                                         \
     prof_begin(prof, #name, stream);                           \
@@ -4070,6 +4149,45 @@ void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed
 void launch_rowwalk_range(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
                           const uint32_t *d_sizes, int row_end, bool resume, hipStream_t stream) {
   hipLaunchKernelGGL(k_dec_rowwalk, dim3(1), dim3(64), 0, stream, g, ws, d_packed, in_stride, d_sizes, row_end, resume ? 1 : 0);
+}
+
+// LRES: every chunk in parallel, chain verified, serial fallback if not; then the predictor
+// inverse into the low-res plane.  d_sizes bounds the readers (the full decode: the packed
+// sizes; the preview: where the LRES chunk ends).
+static void launch_lres_chain(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                              const uint32_t *d_sizes, hipStream_t stream, Profiler *prof) {
+  static const int lres_stage = getenv("HIMG_LRES_STAGE") ? atoi(getenv("HIMG_LRES_STAGE")) : 3;
+  if (lres_stage & 1)
+    HIMG_LAUNCH(k_lres_spec<true>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
+                d_packed, in_stride, d_sizes);
+  else
+    HIMG_LAUNCH(k_lres_spec<false>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
+                d_packed, in_stride, d_sizes);
+  if (lres_stage & 2)
+    HIMG_LAUNCH(k_lres_fix<true>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
+  else
+    HIMG_LAUNCH(k_lres_fix<false>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
+  HIMG_LAUNCH(k_lres_write, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws, d_packed,
+              in_stride, d_sizes);
+  HIMG_LAUNCH(k_lres_finish, dim3((batch + 63) / 64), dim3(64), ws, batch);
+  HIMG_LAUNCH(k_lres_unpredict, dim3((g.mcols + 4 * kUnpredWaves - 1) / (4 * kUnpredWaves), g.mrows, batch * g.C),
+              dim3(64 * kUnpredWaves), g, ws);
+}
+
+void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                    const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
+                    hipStream_t stream, Profiler *prof) {
+  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
+  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8);
+  prof_begin(prof, "memset", stream);
+  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
+                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, nullptr, 0u);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_dec_parse_head, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes, d_head_sizes);
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_head_sizes, stream, prof);
+  const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
+  HIMG_LAUNCH(k_lres_preview, dim3((npix + 1023u) / 1024u, batch), dim3(256), g, ws, d_out);
+  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
@@ -4227,25 +4345,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   } else {
     HIMG_LAUNCH(k_dec_rowwalk, dim3(batch), dim3(64), g, ws, d_packed, in_stride, d_sizes, kWalkAll, 0);
   }
-  if (do_head) {
-    // LRES: every chunk in parallel, chain verified, serial fallback if not.
-    static const int lres_stage = getenv("HIMG_LRES_STAGE") ? atoi(getenv("HIMG_LRES_STAGE")) : 3;
-    if (lres_stage & 1)
-      HIMG_LAUNCH(k_lres_spec<true>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
-                  d_packed, in_stride, d_sizes);
-    else
-      HIMG_LAUNCH(k_lres_spec<false>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
-                  d_packed, in_stride, d_sizes);
-    if (lres_stage & 2)
-      HIMG_LAUNCH(k_lres_fix<true>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
-    else
-      HIMG_LAUNCH(k_lres_fix<false>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
-    HIMG_LAUNCH(k_lres_write, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws, d_packed,
-                in_stride, d_sizes);
-    HIMG_LAUNCH(k_lres_finish, dim3((batch + 63) / 64), dim3(64), ws, batch);
-    HIMG_LAUNCH(k_lres_unpredict, dim3((g.mcols + 4 * kUnpredWaves - 1) / (4 * kUnpredWaves), g.mrows, batch * g.C),
-                dim3(64 * kUnpredWaves), g, ws);
-  }
+  if (do_head) launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
   if (!do_rows) return;
   if (wps) {
     // Rows per workgroup: as many as the transform has lanes for and the LDS holds

@@ -174,6 +174,55 @@ int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_st
                            int num_channels, void *d_out, int32_t *d_status,
                            void *stream);
 
+/* ---- 1/8-scale preview: the low-res picture at the front of the stream ------ */
+/*
+ * The LRES chunk holds one sample per 8x8 block and channel and comes
+ * before QCFG, FMAP and FRES.  A preview is that plane as a picture: ceil(H/8) rows x
+ * ceil(W/8) columns x C channels, interleaved u8, tightly packed, rows and channels in the
+ * order of the full decode's output; pixel (u, v) is the decoder's low-res sample of block
+ * (u, v) (downsampled.cpp:318-382), through the colour inverse YCbCr::YCbCrToRGB
+ * (ycbcr.cpp:54-82) on channels 0..2 when FRMT's colour space is 1 and C >= 3.  A sample is
+ * the box over pixels 8u-3 .. 8u+4 (downsampled.cpp:67-114): the thumbnail sits 3 pixels up and
+ * left of the block grid.  No further filtering.
+ * Verdict: exactly the reference decoder's first four stages (decoder.cpp:95-118: RIFF
+ * including file_size + 8 == packed_size, FRMT, LMAP, LRES with the deviations listed at
+ * HIMG_OPT_FIX_T2, which applies to the LRES stream as in the full decode); damage in QCFG,
+ * FMAP or FRES is not seen.  HIMG_ERR_FORMAT and himg_hip_last_error as himg_hip_decode
+ * for those stages.
+ * Bytes read: nothing at or beyond head_bytes (the end of the LRES chunk) rounded up to the
+ * next multiple of 4 -- the LRES readers work on whole dwords and are bounded there.  So a
+ * caller may preview a file of which only the first head_bytes bytes are present;
+ * packed_size stays the size of the whole stream (the RIFF check needs it).
+ */
+/* Host only, no GPU: the checks of stages 1-3 and the chunk walk to the end of LRES
+ * (decoder.cpp:144-212 and the forward search of :428-461, skipping unknown chunks), on the
+ * `avail` bytes present at `packed` (nothing at or beyond avail is read).  *pw / *ph / *channels:
+ * the preview's geometry; *head_bytes: where the LRES chunk ends.  HIMG_ERR_FORMAT where the
+ * reference rejects the head (stages 1-3, or no LRES chunk); HIMG_ERR_CAPACITY when avail ends
+ * before the end of LRES (*head_bytes then set if the LRES header was reached, else 0);
+ * HIMG_ERR_UNSUPPORTED as himg_hip_peek. */
+int himg_hip_preview_peek(const uint8_t *packed, size_t avail, size_t packed_size, int *pw, int *ph,
+                          int *channels, size_t *head_bytes);
+/* The preview into caller-owned host memory; the capacity protocol of himg_hip_decode_to
+ * (HIMG_ERR_CAPACITY with the geometry set; himg_hip_fetch_last copies the result).  `packed`
+ * holds at least head_bytes bytes; only those are read and uploaded. */
+int himg_hip_preview_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
+                        size_t dst_cap, int *pw, int *ph, int *channels);
+/* n streams, the semantics of himg_hip_decode_batch: geometry per frame from FRMT, a frame that
+ * fails (or whose dst is too small) gets pw[i] = 0 and does not stop the others, the return
+ * value is the first error.  Frames that share a geometry go through one device launch
+ * of up to 256 frames; more such frames take several launches. */
+int himg_hip_preview_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                           int n, uint8_t *const *dst, const size_t *dst_cap, int *pw, int *ph,
+                           int *channels);
+/* The contract of himg_hip_decode_device (the geometry validated on the device against each
+ * stream's FRMT chunk, as there), except that d_out holds
+ * batch x ceil(H/8) x ceil(W/8) x C bytes and each stream is read only up to its head_bytes
+ * rounded up to 4. */
+int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                            const uint32_t *h_sizes, int batch, int width, int height,
+                            int num_channels, void *d_out, int32_t *d_status, void *stream);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
