@@ -202,7 +202,16 @@ struct DecStreams {
                                  // `side2` counts the next one and the caller's stream runs the LRES chain / transforms
   hipEvent_t ev_fork = nullptr;
   hipEvent_t ev_walk[kWalkSegs] = {}, ev_cnt[kWalkSegs] = {}, ev_win[kWalkSegs] = {};
-  int walk_segs = 0;             // HIMG_WALK_SEGS at context creation (0: by frame size)
+};
+
+// What of a context's settings only the host's launch code reads (what the kernels read goes
+// through Geom).  Set once, when the context is created.
+struct HostOpts {
+  bool allow_fused = true;   // HIMG_FORCE_UNFUSED=1: every block row through the generic decode path
+  bool use_side = true;      // HIMG_SIDE_STREAM=0: no side streams (decoder and encoder)
+  int walk_segs = 0;         // HIMG_WALK_SEGS: row ranges of a single frame's decode (0: by frame size)
+  int persist_rows = 1;      // HIMG_PERSIST_ROWS: persistent row workgroups (1: one per CU; 0: off; n > 1: n)
+  int n_cu = 256;            // compute units of the context's device
 };
 
 // The fused row kernel serves this geometry (a block row's symbols and the decode tables fit
@@ -215,7 +224,7 @@ int loop_counts_read_dec(unsigned long long *out);
 
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
-                   int32_t *d_status, hipStream_t stream, Profiler *prof, bool allow_fused,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
@@ -253,6 +262,11 @@ void launch_shard_head(const Geom &g, const EncWs &ws, const StaticChunks &sc, c
                        uint32_t *d_head, int r0, int r1, hipStream_t stream, Profiler *prof);
 void launch_shard_finish(const Geom &g, const EncWs &ws, uint8_t *d_out, size_t out_cap, const uint32_t *d_size,
                          hipStream_t stream, Profiler *prof);
+
+// The dynamic-LDS limits of the kernels that need more than the default, set on the current
+// device (once per context, at creation).
+hipError_t enc_set_kernel_attrs();
+hipError_t dec_set_kernel_attrs();
 
 // Stage timing hook: called before/after every kernel launch when profiling.
 void prof_begin(Profiler *p, const char *stage, hipStream_t s);

@@ -95,10 +95,18 @@ struct himg_hip_ctx {
   std::string err;
   Profiler prof;
   hipStream_t last_stream = nullptr;
-  // HIMG_FORCE_UNFUSED=1 routes every block row through the generic decode path
-  // (symbols via HBM), the one rows wider than the LDS budget always take.
-  bool allow_fused = true;
-  bool use_side = true;  // HIMG_SIDE_STREAM=0 keeps the row-header walk on the caller's stream
+  // Run-time settings: read from the environment once, in himg_hip_create; after that they
+  // change only through himg_hip_set_option.  What the kernels read goes into every call's Geom
+  // (apply_settings), what only the launch code reads is `opts`.
+  HostOpts opts;
+  int fix_t2 = 0;          // HIMG_OPT_FIX_T2 (or HIMG_FIX_T2=1 in the environment)
+  int max_sub = 4096;      // HIMG_MAX_SUB_BITS: test knob, see Geom::max_sub
+  int lead_bits = 128;     // HIMG_LEAD_BITS: tuning knob, see Geom::lead_bits
+  int lres_serial = 0;     // HIMG_FORCE_LRES_SERIAL=1: test knob, see Geom::lres_serial
+  int prefetch_rows = 1;   // HIMG_PREFETCH_ROWS: see Geom::prefetch_rows
+  int count_wave = -1, emit_rows = -1;   // HIMG_OPT_COUNT_WAVE / _EMIT_ROWS (-1: by launch size)
+  int row_tokens = -1;                   // HIMG_OPT_ROW_TOKENS (-1: by launch size)
+  int front = -1;                        // HIMG_OPT_FRONT (-1: by launch size)
   // Side stream + events: the decoder forks its serial row-header walk onto it.
   DecStreams dstr;
   // The encoder's side stream carries its LRES branch, which is on the critical path
@@ -112,13 +120,6 @@ struct himg_hip_ctx {
   // same for every quality, mapper.cpp:213-223), 32769 entries.
   DevBuf fmap_lut;
   size_t host_bytes = 0;   // bytes of the last host-API result still resident in h_out
-  int fix_t2 = 0;          // HIMG_OPT_FIX_T2 (or HIMG_FIX_T2=1 in the environment)
-  int max_sub = 4096;      // HIMG_MAX_SUB_BITS: test knob, see Geom::max_sub
-  int lead_bits = 128;     // HIMG_LEAD_BITS: tuning knob, see Geom::lead_bits
-  int lres_serial = 0;     // HIMG_FORCE_LRES_SERIAL=1: test knob, see Geom::lres_serial
-  int count_wave = -1, emit_rows = -1;   // HIMG_OPT_COUNT_WAVE / _EMIT_ROWS (-1: by launch size)
-  int row_tokens = -1;                   // HIMG_OPT_ROW_TOKENS (-1: by launch size)
-  int front = -1;                        // HIMG_OPT_FRONT (-1: by launch size)
   // Batched host API: H2D of frame i+1, kernels of frame i and D2H of frame i-1 overlap
   // on three streams; staging is double buffered.
   struct Pipe {
@@ -223,10 +224,26 @@ static bool make_geom(int width, int height, int pixel_stride, int num_channels,
   g->lres_serial = 0;
   g->count_wave = g->emit_rows = g->row_tokens = g->front = -1;
   g->wide_q = 0;
-  { static const int pf = [] { const char *e = std::getenv("HIMG_PREFETCH_ROWS"); return e ? atoi(e) : 1; }(); g->prefetch_rows = pf; }
+  g->prefetch_rows = 1;
   g->frame_bytes = (long long)width * height * pixel_stride;
   g->fres_size = fres;
   return true;
+}
+
+// The context's settings that kernels read, into the geometry of one of its calls.  Each
+// kernel reads only its own side's: the encoder's emit_rows / row_tokens / front, the
+// decoder's the rest -- and of those, the parse and row-header walk (all that the index, walk
+// and first-header entries launch) read fix_t2 alone.
+static void apply_settings(const himg_hip_ctx *ctx, Geom *g) {
+  g->fix_t2 = ctx->fix_t2;
+  g->max_sub = ctx->max_sub;
+  g->lead_bits = ctx->lead_bits;
+  g->lres_serial = ctx->lres_serial;
+  g->prefetch_rows = ctx->prefetch_rows;
+  g->count_wave = ctx->count_wave;
+  g->emit_rows = ctx->emit_rows;
+  g->row_tokens = ctx->row_tokens;
+  g->front = ctx->front;
 }
 
 extern "C" size_t himg_hip_max_packed_size(int width, int height, int num_channels) {
@@ -249,9 +266,12 @@ extern "C" int himg_hip_create(int device, himg_hip_ctx **out) {
   if (hipSetDevice(device) != hipSuccess) return HIMG_ERR_HIP;
   himg_hip_ctx *ctx = new himg_hip_ctx();
   ctx->device = device;
-  if (const char *e = std::getenv("HIMG_FORCE_UNFUSED")) ctx->allow_fused = !(e[0] == '1');
-  if (const char *e = std::getenv("HIMG_WALK_SEGS")) ctx->dstr.walk_segs = atoi(e);
-  if (const char *e = std::getenv("HIMG_SIDE_STREAM")) ctx->use_side = !(e[0] == '0');
+  HostOpts &o = ctx->opts;
+  if (const char *e = std::getenv("HIMG_FORCE_UNFUSED")) o.allow_fused = !(e[0] == '1');
+  if (const char *e = std::getenv("HIMG_WALK_SEGS")) o.walk_segs = atoi(e);
+  if (const char *e = std::getenv("HIMG_SIDE_STREAM")) o.use_side = !(e[0] == '0');
+  if (const char *e = std::getenv("HIMG_PERSIST_ROWS")) o.persist_rows = atoi(e);
+  if (const char *e = std::getenv("HIMG_PREFETCH_ROWS")) ctx->prefetch_rows = atoi(e);
   if (const char *e = std::getenv("HIMG_FIX_T2")) ctx->fix_t2 = e[0] == '1';
   if (const char *e = std::getenv("HIMG_FORCE_LRES_SERIAL")) ctx->lres_serial = e[0] == '1';
   if (const char *e = std::getenv("HIMG_MAX_SUB_BITS")) {
@@ -265,6 +285,12 @@ extern "C" int himg_hip_create(int device, himg_hip_ctx **out) {
   if (const char *e = std::getenv("HIMG_LEAD_BITS")) {
     const int v = std::atoi(e);
     if (v >= 0 && v <= 4096) ctx->lead_bits = v;
+  }
+  int n_cu = 0;
+  if (hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && n_cu > 0) o.n_cu = n_cu;
+  if (himg_dev::enc_set_kernel_attrs() != hipSuccess || himg_dev::dec_set_kernel_attrs() != hipSuccess) {
+    delete ctx;
+    return HIMG_ERR_HIP;
   }
   // Companding LUT for every magnitude an int16 can take.
   std::vector<uint8_t> lut(32769);
@@ -451,10 +477,8 @@ static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_
   return HIMG_OK;
 }
 
-static int ensure_enc_ws(himg_hip_ctx *ctx, const Geom &g_in, int batch, bool allow_row_tokens = true, bool force_row_tokens = false) {
+static int ensure_enc_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool allow_row_tokens = true, bool force_row_tokens = false) {
   EncWs &w = ctx->enc_ws;
-  Geom g = g_in;
-  g.row_tokens = ctx->row_tokens;
   // A row-sharded encode in progress belongs to the geometry it was started with.
   {
     const Geom &o = ctx->shard.g;
@@ -649,6 +673,7 @@ extern "C" int himg_hip_encode_device(himg_hip_ctx *ctx, const void *d_frames, i
   Geom g;
   if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  apply_settings(ctx, &g);
   if (g.rows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((out_stride & 255) || out_stride < 1024 || ((uintptr_t)d_out & 15) || ((uintptr_t)d_frames & 15))
     return fail(ctx, HIMG_ERR_ARG, "out_stride must be a multiple of 256; buffers 16-byte aligned");
@@ -662,12 +687,9 @@ extern "C" int himg_hip_encode_device(himg_hip_ctx *ctx, const void *d_frames, i
   if (rc) return fail(ctx, rc, "unsupported table configuration");
   hipStream_t s = (hipStream_t)stream;
   ctx->last_stream = s;
-  g.emit_rows = ctx->emit_rows;
-  g.row_tokens = ctx->row_tokens;
-  g.front = ctx->front;
   launch_encode(g, ctx->enc_ws, batch, (const uint8_t *)d_frames, (uint8_t *)d_out, out_stride,
                 d_sizes, sc, st, lt, (const uint8_t *)ctx->fmap_lut.p, s, &ctx->prof,
-                ctx->use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
+                ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
   if (d_status)
     hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, s, ctx->enc_ws.status,
                        d_status, batch);
@@ -684,11 +706,7 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
-  g.max_sub = ctx->max_sub;
-  g.lead_bits = ctx->lead_bits;
-  g.lres_serial = ctx->lres_serial;
-  g.count_wave = ctx->count_wave;
+  apply_settings(ctx, &g);
   { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
   if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
@@ -705,7 +723,7 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
   if (rc) return rc;
   launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride,
                 (const uint32_t *)ctx->d_sizes.p, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                ctx->allow_fused, ctx->use_side ? &ctx->dstr : nullptr, 0,
+                ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0,
                 g.rows);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
@@ -719,11 +737,7 @@ extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_pack
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
-  g.max_sub = ctx->max_sub;
-  g.lead_bits = ctx->lead_bits;
-  g.lres_serial = ctx->lres_serial;
-  g.count_wave = ctx->count_wave;
+  apply_settings(ctx, &g);
   g.wide_q = wide_q_hint(g, packed_size);
   if (row0 < 0 || row1 < row0 || row1 > g.rows) return fail(ctx, HIMG_ERR_ARG, "bad row range");
   if (g.rows + 1 > 65535 || g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
@@ -740,8 +754,8 @@ extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_pack
   // base so that block row row0 lands at the start of d_out_rows.
   uint8_t *base = (uint8_t *)d_out_rows - (size_t)8 * row0 * g.W * g.C;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->allow_fused,
-                ctx->use_side ? &ctx->dstr : nullptr, row0, row1);
+                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->opts,
+                ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -758,7 +772,7 @@ extern "C" int himg_hip_decode_index_device(himg_hip_ctx *ctx, const void *d_pac
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
+  apply_settings(ctx, &g);
   if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -769,7 +783,7 @@ extern "C" int himg_hip_decode_index_device(himg_hip_ctx *ctx, const void *d_pac
   rc = stage_sizes(ctx, &packed_size, 1, s);
   if (rc) return rc;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->allow_fused,
+                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->opts,
                 nullptr, 0, g.rows, nullptr, true);
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index, ctx->dec_ws.row_off, (size_t)g.rows * 4, hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index + g.rows, ctx->dec_ws.row_len, (size_t)g.rows * 4,
@@ -788,11 +802,7 @@ static int decode_rows_indexed(himg_hip_ctx *ctx, const void *d_packed, uint32_t
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
-  g.max_sub = ctx->max_sub;
-  g.lead_bits = ctx->lead_bits;
-  g.lres_serial = ctx->lres_serial;
-  g.count_wave = ctx->count_wave;
+  apply_settings(ctx, &g);
   g.wide_q = wide_q_hint(g, packed_size);
   if (row0 < 0 || row1 < row0 || row1 > g.rows) return fail(ctx, HIMG_ERR_ARG, "bad row range");
   if (g.rows + 1 > 65535 || g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
@@ -807,8 +817,8 @@ static int decode_rows_indexed(himg_hip_ctx *ctx, const void *d_packed, uint32_t
   if (rc) return rc;
   uint8_t *base = d_out_rows ? (uint8_t *)d_out_rows - (size_t)8 * row0 * g.W * g.C : nullptr;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->allow_fused,
-                ctx->use_side ? &ctx->dstr : nullptr, row0, row1, d_row_index, false, phase);
+                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->opts,
+                ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1, d_row_index, false, phase);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -872,7 +882,7 @@ extern "C" int himg_hip_decode_walk_device(himg_hip_ctx *ctx, const void *d_pack
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
+  apply_settings(ctx, &g);
   if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -882,7 +892,7 @@ extern "C" int himg_hip_decode_walk_device(himg_hip_ctx *ctx, const void *d_pack
   ctx->last_stream = s;
   rc = stage_sizes(ctx, &packed_size, 1, s);
   if (rc) return rc;
-  hipStream_t w = ctx->use_side ? ctx->dstr.side : s;
+  hipStream_t w = ctx->opts.use_side ? ctx->dstr.side : s;
   if (w != s) {
     HIP_TRY(ctx, hipEventRecord(ctx->dstr.ev_fork, s));
     HIP_TRY(ctx, hipStreamWaitEvent(w, ctx->dstr.ev_fork, 0));
@@ -907,7 +917,7 @@ extern "C" int himg_hip_decode_walk_ranges_device(himg_hip_ctx *ctx, const void 
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
+  apply_settings(ctx, &g);
   if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
   for (int k = 0; k < n_ranges; ++k)
@@ -921,7 +931,7 @@ extern "C" int himg_hip_decode_walk_ranges_device(himg_hip_ctx *ctx, const void 
   ctx->last_stream = s;
   rc = stage_sizes(ctx, &packed_size, 1, s);
   if (rc) return rc;
-  hipStream_t w = ctx->use_side ? ctx->dstr.side : s;
+  hipStream_t w = ctx->opts.use_side ? ctx->dstr.side : s;
   if (w != s) {
     HIP_TRY(ctx, hipEventRecord(ctx->dstr.ev_fork, s));
     HIP_TRY(ctx, hipStreamWaitEvent(w, ctx->dstr.ev_fork, 0));
@@ -965,7 +975,7 @@ extern "C" int himg_hip_decode_walk_wait(himg_hip_ctx *ctx) {
   if (!ctx) return HIMG_ERR_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // (without a side stream the walk went to the caller's stream)
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->use_side ? ctx->dstr.side : ctx->last_stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->opts.use_side ? ctx->dstr.side : ctx->last_stream));
   return HIMG_OK;
 }
 
@@ -979,7 +989,7 @@ extern "C" int himg_hip_decode_first_device(himg_hip_ctx *ctx, const void *d_pac
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
+  apply_settings(ctx, &g);
   if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -990,7 +1000,7 @@ extern "C" int himg_hip_decode_first_device(himg_hip_ctx *ctx, const void *d_pac
   rc = stage_sizes(ctx, &packed_size, 1, s);
   if (rc) return rc;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->allow_fused,
+                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->opts,
                 nullptr, 0, 0, nullptr, true);
   HIP_TRY(ctx, hipMemcpyAsync(d_rows_first, &ctx->dec_ws.frames[0].rows_first, 4, hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipGetLastError());
@@ -1507,10 +1517,7 @@ static int preview_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_str
                           void *stream) {
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  g.fix_t2 = ctx->fix_t2;
-  g.max_sub = ctx->max_sub;
-  g.lead_bits = ctx->lead_bits;
-  g.lres_serial = ctx->lres_serial;
+  apply_settings(ctx, &g);
   if (g.mrows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
     return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");

@@ -1379,13 +1379,8 @@ __device__ __forceinline__ bool lean_write_chain(GReader &rd0, const GrpTables &
     if (!CLIP || opa - clip_lo < clip_span) {
       const unsigned long long v = (unsigned long long)by << (8u * (opa & 3u));
       const uint32_t a = opa & ~3u;
-      // (HIMG_DEC_KO: timing builds of tools/dec_knockout.sh -- they decode wrongly on purpose)
-#if !defined(HIMG_DEC_KO) || !(HIMG_DEC_KO & 1)
       lds_or32(a, (uint32_t)v);
-#endif
-#if !defined(HIMG_DEC_KO) || !(HIMG_DEC_KO & 3)
       lds_or32(a + 4u, (uint32_t)(v >> 32));
-#endif
     }
     opa += ((y >> 10) & 511u) + extra;
     bp += n;
@@ -2019,7 +2014,7 @@ constexpr int kLresChunkBits = kDecThreads * kLresSubBits;
 // LDS is a tenth of the L2's.
 constexpr int kLresPayWords = kDecThreads * kLresSubBits / 32 + 8;
 constexpr int kLresMemo = kLresMemoWords;   // starts a lane remembers
-template <bool FIX, bool STAGE>
+template <bool FIX>
 __device__ __forceinline__ void lres_chain_body(const Geom &g, const DecWs &ws, const uint8_t *p, uint32_t stream_size,
                                 const DecFrame *df, int f, int k, const GrpTables &tb, StreamShared *sh,
                                 uint32_t *s_pay) {
@@ -2031,17 +2026,13 @@ __device__ __forceinline__ void lres_chain_body(const Geom &g, const DecWs &ws, 
   uint64_t *end_out = FIX ? ws.fix_end : ws.spec_end;
   GReader gr;
   const uint32_t rel0 = gr.attach(p, stream_size, 8ull * pay_off + cur);
-  typename std::conditional<STAGE, LReader, GReader>::type rd;
-  if constexpr (STAGE) {
-    // Bits up to rel0 + chunk + 46 are consumed and the reader runs three dwords ahead:
-    // all inside the staged words, the clamp at jmax is never the stream's data.
-    stage_payload(gr, s_pay, (uint32_t)kLresPayWords);
-    __syncthreads();
-    rd.w = (const __attribute__((address_space(3))) uint32_t *)s_pay;
-    rd.jmax = kLresPayWords - 1;
-  } else {
-    rd = gr;
-  }
+  LReader rd;
+  // Bits up to rel0 + chunk + 46 are consumed and the reader runs three dwords ahead:
+  // all inside the staged words, the clamp at jmax is never the stream's data.
+  stage_payload(gr, s_pay, (uint32_t)kLresPayWords);
+  __syncthreads();
+  rd.w = (const __attribute__((address_space(3))) uint32_t *)s_pay;
+  rd.jmax = kLresPayWords - 1;
   const unsigned long long rem = P1 - cur;
   const uint32_t rel_end = rel0 + (uint32_t)(rem < (unsigned long long)kLresChunkBits ? rem : kLresChunkBits);
   const uint32_t my_b0 = rel0 + tid * kLresSubBits;
@@ -2077,7 +2068,7 @@ __device__ __forceinline__ void lres_chain_body(const Geom &g, const DecWs &ws, 
     }
   }
   const long long c_in = clock64();
-  lean_fixpoint<false, decltype(rd), kLresMemo>(rd, tb, sh, first, active, lim, &start, &endpos, &cnt, &rounds, FIX,
+  lean_fixpoint<false, LReader, kLresMemo>(rd, tb, sh, first, active, lim, &start, &endpos, &cnt, &rounds, FIX,
                                            (uint32_t)g.lead_bits, nullptr, nullptr, memo);
   const long long c_fix = clock64() - c_in;
   if (!FIX) {
@@ -2104,12 +2095,11 @@ __device__ __forceinline__ void lres_chain_body(const Geom &g, const DecWs &ws, 
 }
 
 // k_lres_spec: every chunk of every frame, speculatively, in parallel.
-template <bool STAGE>
 __global__ __launch_bounds__(kDecThreads) void k_lres_spec(Geom g, DecWs ws, const uint8_t *packed,
                                                            size_t in_stride, const uint32_t *sizes) {
   __shared__ LdsTables T;
   __shared__ StreamShared sh;
-  __shared__ __attribute__((aligned(16))) uint32_t s_pay[STAGE ? kLresPayWords : 4];
+  __shared__ __attribute__((aligned(16))) uint32_t s_pay[kLresPayWords];
   const int k = blockIdx.x, f = blockIdx.y, tid = threadIdx.x;
   DecFrame *df = ws.frames + f;
   if (tid == 0) sh.flag = df->status;
@@ -2125,7 +2115,7 @@ __global__ __launch_bounds__(kDecThreads) void k_lres_spec(Geom g, DecWs ws, con
   load_dec_tables(ws, df, f, 0, &T);
   __syncthreads();
   const GrpTables tb = tables_of(&T);
-  lres_chain_body<false, STAGE>(g, ws, packed + (size_t)f * in_stride, sizes[f], df, f, k, tb, &sh, s_pay);
+  lres_chain_body<false>(g, ws, packed + (size_t)f * in_stride, sizes[f], df, f, k, tb, &sh, s_pay);
 }
 
 // k_lres_fix: correction and verification of ALL chunks of a frame by one workgroup.
@@ -2140,14 +2130,13 @@ __global__ __launch_bounds__(kDecThreads) void k_lres_spec(Geom g, DecWs ws, con
 //      taken from chunk 1's SPECULATIVE end, which is right iff the correction left
 //      that end unchanged -- and so on.  All ends unchanged => every chunk exact
 //      (induction).  Output offsets = scan of the corrected totals.
-template <bool STAGE>
 __global__ __launch_bounds__(kDecThreads) void k_lres_fix(Geom g, DecWs ws, const uint8_t *packed,
                                                           size_t in_stride, const uint32_t *sizes) {
   __shared__ LdsTables T;
   __shared__ StreamShared sh;
   __shared__ uint8_t s_pending[kDecThreads];
   __shared__ int s_bad;
-  __shared__ __attribute__((aligned(16))) uint32_t s_pay[STAGE ? kLresPayWords : 4];
+  __shared__ __attribute__((aligned(16))) uint32_t s_pay[kLresPayWords];
   const int f = blockIdx.x, k = threadIdx.x;
   DecFrame *df = ws.frames + f;
   if (k == 0) { ws.ver_ok[f] = 0; ws.lres_endbit[f] = ~0ull; s_bad = 0; sh.flag = df->status; }
@@ -2195,7 +2184,7 @@ __global__ __launch_bounds__(kDecThreads) void k_lres_fix(Geom g, DecWs ws, cons
   // ---- 2: warm restarts of what is left
   for (int q = 1; q < nact; ++q) {
     if (!s_pending[q]) continue;   // LDS: the same for every lane
-    lres_chain_body<true, STAGE>(g, ws, p, sizes[f], df, f, q, tb, &sh, s_pay);
+    lres_chain_body<true>(g, ws, p, sizes[f], df, f, q, tb, &sh, s_pay);
     __syncthreads();
   }
   // ---- 3: verification and output offsets (other lanes' global writes of this
@@ -2743,12 +2732,7 @@ __device__ __forceinline__ void transform_store_pair(const Geom &g, int cols_rt,
           lr0 = (uint32_t)m[(size_t)v * cols + u] | ((uint32_t)m[(size_t)v * cols + u2] << 8);
           lr8 = (uint32_t)m[(size_t)v2 * cols + u] | ((uint32_t)m[(size_t)v2 * cols + u2] << 8);
         }
-#if defined(HIMG_DEC_KO) && (HIMG_DEC_KO & 4)
-        const int c_addr = cc;   // (both lanes of a pair read planes 0, 1: no bank shared between the half-waves)
-#else
-        const int c_addr = c;
-#endif
-        tile_plane<COLS>(sym + (size_t)c_addr * 64 * cols + u, cols, s_unmap, s_shift + chroma * 64,
+        tile_plane<COLS>(sym + (size_t)c * 64 * cols + u, cols, s_unmap, s_shift + chroma * 64,
                          s_shiftp + chroma * 32, lr0, lr8, O, COLS != 0 ? s_shiftp + 64 + 2 * chroma : nullptr);
       } else {
 #pragma unroll
@@ -2821,12 +2805,7 @@ __device__ __forceinline__ void transform_store_pair(const Geom &g, int cols_rt,
           px[4 * h + 3] = __builtin_amdgcn_perm(w1, t1, 0x07060302u);
         }
       }
-#if defined(HIMG_DEC_KO) && (HIMG_DEC_KO & 16)
-      asm volatile("" :: "v"(px[0]), "v"(px[1]), "v"(px[2]), "v"(px[3]), "v"(px[4]), "v"(px[5]), "v"(px[6]), "v"(px[7]));   // (computed, not stored)
-      if (false) {
-#else
       if (store_ok && (FULL4 || y < bh)) {
-#endif
         uint8_t *dst = img + ((size_t)(8 * v + y) * g.W + 8 * u) * C;
         if (FULL4 || (C == 4 && bw == 8)) {
           uint4 o0, o1;
@@ -4139,7 +4118,29 @@ __global__ __launch_bounds__(256) void k_lres_preview(Geom g, DecWs ws, uint8_t 
 
 int loop_counts_read_dec(unsigned long long *out) { return loop_counts_read(out); }
 
-bool dec_rows_fit_lds(const Geom &g) { return fused_layout(g.row_block).total <= 160u * 1024u; }
+// The fused row kernel's LDS budget (the whole LDS of a CU), and k_row_window's fixed need.
+constexpr uint32_t kLdsMax = 160u * 1024u;
+constexpr uint32_t kRowWindowLds = (uint32_t)sizeof(LdsTables) + 64u + kRowWindow + 2u * kWinGuard + 16u;
+
+bool dec_rows_fit_lds(const Geom &g) { return fused_layout(g.row_block).total <= kLdsMax; }
+
+hipError_t dec_set_kernel_attrs() {
+  const void *fused[] = {reinterpret_cast<const void *>(&k_dec_row_fused<512>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused<256>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused<240>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused<-1>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused<0>)};
+  for (const void *k : fused) {
+    // (the kernel's static LDS counts against the same 160 KiB)
+    hipFuncAttributes fa;
+    hipError_t e = hipFuncGetAttributes(&fa, k);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsMax - fa.sharedSizeBytes));
+    if (e != hipSuccess) return e;
+  }
+  return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_window), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             (int)kRowWindowLds);
+}
 
 void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
                          const uint32_t *d_sizes, hipStream_t stream) {
@@ -4156,17 +4157,8 @@ void launch_rowwalk_range(const Geom &g, const DecWs &ws, const uint8_t *d_packe
 // sizes; the preview: where the LRES chunk ends).
 static void launch_lres_chain(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                               const uint32_t *d_sizes, hipStream_t stream, Profiler *prof) {
-  static const int lres_stage = getenv("HIMG_LRES_STAGE") ? atoi(getenv("HIMG_LRES_STAGE")) : 3;
-  if (lres_stage & 1)
-    HIMG_LAUNCH(k_lres_spec<true>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
-                d_packed, in_stride, d_sizes);
-  else
-    HIMG_LAUNCH(k_lres_spec<false>, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws,
-                d_packed, in_stride, d_sizes);
-  if (lres_stage & 2)
-    HIMG_LAUNCH(k_lres_fix<true>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
-  else
-    HIMG_LAUNCH(k_lres_fix<false>, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
+  HIMG_LAUNCH(k_lres_spec, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
+  HIMG_LAUNCH(k_lres_fix, dim3(batch), dim3(kDecThreads), g, ws, d_packed, in_stride, d_sizes);
   HIMG_LAUNCH(k_lres_write, dim3(ws.lres_chunks, batch), dim3(kDecThreads), g, ws, d_packed,
               in_stride, d_sizes);
   HIMG_LAUNCH(k_lres_finish, dim3((batch + 63) / 64), dim3(64), ws, batch);
@@ -4192,7 +4184,7 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
 
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
-                   int32_t *d_status, hipStream_t stream, Profiler *prof, bool allow_fused,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index, bool index_only, int phase) {
   // d_row_index: the FRES row index is given (k_dec_set_index instead of the serial
@@ -4214,16 +4206,14 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   // Block rows [r0, r1) only (row-sharded decode: every rank decodes the small
   // LRES stream and walks all row headers, then its own FRES rows).
   const int nrows = r1 - r0;
-  static const int rpc_env = [] { const char *e = getenv("HIMG_ROWS_PER_COUNT"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 0; }();
-  // Rows per k_row_count workgroup (tuning knob): a workgroup loads the decode tables once
-  // for its rows; a single frame has too few rows to fill the CUs that way.
+  // Rows per k_row_count workgroup: a workgroup loads the decode tables once for its rows; a
+  // single frame has too few rows to fill the CUs that way.
   const long long all_rows = (long long)batch * nrows;
-  const int rpc = rpc_env ? rpc_env : all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
+  const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
   const unsigned gx = (unsigned)((((g.cols + 31) / 32) * 64 + 255) / 256);   // k_tile_inv: two lanes per tile, 32 tiles per wave
   // Fused row kernel when the row's symbols and the decode tables fit the 160 KiB
   // LDS (width <= 4352 for RGBA); the payload is read in place from L2.
-  constexpr uint32_t kLdsMax = 160u * 1024u;
-  const int wps = (allow_fused && fused_layout(g.row_block).total <= kLdsMax) ? 1 : 0;
+  const int wps = (ho.allow_fused && fused_layout(g.row_block).total <= kLdsMax) ? 1 : 0;
   // A single large frame (nothing else to fill the GPU with while one lane walks its row
   // headers, 1.3 ms for 16384 x 16384): the rows in two ranges -- the walk of a range on
   // `side`, its counts on `side2`, its row kernels on the caller's stream, each behind the
@@ -4231,7 +4221,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   // the sum of the row kernels' own times (two ranges or four); a dependency across
   // streams costs tens of microseconds, so frames of fewer than 1024 block rows (4096^2:
   // 0.40 ms either way, 1024^2: 0.23 -> 0.30 ms) stay in one piece.
-  const int seg_env = ds ? ds->walk_segs : 0;
+  const int seg_env = ho.walk_segs;
   const int seg_want = seg_env ? (seg_env < 1 ? 1 : seg_env > kWalkSegs ? kWalkSegs : seg_env)
                                : (nrows >= 1024 ? (wps ? 2 : kWalkSegs) : 1);   // (rows through windows: three kernels per range in a pipeline)
   const int nseg = (ds && batch == 1 && !d_row_index && r0 == 0 && r1 == g.rows && nrows >= 16 * kWalkSegs) ? seg_want : 1;
@@ -4301,12 +4291,9 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   auto window_pass = [&](hipStream_t s, int a, int b) {
     if (b <= a) return;
     if (window) {
-      const uint32_t lds = (uint32_t)sizeof(LdsTables) + 64u + kRowWindow + 2u * kWinGuard + 16u;
       const unsigned nwin = (unsigned)(((uint32_t)g.row_block + kRowWindow - 1u) / kRowWindow);
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_window),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       prof_begin(prof, "k_row_window", s);
-      hipLaunchKernelGGL(k_row_window, dim3(nwin, b - a, batch), dim3(kDecThreads), lds, s, g, ws, d_packed,
+      hipLaunchKernelGGL(k_row_window, dim3(nwin, b - a, batch), dim3(kDecThreads), kRowWindowLds, s, g, ws, d_packed,
                          in_stride, d_sizes, a);
       prof_end(prof, s);
     }
@@ -4353,28 +4340,18 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     const int per_row = ((g.cols + 31) / 32) * 64;
     int rpw = 1;
     while (rpw < 8 && (rpw + 1) * per_row <= kDecThreads && fused_layout(g.row_block, rpw + 1).total <= kLdsMax) ++rpw;
-    static const int rpw_env = getenv("HIMG_ROWS_PER_FUSED") ? atoi(getenv("HIMG_ROWS_PER_FUSED")) : 0;
-    if (rpw_env > 0 && rpw_env < rpw) rpw = rpw_env;
     if (g.W == 4096 && g.C == 4 && (g.H & 7) == 0) rpw = 1;
     const uint32_t lds = fused_layout(g.row_block, rpw).total;
     // Persistent workgroups (HIMG_PERSIST_ROWS=0: one workgroup per grid element as before): as
     // many as run at once -- one per CU.
-    static const int persist_env = getenv("HIMG_PERSIST_ROWS") ? atoi(getenv("HIMG_PERSIST_ROWS")) : 1;
-    static const int n_cu = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      return n;
-    }();
     // (Sixteen wavefronts of 120+ registers each: one workgroup per CU whatever the LDS leaves.)
-    const int per_cu = 1;
+    const int n_cu = ho.n_cu, per_cu = 1;
 #define HIMG_FUSED_LAUNCH(COLS, A, B)                                                           \
   do {                                                                                          \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_row_fused<COLS>),           \
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);            \
     const int gx_ = ((B) - (A) + rpw - 1) / rpw;                                                \
     const long long all_ = (long long)gx_ * batch;                                              \
-    const int slots_ = persist_env > 1 ? persist_env : n_cu * per_cu;                           \
-    const bool pers_ = persist_env != 0 && all_ > slots_;                                       \
+    const int slots_ = ho.persist_rows > 1 ? ho.persist_rows : n_cu * per_cu;                   \
+    const bool pers_ = ho.persist_rows != 0 && all_ > slots_;                                   \
     RowArgs ra_;                                                                                \
     ra_.g = g; ra_.ws = ws; ra_.packed = d_packed; ra_.in_stride = in_stride; ra_.sizes = d_sizes; \
     ra_.out_frames = d_out; ra_.r0 = (A); ra_.r1 = (B); ra_.rpw = rpw; ra_.gx = gx_; ra_.gy = batch; \
@@ -4389,10 +4366,9 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       if (b <= a) continue;
       prof_begin(prof, "k_dec_row_fused", stream);
       const bool whole4 = g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0;   // FULL4
-      static const bool no_cols = getenv("HIMG_NO_COLS") != nullptr;   // (A/B knob: the run-time-stride variant for every width but 4096)
       if (g.W == 4096 && whole4) HIMG_FUSED_LAUNCH(512, a, b);
-      else if (g.W == 2048 && whole4 && !no_cols) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
-      else if (g.W == 1920 && whole4 && !no_cols) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
+      else if (g.W == 2048 && whole4) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
+      else if (g.W == 1920 && whole4) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
       else if (whole4) HIMG_FUSED_LAUNCH(-1, a, b);
       else HIMG_FUSED_LAUNCH(0, a, b);
       prof_end(prof, stream);

@@ -2822,20 +2822,6 @@ __global__ __launch_bounds__(256) void k_place_fres(Geom g, EncWs ws, const uint
     prof_end(prof, stream);                                    \
   } while (0)
 
-// Occupancy sweeps (BASELINE config 3, tools/occupancy_sweep.py): HIMG_LDS_PAD=<bytes>
-// adds that much unused dynamic LDS to every workgroup of the three wide encode
-// kernels, which lowers the number of workgroups a CU can hold.  0 in production.
-static size_t lds_pad() {
-  static const size_t v = [] { const char *e = getenv("HIMG_LDS_PAD"); const long x = e ? atol(e) : 0; return (size_t)(x > 0 && x <= 150000 ? x : 0); }();
-  return v;
-}
-#define HIMG_LAUNCH_PAD(name, grid, block, ...)                \
-  do {                                                         \
-    prof_begin(prof, #name, stream);                           \
-    hipLaunchKernelGGL(name, grid, block, lds_pad(), stream, __VA_ARGS__); \
-    prof_end(prof, stream);                                    \
-  } while (0)
-
 // Zero `n` dwords at the head of every row of a [batch][stride] dword array, and two
 // small arrays (the histograms and the status words) on the side: one launch instead
 // of three memsets in front of every encode.
@@ -2867,16 +2853,15 @@ static void launch_pix(const Geom &g, const EncWs &ws, const uint8_t *d_frames, 
   const dim3 grid(gxt, n, batch), block(kPixThreads);
   const PixQuant pq = make_pix_quant(st);
 #define HIMG_PIX(Y, COLS, FULL)                                                                  \
-  HIMG_LAUNCH_PAD((k_pix_fwd<Y, COLS, FULL>), grid, block, g, d_frames, ws.low, ws.plane_stride, ws.fres_sym, \
+  HIMG_LAUNCH((k_pix_fwd<Y, COLS, FULL>), grid, block, g, d_frames, ws.low, ws.plane_stride, ws.fres_sym, \
               ws.fres_stride, d_fmap_lut, pq, r0)
   const bool full = g.cols % 64 == 0;
-  static const bool no_cols = getenv("HIMG_NO_COLS") != nullptr;   // (A/B knob, see launch_decode)
   // Compile-time strides (immediate store offsets) for the widths of the BASELINE configurations:
   // 4096 (configs 2, 5), 2048, and 1920 (config 3: 240 tiles, the last wavefront of a row ragged).
   if (g.ycbcr) {
     if (g.cols == 512) HIMG_PIX(true, 512, true);
-    else if (g.cols == 256 && !no_cols) HIMG_PIX(true, 256, true);
-    else if (g.cols == 240 && !no_cols) HIMG_PIX(true, 240, false);
+    else if (g.cols == 256) HIMG_PIX(true, 256, true);
+    else if (g.cols == 240) HIMG_PIX(true, 240, false);
     else if (full) HIMG_PIX(true, 0, true);
     else HIMG_PIX(true, 0, false);
   }
@@ -2900,8 +2885,7 @@ static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames
   const int wpr = (g.cols + 63) / 64, nt = 64 * wpr;
   // ~64 block rows per workgroup (a chunk re-reads two tile rows above it), more chunks when the batch
   // alone does not give every CU two rounds of workgroups; never fewer than 16 rows.
-  static const int chunk_env = [] { const char *e = getenv("HIMG_FRONT_CHUNK"); return e ? atoi(e) : 0; }();   // (A/B knob)
-  const int target = chunk_env > 0 ? chunk_env : 64;
+  constexpr int target = 64;
   int nchunks = g.rows >= target + target / 2 ? (g.rows + target / 2) / target : 1;
   const int slots = 256 * (8 / wpr > 0 ? 8 / wpr : 1);
   nchunks = max(nchunks, min((2 * slots + batch - 1) / batch, max(1, g.rows / 16)));
@@ -2916,26 +2900,32 @@ static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames
                 "k_front indexes the quantiser's words as [table][luma / chroma][coefficient]");
 #define HIMG_FRONT(Y, COLS)                                                                               \
   do {                                                                                                    \
-    static bool attr_done = false;                                                                        \
-    if (!attr_done) {                                                                                     \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_front<Y, COLS>),                        \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);                  \
-      attr_done = true;                                                                                   \
-    }                                                                                                     \
     prof_begin(prof, "k_front", stream);                                                                  \
     hipLaunchKernelGGL((k_front<Y, COLS>), grid, block, lds, stream, fa);                                 \
     prof_end(prof, stream);                                                                               \
   } while (0)
-  static const bool no_cols = getenv("HIMG_NO_COLS") != nullptr;
   if (g.ycbcr) {
     if (g.cols == 512) HIMG_FRONT(true, 512);
-    else if (g.cols == 256 && !no_cols) HIMG_FRONT(true, 256);
-    else if (g.cols == 240 && !no_cols) HIMG_FRONT(true, 240);
+    else if (g.cols == 256) HIMG_FRONT(true, 256);
+    else if (g.cols == 240) HIMG_FRONT(true, 240);
     else HIMG_FRONT(true, 0);
   } else {
     HIMG_FRONT(false, 0);
   }
 #undef HIMG_FRONT
+}
+
+hipError_t enc_set_kernel_attrs() {
+  const void *front[] = {reinterpret_cast<const void *>(&k_front<true, 512>),
+                         reinterpret_cast<const void *>(&k_front<true, 256>),
+                         reinterpret_cast<const void *>(&k_front<true, 240>),
+                         reinterpret_cast<const void *>(&k_front<true, 0>),
+                         reinterpret_cast<const void *>(&k_front<false, 0>)};
+  for (const void *k : front) {
+    const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 constexpr long long kWideRows = 1024;   // up to this many FRES rows per call: 1024 lanes per row (k_tok_hist, k_emit)
@@ -2949,7 +2939,7 @@ static void launch_tok_hist_rows(const Geom &g, const EncWs &ws, int r0, int r1,
   if ((long long)(r1 - r0) * batch <= kWideRows && g.row_block >= 32768)
     hipLaunchKernelGGL(k_tok_hist<1024>, dim3(r1 - r0, batch), dim3(1024), 0, stream, g, ws, g.lres_spans + r0);
   else
-    hipLaunchKernelGGL(k_tok_hist<256>, dim3(r1 - r0, batch), dim3(256), lds_pad(), stream, g, ws, g.lres_spans + r0);
+    hipLaunchKernelGGL(k_tok_hist<256>, dim3(r1 - r0, batch), dim3(256), 0, stream, g, ws, g.lres_spans + r0);
   prof_end(prof, stream);
 }
 
@@ -2968,7 +2958,7 @@ static void launch_emit(const Geom &g, const EncWs &ws, uint8_t *d_out, size_t o
   if (l1 > sp0) {
     hipStream_t ls = lres_stream ? lres_stream : stream;
     prof_begin(prof, "k_emit", ls);
-    hipLaunchKernelGGL(k_emit_t<1>, dim3(l1 - sp0, batch), dim3(256), lds_pad(), ls, g, ws, d_out, out_stride,
+    hipLaunchKernelGGL(k_emit_t<1>, dim3(l1 - sp0, batch), dim3(256), 0, ls, g, ws, d_out, out_stride,
                        d_sizes, sp0, l1);
     prof_end(prof, ls);
   }
@@ -2978,12 +2968,12 @@ static void launch_emit(const Geom &g, const EncWs &ws, uint8_t *d_out, size_t o
     prof_begin(prof, "k_emit", stream);
     if (by_wave)
       hipLaunchKernelGGL(k_emit_t<kEmitRows>, dim3((sp1 - l1 + kEmitRows - 1) / kEmitRows, batch), dim3(64 * kEmitRows),
-                         lds_pad(), stream, g, ws, d_out, out_stride, d_sizes, l1, sp1);
+                         0, stream, g, ws, d_out, out_stride, d_sizes, l1, sp1);
     else if (rows <= kWideRows && g.row_block >= 32768)   // a single frame (or two): 1024 lanes per row
-      hipLaunchKernelGGL((k_emit_t<1, true>), dim3(sp1 - l1, batch), dim3(1024), lds_pad(), stream, g, ws, d_out,
+      hipLaunchKernelGGL((k_emit_t<1, true>), dim3(sp1 - l1, batch), dim3(1024), 0, stream, g, ws, d_out,
                          out_stride, d_sizes, l1, sp1);
     else
-      hipLaunchKernelGGL(k_emit_t<1>, dim3(sp1 - l1, batch), dim3(256), lds_pad(), stream, g, ws, d_out, out_stride,
+      hipLaunchKernelGGL(k_emit_t<1>, dim3(sp1 - l1, batch), dim3(256), 0, stream, g, ws, d_out, out_stride,
                          d_sizes, l1, sp1);
     prof_end(prof, stream);
   }
@@ -3001,18 +2991,15 @@ bool enc_uses_row_tokens(const Geom &g, int batch) {
 // segment and the ragged last step of k_emit_tok per segment stay small (measured, r06_experiments.md:
 // sixteen segments cost 3 % at 4096 pixels, 10 % at 1080p and 20 % at 1024 pixels).
 int enc_tok_seg(const Geom &g) {
-  static const int seg_env = [] { const char *e = getenv("HIMG_TOK_SEG"); return e ? atoi(e) : 0; }();   // (A/B knob)
   const int nseg = g.row_block >= 65536 ? 8 : 4;
   const int per = (g.row_block + nseg - 1) / nseg;
-  int seg = (per + kTokIter - 1) / kTokIter * kTokIter;
-  if (seg_env > 0) seg = (seg_env + kTokIter - 1) / kTokIter * kTokIter;
-  return seg;
+  return (per + kTokIter - 1) / kTokIter * kTokIter;
 }
 
 static void launch_tok_rows(const Geom &g, const EncWs &ws, int r0, int r1, int batch, hipStream_t stream, Profiler *prof) {
   if (r1 <= r0) return;
   prof_begin(prof, "k_tok", stream);
-  hipLaunchKernelGGL(k_tok, dim3(r1 - r0, batch), dim3(kTokThreads), lds_pad(), stream, g, ws, r0);
+  hipLaunchKernelGGL(k_tok, dim3(r1 - r0, batch), dim3(kTokThreads), 0, stream, g, ws, r0);
   prof_end(prof, stream);
 }
 
@@ -3020,12 +3007,8 @@ static void launch_emit_tok(const Geom &g, const EncWs &ws, uint8_t *d_out, size
                             int r0, int r1, int batch, hipStream_t stream, Profiler *prof) {
   if (r1 <= r0) return;
   prof_begin(prof, "k_emit_tok", stream);
-  static const int rows_env = [] { const char *e = getenv("HIMG_EMIT_TOK_ROWS"); return e ? atoi(e) : 0; }();   // (A/B knob)
-  if (rows_env == 4)
-    hipLaunchKernelGGL(k_emit_tok<4>, dim3((r1 - r0 + 3) / 4, batch), dim3(256), 0, stream, g, ws, d_out, out_stride, d_sizes, r0, r1);
-  else
-    hipLaunchKernelGGL(k_emit_tok<kEmitRows>, dim3((r1 - r0 + kEmitRows - 1) / kEmitRows, batch), dim3(64 * kEmitRows), 0,
-                       stream, g, ws, d_out, out_stride, d_sizes, r0, r1);
+  hipLaunchKernelGGL(k_emit_tok<kEmitRows>, dim3((r1 - r0 + kEmitRows - 1) / kEmitRows, batch), dim3(64 * kEmitRows), 0,
+                     stream, g, ws, d_out, out_stride, d_sizes, r0, r1);
   prof_end(prof, stream);
 }
 

@@ -1,7 +1,8 @@
 """GPU (-m gpu): the forms of the decoder's row kernel chosen by environment knobs
 (HIMG_PERSIST_ROWS: persistent workgroups or one workgroup per row; HIMG_PREFETCH_ROWS: touch
 loads for the next row's packed bytes) decode the same streams to the same pixels as the CPU
-oracle.  The knobs are read once per process, so every form runs in a child process."""
+oracle.  The knobs are read from the environment when a context is created; every form runs in a
+child process with its own environment."""
 import os
 import subprocess
 import sys

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Stage times (HIP events per kernel) of the batch encode, no result check: for A/B runs of
-environment knobs (HIMG_ROW_TOKENS, HIMG_EMIT_TOK_ROWS ...) on the GPU box.
+environment knobs (HIMG_ROW_TOKENS, HIMG_FRONT ...) on the GPU box.
 args: width height batch [iters] [quality]"""
 import os, sys
 import numpy as np

@@ -2,7 +2,7 @@
 # Everything profiles/ holds for one round, in one GPU-box call (from the repo root):
 #   tools/refresh_profiles.sh <outdir under gpurun_out> [git sha]
 # the bench line, kernel stats (default run and one stream), PMC passes + traffic,
-# the config-3 occupancy sweep, the config-4 row profile, single-frame latency.
+# the config-4 row profile, single-frame latency.
 set -u
 OUT=${1:-gpurun_out/refresh}
 SHA=${2:-unknown}
@@ -17,7 +17,6 @@ mkdir -p "$ROOT/$OUT"
 python3 "$ROOT/bench.py" --full > "$ROOT/$OUT/bench.json" 2> "$ROOT/$OUT/bench.err"
 # The same with 64 frames per launch: the batch DESIGN.md's per-kernel discussion is written for.
 python3 "$ROOT/bench.py" --full --batch 64 --no-rows --no-extras --no-cpu-baseline > "$ROOT/$OUT/bench_b64.json" 2> "$ROOT/$OUT/bench_b64.err"
-python3 "$ROOT/tools/occupancy_sweep.py" > "$ROOT/$OUT/cfg3_sweep.json" 2> "$ROOT/$OUT/cfg3_sweep.err"
 python3 "$ROOT/tools/rows_profile.py" > "$ROOT/$OUT/cfg4_rows.json" 2> "$ROOT/$OUT/cfg4_rows.err"
 python3 "$ROOT/tools/latency_profile.py" > "$ROOT/$OUT/latency.json" 2> "$ROOT/$OUT/latency.err"
 # Other shapes of the same workload: config 5 (quality sweep), 2048^2 / 1024^2 / 1080p batches.
