@@ -96,6 +96,9 @@ def lib():
     L.himg_hip_decode_walk_wait_range.argtypes = [vp, i32]
     L.himg_hip_index_host.argtypes = [vp, sz, i32, P(i32), P(i32), P(i32), vp, sz, P(C.c_uint32)]
     L.himg_hip_preview_peek.argtypes = [vp, sz, sz, P(i32), P(i32), P(i32), P(sz)]
+    L.himg_hip_region_peek.argtypes = [vp, sz, i32, i32, i32, i32, i32, vp]
+    L.himg_hip_decode_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
+    L.himg_hip_decode_region_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -343,6 +346,34 @@ class Engine:
                                            batch, width, height, channels, _ptr(d_out),
                                            _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "preview_device")
+
+    def decode_region(self, packed, x, y, w, h, out=None):
+        """Rectangle (x, y, w, h) at full resolution (himg_hip_decode_region_to) as an (h, w, C)
+        uint8 array: pixel (i, j) is pixel (y + i, x + j) of decode().  Only the stream's head and
+        the block rows the rectangle touches are uploaded (region_peek)."""
+        packed = _as_u8(packed)
+        wo, ho, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+        if lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK:
+            n = max(int(w), 0) * max(int(h), 0) * cc.value
+            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
+                out = np.empty(max(n, 1), np.uint8)
+            dst, cap = out.ctypes.data, n
+        rc = lib().himg_hip_decode_region_to(self._ctx, packed.ctypes.data, packed.nbytes, int(x), int(y), int(w), int(h),
+                                             dst, cap, C.byref(wo), C.byref(ho), C.byref(c))
+        self._check(rc, "decode_region")
+        return out.ravel()[: ho.value * wo.value * c.value].reshape(ho.value, wo.value, c.value)
+
+    def decode_region_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, x, y, w, h,
+                             d_out, d_status, stream=0):
+        """himg_hip_decode_region_device: the contract of decode_device, one rectangle for the
+        batch; d_out holds batch x h x w x C bytes (frame f at f * h * w * C)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_region_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch, width,
+                                                 height, channels, int(x), int(y), int(w), int(h), _ptr(d_out),
+                                                 _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_region_device")
 
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""
@@ -613,6 +644,25 @@ def preview_peek(packed, avail=None, packed_size=None):
         e.head_bytes = hb.value
         raise e
     return pw.value, ph.value, c.value, hb.value
+
+
+class RegionPlan(C.Structure):
+    """himg_hip_region_plan."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("num_channels", C.c_int), ("row0", C.c_int),
+                ("row1", C.c_int), ("head_bytes", C.c_size_t), ("rows_begin", C.c_size_t), ("rows_end", C.c_size_t)]
+
+
+def region_peek(packed, x, y, w, h, fix_t2=False):
+    """himg_hip_region_peek (no GPU): the plan of rectangle (x, y, w, h) as a dict -- width,
+    height, num_channels, row0, row1, head_bytes, rows_begin, rows_end.  Raises HimgError
+    (HIMG_ERR_ARG for a bad rectangle, HIMG_ERR_FORMAT / HIMG_ERR_UNSUPPORTED as index_host)."""
+    a = _as_u8(packed)
+    plan = RegionPlan()
+    rc = lib().himg_hip_region_peek(a.ctypes.data, a.nbytes, 1 if fix_t2 else 0, int(x), int(y), int(w), int(h),
+                                    C.byref(plan))
+    if rc != 0:
+        raise HimgError(rc, "region_peek")
+    return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
 
 
 def _as_u8(x):

@@ -554,7 +554,8 @@ static int wide_q_hint(const Geom &g, uint32_t max_packed_size) {
 // head_only (the 1/8-scale preview): what the head phase touches and nothing of the FRES rows --
 // no row index, lane records or FRES symbol plane (a 16384^2 frame's would be hundreds of MB),
 // the LRES stream's tables only; d_sizes holds the packed sizes, then where each LRES chunk ends.
-static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_only = false) {
+// region (the region decode): no FRES symbol plane and no quarter records either.
+static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_only = false, bool region = false) {
   DecWs &w = ctx->dec_ws;
   ctx->head.valid = false;   // whatever decode this is, it overwrites what a head phase left
   const size_t plane = round_up((size_t)g.C * g.rows * g.cols, 256);
@@ -574,9 +575,9 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_
       !ctx->d_grp.reserve((size_t)batch * 2 * (1u << kLutBits) * 8) ||
       !ctx->d_gyc.reserve((size_t)batch * 2 * (1u << kLutBits) * 4) ||
       !ctx->d_sub.reserve((size_t)batch * 2 * kSubEntries * 8) ||
-      !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
+      !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (region || himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
       !ctx->d_rows.reserve((size_t)batch * g.rows * 4 * 2) || !ctx->d_lres.reserve(lres * batch) ||
-      !ctx->d_fres.reserve(fres * batch) || !ctx->d_planes.reserve(plane * batch) ||
+      (!region && !ctx->d_fres.reserve(fres * batch)) || !ctx->d_planes.reserve(plane * batch) ||
       !ctx->d_sizes.reserve((size_t)batch * 4) ||
       !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4 + (size_t)batch * g.rows * 8) * 4))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
@@ -587,11 +588,11 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_
   w.sub = (uint2 *)ctx->d_sub.p;
   w.lane_start = head_only ? nullptr : (uint32_t *)ctx->d_lane.p;
   w.lane_off = head_only ? nullptr : w.lane_start + (size_t)batch * g.rows * kDecThreads;
-  w.lane_q = (head_only || himg_dev::dec_rows_fit_lds(g)) ? nullptr : w.lane_off + (size_t)batch * g.rows * (kDecThreads + himg_dev::kRecHdr);
+  w.lane_q = (head_only || region || himg_dev::dec_rows_fit_lds(g)) ? nullptr : w.lane_off + (size_t)batch * g.rows * (kDecThreads + himg_dev::kRecHdr);
   w.row_off = head_only ? nullptr : (uint32_t *)ctx->d_rows.p;
   w.row_len = head_only ? nullptr : w.row_off + (size_t)batch * g.rows;
   w.lres_sym = (uint8_t *)ctx->d_lres.p; w.lres_stride = lres;
-  w.fres_sym = head_only ? nullptr : (uint8_t *)ctx->d_fres.p; w.fres_stride = head_only ? 0 : fres;
+  w.fres_sym = (head_only || region) ? nullptr : (uint8_t *)ctx->d_fres.p; w.fres_stride = (head_only || region) ? 0 : fres;
   w.low = (uint8_t *)ctx->d_planes.p; w.plane_stride = plane;
   w.stats = (uint32_t *)ctx->d_stats.p;
   w.parse_stats = w.stats + (size_t)batch * (g.rows + 1) * 8;
@@ -1651,6 +1652,186 @@ extern "C" int himg_hip_preview_batch(himg_hip_ctx *ctx, const uint8_t *const *p
     HIP_TRY(ctx, hipStreamSynchronize(nullptr));
   }
   return first_err;
+}
+
+// ---------------------------------------------------------------------------
+// Region decode: one rectangle at full resolution (kernels_dec.hip, launch_region).
+// ---------------------------------------------------------------------------
+static bool region_ok(int W, int H, int x, int y, int w, int h) {
+  return w >= 1 && h >= 1 && x >= 0 && y >= 0 && (long long)x + w <= W && (long long)y + h <= H;
+}
+
+// himg_hip_index_host bounded at the rectangle's last block row: the chunk search, the length of
+// the FRES tree, the row headers of rows 0 .. row1-1 (to the end of the chunk when row1 is the
+// last row: the reference's Init walks them all).  row_index (2 x rows words, or nullptr): the
+// offsets and lengths of rows row0 .. row1-1.
+static int region_index(const uint8_t *packed, size_t packed_size, int fix_t2, int x, int y, int w, int h,
+                        himg_hip_region_plan *plan, uint32_t *row_index) {
+  int W = 0, H = 0, C = 0;
+  int rc = himg_hip_peek(packed, packed_size, &W, &H, &C);
+  if (rc) return rc;
+  plan->width = W; plan->height = H; plan->num_channels = C;
+  if (!region_ok(W, H, x, y, w, h)) return HIMG_ERR_ARG;
+  const int rows = (H + 7) / 8, r0 = y / 8, r1 = (y + h + 7) / 8;
+  plan->row0 = r0; plan->row1 = r1;
+  static const uint32_t tags[6] = {0x544d5246u, 0x50414d4cu, 0x5345524cu, 0x47464351u, 0x50414d46u, 0x53455246u};
+  size_t idx = 12;
+  uint32_t sz = 0;
+  for (int t = 0; t < 6; ++t) {
+    if (!host_find_chunk(packed, packed_size, &idx, tags[t], &sz)) return HIMG_ERR_FORMAT;
+    if (t < 5) idx += sz;
+  }
+  const size_t coff = idx, end = idx + sz;
+  size_t bit = 0;
+  {
+    const size_t bit_end = 8 * (size_t)(sz < (uint32_t)kTreeStride ? sz : (uint32_t)kTreeStride);
+    int open = 1, count = 0;
+    while (open > 0) {
+      if (count >= 2 * kNumSym - 1 || bit >= bit_end) return HIMG_ERR_FORMAT;
+      ++count;
+      if ((packed[coff + (bit >> 3)] >> (bit & 7)) & 1) {
+        if (bit + 10 > bit_end) return HIMG_ERR_FORMAT;
+        bit += 10;
+        --open;
+      } else {
+        bit += 1;
+        ++open;
+      }
+    }
+  }
+  size_t q = coff + ((bit + 7) >> 3);
+  if (q >= end) return HIMG_ERR_FORMAT;
+  plan->head_bytes = q;
+  if (fix_t2 && rows == 1) {   // one block row without a size header
+    plan->rows_begin = q; plan->rows_end = end;
+    if (row_index) { row_index[0] = (uint32_t)q; row_index[rows] = (uint32_t)(end - q); }
+    return HIMG_OK;
+  }
+  int r = 0;
+  while (q != end && (r < r1 || r1 == rows)) {
+    if (q + 2 > end) return HIMG_ERR_FORMAT;
+    const size_t hdr = q;
+    uint32_t len = packed[q] | (packed[q + 1] << 8);
+    q += 2;
+    if (len & 0x8000u) {
+      if (q + 2 > end) return HIMG_ERR_FORMAT;
+      len = (len & 0x7fffu) | ((uint32_t)(packed[q] | (packed[q + 1] << 8)) << 15);
+      q += 2;
+    }
+    if (len > end - q) return HIMG_ERR_FORMAT;
+    if (r == r0) plan->rows_begin = hdr;
+    if (r == r1 - 1) plan->rows_end = q + len;
+    if (row_index && r >= r0 && r < r1) { row_index[r] = (uint32_t)q; row_index[rows + r] = len; }
+    ++r;
+    q += len;
+  }
+  return r < r1 || (r1 == rows && r < rows) ? HIMG_ERR_FORMAT : HIMG_OK;
+}
+
+extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int x, int y, int w, int h,
+                                    himg_hip_region_plan *plan) {
+  if (!packed || !plan) return HIMG_ERR_ARG;
+  *plan = himg_hip_region_plan();
+  return region_index(packed, packed_size, fix_t2, x, y, w, h, plan, nullptr);
+}
+
+// The device launch behind both entry points; d_row_index: the host's index (one frame).
+static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
+                         int width, int height, int num_channels, int x, int y, int w, int h,
+                         const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream) {
+  Geom g;
+  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  apply_settings(ctx, &g);
+  if (!region_ok(width, height, x, y, w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
+    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_dec_ws(ctx, g, batch, false, true);
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ctx->last_stream = s;
+  rc = stage_sizes(ctx, h_sizes, batch, s);
+  if (rc) return rc;
+  launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
+                d_row_index, x, y, w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
+                ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_region_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_sizes, int batch, int width, int height,
+                                             int num_channels, int x, int y, int w, int h, void *d_out,
+                                             int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  for (int i = 0; i < batch; ++i)
+    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
+      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, x, y, w, h, nullptr,
+                       d_out, d_status, stream);
+}
+
+extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
+                                         int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height,
+                                         int *channels) {
+  if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  if (const char *msg = parse_header(packed, packed_size, &W, &H, &C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
+  Geom g;
+  if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  if (!region_ok(W, H, x, y, w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  const size_t in_cap = round_up(packed_size + 16, 256);
+  const size_t out_bytes = (size_t)w * h * C;
+  const size_t n_idx = 2 * (size_t)g.rows;
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256) ||
+      !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  if (ctx->hp_index_cap < n_idx) {
+    if (ctx->hp_index) hipHostFree(ctx->hp_index);
+    ctx->hp_index = nullptr;
+    ctx->hp_index_cap = 0;
+    if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
+      return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
+    ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
+  }
+  uint8_t *in = (uint8_t *)ctx->h_in.p;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  himg_hip_region_plan plan = himg_hip_region_plan();
+  // The host walks the headers up to row1 and uploads the head and the touched rows, each at its
+  // offset; a stream it does not index goes up whole and takes the device walk, which words the verdict.
+  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, x, y, w, h, &plan, ctx->hp_index) == HIMG_OK;
+  if (indexed) {
+    HIP_TRY(ctx, hipMemcpyAsync(in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(in + plan.rows_begin, packed + plan.rows_begin, plan.rows_end - plan.rows_begin,
+                                hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  } else {
+    HIP_TRY(ctx, hipMemsetAsync(in + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(in, packed, packed_size, hipMemcpyHostToDevice, nullptr));
+  }
+  int rc = region_launch(ctx, in, in_cap, &sz32, 1, W, H, C, x, y, w, h,
+                         indexed ? (const uint32_t *)ctx->h_index.p : nullptr, ctx->h_out.p,
+                         (int32_t *)ctx->h_status.p, nullptr);
+  if (rc) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffer
+    return rc;
+  }
+  int32_t st = 0;
+  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
+  if (st) {
+    const int code = status_to_code(st);
+    if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
+    else fail(ctx, code, "device decode reported an error");   // (himg_hip_decode's wording)
+    return code;
+  }
+  ctx->host_bytes = out_bytes;
+  *width = w; *height = h; *channels = C;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
 }
 
 // ---------------------------------------------------------------------------

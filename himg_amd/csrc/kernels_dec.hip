@@ -4109,6 +4109,325 @@ __global__ __launch_bounds__(256) void k_lres_preview(Geom g, DecWs ws, uint8_t 
       if ((uint32_t)k < np && c < C) dst[(size_t)(p0 + k) * C + c] = (uint8_t)v[k][c];
 }
 
+// ---------------------------------------------------------------------------
+// k_dec_region: rectangle R = (x, y, w, h) of every frame of the batch at full resolution,
+// h x w x C interleaved bytes per frame.  A workgroup per (column strip, touched block row,
+// frame): the row's count record (k_row_count<false> / k_row_count_w over the touched rows only,
+// every row in one chunk: launch_region),
+// then a write pass that keeps only the strip's symbols, [C][64][strip tiles] in LDS, then
+// the transform of the strip's tiles and cropped stores.  Nothing of the row's symbols goes
+// to HBM and no tile outside the rectangle is transformed.
+//   * symbol layout: segment (c, k) of the row's [C][64][cols] symbols is `S` bytes of LDS, a
+//     guard dword, the strip's tiles, at least four guard bytes: a group's 4 bytes OR-ed in at
+//     a column within three of the strip lands its outside bytes on the guards (RegionWin::put);
+//   * a lane whose recorded symbols hold no strip column does not walk; one that does stops
+//     behind its last strip symbol -- unless the frame's tree has a leaf the reference rejects
+//     (the only symbol a walk can fail on: the parse rejects trees deeper than the walk), so
+//     that every symbol the reference reads is still checked.  The lane that completes the
+//     block always walks its whole range: it carries the row's verdict;
+//   * a row without a usable record (the count kernels leave only rows of 2^22 symbols or more
+//     without one here): lane 0 walks the whole row with the reference's checks;
+//   * the payload is read in place, bounded by the row's last dword.
+// ---------------------------------------------------------------------------
+struct RegionArgs {
+  int r0;              // first touched block row (blockIdx.y = row - r0)
+  int u0, u1;          // touched tile columns [u0, u1)
+  int sw;              // tiles per column strip (blockIdx.x = strip)
+  int x, y, w, h;      // the rectangle
+  uint8_t *out;        // frame f's pixels at out + f * h * w * C
+};
+
+// LDS of k_dec_region: decode tables, the row's verdict state, the row tables (DecFrame::row_tabs),
+// then the symbol segments.
+struct RegionShared {
+  unsigned long long endbit;   // where the block became complete (relative to the payload)
+  int flag, err;
+};
+struct RegionLayout {
+  uint32_t tab, sh, rowtab, sym, seg, total;
+};
+__host__ __device__ inline RegionLayout region_layout(int C, int sw) {
+  RegionLayout L;
+  uint32_t o = 0;
+  auto carve = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  L.tab = carve((uint32_t)sizeof(LdsTables));
+  L.sh = carve((uint32_t)sizeof(RegionShared));
+  L.rowtab = carve(4u * kRowTabWords);
+  L.seg = (((uint32_t)sw + 3u) & ~3u) + 8u;
+  L.sym = carve(L.seg * 64u * (uint32_t)C);
+  L.total = o;
+  return L;
+}
+
+// The strip of a block row's symbols in LDS.  put(op, by): a group's bytes `by` at symbol op of
+// the row.  Symbol op is column op % cols of segment op / cols; the group's bytes may reach into
+// the next segment (up to three more for rows of fewer than four tiles).
+struct RegionWin {
+  uint32_t base;        // LDS address of segment 0
+  uint32_t cols, u0, ww, seg, nseg;
+  __device__ __forceinline__ void put(uint32_t op, uint32_t by) const {
+    if (by == 0) return;   // (zeros are the clear's)
+    const uint32_t s0 = op / cols;
+    const int c0 = (int)(op - s0 * cols);
+#pragma unroll 1
+    for (uint32_t j = 0; j < 4u; ++j) {
+      const int c = c0 - (int)(j * cols) - (int)u0;   // the group's first byte, relative to the strip
+      if (c0 - (int)(j * cols) < -3 || s0 + j >= nseg) break;
+      if (c >= -3 && c < (int)ww) {
+        const uint32_t a = base + (s0 + j) * seg + (uint32_t)(4 + c);
+        const unsigned long long v = (unsigned long long)by << (8u * (a & 3u));
+        lds_or32(a & ~3u, (uint32_t)v);
+        lds_or32((a & ~3u) + 4u, (uint32_t)(v >> 32));
+      }
+    }
+  }
+};
+
+// One lane's walk over the tokens that start in [bp, lim), symbols from op on.  !EXACT: every
+// symbol of the range lies inside the block; the walk ends at lim or once op passes `stop`.
+// EXACT (exact_write_body): the lane in whose range the block completes -- whole groups while the
+// block stays incomplete behind them, then token by token with the reference's end-of-block
+// checks (huffman_dec.cpp:353-354,361-417); *end_bp = where the block became complete.
+template <bool EXACT>
+__device__ __forceinline__ bool region_walk(GReader &rd, const GrpTables &t, uint32_t bp, uint32_t lim, uint32_t op,
+                                            uint32_t stop, uint32_t out_size, const RegionWin &win, uint32_t *end_bp) {
+  if (!(bp < lim) || op >= out_size) return true;
+  rd.init(bp);
+  bool bad = false;
+  const int limk = (int)lim - kLutBits;
+  while ((int)bp <= limk && op <= stop) {
+    const GReader saved = rd;
+    uint32_t nbits, cnt, by;
+    bool gbad = false;
+    lean_step<true>(rd, t, false, &nbits, &cnt, &by, &gbad);
+    if (EXACT && (gbad || op + cnt >= out_size)) { rd = saved; break; }
+    bad |= gbad;
+    win.put(op, by);
+    op += cnt;
+    bp += nbits;
+  }
+  if (!EXACT) {
+    while (bp < lim && op <= stop) {
+      uint32_t nbits, cnt, by;
+      lean_step<true>(rd, t, true, &nbits, &cnt, &by, &bad);
+      win.put(op, by);
+      op += cnt;
+      bp += nbits;
+    }
+    rd.retire();
+    return !bad;
+  }
+  bool ok = true;
+  for (;;) {
+    uint32_t nbits, cnt, by;
+    lean_step<true>(rd, t, true, &nbits, &cnt, &by, &bad);
+    if (bad || op + cnt > out_size) { ok = false; break; }   // a zero run overruns the block
+    win.put(op, by);
+    op += cnt;
+    bp += nbits;
+    if (op >= out_size) { *end_bp = bp; break; }
+    if (!(bp < lim)) break;
+  }
+  rd.retire();
+  return ok;
+}
+
+// The transform of one tile half (transform_store_pair's lane pair, generic channel count) for the
+// region: the symbols at sym with segment stride `sstride`, the low-res corners from the frame's
+// planes at the global tile u, and the stores cropped to the rectangle (row pitch w * C).
+__device__ __forceinline__ void transform_store_region(const Geom &g, int sstride, const uint8_t *sym,
+                                                       const uint8_t *low, const int16_t *s_unmap,
+                                                       const uint8_t *s_shift, const uint32_t *s_shiftp, int ycbcr,
+                                                       int u, int s, int v, const RegionArgs &ra, uint8_t *img,
+                                                       bool store_ok) {
+  const int cols = g.cols, C = g.C;
+  const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
+  uint32_t QA[16], QB[16];
+#pragma unroll
+  for (int cc = 0; cc < 2; ++cc) {
+    const int c = 2 * s + cc;
+    uint32_t O[16];
+    if (c < C) {
+      const uint8_t *m = low + (size_t)c * g.rows * cols;
+      const int chroma = (ycbcr && (c == 1 || c == 2)) ? 1 : 0;  // decoder.cpp:376
+      const uint32_t lr0 = (uint32_t)m[(size_t)v * cols + u] | ((uint32_t)m[(size_t)v * cols + u2] << 8);
+      const uint32_t lr8 = (uint32_t)m[(size_t)v2 * cols + u] | ((uint32_t)m[(size_t)v2 * cols + u2] << 8);
+      tile_plane<0>(sym + (size_t)c * 64 * sstride, sstride, s_unmap, s_shift + chroma * 64, s_shiftp + chroma * 32,
+                    lr0, lr8, O, nullptr);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) O[i] = 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      if (cc == 0) QA[i] = O[i];
+      else QB[i] = O[i];
+    }
+  }
+  uint32_t ch0[8], ch1[8], ch2[8], ch3[8];   // [r*2+h]: pixel row 4s+r, x = 4h..4h+3 (see transform_store_pair)
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const auto ra_ = __builtin_amdgcn_permlane32_swap(QA[i], QA[8 + i], false, false);
+    const auto rb_ = __builtin_amdgcn_permlane32_swap(QB[i], QB[8 + i], false, false);
+    ch0[i] = ra_[0]; ch2[i] = ra_[1];
+    ch1[i] = rb_[0]; ch3[i] = rb_[1];
+  }
+  if (!store_ok) return;
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int py = 8 * v + 4 * s + rr - ra.y;   // pixel row in the rectangle
+    if (py < 0 || py >= ra.h) continue;
+    uint8_t *drow = img + (size_t)py * ra.w * C;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      uint32_t q0 = ch0[rr * 2 + h], q1 = ch1[rr * 2 + h], q2 = ch2[rr * 2 + h], q3 = ch3[rr * 2 + h];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int px = 8 * u + 4 * h + k - ra.x;
+        uint32_t c0 = (q0 >> (8 * k)) & 255u, c1 = (q1 >> (8 * k)) & 255u, c2 = (q2 >> (8 * k)) & 255u;
+        const uint32_t c3 = (q3 >> (8 * k)) & 255u;
+        if (px < 0 || px >= ra.w) continue;
+        if (ycbcr) ycc_to_rgb(c0, c1, c2);   // ycbcr.cpp:54-82
+        uint8_t *d = drow + (size_t)px * C;
+        if (C == 4) {
+          *reinterpret_cast<uint32_t *>(d) = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);   // (4 w C per row: dword aligned)
+        } else {
+          d[0] = (uint8_t)c0;
+          if (C > 1) d[1] = (uint8_t)c1;
+          if (C > 2) d[2] = (uint8_t)c2;
+        }
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                           const uint32_t *sizes, RegionArgs ra) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const RegionLayout L = region_layout(g.C, ra.sw);
+  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
+  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
+  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift, shiftp: contiguous
+  const uint8_t *s_shift = smem + L.rowtab + 512;
+  const uint32_t *s_shiftp = reinterpret_cast<const uint32_t *>(smem + L.rowtab + 640);
+  uint8_t *sym = smem + L.sym;
+  const int tid = threadIdx.x, f = blockIdx.z, r = ra.r0 + (int)blockIdx.y;
+  const int su0 = ra.u0 + (int)blockIdx.x * ra.sw, ww = min(ra.sw, ra.u1 - su0);
+  DecFrame *df = ws.frames + f;
+  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
+  __syncthreads();
+  if (sh->flag) return;
+  load_dec_tables(ws, df, f, 1, &T);
+  if (tid < kRowTabWords / 4)
+    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
+  const uint32_t nsym16 = (L.seg * 64u * (uint32_t)g.C + 15u) / 16u;
+  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
+  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
+  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
+  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+
+  const size_t ri = (size_t)f * g.rows + (size_t)r;
+  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
+  const GrpTables tb = tables_of(&T);
+  RegionWin win;
+  win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
+  win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
+  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
+  const uint32_t valid = po[kDecThreads + 2];
+  const bool rec = valid != 0 && pay_len != 0;
+  const unsigned long long P1 = 8ull * pay_len;
+  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
+  bool ok = true;
+  if (pay_len != 0) {
+    GReader rd;
+    rel0 = rd.attach(p, end, 8ull * pay_off);
+    const uint32_t rel_end = rel0 + (uint32_t)P1;
+    if (rec) {
+      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
+      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
+      tot = po[kDecThreads];
+      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
+      const uint32_t cnt = nxt - off;
+      if (off + cnt < out_size) {
+        // The lane's last strip symbol (stop), if its symbols [off, off + cnt) hold one.
+        uint32_t stop = ~0u;
+        bool walk = true;
+        if (!strict) {
+          const uint32_t e = off + cnt - 1u, se = e / (uint32_t)g.cols, ce = e - se * (uint32_t)g.cols;
+          long long last;
+          if (ce >= (uint32_t)(su0 + ww)) last = (long long)se * g.cols + su0 + ww - 1;
+          else if (ce >= (uint32_t)su0) last = e;
+          else last = se ? (long long)(se - 1u) * g.cols + su0 + ww - 1 : -1;
+          walk = cnt != 0 && last >= (long long)off;
+          stop = walk ? (uint32_t)last : 0u;
+        }
+        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
+      } else if (off < out_size) {
+        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
+      }
+    } else if (tid == 0) {
+      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
+    }
+  }
+  if (!ok) sh->err = 1;
+  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
+  __syncthreads();
+  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
+  int bad = sh->err || pay_len == 0;
+  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
+  const unsigned long long E = sh->endbit;
+  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
+  if (bad) {
+    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+    return;
+  }
+  // ---- the strip's tiles: transform, colour inverse, cropped stores ----
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  uint8_t *img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
+  const int ycbcr = df->ycbcr;
+  const int per_row = ((ww + 31) >> 5) * 64;   // whole wavefronts: both lanes of a pair are active
+#pragma unroll 1
+  for (int it = tid; it < per_row; it += kDecThreads) {
+    const int ul = pair_tile(it);
+    const bool in_strip = ul < ww;
+    const int uc = in_strip ? ul : ww - 1;
+    transform_store_region(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
+                           pair_half(it), r, ra, img, in_strip);
+  }
+}
+
+// k_region_walk_end: k_dec_rowwalk stopped at row_end = r1 < rows flags a FRES chunk that ends right
+// behind row r1 - 1 as "fewer blocks than block rows" -- a verdict on the rows from r1 on, which
+// the region decode does not look at (region_index accepts such a stream).  For a frame whose parse
+// passed and whose walk says so, the headers of rows 0 .. r1-1 are walked again (only those bytes):
+// where they are whole and the chunk ends exactly behind row r1 - 1, the verdict is withdrawn.
+__global__ void k_region_walk_end(DecWs ws, const uint8_t *packed, size_t in_stride, int r1, int batch) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= batch) return;
+  DecFrame *df = ws.frames + f;
+  if (df->parse_status != 0 || df->walk_status != fmt_err(7, 1) || df->walk_q != 0) return;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = df->s[1].chunk_end;
+  uint32_t q = df->s[1].payload_off;
+  for (int r = 0; r < r1; ++r) {   // (k_dec_rowwalk's header rules)
+    if (q + 2 > end) return;
+    uint32_t len = p[q] | (p[q + 1] << 8);
+    q += 2;
+    if (len & 0x8000u) {
+      if (q + 2 > end) return;
+      len = (len & 0x7fffu) | ((uint32_t)(p[q] | (p[q + 1] << 8)) << 15);
+      q += 2;
+    }
+    if (len > end - q) return;
+    q += len;
+  }
+  if (q == end) df->walk_status = 0;
+}
+
 #define HIMG_LAUNCH(name, grid, block, ...)                    \
   do {                                                         \
     prof_begin(prof, #name, stream);                           \
@@ -4138,8 +4457,21 @@ hipError_t dec_set_kernel_attrs() {
       e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsMax - fa.sharedSizeBytes));
     if (e != hipSuccess) return e;
   }
-  return hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_window), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)kRowWindowLds);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_window), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)kRowWindowLds);
+  if (e != hipSuccess) return e;
+  hipFuncAttributes fa;
+  e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(kLdsMax - fa.sharedSizeBytes));
+  return e;
+}
+
+int region_strip_tiles(const Geom &g) {
+  const uint32_t fixed = region_layout(g.C, 0).total - region_layout(g.C, 0).seg * 64u * (uint32_t)g.C;
+  const uint32_t seg = (kLdsMax - 1024u - fixed) / (64u * (uint32_t)g.C) & ~3u;   // (room for the kernel's static LDS)
+  return (int)(seg - 8u);
 }
 
 void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
@@ -4179,6 +4511,69 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_head_sizes, stream, prof);
   const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
   HIMG_LAUNCH(k_lres_preview, dim3((npix + 1023u) / 1024u, batch), dim3(256), g, ws, d_out);
+  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, int x, int y, int w, int h, uint8_t *d_out,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  constexpr int kWalkAll = 0x7fffffff;
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_row_count<false>)
+  const int r0 = y / 8, r1 = (y + h + 7) / 8, u0 = x / 8, u1 = (x + w + 7) / 8;
+  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
+  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
+  prof_begin(prof, "memset", stream);
+  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
+                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
+  prof_end(prof, stream);
+  // The row headers up to r1 (all of them for the whole frame's last row: the full decode's verdict),
+  // on the side stream beside k_dec_parse and the LRES chain where there is one (launch_decode's fork:
+  // the serial walk to a row deep in a 16384^2 frame is as long as the LRES chain).
+  hipStream_t ws_ = ds ? ds->side : stream;
+  if (ds) {
+    (void)hipEventRecord(ds->ev_fork, stream);
+    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
+  }
+  prof_begin(prof, d_row_index ? "k_dec_set_index" : "k_dec_rowwalk", ws_);
+  if (d_row_index)
+    hipLaunchKernelGGL(k_dec_set_index, dim3(1), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, r0, r1);
+  else
+    hipLaunchKernelGGL(k_dec_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes,
+                       r1 == g.rows ? kWalkAll : r1, 0);
+  prof_end(prof, ws_);
+  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
+  HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
+  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
+  if (!d_row_index && r1 < g.rows)
+    HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), ws, d_packed, in_stride, r1, batch);
+  const int nrows = r1 - r0;
+  const long long all_rows = (long long)batch * nrows;
+  const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // (launch_decode's rule)
+  // Every touched row gets a record: the count kernels that read the payload in place (k_row_count<true>
+  // gives up on rows beyond its LDS staging buffer, 36 KiB -- a 4096-pixel row above q50), and no limit on
+  // a lane's share of the row (max_sub: the full decode splits longer rows into chunks, which k_dec_region
+  // has no parallel path for).  The lanes' ranges are 32-bit bit positions: any row a stream holds.
+  Geom gc = g;
+  gc.max_sub = 0x7fffffff;
+  if (count_wave) {
+    HIMG_LAUNCH(k_row_count_w, dim3((nrows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), gc, ws, d_packed,
+                in_stride, d_sizes, r0, r1);
+  } else {
+    const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
+    HIMG_LAUNCH(k_row_count<false>, dim3((nrows + rpc - 1) / rpc, batch), dim3(kDecThreads), gc, ws, d_packed, in_stride,
+                d_sizes, r0, r1, rpc);
+  }
+  RegionArgs ra;
+  ra.r0 = r0; ra.u0 = u0; ra.u1 = u1;
+  const int smax = region_strip_tiles(g), nstrip = (u1 - u0 + smax - 1) / smax;
+  ra.sw = (u1 - u0 + nstrip - 1) / nstrip;   // (strips of equal width)
+  ra.x = x; ra.y = y; ra.w = w; ra.h = h; ra.out = d_out;
+  prof_begin(prof, "k_dec_region", stream);
+  hipLaunchKernelGGL(k_dec_region, dim3(nstrip, nrows, batch), dim3(kDecThreads), region_layout(g.C, ra.sw).total, stream,
+                     g, ws, d_packed, in_stride, d_sizes, ra);
+  prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 

@@ -223,6 +223,56 @@ int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_s
                             const uint32_t *h_sizes, int batch, int width, int height,
                             int num_channels, void *d_out, int32_t *d_status, void *stream);
 
+/* ---- region decode: one rectangle at full resolution --------------------------- */
+/*
+ * A rectangle R = (x, y, w, h) with w, h >= 1, x, y >= 0, x + w <= W and y + h <= H (any other
+ * rectangle: HIMG_ERR_ARG).  R touches block rows r0 = y / 8 .. r1 = ceil((y + h) / 8) and tile
+ * columns x / 8 .. ceil((x + w) / 8).  Output: h rows x w columns x C channels, interleaved u8,
+ * tightly packed; pixel (i, j) is byte for byte pixel (y + i, x + j) of himg_hip_decode's output,
+ * under the same HIMG_OPT_FIX_T2 setting.
+ * Verdict: HIMG_ERR_FORMAT, with himg_hip_decode's himg_hip_last_error wording, wherever the
+ * reference fails in the container stages (RIFF .. FMAP), the FRES chunk and its tree, the size
+ * headers of rows 0 .. r1-1, or the entropy decode of rows r0 .. r1-1 with each row's
+ * end-of-block checks.  Damage elsewhere -- row headers from r1 on, payloads of rows outside
+ * [r0, r1) -- is not seen; when r1 is the last block row the headers are walked to the end of
+ * the chunk, so that a whole-frame rectangle gets himg_hip_decode's verdict for every stream.
+ * Bytes used: [0, head_bytes) (container, LRES, QCFG, FMAP, the FRES tree), the size header of
+ * each row 0 .. r1-1 and the payloads of rows r0 .. r1-1.  Nothing else decides the pixels or the
+ * verdict.  The kernels do load a little more and ignore it: whole dwords around these bytes, the
+ * first 384 bytes of the FRES chunk (the tree is staged in one piece, which may reach into the
+ * first rows), and a few dwords behind a row's payload (the bit readers' look-ahead).  Every load
+ * stays inside the stream.
+ */
+typedef struct himg_hip_region_plan {
+  int width, height, num_channels;   /* the frame's geometry (FRMT) */
+  int row0, row1;                    /* touched block rows [row0, row1) */
+  size_t head_bytes;                 /* where the first row header starts (rows_first) */
+  size_t rows_begin, rows_end;       /* bytes of rows row0 .. row1-1 with their size headers */
+} himg_hip_region_plan;
+/* Host only, no GPU: validates R against FRMT and walks the row headers up to row1 only (a
+ * bounded himg_hip_index_host; error codes as there: HIMG_ERR_FORMAT for a container, tree or
+ * header the decoder rejects, HIMG_ERR_UNSUPPORTED as himg_hip_peek, HIMG_ERR_ARG for a bad
+ * rectangle).  himg_hip_decode_region_to indexes on the host and uploads [0, head_bytes) and
+ * [rows_begin, rows_end), each at its offset in the stream; a caller of
+ * himg_hip_decode_region_device provides the size headers of rows 0 .. row0-1 as well (the device
+ * walks them).  Other bytes of the buffer may hold anything. */
+int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int x, int y, int w, int h,
+                         himg_hip_region_plan *plan);
+/* R of one host stream into caller-owned host memory; the capacity protocol of himg_hip_decode_to
+ * (HIMG_ERR_CAPACITY with *width = w, *height = h, *channels = C set; himg_hip_fetch_last copies
+ * the resident result).  Only the two ranges of the plan are uploaded. */
+int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
+                              int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height,
+                              int *channels);
+/* R of every stream of a batch in HBM (one rectangle for the batch): the argument and alignment
+ * contract of himg_hip_decode_device, except that d_out holds batch x h x w x C bytes, frame f at
+ * f * h * w * C (no alignment asked of a frame's start), and only the bytes used (above) of each
+ * stream decide the result. */
+int himg_hip_decode_region_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                  const uint32_t *h_sizes, int batch, int width, int height,
+                                  int num_channels, int x, int y, int w, int h, void *d_out,
+                                  int32_t *d_status, void *stream);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
