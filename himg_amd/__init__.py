@@ -99,6 +99,8 @@ def lib():
     L.himg_hip_region_peek.argtypes = [vp, sz, i32, i32, i32, i32, i32, vp]
     L.himg_hip_decode_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_region_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_regions_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -374,6 +376,41 @@ class Engine:
                                                  height, channels, int(x), int(y), int(w), int(h), _ptr(d_out),
                                                  _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_region_device")
+
+    def decode_regions(self, streams, rects, outs=None):
+        """himg_hip_decode_regions_batch: rectangle rects[i] = (x, y, w, h) of stream i at full
+        resolution, as one (h_i, w_i, C_i) uint8 array per frame (frames that share the geometry and
+        the window size share device launches of up to 256 frames; only each stream's head and the
+        block rows its rectangle touches are uploaded).  `outs` (optional) are reusable uint8 buffers."""
+        streams = [_as_u8(s_) for s_ in streams]
+        n = len(streams)
+        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
+        if outs is None:
+            outs = []
+            for s_, (_, _, w, h) in zip(streams, rc_):
+                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+                ok = lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK
+                outs.append(np.empty(max(max(int(w), 0) * max(int(h), 0) * cc.value, 1) if ok else 1, np.uint8))
+        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
+        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        rc = lib().himg_hip_decode_regions_batch(self._ctx, src, szs, n, rc_.ctypes.data, dst, caps, ws, hs, cs)
+        self._check(rc, "decode_regions")
+        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+    def decode_regions_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, origins, w, h,
+                              d_out, d_status, stream=0):
+        """himg_hip_decode_regions_device: the contract of decode_region_device, with the window
+        w x h at origin (x_f, y_f) = origins[f] in frame f (origins: (batch, 2) int32, on the host);
+        d_out holds batch x h x w x C bytes (frame f at f * h * w * C)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_decode_regions_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch, width,
+                                                  height, channels, org.ctypes.data, int(w), int(h), _ptr(d_out),
+                                                  _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_regions_device")
 
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""

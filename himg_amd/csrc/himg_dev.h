@@ -236,16 +236,19 @@ constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                     const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
                     hipStream_t stream, Profiler *prof);
-// The region decode (k_dec_region): the head phase of the full decode (zeroing, k_dec_parse, the
-// LRES chain), the row index up to block row r1 = ceil((y + h) / 8) (d_row_index: given for rows
-// [y / 8, r1) of one frame, k_dec_set_index; else k_dec_rowwalk stopping there, or walking on to
-// the end of the chunk when r1 is the last row; on ds->side beside the head phase when ds is
-// given), the counts of rows [y / 8, r1), then the region
-// kernel: batch x h x w x C interleaved bytes at d_out (frame f at f h w C).  No FRES symbol
-// plane, no quarter records.
+// The region decode (k_dec_region): the window w x h at frame f's own origin (x_f, y_f) =
+// org[2 f], org[2 f + 1] (h_org on the host, d_org the same on the device, both in range), every
+// frame of the batch.  The head phase of the full decode (zeroing, k_dec_parse, the LRES chain),
+// each frame's row index up to its block row r1_f = ceil((y_f + h) / 8) (d_row_index: given for
+// rows [y_f / 8, r1_f) of each frame at 2 f rows words, k_region_set_index; else k_region_rowwalk
+// stopping there, or walking on to the end of the chunk when r1_f is the last row; on ds->side
+// beside the head phase when ds is given), the counts of each frame's rows [y_f / 8, r1_f), then
+// the region kernel: batch x h x w x C interleaved bytes at d_out (frame f at f h w C).  No FRES
+// symbol plane, no quarter records.
 void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
-                   const uint32_t *d_sizes, const uint32_t *d_row_index, int x, int y, int w, int h, uint8_t *d_out,
-                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
+                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
+                   const DecStreams *ds);
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
 // The row-header walk of one frame alone (row-sharded decode: beside the head phase).

@@ -455,23 +455,26 @@ static int build_static(const Geom &g, int quality, StaticChunks *sc, ShiftTable
 // ---------------------------------------------------------------------------
 // Workspaces.
 // ---------------------------------------------------------------------------
-// Copy `n` packed sizes into the next pinned slot and start the H2D copy from there.
-static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s) {
+// Copy `n` packed sizes into the next pinned slot and start the H2D copy from there.  org (the
+// region decode): n origins (x, y) follow the sizes, in the same slot and the same copy.
+static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s, const int32_t *org = nullptr) {
   auto &r = ctx->sizes_ring;
   const int k = r.next;
   r.next = (k + 1) % himg_hip_ctx::SizeRing::kSlots;
   if (!r.ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
   if (r.busy[k]) HIP_TRY(ctx, hipEventSynchronize(r.ev[k]));
-  if (r.cap[k] < (size_t)n) {
+  const size_t words = (size_t)n * (org ? 3 : 1);
+  if (r.cap[k] < words) {
     if (r.h[k]) hipHostFree(r.h[k]);
     r.h[k] = nullptr;
     r.cap[k] = 0;
-    const size_t want = (size_t)n < 64 ? 64 : (size_t)n;
+    const size_t want = words < 64 ? 64 : words;
     HIP_TRY(ctx, hipHostMalloc((void **)&r.h[k], want * 4, hipHostMallocDefault));
     r.cap[k] = want;
   }
   memcpy(r.h[k], src, (size_t)n * 4);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sizes.p, r.h[k], (size_t)n * 4, hipMemcpyHostToDevice, s));
+  if (org) memcpy(r.h[k] + n, org, (size_t)n * 8);
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sizes.p, r.h[k], words * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(ctx, hipEventRecord(r.ev[k], s));
   r.busy[k] = true;
   return HIMG_OK;
@@ -554,7 +557,8 @@ static int wide_q_hint(const Geom &g, uint32_t max_packed_size) {
 // head_only (the 1/8-scale preview): what the head phase touches and nothing of the FRES rows --
 // no row index, lane records or FRES symbol plane (a 16384^2 frame's would be hundreds of MB),
 // the LRES stream's tables only; d_sizes holds the packed sizes, then where each LRES chunk ends.
-// region (the region decode): no FRES symbol plane and no quarter records either.
+// region (the region decode): no FRES symbol plane and no quarter records either; d_sizes holds the
+// packed sizes, then each frame's origin (x, y).
 static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_only = false, bool region = false) {
   DecWs &w = ctx->dec_ws;
   ctx->head.valid = false;   // whatever decode this is, it overwrites what a head phase left
@@ -578,7 +582,7 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_
       !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (region || himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
       !ctx->d_rows.reserve((size_t)batch * g.rows * 4 * 2) || !ctx->d_lres.reserve(lres * batch) ||
       (!region && !ctx->d_fres.reserve(fres * batch)) || !ctx->d_planes.reserve(plane * batch) ||
-      !ctx->d_sizes.reserve((size_t)batch * 4) ||
+      !ctx->d_sizes.reserve((size_t)batch * (region ? 12 : 4)) ||
       !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4 + (size_t)batch * g.rows * 8) * 4))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
   w.frames = (DecFrame *)ctx->d_frames.p;
@@ -1735,14 +1739,17 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
   return region_index(packed, packed_size, fix_t2, x, y, w, h, plan, nullptr);
 }
 
-// The device launch behind both entry points; d_row_index: the host's index (one frame).
+// The device launch behind every region entry point: the window w x h at frame f's origin
+// (h_org[2 f], h_org[2 f + 1]); every origin is checked before anything is launched.
+// d_row_index: the host's index, 2 x rows words per frame (rows r0_f .. r1_f - 1 filled).
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
-                         int width, int height, int num_channels, int x, int y, int w, int h,
+                         int width, int height, int num_channels, const int32_t *h_org, int w, int h,
                          const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream) {
   Geom g;
   if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
   apply_settings(ctx, &g);
-  if (!region_ok(width, height, x, y, w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  for (int f = 0; f < batch; ++f)
+    if (!region_ok(width, height, h_org[2 * f], h_org[2 * f + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
   if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
     return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
@@ -1751,12 +1758,20 @@ static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stri
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   ctx->last_stream = s;
-  rc = stage_sizes(ctx, h_sizes, batch, s);
+  rc = stage_sizes(ctx, h_sizes, batch, s, h_org);   // (the origins ride with the sizes: no extra copy, no wait)
   if (rc) return rc;
-  launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
-                d_row_index, x, y, w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
+  const uint32_t *d_sizes = (const uint32_t *)ctx->d_sizes.p;
+  launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
+                (const int32_t *)(d_sizes + batch), w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
                 ctx->opts.use_side ? &ctx->dstr : nullptr);
   HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+static int region_device_args(himg_hip_ctx *ctx, const uint32_t *h_sizes, int batch, size_t in_stride) {
+  for (int i = 0; i < batch; ++i)
+    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
+      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
   return HIMG_OK;
 }
 
@@ -1765,11 +1780,42 @@ extern "C" int himg_hip_decode_region_device(himg_hip_ctx *ctx, const void *d_pa
                                              int num_channels, int x, int y, int w, int h, void *d_out,
                                              int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
-  for (int i = 0; i < batch; ++i)
-    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
-      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
-  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, x, y, w, h, nullptr,
+  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  std::vector<int32_t> org(2 * (size_t)batch);
+  for (int f = 0; f < batch; ++f) { org[2 * f] = x; org[2 * f + 1] = y; }
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, org.data(), w, h, nullptr,
                        d_out, d_status, stream);
+}
+
+extern "C" int himg_hip_decode_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                              const uint32_t *h_sizes, int batch, int width, int height,
+                                              int num_channels, const int32_t *h_origins, int w, int h, void *d_out,
+                                              int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_origins || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
+                       d_out, d_status, stream);
+}
+
+// The pinned staging of host row indices (decode_region_to, decode_regions_batch), n_idx dwords.
+static int reserve_hp_index(himg_hip_ctx *ctx, size_t n_idx) {
+  if (ctx->hp_index_cap >= n_idx) return HIMG_OK;
+  if (ctx->hp_index) hipHostFree(ctx->hp_index);
+  ctx->hp_index = nullptr;
+  ctx->hp_index_cap = 0;
+  if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
+    return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
+  ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
+  return HIMG_OK;
+}
+
+// A device status as decode_region_to reports it.
+static int region_status_error(himg_hip_ctx *ctx, int32_t st) {
+  const int code = status_to_code(st);
+  if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
+  else fail(ctx, code, "device decode reported an error");   // (himg_hip_decode's wording)
+  return code;
 }
 
 extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
@@ -1789,14 +1835,7 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256) ||
       !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  if (ctx->hp_index_cap < n_idx) {
-    if (ctx->hp_index) hipHostFree(ctx->hp_index);
-    ctx->hp_index = nullptr;
-    ctx->hp_index_cap = 0;
-    if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
-      return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
-    ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
-  }
+  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
   uint8_t *in = (uint8_t *)ctx->h_in.p;
   const uint32_t sz32 = (uint32_t)packed_size;
   himg_hip_region_plan plan = himg_hip_region_plan();
@@ -1812,7 +1851,8 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
     HIP_TRY(ctx, hipMemsetAsync(in + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
     HIP_TRY(ctx, hipMemcpyAsync(in, packed, packed_size, hipMemcpyHostToDevice, nullptr));
   }
-  int rc = region_launch(ctx, in, in_cap, &sz32, 1, W, H, C, x, y, w, h,
+  const int32_t org[2] = {x, y};   // (a batch of one)
+  int rc = region_launch(ctx, in, in_cap, &sz32, 1, W, H, C, org, w, h,
                          indexed ? (const uint32_t *)ctx->h_index.p : nullptr, ctx->h_out.p,
                          (int32_t *)ctx->h_status.p, nullptr);
   if (rc) {
@@ -1821,17 +1861,134 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   }
   int32_t st = 0;
   HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) {
-    const int code = status_to_code(st);
-    if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
-    else fail(ctx, code, "device decode reported an error");   // (himg_hip_decode's wording)
-    return code;
-  }
+  if (st) return region_status_error(ctx, st);
   ctx->host_bytes = out_bytes;
   *width = w; *height = h; *channels = C;
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return HIMG_OK;
+}
+
+// decode_regions_batch's launches: at most kRegionLaunch frames (the grids take batch x C <= 65535),
+// whose staging stays within kRegionStageBytes (one frame at least).  A stream occupies its whole size
+// there, rounded up to the launch's stride (the largest of its streams): only its plan is uploaded, but
+// the kernels bound their reads by the stream's size, so the rest of it must be addressable.  Windows
+// near the bottom of large frames are what fill it: their plans end near the end of the stream.
+constexpr int kRegionLaunch = 256;
+constexpr size_t kRegionStageBytes = (size_t)1 << 30;
+
+// One launch of decode_regions_batch: frames grp (one geometry and window size, each planned on the
+// host) at `stride` in the staging, their plans and host indices uploaded.
+static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                         const int32_t *rects, const std::vector<int> &grp, size_t stride, int W, int H, int C,
+                         uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights, int *channels,
+                         int *first_err) {
+  const int m = (int)grp.size(), w = rects[4 * (size_t)grp[0] + 2], h = rects[4 * (size_t)grp[0] + 3];
+  const int rows = (H + 7) / 8;
+  const size_t n_idx = 2 * (size_t)rows * m, out_bytes = (size_t)w * h * C;
+  if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
+      !ctx->h_status.reserve(round_up((size_t)m * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  uint8_t *in = (uint8_t *)ctx->h_in.p;
+  std::vector<uint32_t> sz(m);
+  std::vector<int32_t> org(2 * (size_t)m), st(m);
+  for (int k = 0; k < m; ++k) {
+    const int i = grp[k];
+    const int32_t *R = rects + 4 * (size_t)i;
+    himg_hip_region_plan plan = himg_hip_region_plan();
+    (void)region_index(packed[i], packed_sizes[i], ctx->fix_t2, R[0], R[1], R[2], R[3], &plan,
+                       ctx->hp_index + (size_t)k * 2 * rows);   // (it passed when the frame was planned)
+    uint8_t *d = in + (size_t)k * stride;
+    HIP_TRY(ctx, hipMemcpyAsync(d, packed[i], plan.head_bytes, hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(d + plan.rows_begin, packed[i] + plan.rows_begin, plan.rows_end - plan.rows_begin,
+                                hipMemcpyHostToDevice, nullptr));
+    sz[k] = (uint32_t)packed_sizes[i];
+    org[2 * k] = R[0];
+    org[2 * k + 1] = R[1];
+  }
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  int rc = region_launch(ctx, in, stride, sz.data(), m, W, H, C, org.data(), w, h, (const uint32_t *)ctx->h_index.p,
+                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
+  if (rc) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
+    return rc;
+  }
+  HIP_TRY(ctx, hipMemcpy(st.data(), ctx->h_status.p, (size_t)m * 4, hipMemcpyDeviceToHost));
+  for (int k = 0; k < m; ++k) {
+    const int i = grp[k];
+    int err = HIMG_OK;
+    if (st[k]) err = region_status_error(ctx, st[k]);
+    else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+    if (err) { if (!*first_err) *first_err = err; continue; }
+    HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
+                                hipMemcpyDeviceToHost, nullptr));
+    widths[i] = w; heights[i] = h; channels[i] = C;
+  }
+  HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                             const size_t *packed_sizes, int n, const int32_t *rects,
+                                             uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights,
+                                             int *channels) {
+  if (!ctx || !packed || !packed_sizes || !rects || !dst || !dst_cap || !widths || !heights || !channels || n < 0)
+    return HIMG_ERR_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int first_err = HIMG_OK;
+  std::vector<int> W(n), H(n), Cc(n), done(n, 1);
+  for (int i = 0; i < n; ++i) {
+    widths[i] = heights[i] = channels[i] = 0;
+    const int32_t *R = rects + 4 * (size_t)i;
+    Geom g;
+    int err = HIMG_OK;
+    if (const char *msg = packed[i] ? parse_header(packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i]) : "Not a RIFF HIMG file.\n")
+      err = fail(ctx, HIMG_ERR_FORMAT, msg);
+    else if (!make_geom(W[i], H[i], Cc[i], Cc[i], 1, &g))
+      err = fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+    else if (!region_ok(W[i], H[i], R[0], R[1], R[2], R[3]))
+      err = fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+    if (err) {
+      if (!first_err) first_err = err;
+      continue;
+    }
+    himg_hip_region_plan plan = himg_hip_region_plan();
+    if (g.rows >= 2 && region_index(packed[i], packed_sizes[i], ctx->fix_t2, R[0], R[1], R[2], R[3], &plan, nullptr) == HIMG_OK) {
+      done[i] = 0;   // planned: it goes through a shared launch below
+      continue;
+    }
+    // A stream the host does not index goes through decode_region_to's own path (uploaded whole, the
+    // device walk words the verdict), so that its status and message are that call's.
+    int w = 0, h = 0, c = 0;
+    const int rc = himg_hip_decode_region_to(ctx, packed[i], packed_sizes[i], R[0], R[1], R[2], R[3], dst[i], dst_cap[i],
+                                             &w, &h, &c);
+    if (rc == HIMG_ERR_HIP) return rc;
+    if (rc) { if (!first_err) first_err = rc; continue; }
+    widths[i] = w; heights[i] = h; channels[i] = c;
+  }
+  ctx->host_bytes = 0;   // (nothing resident for himg_hip_fetch_last, as in himg_hip_decode_batch)
+  // Frames that share (W, H, C, w, h): one launch, in the order of their first frame.
+  for (int i0 = 0; i0 < n; ++i0) {
+    if (done[i0]) continue;
+    const int32_t *R0 = rects + 4 * (size_t)i0;
+    const int lim = kRegionLaunch < 65535 / Cc[i0] ? kRegionLaunch : 65535 / Cc[i0];
+    std::vector<int> grp;
+    size_t stride = 0;
+    for (int i = i0; i < n && (int)grp.size() < lim; ++i) {
+      const int32_t *R = rects + 4 * (size_t)i;
+      if (done[i] || W[i] != W[i0] || H[i] != H[i0] || Cc[i] != Cc[i0] || R[2] != R0[2] || R[3] != R0[3]) continue;
+      const size_t si = round_up(packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
+      if (!grp.empty() && s2 * (grp.size() + 1) > kRegionStageBytes) break;
+      stride = s2;
+      grp.push_back(i);
+      done[i] = 1;
+    }
+    const int rc = regions_group(ctx, packed, packed_sizes, rects, grp, stride, W[i0], H[i0], Cc[i0], dst, dst_cap,
+                                 widths, heights, channels, &first_err);
+    if (rc) return rc;
+  }
+  return first_err;
 }
 
 // ---------------------------------------------------------------------------

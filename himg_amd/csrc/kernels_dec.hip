@@ -677,126 +677,22 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse_head(Geom g, DecWs 
 // A single frame's walk is cut into row ranges, one launch each (row_end: walk the rows in
 // front of it; the last launch walks to the end of the chunk; resume: continue where the
 // launch before stopped, DecFrame::walk_q / walk_r): the counts and the row kernels of a
-// range run while the next range is walked (launch_decode).
+// range run while the next range is walked (launch_decode).  The body (dec_body_rowwalk.inc) is
+// also the region decode's per-frame form's, k_region_rowwalk.
 __global__ __launch_bounds__(64) void k_dec_rowwalk(Geom g, DecWs ws, const uint8_t *packed,
                                                     size_t in_stride, const uint32_t *sizes,
                                                     int row_end, int resume) {
-  // The walk needs where the FRES payload starts and ends -- which k_dec_parse knows
-  // only after its tree recovery.  It finds both by itself (the same chunk
-  // look-ups, then only the LENGTH of the serialised tree: a leaf is 1 + 9 bits, a
-  // branch 1 bit, pre-order, huffman_dec.cpp:152-229) and so runs beside k_dec_parse
-  // instead of behind it.  Whatever is wrong with the headers or the tree is
-  // k_dec_parse's to report; this kernel reports the row headers only, in
-  // walk_status, which k_row_count / k_dec_status merge once both kernels are done.
-  __shared__ uint32_t s_tree[(kTreeStride + 16) / 4];
-  __shared__ uint32_t s_hdr[2];
-  const int f = blockIdx.x, lane = threadIdx.x;
-  DecFrame *df = ws.frames + f;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  uint32_t q = 0, end = 0;
-  int r = 0;
-  if (resume) {
-    if (lane != 0) return;
-    q = df->walk_q; r = (int)df->walk_r; end = df->walk_end;
-    if (q == 0) return;   // finished (or never started): the verdict is in
-  } else {
-    const uint32_t n = sizes[f];
-    if (lane == 0) {
-      uint32_t idx = 12, sz = 0;
-      bool ok = n >= 12;
-      const uint32_t tags[6] = {0x544d5246u /*FRMT*/, 0x50414d4cu /*LMAP*/, 0x5345524cu /*LRES*/,
-                                0x47464351u /*QCFG*/, 0x50414d46u /*FMAP*/, 0x53455246u /*FRES*/};
-      for (int t = 0; ok && t < 6; ++t) {   // the order of k_dec_parse (decoder.cpp:144-290)
-        ok = find_chunk(p, n, &idx, tags[t], &sz);
-        if (ok && t < 5) idx += sz;
-      }
-      s_hdr[0] = ok ? idx : 0u;
-      s_hdr[1] = ok ? sz : 0u;
-      df->walk_status = 0;
-      df->rows_first = 0;
-      df->walk_q = 0;
-    }
-    __syncthreads();
-    const uint32_t coff = s_hdr[0], csz = s_hdr[1];
-    if (coff == 0) return;
-    const uint32_t cnt = csz < (uint32_t)kTreeStride ? csz : (uint32_t)kTreeStride;
-    for (uint32_t k = lane; k < (uint32_t)kTreeStride + 16u; k += 64u)
-      reinterpret_cast<uint8_t *>(s_tree)[k] = k < cnt ? p[coff + k] : (uint8_t)0;
-    __syncthreads();
-    if (lane != 0) return;
-    uint32_t bit = 0;
-    {
-      // Length of the serialised tree over a 64-bit register window.
-      unsigned long long win = ((unsigned long long)s_tree[1] << 32) | s_tree[0];
-      uint32_t next = 2, ahead = s_tree[2];
-      const uint32_t bit_end = 8u * cnt;
-      int open = 1, count = 0, nb = 64;
-      while (open > 0) {
-        if (count >= kMaxNodes || bit >= bit_end) return;   // k_dec_parse rejects this tree
-        ++count;
-        if (nb <= 32) { win |= (unsigned long long)ahead << nb; nb += 32; ahead = s_tree[++next]; }
-        if (win & 1ull) {
-          if (bit + 10u > bit_end) return;
-          win >>= 10; nb -= 10; bit += 10u;
-          --open;
-        } else {
-          win >>= 1; nb -= 1; bit += 1u;
-          ++open;
-        }
-      }
-    }
-    q = coff + ((bit + 7u) >> 3);   // AlignToByte, huffman_dec.cpp:229
-    end = coff + csz;
-    if (q >= end) return;                    // nothing behind the tree: k_dec_parse's verdict
-    df->rows_first = q;
-    if (g.fix_t2 && g.rows == 1) {   // the encoder writes one block row without a size header
-      ws.row_off[(size_t)f * g.rows] = q;
-      ws.row_len[(size_t)f * g.rows] = end - q;
-      return;
-    }
-  }
-  uint32_t *ro = ws.row_off + (size_t)f * g.rows, *rl = ws.row_len + (size_t)f * g.rows;
-  int st = 0;
-  while (q != end && r < row_end) {
-    if (q + 2 > end) { st = fmt_err(7, 1); break; }
-    uint32_t len = p[q] | (p[q + 1] << 8);
-    q += 2;
-    if (len & 0x8000u) {
-      if (q + 2 > end) { st = fmt_err(7, 1); break; }
-      len = (len & 0x7fffu) | ((uint32_t)(p[q] | (p[q + 1] << 8)) << 15);
-      q += 2;
-    }
-    if (len > end - q) { st = fmt_err(7, 1); break; }
-    if (r < g.rows) { ro[r] = q; rl[r] = len; }
-    ++r;
-    q += len;
-  }
-  if (st || q == end) {
-    if (!st && r < g.rows) st = fmt_err(7, 1);  // fewer blocks than block rows
-    df->walk_status = st;
-    df->walk_q = 0;
-  } else {   // the next launch goes on from here
-    df->walk_q = q; df->walk_r = (uint32_t)r; df->walk_end = end;
-  }
+#include "dec_body_rowwalk.inc"
 }
 
 // k_dec_set_index: the row index comes from the caller (row-sharded decode: the rank
 // that holds the whole stream walked the headers once, the others hold only their own
 // rows' bytes and cannot) -- [rows] payload offsets, then [rows] lengths.  Rows whose
-// payload would leave the stream are flagged like a damaged header.
+// payload would leave the stream are flagged like a damaged header.  The body (dec_body_set_index.inc)
+// is also the region decode's per-frame form's, k_region_set_index.
 __global__ __launch_bounds__(256) void k_dec_set_index(Geom g, DecWs ws, const uint32_t *index,
                                                        const uint32_t *sizes, int r0, int r1) {
-  DecFrame *df = ws.frames;   // (one frame)
-  const uint32_t n = sizes[0];
-  int bad = 0;
-  for (int r = r0 + (int)threadIdx.x; r < r1; r += 256) {
-    const uint32_t off = index[r], len = index[g.rows + r];
-    ws.row_off[r] = off;
-    ws.row_len[r] = len;
-    if (off > n || len > n - off) bad = 1;
-  }
-  bad = __syncthreads_or(bad);
-  if (threadIdx.x == 0) { df->walk_status = bad ? fmt_err(7, 1) : 0; df->rows_first = 0; }
+#include "dec_body_set_index.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -3281,89 +3177,13 @@ __device__ __forceinline__ void row_count_one(RD &rd, const GrpTables &tb, Strea
 
 // LDSPAY: the row's payload is staged in LDS (rows of up to 36 KiB -- every shape
 // the fused row kernel serves); otherwise (wide rows, generic path) the lanes read
-// it in place.
+// it in place.  The body (dec_body_row_count.inc) is also the region decode's per-frame
+// form's, k_region_count.
 template <bool LDSPAY>
 __global__ __launch_bounds__(kDecThreads, 8) void k_row_count(Geom g, DecWs ws, const uint8_t *packed,
                                                            size_t in_stride, const uint32_t *sizes,
                                                            int r0, int r1, int rows_per_wg) {
-  // Both tables as two arrays: the step words (gy), then their .x words (gx).
-  __shared__ __attribute__((aligned(16))) uint32_t gyx[2 * kTabEntries];
-  __shared__ __attribute__((aligned(16))) uint32_t s_pay[LDSPAY ? kPayWords : 4];   // the row's payload
-  __shared__ uint32_t nd[kMaxNodes + 1];
-  uint32_t *gy = gyx, *gx = gyx + kTabEntries;
-  __shared__ uint32_t sm32[kDecThreads / 64];
-  __shared__ StreamShared sh;
-  const int f = blockIdx.y, tid = threadIdx.x;
-  DecFrame *df = ws.frames + f;
-  // One read for the whole workgroup: the LRES kernels run concurrently on the
-  // other stream and may flag the frame while this kernel starts.
-  if (tid == 0) {
-    // The row walk ran beside k_dec_parse: its verdict counts if the parse passed.
-    const int w = df->parse_status == 0 ? df->walk_status : 0;
-    if (w && blockIdx.x == 0) atomicMax(&df->status, w);
-    sh.flag = df->status | w;
-  }
-  __syncthreads();
-  const int failed = sh.flag;
-  if (!failed) {   // load_dec_tables with the count-only step words next to the long-code descriptors
-    const uint32_t *nodes = ws.nodes + ((size_t)f * 2 + 1) * (kMaxNodes + 1);
-    const int nn = df->s[1].num_nodes;
-    for (int k = tid; k < nn; k += kDecThreads) nd[k] = nodes[k];
-    const uint4 *gg = reinterpret_cast<const uint4 *>(ws.grp + ((size_t)f * 2 + 1) * (1u << kLutBits));
-    const uint2 *gc = reinterpret_cast<const uint2 *>(ws.gyc + ((size_t)f * 2 + 1) * (1u << kLutBits));
-    for (int k = tid; k < (1 << kLutBits) / 2; k += kDecThreads) {
-      const uint4 q = gg[k];
-      reinterpret_cast<uint2 *>(gx)[k] = make_uint2(q.x, q.z);   // long-code descriptors
-      reinterpret_cast<uint2 *>(gy)[k] = gc[k];                  // count-only step words
-    }
-    const uint4 *gs = reinterpret_cast<const uint4 *>(ws.sub + ((size_t)f * 2 + 1) * kSubEntries);
-    for (int k = tid; k < kSubEntries / 2; k += kDecThreads) {
-      const uint4 q = gs[k];
-      reinterpret_cast<uint2 *>(gx + (1 << kLutBits))[k] = make_uint2(q.x, q.z);
-      reinterpret_cast<uint2 *>(gy + (1 << kLutBits))[k] = make_uint2(q.y, q.w);
-    }
-  }
-  GrpTables tb;
-  tb.grp = nullptr; tb.gx = gx; tb.gy = gy; tb.nd = nd;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  const int rb = r0 + (int)blockIdx.x * rows_per_wg;
-  for (int r = rb; r < min(rb + rows_per_wg, r1); ++r) {
-    const long long c_in = clock64();
-    uint32_t *l_start = ws.lane_start + ((size_t)f * g.rows + r) * kDecThreads;
-    uint32_t *l_off = ws.lane_off + ((size_t)f * g.rows + r) * (kDecThreads + kRecHdr);
-    uint32_t *rc = ws.rc_stats ? ws.rc_stats + ((size_t)f * g.rows + r) * 8 : nullptr;
-    if (tid == 0) { l_off[kDecThreads + 2] = 0; sh.dbg[0] = sh.dbg[1] = 0; }   // not usable until proven otherwise
-    if (tid >= kRecWin && tid < kRecHdr) l_off[kDecThreads + tid] = ~0u;            // no window index yet (k_row_window checks what it finds)
-    const uint32_t pay_off = ws.row_off[(size_t)f * g.rows + r], pay_len = ws.row_len[(size_t)f * g.rows + r];
-    const unsigned long long rem = 8ull * pay_len;
-    uint32_t sb = (uint32_t)((rem + kDecThreads - 1) / kDecThreads);
-    sb = (sb + 31u) & ~31u;
-    sb = sb < kMinSubBits ? kMinSubBits : sb;
-    // More than one chunk: the fused kernel does it all.
-    if (failed || sb > (uint32_t)g.max_sub || rem == 0 || g.row_block >= (1 << 22)) continue;
-    GReader rd;
-    const uint32_t rel0 = rd.attach(p, sizes[f], 8ull * pay_off);
-    if (LDSPAY) {
-      const uint32_t nd = (rel0 + (uint32_t)rem + 31u) / 32u;   // dwords that hold payload bits
-      // A payload beyond the staging buffer is left to the row kernels, like a row of
-      // several chunks.
-      if (nd + kPayPad > (uint32_t)kPayWords) continue;
-      __syncthreads();   // the previous row's readers are done with s_pay (and the tables are in)
-      stage_payload(rd, s_pay, nd + kPayPad);
-      __syncthreads();
-      LReader lr;
-      lr.w = (const __attribute__((address_space(3))) uint32_t *)s_pay;
-      lr.jmax = nd + kPayPad - 1u;
-      row_count_one(lr, tb, &sh, sm32, rel0, (uint32_t)rem, sb, (uint32_t)g.lead_bits, l_start, l_off, rc, c_in);
-    } else {
-      __syncthreads();   // the tables are in / the previous row is done with the exchange slots
-      if (ws.lane_q)     // rows that go through windows: four records per lane
-        row_count_one<GReader, true>(rd, tb, &sh, sm32, rel0, (uint32_t)rem, sb, (uint32_t)g.lead_bits, l_start, l_off, rc, c_in,
-                                     ws.lane_q + ((size_t)f * g.rows + r) * (6 * kDecThreads), (uint32_t)g.row_block, kRowWindow);
-      else
-        row_count_one(rd, tb, &sh, sm32, rel0, (uint32_t)rem, sb, (uint32_t)g.lead_bits, l_start, l_off, rc, c_in);
-    }
-  }
+#include "dec_body_row_count.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -3487,178 +3307,12 @@ __device__ __forceinline__ void grp_count_lds(const LdsBits &bits, const GrpTabl
 // Rows whose sub-sequences are at most kStageSubBits bits long (4096-pixel rows up to
 // ~2.4 bits per symbol): every phase's piece of the payload goes to LDS first -- coalesced
 // 16-byte loads -- and the walks read it on demand (grp_count_lds); longer rows are read in
-// place through register windows (wave-uniform choice per row).
+// place through register windows (wave-uniform choice per row).  The body (dec_body_row_count_w.inc)
+// is also the region decode's per-frame form's, k_region_count_w.
 __global__ __launch_bounds__(kDecThreads, 8) void k_row_count_w(Geom g, DecWs ws, const uint8_t *packed,
                                                                size_t in_stride, const uint32_t *sizes,
                                                                int r0, int r1) {
-  __shared__ __attribute__((aligned(16))) uint32_t gyx[2 * kTabEntries];
-  __shared__ uint32_t nd[kMaxNodes + 1];
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[kCountRowsW * kStageAlloc];
-  __shared__ int s_flag;
-  uint32_t *gy = gyx, *gx = gyx + kTabEntries;
-  const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
-  DecFrame *df = ws.frames + f;
-  if (tid == 0) {
-    // The row walk ran beside k_dec_parse: its verdict counts if the parse passed.
-    const int w = df->parse_status == 0 ? df->walk_status : 0;
-    if (w && blockIdx.x == 0) atomicMax(&df->status, w);
-    s_flag = df->status | w;
-  }
-  __syncthreads();
-  const int failed = s_flag;
-  if (!failed) {   // load_dec_tables with the count-only step words next to the long-code descriptors
-    const uint32_t *nodes = ws.nodes + ((size_t)f * 2 + 1) * (kMaxNodes + 1);
-    const int nn = df->s[1].num_nodes;
-    for (int k = tid; k < nn; k += kDecThreads) nd[k] = nodes[k];
-    const uint4 *gg = reinterpret_cast<const uint4 *>(ws.grp + ((size_t)f * 2 + 1) * (1u << kLutBits));
-    for (int k = tid; k < (1 << kLutBits) / 2; k += kDecThreads) {
-      const uint4 q = gg[k];
-      reinterpret_cast<uint2 *>(gx)[k] = make_uint2(q.x, q.z);   // bytes / long-code descriptors
-      // The step words of the WRITE pass's groups (at most four output bytes), not the
-      // count-only ones: a row kernel that walks those groups from a lane's recorded start
-      // follows exactly this kernel's chain and lands on the next lane's start -- no
-      // token-by-token tail there (1.3 % more steps here than with the longer groups).
-      reinterpret_cast<uint2 *>(gy)[k] = make_uint2(q.y, q.w);
-    }
-    const uint4 *gs = reinterpret_cast<const uint4 *>(ws.sub + ((size_t)f * 2 + 1) * kSubEntries);
-    for (int k = tid; k < kSubEntries / 2; k += kDecThreads) {
-      const uint4 q = gs[k];
-      reinterpret_cast<uint2 *>(gx + (1 << kLutBits))[k] = make_uint2(q.x, q.z);
-      reinterpret_cast<uint2 *>(gy + (1 << kLutBits))[k] = make_uint2(q.y, q.w);
-    }
-  }
-  __syncthreads();
-  GrpTables tb;
-  tb.grp = nullptr; tb.gx = gx; tb.gy = gy; tb.nd = nd;
-  const int r = r0 + (int)blockIdx.x * kCountRowsW + (tid >> 6);
-  if (r >= r1) return;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  uint32_t *l_start = ws.lane_start + ((size_t)f * g.rows + r) * kDecThreads;
-  uint32_t *l_off = ws.lane_off + ((size_t)f * g.rows + r) * (kDecThreads + kRecHdr);
-  if (lane == 0) l_off[kDecThreads + 2] = 0;   // not usable until proven otherwise
-  const uint32_t pay_off = ws.row_off[(size_t)f * g.rows + r], pay_len = ws.row_len[(size_t)f * g.rows + r];
-  const unsigned long long rem64 = 8ull * pay_len;
-  uint32_t sb = (uint32_t)((rem64 + kDecThreads - 1) / kDecThreads);
-  sb = (sb + 31u) & ~31u;
-  sb = sb < kMinSubBits ? kMinSubBits : sb;
-  // More than one chunk, or nothing to do: the row kernels do it all (k_row_count's rule).
-  if (failed || sb > (uint32_t)g.max_sub || rem64 == 0 || g.row_block >= (1 << 22)) return;
-  const uint32_t rem = (uint32_t)rem64;
-  GReader rd;
-  const uint32_t rel0 = rd.attach(p, sizes[f], 8ull * pay_off);
-  const uint32_t rel_end = rel0 + rem;
-  const uint32_t lead = (uint32_t)g.lead_bits;
-  uint32_t first = rel0;   // where the phase's first lane starts: exact
-  uint32_t base = 0;       // symbols in front of the phase
-  uint32_t rounds = 0;
-  uint32_t *stage = s_stage + (tid >> 6) * kStageAlloc;
-  LdsBits bits;
-  bits.base = lds_addr(stage);
-  auto phases = [&](auto staged_c) {
-  constexpr bool STAGED = decltype(staged_c)::value;
-#pragma unroll 1
-  for (int j = 0; j < kDecThreads / 64; ++j) {
-    const int v = 64 * j + lane;
-    const SubGrid q = sub_grid(rel0, rem, sb, v);
-    const bool active = q.active;
-    const uint32_t pb0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)q.b0);   // the phase's first lane: its nominal start
-    if (pb0 >= rel_end) {   // a phase beyond the payload: its lanes own nothing
-      l_start[v] = rem;
-      l_off[v] = base;
-      continue;
-    }
-    // STAGED: positions below are relative to the dword `w0` of the reader's window, the
-    // first one staged: the one that holds the first bit of the phase's first lane.
-    uint32_t shift = 0;
-    if constexpr (STAGED) {
-      const uint32_t w0 = pb0 >> 5;
-      shift = 32u * w0;
-      wave_lds_sync();   // the walks of the phase before are done with the buffer
-      for (uint32_t k = (uint32_t)lane; 4u * k < kStageWords; k += 64u) {
-        const uint32_t w = w0 + 4u * k;
-        uint4 x;
-        if (w + 3u <= rd.jmax) {
-          const PackedU4 u = *reinterpret_cast<const PackedU4 *>(rd.w + w);
-          x.x = u.x; x.y = u.y; x.z = u.z; x.w = u.w;
-        } else {
-          x.x = rd.ld(w); x.y = rd.ld(w + 1u); x.z = rd.ld(w + 2u); x.w = rd.ld(w + 3u);
-        }
-        // Blocks of 33 (see LdsBits): four dwords of one block, and the block's first dword
-        // once more behind the block before it.
-        uint32_t *d = stage + 4u * k + (k >> 3);
-        d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
-        if ((k & 7u) == 0u && k) d[-1] = x.x;
-      }
-      wave_lds_sync();
-    }
-    auto walk = [&](uint32_t from, uint32_t to, uint32_t *e, uint32_t *c, bool cont) {
-      if constexpr (STAGED) { (void)cont; grp_count_lds(bits, tb, from, to, e, c); }
-      else lean_count<true, GReader, true>(rd, tb, from, to, e, c, cont);
-    };
-    const uint32_t b0 = q.b0 - shift, lim = q.lim - shift, lo0 = rel0 - shift, fst = first - shift;
-    uint32_t start = active ? b0 : rel_end - shift;
-    if (lane == 0 && active) start = fst;
-    // Lead-in (see lean_fixpoint): a boundary of the token chain at or past the nominal
-    // start, found from lead_bits in front of it.
-    bool at_start = false;   // the reader stands at `start`
-    if (lane > 0 && active && lead) {
-      uint32_t from = start - lo0 > lead ? start - lead : lo0;
-      if (from < pb0 - shift) from = pb0 - shift;   // (a lead-in longer than a sub-sequence: not in front of the phase)
-      uint32_t guess, none;
-      walk(from, start, &guess, &none, false);
-      start = guess;
-      at_start = true;
-    }
-    uint32_t endpos = start, cnt = 0;
-    bool dirty = active;
-    // Re-join (see lean_fixpoint): the walk is cut at T = nominal start + kJoinBits; a lane
-    // whose start moves in a later round walks up to T again, and if it arrives at the
-    // same boundary everything behind is what it already has.  A round after the first
-    // then costs the wavefront kJoinBits instead of a whole sub-sequence.
-    uint32_t T = (active ? b0 : rel_end - shift) + kJoinBits;
-    if (T > lim || T < b0) T = lim;
-    uint32_t posT = ~0u, cT = 0;
-    for (;;) {
-      if (dirty) {
-        uint32_t p1, c1;
-        walk(start, T, &p1, &c1, at_start);
-        if (p1 == posT) {
-          cnt = c1 + (cnt - cT);
-        } else {
-          uint32_t c2;
-          walk(p1, lim, &endpos, &c2, start < T || at_start);
-          cnt = c1 + c2;
-        }
-        posT = p1;
-        cT = c1;
-        at_start = false;
-      }
-      // The chain: a lane starts where its left neighbour ended (one DPP move).
-      const uint32_t ns = wave_shr1_dpp(fst, endpos);
-      dirty = active && ns != start;
-      if (active) start = ns;
-      ++rounds;
-      if (!__any(dirty ? 1 : 0)) break;
-    }
-    // Exclusive prefix of the counts (k_row_count's clamp: see row_count_one).
-    const uint32_t c = min(cnt, 0x3fffffu);
-    const uint32_t incl = wave_scan_add_dpp(c);
-    l_start[v] = start + shift - rel0;
-    l_off[v] = base + incl - c;
-    if (v == q.last_active) l_off[kDecThreads + 1] = endpos + shift - rel0;
-    base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    // The next phase starts where this one's last lane ended (a phase of inactive lanes: nowhere).
-    first = (uint32_t)__builtin_amdgcn_readlane((int)(active ? endpos + shift : rel_end), 63);
-  }
-  };
-  if (sb <= kStageSubBits) phases(std::true_type{});
-  else phases(std::false_type{});
-  if (lane == 0) {
-    l_off[kDecThreads] = base;
-    l_off[kDecThreads + 3] = rounds;
-    l_off[kDecThreads + 4] = 0;   // one record per lane (no boundaries inside the lanes' ranges)
-    l_off[kDecThreads + 2] = 3;   // boundaries of the write pass's chain of groups (no fence: the consumer is a later kernel)
-  }
+#include "dec_body_row_count_w.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -4110,10 +3764,14 @@ __global__ __launch_bounds__(256) void k_lres_preview(Geom g, DecWs ws, uint8_t 
 }
 
 // ---------------------------------------------------------------------------
-// k_dec_region: rectangle R = (x, y, w, h) of every frame of the batch at full resolution,
-// h x w x C interleaved bytes per frame.  A workgroup per (column strip, touched block row,
-// frame): the row's count record (k_row_count<false> / k_row_count_w over the touched rows only,
-// every row in one chunk: launch_region),
+// k_dec_region: the window w x h at frame f's own origin (x_f, y_f) (RegionArgs::org) of every
+// frame of the batch at full resolution, h x w x C interleaved bytes per frame.  Frame f touches
+// block rows r0_f = y_f / 8 .. r1_f = ceil((y_f + h) / 8) and tile columns u0_f = x_f / 8 ..
+// u1_f = ceil((x_f + w) / 8); for a fixed w x h these counts differ between frames by at most one.
+// A workgroup per (column strip of sw tiles, touched block row, frame) -- the grid is sized by
+// the batch's largest counts, and a workgroup past its frame's last row or last tile returns
+// first thing: the row's count record (k_region_count / k_region_count_w over the frame's
+// touched rows only, every row in one chunk: launch_region),
 // then a write pass that keeps only the strip's symbols, [C][64][strip tiles] in LDS, then
 // the transform of the strip's tiles and cropped stores.  Nothing of the row's symbols goes
 // to HBM and no tile outside the rectangle is transformed.
@@ -4130,11 +3788,14 @@ __global__ __launch_bounds__(256) void k_lres_preview(Geom g, DecWs ws, uint8_t 
 //   * the payload is read in place, bounded by the row's last dword.
 // ---------------------------------------------------------------------------
 struct RegionArgs {
-  int r0;              // first touched block row (blockIdx.y = row - r0)
-  int u0, u1;          // touched tile columns [u0, u1)
-  int sw;              // tiles per column strip (blockIdx.x = strip)
-  int x, y, w, h;      // the rectangle
+  const int32_t *org;  // frame f's origin (x_f, y_f) at org[2 f], org[2 f + 1] (blockIdx.y = row - r0_f)
+  int sw;              // tiles per column strip (blockIdx.x = strip, from u0_f on)
+  int w, h;            // the window
   uint8_t *out;        // frame f's pixels at out + f * h * w * C
+};
+// One frame's rectangle (transform_store_region's crop).
+struct RegionRect {
+  int x, y, w, h;
 };
 
 // LDS of k_dec_region: decode tables, the row's verdict state, the row tables (DecFrame::row_tabs),
@@ -4238,7 +3899,7 @@ __device__ __forceinline__ bool region_walk(GReader &rd, const GrpTables &t, uin
 __device__ __forceinline__ void transform_store_region(const Geom &g, int sstride, const uint8_t *sym,
                                                        const uint8_t *low, const int16_t *s_unmap,
                                                        const uint8_t *s_shift, const uint32_t *s_shiftp, int ycbcr,
-                                                       int u, int s, int v, const RegionArgs &ra, uint8_t *img,
+                                                       int u, int s, int v, const RegionRect &ra, uint8_t *img,
                                                        bool store_ok) {
   const int cols = g.cols, C = g.C;
   const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
@@ -4311,8 +3972,14 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, co
   const uint8_t *s_shift = smem + L.rowtab + 512;
   const uint32_t *s_shiftp = reinterpret_cast<const uint32_t *>(smem + L.rowtab + 640);
   uint8_t *sym = smem + L.sym;
-  const int tid = threadIdx.x, f = blockIdx.z, r = ra.r0 + (int)blockIdx.y;
-  const int su0 = ra.u0 + (int)blockIdx.x * ra.sw, ww = min(ra.sw, ra.u1 - su0);
+  const int tid = threadIdx.x, f = blockIdx.z;
+  // The frame's own rectangle: its rows and tile columns; a workgroup past either has nothing to do.
+  RegionRect rr;
+  rr.x = ra.org[2 * f]; rr.y = ra.org[2 * f + 1]; rr.w = ra.w; rr.h = ra.h;
+  const int r = rr.y / 8 + (int)blockIdx.y, u1 = (rr.x + rr.w + 7) / 8;
+  const int su0 = rr.x / 8 + (int)blockIdx.x * ra.sw;
+  if (r >= (rr.y + rr.h + 7) / 8 || su0 >= u1) return;
+  const int ww = min(ra.sw, u1 - su0);
   DecFrame *df = ws.frames + f;
   if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
   __syncthreads();
@@ -4396,8 +4063,58 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, co
     const bool in_strip = ul < ww;
     const int uc = in_strip ? ul : ww - 1;
     transform_store_region(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
-                           pair_half(it), r, ra, img, in_strip);
+                           pair_half(it), r, rr, img, in_strip);
   }
+}
+
+// The region decode's per-frame forms of the kernels it shares with the full decode: frame f's
+// touched rows [r0_f, r1_f) come from its origin (org[2 f + 1] = y_f) and the window height h.
+// The grids are sized by the batch's largest row count; a workgroup past its frame's last row
+// returns before it loads anything.  Each includes the body of the full decode's kernel
+// (dec_body_*.inc) behind its own per-frame values of that kernel's parameters: the full decode's
+// kernels keep their code instruction for instruction, and there is one copy of each body.
+__device__ __forceinline__ int region_r0(const int32_t *org, int f) { return org[2 * f + 1] / 8; }
+__device__ __forceinline__ int region_r1(const int32_t *org, int f, int h) { return (org[2 * f + 1] + h + 7) / 8; }
+
+// k_dec_rowwalk stopping at each frame's own r1_f (to the end of the chunk where r1_f is the last row).
+__global__ __launch_bounds__(64) void k_region_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                       const uint32_t *sizes, const int32_t *org, int h) {
+  const int r1_f = region_r1(org, blockIdx.x, h);
+  const int row_end = r1_f == g.rows ? 0x7fffffff : r1_f, resume = 0;
+#include "dec_body_rowwalk.inc"
+}
+
+// k_dec_set_index over a batch: frame f = blockIdx.x sees its own record, size, row tables and index
+// (at index + 2 f rows), rows [r0_f, r1_f) filled.
+__global__ __launch_bounds__(256) void k_region_set_index(Geom g, DecWs ws_all, const uint32_t *index_all,
+                                                          const uint32_t *sizes_all, const int32_t *org, int h) {
+  const int f_ = blockIdx.x;
+  DecWs ws = ws_all;
+  ws.frames += f_;
+  ws.row_off += (size_t)f_ * g.rows;
+  ws.row_len += (size_t)f_ * g.rows;
+  const uint32_t *index = index_all + (size_t)f_ * 2 * g.rows, *sizes = sizes_all + f_;
+  const int r0 = region_r0(org, f_), r1 = region_r1(org, f_, h);
+#include "dec_body_set_index.inc"
+}
+
+// k_row_count<false> over each frame's own rows (rows_per_wg of them per workgroup).
+__global__ __launch_bounds__(kDecThreads, 8) void k_region_count(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                const int32_t *org, int h, int rows_per_wg) {
+  constexpr bool LDSPAY = false;
+  const int r0 = region_r0(org, blockIdx.y), r1 = region_r1(org, blockIdx.y, h);
+  if (r0 + (int)blockIdx.x * rows_per_wg >= r1) return;
+#include "dec_body_row_count.inc"
+}
+
+// k_row_count_w over each frame's own rows.
+__global__ __launch_bounds__(kDecThreads, 8) void k_region_count_w(Geom g, DecWs ws, const uint8_t *packed,
+                                                                  size_t in_stride, const uint32_t *sizes,
+                                                                  const int32_t *org, int h) {
+  const int r0 = region_r0(org, blockIdx.y), r1 = region_r1(org, blockIdx.y, h);
+  if (r0 + (int)blockIdx.x * kCountRowsW >= r1) return;
+#include "dec_body_row_count_w.inc"
 }
 
 // k_region_walk_end: k_dec_rowwalk stopped at row_end = r1 < rows flags a FRES chunk that ends right
@@ -4405,9 +4122,13 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, co
 // the region decode does not look at (region_index accepts such a stream).  For a frame whose parse
 // passed and whose walk says so, the headers of rows 0 .. r1-1 are walked again (only those bytes):
 // where they are whole and the chunk ends exactly behind row r1 - 1, the verdict is withdrawn.
-__global__ void k_region_walk_end(DecWs ws, const uint8_t *packed, size_t in_stride, int r1, int batch) {
+// r1 = r1_f, the frame's own; a frame whose r1_f is the last row walked to the end of the chunk.
+__global__ void k_region_walk_end(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride, const int32_t *org, int h,
+                                  int batch) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= batch) return;
+  const int r1 = region_r1(org, f, h);
+  if (r1 >= g.rows) return;
   DecFrame *df = ws.frames + f;
   if (df->parse_status != 0 || df->walk_status != fmt_err(7, 1) || df->walk_q != 0) return;
   const uint8_t *p = packed + (size_t)f * in_stride;
@@ -4515,41 +4236,50 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
 }
 
 void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                   const uint32_t *d_sizes, const uint32_t *d_row_index, int x, int y, int w, int h, uint8_t *d_out,
-                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds) {
-  constexpr int kWalkAll = 0x7fffffff;
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
+                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
+                   const DecStreams *ds) {
   DecWs ws = ws_in;
-  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_row_count<false>)
-  const int r0 = y / 8, r1 = (y + h + 7) / 8, u0 = x / 8, u1 = (x + w + 7) / 8;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
+  // The batch's largest row and tile counts (the grids) and its touched rows (the count kernels' rule);
+  // for a fixed w x h a frame's counts are within one of these.
+  int nrows = 0, ntiles = 0;
+  bool stop_early = false;   // a frame whose walk stops before the last row
+  long long all_rows = 0;
+  for (int f = 0; f < batch; ++f) {
+    const int x = h_org[2 * f], y = h_org[2 * f + 1];
+    const int r0 = y / 8, r1 = (y + h + 7) / 8, nt = (x + w + 7) / 8 - x / 8;
+    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
+    ntiles = nt > ntiles ? nt : ntiles;
+    stop_early |= r1 < g.rows;
+    all_rows += r1 - r0;
+  }
   const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
   const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
   prof_begin(prof, "memset", stream);
   hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
                      reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
   prof_end(prof, stream);
-  // The row headers up to r1 (all of them for the whole frame's last row: the full decode's verdict),
-  // on the side stream beside k_dec_parse and the LRES chain where there is one (launch_decode's fork:
-  // the serial walk to a row deep in a 16384^2 frame is as long as the LRES chain).
+  // Each frame's row headers up to its r1_f (all of them for the whole frame's last row: the full decode's
+  // verdict), on the side stream beside k_dec_parse and the LRES chain where there is one (launch_decode's
+  // fork: the serial walk to a row deep in a 16384^2 frame is as long as the LRES chain).
   hipStream_t ws_ = ds ? ds->side : stream;
   if (ds) {
     (void)hipEventRecord(ds->ev_fork, stream);
     (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
   }
-  prof_begin(prof, d_row_index ? "k_dec_set_index" : "k_dec_rowwalk", ws_);
+  prof_begin(prof, d_row_index ? "k_region_set_index" : "k_region_rowwalk", ws_);
   if (d_row_index)
-    hipLaunchKernelGGL(k_dec_set_index, dim3(1), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, r0, r1);
+    hipLaunchKernelGGL(k_region_set_index, dim3(batch), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, d_org, h);
   else
-    hipLaunchKernelGGL(k_dec_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes,
-                       r1 == g.rows ? kWalkAll : r1, 0);
+    hipLaunchKernelGGL(k_region_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, d_org, h);
   prof_end(prof, ws_);
   if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
   HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
   if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
-  if (!d_row_index && r1 < g.rows)
-    HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), ws, d_packed, in_stride, r1, batch);
-  const int nrows = r1 - r0;
-  const long long all_rows = (long long)batch * nrows;
+  if (!d_row_index && stop_early)
+    HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), g, ws, d_packed, in_stride, d_org, h, batch);
   const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // (launch_decode's rule)
   // Every touched row gets a record: the count kernels that read the payload in place (k_row_count<true>
   // gives up on rows beyond its LDS staging buffer, 36 KiB -- a 4096-pixel row above q50), and no limit on
@@ -4558,18 +4288,18 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   Geom gc = g;
   gc.max_sub = 0x7fffffff;
   if (count_wave) {
-    HIMG_LAUNCH(k_row_count_w, dim3((nrows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), gc, ws, d_packed,
-                in_stride, d_sizes, r0, r1);
+    HIMG_LAUNCH(k_region_count_w, dim3((nrows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), gc, ws,
+                d_packed, in_stride, d_sizes, d_org, h);
   } else {
     const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
-    HIMG_LAUNCH(k_row_count<false>, dim3((nrows + rpc - 1) / rpc, batch), dim3(kDecThreads), gc, ws, d_packed, in_stride,
-                d_sizes, r0, r1, rpc);
+    HIMG_LAUNCH(k_region_count, dim3((nrows + rpc - 1) / rpc, batch), dim3(kDecThreads), gc, ws, d_packed, in_stride,
+                d_sizes, d_org, h, rpc);
   }
   RegionArgs ra;
-  ra.r0 = r0; ra.u0 = u0; ra.u1 = u1;
-  const int smax = region_strip_tiles(g), nstrip = (u1 - u0 + smax - 1) / smax;
-  ra.sw = (u1 - u0 + nstrip - 1) / nstrip;   // (strips of equal width)
-  ra.x = x; ra.y = y; ra.w = w; ra.h = h; ra.out = d_out;
+  ra.org = d_org;
+  const int smax = region_strip_tiles(g), nstrip = (ntiles + smax - 1) / smax;
+  ra.sw = (ntiles + nstrip - 1) / nstrip;   // (strips of equal width)
+  ra.w = w; ra.h = h; ra.out = d_out;
   prof_begin(prof, "k_dec_region", stream);
   hipLaunchKernelGGL(k_dec_region, dim3(nstrip, nrows, batch), dim3(kDecThreads), region_layout(g.C, ra.sw).total, stream,
                      g, ws, d_packed, in_stride, d_sizes, ra);

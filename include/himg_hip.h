@@ -223,7 +223,7 @@ int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_s
                             const uint32_t *h_sizes, int batch, int width, int height,
                             int num_channels, void *d_out, int32_t *d_status, void *stream);
 
-/* ---- region decode: one rectangle at full resolution --------------------------- */
+/* ---- region decode: rectangles at full resolution ------------------------------ */
 /*
  * A rectangle R = (x, y, w, h) with w, h >= 1, x, y >= 0, x + w <= W and y + h <= H (any other
  * rectangle: HIMG_ERR_ARG).  R touches block rows r0 = y / 8 .. r1 = ceil((y + h) / 8) and tile
@@ -264,7 +264,8 @@ int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, 
 int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
                               int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height,
                               int *channels);
-/* R of every stream of a batch in HBM (one rectangle for the batch): the argument and alignment
+/* R of every stream of a batch in HBM (the same R in every frame; himg_hip_decode_regions_device
+ * below takes an origin per frame): the argument and alignment
  * contract of himg_hip_decode_device, except that d_out holds batch x h x w x C bytes, frame f at
  * f * h * w * C (no alignment asked of a frame's start), and only the bytes used (above) of each
  * stream decide the result. */
@@ -272,6 +273,36 @@ int himg_hip_decode_region_device(himg_hip_ctx *ctx, const void *d_packed, size_
                                   const uint32_t *h_sizes, int batch, int width, int height,
                                   int num_channels, int x, int y, int w, int h, void *d_out,
                                   int32_t *d_status, void *stream);
+/* The window w x h at origin (x_f, y_f) = h_origins[2f], h_origins[2f+1] in frame f of a batch in
+ * HBM: himg_hip_decode_region_device with a rectangle per frame.  h_origins is a HOST array of
+ * 2 x batch values, like h_sizes; it reaches the device with the sizes (no host synchronisation).
+ * Every rectangle is checked on the host before anything is launched: one outside its frame makes
+ * the call return HIMG_ERR_ARG and nothing is written (neither d_out nor d_status).  d_out holds
+ * batch x h x w x C bytes, frame f at f * h * w * C.  Grid limits: batch <= 65535,
+ * batch x C <= 65535, block rows + 1 <= 65535.  Frame f's verdict and bytes used are exactly those
+ * of its own rectangle alone (above): damage its rectangle does not look at, or damage in another
+ * frame, changes neither its status nor its pixels. */
+int himg_hip_decode_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                   const uint32_t *h_sizes, int batch, int width, int height,
+                                   int num_channels, const int32_t *h_origins, int w, int h,
+                                   void *d_out, int32_t *d_status, void *stream);
+/* n host streams, rectangle i = rects[4i .. 4i+3] = {x, y, w, h}; any geometry and window size
+ * per frame.  Frame i's output goes to dst[i] (capacity dst_cap[i] >= w x h x C) and its
+ * widths / heights / channels are set on success.  A frame that fails -- a NULL or bad stream, an
+ * unsupported geometry, a bad rectangle (HIMG_ERR_ARG), a NULL or too-small dst
+ * (HIMG_ERR_CAPACITY), or the decode's verdict -- gets widths[i] = heights[i] = channels[i] = 0;
+ * the other frames go on, and the call returns the first such error.  Frame i's status is the one
+ * himg_hip_decode_region_to gives for its rectangle alone.  Each frame is planned on the host
+ * (himg_hip_region_peek, under the context's HIMG_OPT_FIX_T2) and only its [0, head_bytes) and
+ * [rows_begin, rows_end) are uploaded, with the host's row index.  Frames that share
+ * (W, H, C, w, h) go through one device launch, in the order of their first frame, of at most 256
+ * frames whose streams -- each taking the launch's largest stream size in the staging buffer --
+ * fit in 1 GiB (one frame at least).  A stream the host cannot plan (or of one block row) goes
+ * through himg_hip_decode_region_to's own path, uploaded whole. */
+int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                  const size_t *packed_sizes, int n, const int32_t *rects,
+                                  uint8_t *const *dst, const size_t *dst_cap,
+                                  int *widths, int *heights, int *channels);
 
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
