@@ -101,6 +101,10 @@ def lib():
     L.himg_hip_decode_region_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
     L.himg_hip_decode_regions_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.himg_hip_scaled_size.argtypes = [i32, i32, i32, P(i32), P(i32)]
+    L.himg_hip_decode_scaled_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_scaled_to.argtypes = [vp, vp, sz, i32, vp, sz, P(i32), P(i32), P(i32)]
+    L.himg_hip_decode_scaled_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -412,6 +416,60 @@ class Engine:
                                                   _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_regions_device")
 
+    def decode_scaled(self, packed, scale_log2, out=None):
+        """The picture at 1/2 (scale_log2 = 1) or 1/4 (2) scale (himg_hip_decode_scaled_to) as a
+        (ceil(H/F), ceil(W/F), C) uint8 array, F = 2 ** scale_log2: the decode the format defines
+        at that scale from each tile's lowest-sequency coefficients, not a shrunken decode()."""
+        packed = _as_u8(packed)
+        wo, ho, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+        if (scale_log2 in (1, 2) and
+                lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK):
+            ow, oh = scaled_size(ww.value, hh.value, scale_log2)
+            n = ow * oh * cc.value
+            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
+                out = np.empty(max(n, 1), np.uint8)
+            dst, cap = out.ctypes.data, n
+        rc = lib().himg_hip_decode_scaled_to(self._ctx, packed.ctypes.data, packed.nbytes, int(scale_log2), dst, cap,
+                                             C.byref(wo), C.byref(ho), C.byref(c))
+        self._check(rc, "decode_scaled")
+        return out.ravel()[: ho.value * wo.value * c.value].reshape(ho.value, wo.value, c.value)
+
+    def decode_scaled_batch(self, streams, scale_log2, outs=None):
+        """himg_hip_decode_scaled_batch: several streams at 1/2 or 1/4 scale (frames of one
+        geometry share device launches of up to 256 frames); `outs` (optional) are reusable uint8
+        buffers."""
+        streams = [_as_u8(s_) for s_ in streams]
+        n = len(streams)
+        if outs is None:
+            outs = []
+            for s_ in streams:
+                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+                ok = (scale_log2 in (1, 2) and
+                      lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK)
+                if ok:
+                    ow, oh = scaled_size(ww.value, hh.value, scale_log2)
+                outs.append(np.empty(max(ow * oh * cc.value, 1) if ok else 1, np.uint8))
+        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
+        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        rc = lib().himg_hip_decode_scaled_batch(self._ctx, src, szs, n, int(scale_log2), dst, caps, ws, hs, cs)
+        self._check(rc, "decode_scaled_batch")
+        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+    def decode_scaled_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, scale_log2,
+                             d_out, d_status, stream=0):
+        """himg_hip_decode_scaled_device: the contract of decode_device; d_out holds
+        batch x ceil(H/F) x ceil(W/F) x C bytes, F = 2 ** scale_log2 (frame f at f * oh * ow * C)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_scaled_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch, width,
+                                                 height, channels, int(scale_log2), _ptr(d_out), _ptr(d_status),
+                                                 C.c_void_p(stream))
+        self._check(rc, "decode_scaled_device")
+
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""
         opt = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}[option] if isinstance(option, str) else int(option)
@@ -681,6 +739,16 @@ def preview_peek(packed, avail=None, packed_size=None):
         e.head_bytes = hb.value
         raise e
     return pw.value, ph.value, c.value, hb.value
+
+
+def scaled_size(w, h, scale_log2):
+    """himg_hip_scaled_size (no GPU): (ow, oh) = (ceil(w / F), ceil(h / F)), F = 2 ** scale_log2,
+    scale_log2 1 or 2.  Raises HimgError (HIMG_ERR_ARG) for another scale or a non-positive size."""
+    ow, oh = C.c_int(), C.c_int()
+    rc = lib().himg_hip_scaled_size(int(w), int(h), int(scale_log2), C.byref(ow), C.byref(oh))
+    if rc != 0:
+        raise HimgError(rc, "scaled_size")
+    return ow.value, oh.value
 
 
 class RegionPlan(C.Structure):

@@ -5,10 +5,14 @@
 // the input cannot be read, decoded or the output cannot be written.  The picture
 // is written as binary PGM / PPM / PAM by channel count (the reference writes PNG
 // through FreeImage, which this image does not have).
+// One addition: an optional leading "-s2" / "-s4" writes the picture at 1/2 / 1/4 scale
+// (himg_hip_decode_scaled_to: the decode the format defines at that scale).
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "decoder.h"
+#include "himg_hip.h"
 #include "pnm_io.h"
 
 namespace {
@@ -26,12 +30,44 @@ int main(int argc, const char **argv) {
     printf("Usage: %s image outfile\n", argv[0]);
     return 0;
   }
-  const char *in_path = argv[1], *out_path = argv[2];
+  int scale_log2 = 0;
+  if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
+  else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
+  const char *in_path = argv[scale_log2 ? 2 : 1], *out_path = argv[scale_log2 ? 3 : 2];
 
   std::vector<uint8_t> stream;
   if (!pnm::slurp(in_path, &stream)) return fail("Unable to read file", in_path);
   printf("File size: %zu\n", stream.size());
   fflush(stdout);   // the library reports through std::cout
+
+  if (scale_log2) {
+    himg_hip_ctx *ctx = nullptr;
+    if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
+    pnm::Image picture;
+    int w = 0, h = 0, c = 0;
+    std::vector<uint8_t> pixels;
+    int rc = himg_hip_decode_scaled_to(ctx, stream.data(), stream.size(), scale_log2, nullptr, 0, &w, &h, &c);
+    if (rc == HIMG_ERR_CAPACITY) {
+      size_t n = 0;
+      pixels.resize(static_cast<size_t>(w) * h * c);
+      rc = himg_hip_fetch_last(ctx, pixels.data(), pixels.size(), &n);
+    }
+    if (rc != HIMG_OK) {
+      const char *msg = himg_hip_last_error(ctx);
+      printf("%s%s", msg, (*msg && msg[std::strlen(msg) - 1] == '\n') ? "" : "\n");
+      himg_hip_destroy(ctx);
+      return fail("Unable to decode image.", nullptr);
+    }
+    himg_hip_destroy(ctx);
+    picture.width = w;
+    picture.height = h;
+    picture.channels = c;
+    picture.data.resize(pixels.size());
+    pnm::flip_and_swap(pixels.data(), picture.data.data(), w, h, c);
+    const bool writable = c == 1 || c == 3 || c == 4;
+    if (!writable || !pnm::write(out_path, picture)) return fail("Unable to write file", out_path);
+    return 0;
+  }
 
   himg::Decoder decoder;
   if (!decoder.Decode(stream.data(), static_cast<int>(stream.size()))) return fail("Unable to decode image.", nullptr);

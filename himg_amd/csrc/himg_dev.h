@@ -251,6 +251,17 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    const DecStreams *ds);
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
+// The scaled decode (k_dec_scaled): every frame of the batch at 1 / 2^scale_log2 (1 or 2) of its
+// size from the S x S lowest-sequency coefficients of every tile (S = 8 >> scale_log2; the
+// definition: include/himg_hip.h).  The head phase, the row walk and the count kernels are the
+// full decode's (every row one record, as in launch_region); d_row_index: the host's index of
+// one frame (batch == 1).  batch x ceil(H / F) x ceil(W / F) x C interleaved bytes at d_out.
+// No FRES symbol plane, no quarter records.
+void launch_scaled(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, int scale_log2, uint8_t *d_out,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
+// Widest column strip of the scaled kernel, in tiles (its LDS holds C x S x S segments of a strip).
+int scaled_strip_tiles(const Geom &g, int scale_log2);
 // The row-header walk of one frame alone (row-sharded decode: beside the head phase).
 void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
                          const uint32_t *d_sizes, hipStream_t stream);

@@ -1992,6 +1992,173 @@ extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *c
 }
 
 // ---------------------------------------------------------------------------
+// Scaled decode: the picture at 1/2 and 1/4 scale (kernels_dec.hip, launch_scaled).
+// ---------------------------------------------------------------------------
+extern "C" int himg_hip_scaled_size(int width, int height, int scale_log2, int *ow, int *oh) {
+  if (!ow || !oh || width < 1 || height < 1 || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
+  const int F = 1 << scale_log2;
+  *ow = (int)(((long long)width + F - 1) / F);
+  *oh = (int)(((long long)height + F - 1) / F);
+  return HIMG_OK;
+}
+
+// The device launch behind every scaled entry point.  d_row_index: the host's index (one frame).
+static int scaled_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
+                         int width, int height, int num_channels, int scale_log2, const uint32_t *d_row_index,
+                         void *d_out, int32_t *d_status, void *stream) {
+  Geom g;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  apply_settings(ctx, &g);
+  if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
+    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_dec_ws(ctx, g, batch, false, true);   // (the region decode's workspace: no FRES plane)
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  ctx->last_stream = s;
+  rc = stage_sizes(ctx, h_sizes, batch, s);
+  if (rc) return rc;
+  launch_scaled(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
+                d_row_index, scale_log2, (uint8_t *)d_out, d_status, s, &ctx->prof,
+                ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_scaled_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_sizes, int batch, int width, int height,
+                                             int num_channels, int scale_log2, void *d_out, int32_t *d_status,
+                                             void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  return scaled_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, scale_log2, nullptr, d_out,
+                       d_status, stream);
+}
+
+extern "C" int himg_hip_decode_scaled_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2,
+                                         uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels) {
+  if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  int W = 0, H = 0, C = 0;
+  if (const char *msg = parse_header(packed, packed_size, &W, &H, &C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
+  Geom g;
+  if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  int ow = 0, oh = 0;
+  (void)himg_hip_scaled_size(W, H, scale_log2, &ow, &oh);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  const size_t in_cap = round_up(packed_size + 16, 256);
+  const size_t out_bytes = (size_t)ow * oh * C;
+  const size_t n_idx = 2 * (size_t)g.rows;
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256) ||
+      !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  uint8_t *in = (uint8_t *)ctx->h_in.p;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  // The host walks every row header (the whole frame as a rectangle); a stream it does not index
+  // takes the device walk, which words the verdict.
+  himg_hip_region_plan plan = himg_hip_region_plan();
+  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, 0, 0, W, H, &plan, ctx->hp_index) == HIMG_OK;
+  HIP_TRY(ctx, hipMemsetAsync(in + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
+  HIP_TRY(ctx, hipMemcpyAsync(in, packed, packed_size, hipMemcpyHostToDevice, nullptr));
+  if (indexed) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  int rc = scaled_launch(ctx, in, in_cap, &sz32, 1, W, H, C, scale_log2, indexed ? (const uint32_t *)ctx->h_index.p : nullptr,
+                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
+  if (rc) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffer
+    return rc;
+  }
+  int32_t st = 0;
+  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
+  if (st) return region_status_error(ctx, st);
+  ctx->host_bytes = out_bytes;
+  *width = ow; *height = oh; *channels = C;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                                            int n, int scale_log2, uint8_t *const *dst, const size_t *dst_cap,
+                                            int *widths, int *heights, int *channels) {
+  if (!ctx || !packed || !packed_sizes || !dst || !dst_cap || !widths || !heights || !channels || n < 0)
+    return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;   // (nothing resident for himg_hip_fetch_last, as in himg_hip_decode_batch)
+  int first_err = HIMG_OK;
+  std::vector<int> W(n), H(n), Cc(n), done(n, 0);
+  for (int i = 0; i < n; ++i) {
+    widths[i] = heights[i] = channels[i] = 0;
+    Geom g;
+    int err = HIMG_OK;
+    if (const char *msg = packed[i] ? parse_header(packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i]) : "Not a RIFF HIMG file.\n")
+      err = fail(ctx, HIMG_ERR_FORMAT, msg);
+    else if (!make_geom(W[i], H[i], Cc[i], Cc[i], 1, &g))
+      err = fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+    if (err) {
+      done[i] = 1;
+      if (!first_err) first_err = err;
+    }
+  }
+  // Frames that share a geometry: one launch (in the order of their first frame) of at most
+  // kRegionLaunch frames whose streams, each at the launch's largest size, fit kRegionStageBytes.
+  for (int i0 = 0; i0 < n; ++i0) {
+    if (done[i0]) continue;
+    const int lim = kRegionLaunch < 65535 / Cc[i0] ? kRegionLaunch : 65535 / Cc[i0];
+    std::vector<int> grp;
+    size_t stride = 0;
+    for (int i = i0; i < n && (int)grp.size() < lim; ++i) {
+      if (done[i] || W[i] != W[i0] || H[i] != H[i0] || Cc[i] != Cc[i0]) continue;
+      const size_t si = round_up(packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
+      if (!grp.empty() && s2 * (grp.size() + 1) > kRegionStageBytes) break;
+      stride = s2;
+      grp.push_back(i);
+      done[i] = 1;
+    }
+    const int m = (int)grp.size();
+    int ow = 0, oh = 0;
+    (void)himg_hip_scaled_size(W[i0], H[i0], scale_log2, &ow, &oh);
+    const size_t out_bytes = (size_t)ow * oh * Cc[i0];
+    if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
+        !ctx->h_status.reserve(round_up((size_t)m * 4, 256)))
+      return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+    uint8_t *in = (uint8_t *)ctx->h_in.p;
+    std::vector<uint32_t> sz(m);
+    std::vector<int32_t> st(m);
+    for (int k = 0; k < m; ++k) {
+      const int i = grp[k];
+      const size_t lo = packed_sizes[i] & ~(size_t)15;
+      HIP_TRY(ctx, hipMemsetAsync(in + (size_t)k * stride + lo, 0, stride - lo, nullptr));
+      HIP_TRY(ctx, hipMemcpyAsync(in + (size_t)k * stride, packed[i], packed_sizes[i], hipMemcpyHostToDevice, nullptr));
+      sz[k] = (uint32_t)packed_sizes[i];
+    }
+    int rc = scaled_launch(ctx, in, stride, sz.data(), m, W[i0], H[i0], Cc[i0], scale_log2, nullptr, ctx->h_out.p,
+                           (int32_t *)ctx->h_status.p, nullptr);
+    if (rc) {
+      (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's buffers
+      return rc;
+    }
+    HIP_TRY(ctx, hipMemcpy(st.data(), ctx->h_status.p, (size_t)m * 4, hipMemcpyDeviceToHost));
+    for (int k = 0; k < m; ++k) {
+      const int i = grp[k];
+      int err = HIMG_OK;
+      if (st[k]) err = region_status_error(ctx, st[k]);
+      else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+      if (err) { if (!first_err) first_err = err; continue; }
+      HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
+                                  hipMemcpyDeviceToHost, nullptr));
+      widths[i] = ow; heights[i] = oh; channels[i] = Cc[i0];
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+  }
+  return first_err;
+}
+
+// ---------------------------------------------------------------------------
 // Row-sharded encode of one frame over several GPUs (one context per rank).
 // ---------------------------------------------------------------------------
 extern "C" int himg_hip_shard_stats(himg_hip_ctx *ctx, const void *d_frame_base, int width,

@@ -15,6 +15,9 @@
 //   k_dec_huff, k_tile_inv
 //                     the same two steps through HBM for rows wider than the LDS, and
 //                     the serial LRES fallback
+//   k_dec_region, k_dec_scaled
+//                     a rectangle at full resolution; the picture at 1/2 and 1/4 scale from each
+//                     tile's lowest-sequency coefficients (no counterpart in the reference)
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
 #include "loop_counts.h"
@@ -3849,9 +3852,9 @@ struct RegionWin {
 // EXACT (exact_write_body): the lane in whose range the block completes -- whole groups while the
 // block stays incomplete behind them, then token by token with the reference's end-of-block
 // checks (huffman_dec.cpp:353-354,361-417); *end_bp = where the block became complete.
-template <bool EXACT>
+template <bool EXACT, class WIN = RegionWin>
 __device__ __forceinline__ bool region_walk(GReader &rd, const GrpTables &t, uint32_t bp, uint32_t lim, uint32_t op,
-                                            uint32_t stop, uint32_t out_size, const RegionWin &win, uint32_t *end_bp) {
+                                            uint32_t stop, uint32_t out_size, const WIN &win, uint32_t *end_bp) {
   if (!(bp < lim) || op >= out_size) return true;
   rd.init(bp);
   bool bad = false;
@@ -4149,6 +4152,384 @@ __global__ void k_region_walk_end(Geom g, DecWs ws, const uint8_t *packed, size_
   if (q == end) df->walk_status = 0;
 }
 
+// ---------------------------------------------------------------------------
+// k_dec_scaled<S>: the decode at 1/2 scale (S = 4) and 1/4 scale (S = 2): of every tile the
+// S x S lowest-sequency coefficients, the S-point inverse transform, the low-res part as the
+// rounded mean of F x F boxes (F = 8 / S) of the tile's interpolated low-res block -- the
+// definition is in include/himg_hip.h (himg_hip_decode_scaled_device).  The coefficient scan walks
+// square shells, so what a channel needs of a block row's [C][64][cols] symbols is the channel's
+// first S * S segments.  The kernel is k_dec_region's shape: a workgroup per (column strip, block
+// row, frame); the LDS holds the decode tables, the row tables and C x S * S symbol segments
+// (guard dword, the strip's tiles, at least four guard bytes); the write pass follows the count
+// record and the same verdict:
+//   * a lane whose recorded symbols hold none of the needed ones (scan position below S * S, column
+//     in the strip) does not walk, one that does stops behind its last needed symbol -- unless
+//     the frame's tree has a leaf the reference rejects; the lane that completes the block always
+//     walks its whole range with the reference's end-of-block checks;
+//   * a row without a usable record: lane 0 walks the whole row with those checks;
+//   * the transform: a lane per tile, scalar int32 with the int16 stores of quantize.cpp:153-165
+//     and hadamard.cpp:47-74 at their places (S * S coefficients per plane: 2 x S sums of S);
+//     a lane finishes its tile's S x S pixels -- RGBA: S stores of 4 S bytes, neighbouring lanes
+//     neighbouring tiles, so a wavefront's stores of an output row are 1024 (512) contiguous bytes.
+// A strip holds (64 / (S * S)) x region_strip_tiles' tiles: every width up to 16384 pixels is one
+// strip; wider rows take several, each walking the records again.
+// ---------------------------------------------------------------------------
+struct ScaledArgs {
+  int sw;          // tiles per column strip (blockIdx.x = strip)
+  int ow, oh;      // the output's size, ceil(W / F) x ceil(H / F)
+  uint8_t *out;    // frame f's samples at out + f * oh * ow * C
+};
+
+template <int S>
+__host__ __device__ inline RegionLayout scaled_layout(int C, int sw) {
+  RegionLayout L;
+  uint32_t o = 0;
+  auto carve = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  L.tab = carve((uint32_t)sizeof(LdsTables));
+  L.sh = carve((uint32_t)sizeof(RegionShared));
+  L.rowtab = carve(4u * kRowTabWords);
+  L.seg = (((uint32_t)sw + 3u) & ~3u) + 8u;
+  L.sym = carve(L.seg * (uint32_t)(S * S) * (uint32_t)C);
+  L.total = o;
+  return L;
+}
+
+// The layout when the whole row is one strip (ONE: every width up to 16384 pixels): a channel's
+// S * S needed segments are one contiguous run of the row's symbols, so the LDS keeps them as they
+// lie in the row -- per channel a guard dword, S * S * cols symbols, at least four guard bytes
+// (L.seg: the channel stride) -- and a symbol's address is linear in its position.
+template <int S>
+__host__ __device__ inline RegionLayout scaled_layout_one(int C, int cols) {
+  RegionLayout L;
+  uint32_t o = 0;
+  auto carve = [&](uint32_t bytes) { uint32_t r = o; o += (bytes + 15u) & ~15u; return r; };
+  L.tab = carve((uint32_t)sizeof(LdsTables));
+  L.sh = carve((uint32_t)sizeof(RegionShared));
+  L.rowtab = carve(4u * kRowTabWords);
+  L.seg = (((uint32_t)(S * S) * (uint32_t)cols + 3u) & ~3u) + 8u;
+  L.sym = carve(L.seg * (uint32_t)C);
+  L.total = o;
+  return L;
+}
+
+// ONE: put without a division.  The channel is that of the group's LAST byte (three compares
+// against the channels' first symbols), so a group that starts up to three symbols in front of a
+// channel lands its first bytes on that channel's front guard; a group's bytes behind a channel's
+// needed run land on the tail guard, or inside the run's padding.
+template <int S>
+struct ScaledWinOne {
+  uint32_t base;        // LDS address of channel 0's guard dword
+  uint32_t chan, need, cstride, nch;   // symbols per channel (64 cols), needed ones (S * S cols), LDS channel stride, C
+  __device__ __forceinline__ void put(uint32_t op, uint32_t by) const {
+    const uint32_t q = op + 3u;
+    const uint32_t c = (q >= chan ? 1u : 0u) + (q >= 2u * chan ? 1u : 0u) + (q >= 3u * chan ? 1u : 0u);
+    const uint32_t rel = q - c * chan;   // (position in the channel) + 3
+    if (rel < need + 3u && c < nch) {   // (c == C: the last bytes of a group at the row's end, zeros)
+      const uint32_t a = base + c * cstride + 1u + rel;
+      const unsigned long long v = (unsigned long long)by << (8u * (a & 3u));
+      lds_or32(a & ~3u, (uint32_t)v);
+      lds_or32((a & ~3u) + 4u, (uint32_t)(v >> 32));
+    }
+  }
+};
+
+// RegionWin with only the needed segments kept: segment sj = 64 c + k of the row lives at
+// LDS segment S * S * c + k when k < S * S, and nowhere otherwise.
+template <int S>
+struct ScaledWin {
+  uint32_t base;        // LDS address of segment 0
+  uint32_t cols, u0, ww, seg, nseg;   // nseg = 64 C, the ROW's segments
+  __device__ __forceinline__ void put(uint32_t op, uint32_t by) const {
+    if (by == 0) return;   // (zeros are the clear's)
+    const uint32_t s0 = op / cols;
+    const int c0 = (int)(op - s0 * cols);
+#pragma unroll 1
+    for (uint32_t j = 0; j < 4u; ++j) {
+      const uint32_t sj = s0 + j;
+      const int c = c0 - (int)(j * cols) - (int)u0;   // the group's first byte, relative to the strip
+      if (c0 - (int)(j * cols) < -3 || sj >= nseg) break;
+      if ((sj & 63u) < (uint32_t)(S * S) && c >= -3 && c < (int)ww) {
+        const uint32_t a = base + ((sj >> 6) * (uint32_t)(S * S) + (sj & 63u)) * seg + (uint32_t)(4 + c);
+        const unsigned long long v = (unsigned long long)by << (8u * (a & 3u));
+        lds_or32(a & ~3u, (uint32_t)v);
+        lds_or32((a & ~3u) + 4u, (uint32_t)(v >> 32));
+      }
+    }
+  }
+};
+
+// The last symbol at or before symbol e of the row that the scaled decode reads (scan position
+// below S * S, column in the strip [u0, u0 + ww)); -1: there is none.
+template <int S>
+__device__ __forceinline__ long long scaled_last_needed(uint32_t e, uint32_t cols, uint32_t u0, uint32_t ww) {
+  uint32_t se = e / cols;
+  const uint32_t ce = e - se * cols;
+  if ((se & 63u) < (uint32_t)(S * S)) {
+    if (ce >= u0 + ww) return (long long)se * cols + u0 + ww - 1;
+    if (ce >= u0) return (long long)e;
+    if (se & 63u) se -= 1u;                                   // the needed segment in front of se
+    else if (se >= 64u) se = se - 64u + (uint32_t)(S * S) - 1u;
+    else return -1;
+  } else {
+    se = (se & ~63u) + (uint32_t)(S * S) - 1u;
+  }
+  return (long long)se * cols + u0 + ww - 1;
+}
+
+// The S-point inverse transform of hadamard.cpp:47-74 (inputs S.. zero, every F-th output; >> 3
+// and the int16 store as there).
+template <int S>
+__device__ __forceinline__ void iwht_short(int a[S]) {
+  if (S == 4) {
+    const int p = a[0] + a[1], m = a[0] - a[1], q = a[2] + a[3], n = a[2] - a[3];
+    a[0] = (int)(int16_t)((p + q) >> 3);
+    a[1] = (int)(int16_t)((p - q) >> 3);
+    a[2] = (int)(int16_t)((m - n) >> 3);
+    a[3] = (int)(int16_t)((m + n) >> 3);
+  } else {
+    const int p = a[0] + a[1], m = a[0] - a[1];
+    a[0] = (int)(int16_t)(p >> 3);
+    a[1] = (int)(int16_t)(m >> 3);
+  }
+}
+
+__device__ __forceinline__ void interp9d(int a[9]) {   // downsampled.cpp:116-128
+  a[4] = (a[0] + a[8] + 1) >> 1;
+  a[2] = (a[0] + a[4] + 1) >> 1;
+  a[6] = (a[4] + a[8] + 1) >> 1;
+  a[1] = (a[0] + a[2] + 1) >> 1;
+  a[3] = (a[2] + a[4] + 1) >> 1;
+  a[5] = (a[4] + a[6] + 1) >> 1;
+  a[7] = (a[6] + a[8] + 1) >> 1;
+}
+
+__device__ __forceinline__ void interp9pk(uint32_t a[9]) {   // interp9d on both halves of each register
+  auto avg = [](uint32_t x, uint32_t y) { return ((x + y + 0x00010001u) >> 1) & 0x00ff00ffu; };
+  a[4] = avg(a[0], a[8]);
+  a[2] = avg(a[0], a[4]);
+  a[6] = avg(a[4], a[8]);
+  a[1] = avg(a[0], a[2]);
+  a[3] = avg(a[2], a[4]);
+  a[5] = avg(a[4], a[6]);
+  a[7] = avg(a[6], a[8]);
+}
+
+// One tile at scale S / 8: sym = the tile's symbol in LDS segment 0 (segment (c, k) at
+// c cstride + k sstride), the low-res corners from the frame's planes at tile (u, v), S x S samples
+// per channel to (S u + X, S v + Y) of the ow x oh output, clipped.  scaled_tile_rows: the output rows
+// Y0 .. Y0 + NY - 1 of the tile.
+template <int S, int Y0, int NY>
+__device__ __forceinline__ void scaled_tile_rows(const Geom &g, int sstride, int cstride, const uint8_t *sym, const uint8_t *low,
+                                                  const int16_t *s_unmap, const uint8_t *s_shift, int ycbcr, int u,
+                                                  int v, const ScaledArgs &sa, uint8_t *img) {
+  constexpr int F = 8 / S, LG = S == 4 ? 1 : 2;
+  const int cols = g.cols, C = g.C;
+  const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
+  uint32_t q[NY * S];   // [(Y - Y0) * S + X]: the pixel's channels in bytes 0..3
+#pragma unroll
+  for (int i = 0; i < NY * S; ++i) q[i] = 0u;
+#pragma unroll 1
+  for (int c = 0; c < C; ++c) {   // (not unrolled: four planes' loads in flight at once cost registers)
+    const uint8_t *m = low + (size_t)c * g.rows * cols;
+    const int chroma = (ycbcr && (c == 1 || c == 2)) ? 1 : 0;  // decoder.cpp:376
+    const uint8_t *sh = s_shift + chroma * 64;
+    // quantize.cpp:153-165 on the top-left S x S: d[j][i], row j, column i.
+    int d[S][S];
+#pragma unroll
+    for (int k = 0; k < S * S; ++k) {
+      const int pos = kScanD[k], j = pos >> 3, i = pos & 7;
+      const uint32_t code = sym[(size_t)c * cstride + (size_t)k * sstride];
+      d[j][i] = (int)(int16_t)(uint16_t)((uint32_t)(int)s_unmap[code] << sh[pos]);
+    }
+#pragma unroll
+    for (int j = 0; j < S; ++j) iwht_short<S>(d[j]);   // rows: d[j][X]
+    int p[S][S];
+#pragma unroll
+    for (int X = 0; X < S; ++X) {
+      int col[S];
+#pragma unroll
+      for (int j = 0; j < S; ++j) col[j] = d[j][X];
+      iwht_short<S>(col);
+#pragma unroll
+      for (int Y = 0; Y < S; ++Y) p[Y][X] = col[Y];
+    }
+    // The low-res block (downsampled.cpp:130-169) and its F x F box means, an output row at a time.
+    // The left and the right column are interpolated together, one in each half of a register
+    // (values below 256: the bit a half's sum hands down is masked away).
+    uint32_t lr[9];
+    lr[0] = (uint32_t)m[(size_t)v * cols + u] | ((uint32_t)m[(size_t)v * cols + u2] << 16);
+    lr[8] = (uint32_t)m[(size_t)v2 * cols + u] | ((uint32_t)m[(size_t)v2 * cols + u2] << 16);
+    interp9pk(lr);
+#pragma unroll
+    for (int Y = Y0; Y < Y0 + NY; ++Y) {
+      int acc[S];
+#pragma unroll
+      for (int X = 0; X < S; ++X) acc[X] = F * F / 2;
+#pragma unroll
+      for (int y = Y * F; y < Y * F + F; ++y) {
+        int a[9];
+        a[0] = (int)(lr[y] & 0xffffu);
+        a[8] = (int)(lr[y] >> 16);
+        interp9d(a);
+#pragma unroll
+        for (int x = 0; x < 8; ++x) acc[x / F] += a[x];
+      }
+#pragma unroll
+      for (int X = 0; X < S; ++X) {
+        const int smp = clamp255d((int)(int16_t)(p[Y][X] + (acc[X] >> (2 * LG))));   // decoder.cpp:36-75
+        q[(Y - Y0) * S + X] |= (uint32_t)smp << (8 * c);
+      }
+    }
+  }
+  if (ycbcr) {
+#pragma unroll
+    for (int i = 0; i < NY * S; ++i) {
+      uint32_t c0 = q[i] & 255u, c1 = (q[i] >> 8) & 255u, c2 = (q[i] >> 16) & 255u;
+      ycc_to_rgb(c0, c1, c2);   // ycbcr.cpp:54-82
+      q[i] = (q[i] & 0xff000000u) | c0 | (c1 << 8) | (c2 << 16);
+    }
+  }
+  const int x0 = S * u;
+#pragma unroll
+  for (int Y = Y0; Y < Y0 + NY; ++Y) {
+    const int py = S * v + Y;
+    if (py >= sa.oh) break;
+    const uint32_t *qr = q + (Y - Y0) * S;
+    uint8_t *d = img + ((size_t)py * sa.ow + x0) * C;
+    if (C == 4) {
+      if (x0 + S <= sa.ow && ((uintptr_t)d & (uintptr_t)(4 * S - 1)) == 0) {
+        if (S == 4) *reinterpret_cast<uint4 *>(d) = make_uint4(qr[0], qr[1], qr[2], qr[3]);
+        else *reinterpret_cast<uint2 *>(d) = make_uint2(qr[0], qr[1]);
+      } else {
+#pragma unroll
+        for (int X = 0; X < S; ++X)
+          if (x0 + X < sa.ow) reinterpret_cast<uint32_t *>(d)[X] = qr[X];   // (4 ow per row: dword aligned)
+      }
+    } else {
+#pragma unroll
+      for (int X = 0; X < S; ++X) {
+        if (x0 + X >= sa.ow) break;
+        d[X * C] = (uint8_t)qr[X];
+        if (C > 1) d[X * C + 1] = (uint8_t)(qr[X] >> 8);
+        if (C > 2) d[X * C + 2] = (uint8_t)(qr[X] >> 16);
+      }
+    }
+  }
+}
+
+// S = 4: the tile in two halves of two output rows, each gathering and transforming the tile again
+// (sixteen symbols per plane) -- one pass keeps 16 + 16 + 16 values live beside the low-res block and
+// does not fit the 64 registers that let two workgroups share a CU.
+template <int S>
+__device__ __forceinline__ void scaled_tile_store(const Geom &g, int sstride, int cstride, const uint8_t *sym, const uint8_t *low,
+                                                  const int16_t *s_unmap, const uint8_t *s_shift, int ycbcr, int u,
+                                                  int v, const ScaledArgs &sa, uint8_t *img) {
+  if (S == 4) {
+    scaled_tile_rows<S, 0, S / 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+    asm volatile("" ::: "memory");   // (the second half reads the symbols again)
+    scaled_tile_rows<S, S / 2, S / 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+  } else {
+    scaled_tile_rows<S, 0, S>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+  }
+}
+
+template <int S, bool ONE>
+__global__ __launch_bounds__(kDecThreads, 8) void k_dec_scaled(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                           const uint32_t *sizes, ScaledArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const RegionLayout L = ONE ? scaled_layout_one<S>(g.C, g.cols) : scaled_layout<S>(g.C, sa.sw);
+  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
+  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
+  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift: contiguous
+  const uint8_t *s_shift = smem + L.rowtab + 512;
+  uint8_t *sym = smem + L.sym;
+  const int tid = threadIdx.x, f = blockIdx.z, r = blockIdx.y;
+  const int su0 = (int)blockIdx.x * sa.sw;
+  if (su0 >= g.cols) return;
+  const int ww = min(sa.sw, g.cols - su0);
+  DecFrame *df = ws.frames + f;
+  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
+  __syncthreads();
+  if (sh->flag) return;
+  load_dec_tables(ws, df, f, 1, &T);
+  if (tid < kRowTabWords / 4)
+    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
+  const uint32_t nsym16 = (L.seg * (ONE ? 1u : (uint32_t)(S * S)) * (uint32_t)g.C + 15u) / 16u;
+  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
+  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
+  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
+  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+
+  const size_t ri = (size_t)f * g.rows + (size_t)r;
+  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
+  const GrpTables tb = tables_of(&T);
+  typename std::conditional<ONE, ScaledWinOne<S>, ScaledWin<S>>::type win;
+  if constexpr (ONE) {
+    win.base = lds_addr(sym); win.chan = 64u * (uint32_t)g.cols; win.need = (uint32_t)(S * S) * (uint32_t)g.cols;
+    win.cstride = L.seg; win.nch = (uint32_t)g.C;
+  } else {
+    win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
+    win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
+  }
+  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
+  const uint32_t valid = po[kDecThreads + 2];
+  const bool rec = valid != 0 && pay_len != 0;
+  const unsigned long long P1 = 8ull * pay_len;
+  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
+  bool ok = true;
+  if (pay_len != 0) {
+    GReader rd;
+    rel0 = rd.attach(p, end, 8ull * pay_off);
+    const uint32_t rel_end = rel0 + (uint32_t)P1;
+    if (rec) {
+      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
+      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
+      tot = po[kDecThreads];
+      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
+      const uint32_t cnt = nxt - off;
+      if (off + cnt < out_size) {
+        // The lane's last needed symbol (stop), if its symbols [off, off + cnt) hold one.
+        uint32_t stop = ~0u;
+        bool walk = true;
+        if (!strict) {
+          const long long last = cnt ? scaled_last_needed<S>(off + cnt - 1u, (uint32_t)g.cols, (uint32_t)su0, (uint32_t)ww) : -1;
+          walk = cnt != 0 && last >= (long long)off;
+          stop = walk ? (uint32_t)last : 0u;
+        }
+        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
+      } else if (off < out_size) {
+        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
+      }
+    } else if (tid == 0) {
+      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
+    }
+  }
+  if (!ok) sh->err = 1;
+  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
+  __syncthreads();
+  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
+  int bad = sh->err || pay_len == 0;
+  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
+  const unsigned long long E = sh->endbit;
+  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
+  if (bad) {
+    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+    return;
+  }
+  // ---- the strip's tiles: a lane per tile ----
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  uint8_t *img = sa.out + (size_t)f * ((size_t)sa.oh * sa.ow * g.C);
+  const int ycbcr = df->ycbcr;
+#pragma unroll 1
+  for (int ul = tid; ul < ww; ul += kDecThreads)
+    scaled_tile_store<S>(g, ONE ? g.cols : (int)L.seg, ONE ? (int)L.seg : S * S * (int)L.seg, sym + 4 + ul, low, s_unmap,
+                         s_shift, ycbcr, su0 + ul, r, sa, img);
+}
+
 #define HIMG_LAUNCH(name, grid, block, ...)                    \
   do {                                                         \
     prof_begin(prof, #name, stream);                           \
@@ -4186,12 +4567,27 @@ hipError_t dec_set_kernel_attrs() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(kLdsMax - fa.sharedSizeBytes));
+  const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
+                          reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>)};
+  for (const void *k : scaled) {
+    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, k);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsMax - fa.sharedSizeBytes));
+  }
   return e;
 }
 
 int region_strip_tiles(const Geom &g) {
   const uint32_t fixed = region_layout(g.C, 0).total - region_layout(g.C, 0).seg * 64u * (uint32_t)g.C;
   const uint32_t seg = (kLdsMax - 1024u - fixed) / (64u * (uint32_t)g.C) & ~3u;   // (room for the kernel's static LDS)
+  return (int)(seg - 8u);
+}
+
+int scaled_strip_tiles(const Geom &g, int scale_log2) {
+  const uint32_t nseg = (scale_log2 == 1 ? 16u : 4u) * (uint32_t)g.C;
+  const RegionLayout L0 = scale_log2 == 1 ? scaled_layout<4>(g.C, 0) : scaled_layout<2>(g.C, 0);
+  const uint32_t fixed = L0.total - L0.seg * nseg;
+  const uint32_t seg = (kLdsMax - 1024u - fixed) / nseg & ~3u;   // (room for the kernel's static LDS)
   return (int)(seg - 8u);
 }
 
@@ -4303,6 +4699,84 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   prof_begin(prof, "k_dec_region", stream);
   hipLaunchKernelGGL(k_dec_region, dim3(nstrip, nrows, batch), dim3(kDecThreads), region_layout(g.C, ra.sw).total, stream,
                      g, ws, d_packed, in_stride, d_sizes, ra);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, int scale_log2, uint8_t *d_out,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  constexpr int kWalkAll = 0x7fffffff;
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_row_count<false>)
+  const int F = 1 << scale_log2;
+  const long long all_rows = (long long)batch * g.rows;
+  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
+  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
+  prof_begin(prof, "memset", stream);
+  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
+                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
+  prof_end(prof, stream);
+  // launch_decode's order: the whole row index on the side stream beside k_dec_parse, the counts
+  // behind both on the side stream beside the LRES chain, the row kernel behind the join.
+  hipStream_t side = ds ? ds->side : stream;
+  auto walk = [&](hipStream_t s) {
+    prof_begin(prof, d_row_index ? "k_dec_set_index" : "k_dec_rowwalk", s);
+    if (d_row_index)   // (one frame: himg_hip_decode_scaled_to)
+      hipLaunchKernelGGL(k_dec_set_index, dim3(1), dim3(256), 0, s, g, ws, d_row_index, d_sizes, 0, g.rows);
+    else
+      hipLaunchKernelGGL(k_dec_rowwalk, dim3(batch), dim3(64), 0, s, g, ws, d_packed, in_stride, d_sizes, kWalkAll, 0);
+    prof_end(prof, s);
+  };
+  // Every row gets one record: the count kernels that read the payload in place, and no limit on a
+  // lane's share of the row (launch_region's reasons).
+  Geom gc = g;
+  gc.max_sub = 0x7fffffff;
+  const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // (launch_decode's rule)
+  auto row_count = [&](hipStream_t s) {
+    prof_begin(prof, "k_row_count", s);
+    if (count_wave) {
+      hipLaunchKernelGGL(k_row_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s, gc,
+                         ws, d_packed, in_stride, d_sizes, 0, g.rows);
+    } else {
+      const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
+      hipLaunchKernelGGL(k_row_count<false>, dim3((g.rows + rpc - 1) / rpc, batch), dim3(kDecThreads), 0, s, gc, ws,
+                         d_packed, in_stride, d_sizes, 0, g.rows, rpc);
+    }
+    prof_end(prof, s);
+  };
+  if (ds) {
+    (void)hipEventRecord(ds->ev_fork, stream);
+    (void)hipStreamWaitEvent(side, ds->ev_fork, 0);
+    walk(side);
+  }
+  HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
+  if (ds) {
+    (void)hipEventRecord(ds->ev_fork, stream);
+    (void)hipStreamWaitEvent(side, ds->ev_fork, 0);
+    row_count(side);
+    (void)hipEventRecord(ds->ev_cnt[0], side);
+  } else {
+    walk(stream);
+  }
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
+  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_cnt[0], 0);
+  else row_count(stream);
+  ScaledArgs sa;
+  const uint32_t lds_one = scale_log2 == 1 ? scaled_layout_one<4>(g.C, g.cols).total : scaled_layout_one<2>(g.C, g.cols).total;
+  const bool one = lds_one <= kLdsMax - 1024u;   // (room for the kernel's static LDS)
+  const int smax = scaled_strip_tiles(g, scale_log2), nstrip = one ? 1 : (g.cols + smax - 1) / smax;
+  sa.sw = (g.cols + nstrip - 1) / nstrip;   // (strips of equal width)
+  sa.ow = (g.W + F - 1) / F; sa.oh = (g.H + F - 1) / F; sa.out = d_out;
+  prof_begin(prof, "k_dec_scaled", stream);
+#define HIMG_SCALED_LAUNCH(S_, ONE_, LDS_)                                                                        \
+  hipLaunchKernelGGL((k_dec_scaled<S_, ONE_>), dim3(nstrip, g.rows, batch), dim3(kDecThreads), LDS_, stream, g, ws, \
+                     d_packed, in_stride, d_sizes, sa)
+  if (scale_log2 == 1 && one) HIMG_SCALED_LAUNCH(4, true, lds_one);
+  else if (scale_log2 == 1) HIMG_SCALED_LAUNCH(4, false, scaled_layout<4>(g.C, sa.sw).total);
+  else if (one) HIMG_SCALED_LAUNCH(2, true, lds_one);
+  else HIMG_SCALED_LAUNCH(2, false, scaled_layout<2>(g.C, sa.sw).total);
+#undef HIMG_SCALED_LAUNCH
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }

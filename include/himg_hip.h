@@ -304,6 +304,57 @@ int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packe
                                   uint8_t *const *dst, const size_t *dst_cap,
                                   int *widths, int *heights, int *channels);
 
+/* ---- scaled decode: the picture at 1/2 and 1/4 scale ----------------------------- */
+/*
+ * scale_log2 = 1 or 2: F = 2^scale_log2 pixels per output sample and side, S = 8 / F coefficients
+ * per tile and side.  Output: oh = ceil(H / F) rows x ow = ceil(W / F) columns x C channels,
+ * interleaved u8, tightly packed, channels in the order of the full decode.  Tile (u, v)
+ * contributes the samples (X, Y), 0 <= X, Y < S, at (S u + X, S v + Y), dropped outside ow x oh.
+ * The transform is the sequency-ordered 8-point Walsh-Hadamard (hadamard.cpp:47-103) and the
+ * coefficient scan walks square shells (common.cpp:13-22), so the mean of every F x F box of a
+ * tile's inverse transform is, in exact arithmetic, the S-point inverse transform of the tile's
+ * top-left S x S coefficients -- the first S * S scan positions of each channel.  The decode the
+ * format defines at this scale, per tile and channel, with the decoder's own FMAP table and shift
+ * table per channel (decoder.cpp:376):
+ *   1. d[j][i] = (int16)(unmap(sym) << shift[8 j + i]) for 0 <= i, j < S (quantize.cpp:153-165
+ *      restricted to the top-left S x S, the int16 wrap included);
+ *   2. rows, then columns: t = (int16)((sum_i d[j][i] w_i(X)) >> 3), p = (int16)((sum_j t[j][X]
+ *      w_j(Y)) >> 3), w the S-point sequency-ordered Walsh matrix (S = 4: ++++, ++--, +--+, +-+-;
+ *      S = 2: ++, +-): hadamard.cpp:47-74 with its inputs S.. zero and every F-th output;
+ *   3. L[Y][X] = (the sum of the F x F box of the tile's interpolated low-res block
+ *      (downsampled.cpp:116-169) + F F / 2) >> (2 scale_log2);
+ *   4. sample = clamp8((int16)(p + L)) (decoder.cpp:36-75), then YCbCr::YCbCrToRGB
+ *      (ycbcr.cpp:54-82) per output pixel where FRMT's colour space is 1 and C >= 3.
+ * This is NOT the box-downsample of himg_hip_decode's bytes: the roundings and the clamp come in a
+ * different order.  How close the two are is measured in tests/test_scaled_host.py
+ * (profiles/scaled_closeness.json).
+ * Verdict: exactly himg_hip_decode's, for every stream, under either HIMG_OPT_FIX_T2 setting, with
+ * the same himg_hip_last_error wording (decoder.cpp:95-135,298-426): the whole stream is looked at.
+ */
+/* Host only, no GPU.  HIMG_ERR_ARG for a scale other than 1 or 2 or a non-positive size. */
+int himg_hip_scaled_size(int width, int height, int scale_log2, int *ow, int *oh);
+/* Streams of a batch in HBM: the argument and alignment contract of himg_hip_decode_device, except
+ * that d_out holds batch x oh x ow x C bytes, frame f at f * oh * ow * C (no alignment asked of a
+ * frame's start).  Asynchronous, no host synchronisation.  Stands in for Decoder::Decode
+ * (decoder.cpp:95-135) followed by a shrink. */
+int himg_hip_decode_scaled_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                  const uint32_t *h_sizes, int batch, int width, int height,
+                                  int num_channels, int scale_log2, void *d_out, int32_t *d_status,
+                                  void *stream);
+/* One host stream into caller-owned host memory; the capacity protocol of himg_hip_decode_to
+ * (HIMG_ERR_CAPACITY with *width = ow, *height = oh, *channels = C set; himg_hip_fetch_last copies
+ * the resident result).  The row index comes from the host (himg_hip_index_host's walk) where the
+ * host can build it, as in himg_hip_decode_to. */
+int himg_hip_decode_scaled_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2,
+                              uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels);
+/* n host streams, the semantics of himg_hip_decode_batch: geometry per frame from FRMT, a frame
+ * that fails (or whose dst is NULL or too small) gets widths[i] = 0 and does not stop the others,
+ * the return value is the first error.  Frames that share a geometry go through one device launch
+ * of up to 256 frames whose streams fit 1 GiB of staging; more take several launches. */
+int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                                 int n, int scale_log2, uint8_t *const *dst, const size_t *dst_cap,
+                                 int *widths, int *heights, int *channels);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
