@@ -105,6 +105,10 @@ def lib():
     L.himg_hip_decode_scaled_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_scaled_to.argtypes = [vp, vp, sz, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_scaled_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_scaled_region_peek.argtypes = [vp, sz, i32, i32, i32, i32, i32, i32, vp]
+    L.himg_hip_decode_scaled_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
+    L.himg_hip_decode_scaled_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_scaled_regions_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp]
     L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
@@ -470,6 +474,64 @@ class Engine:
                                                  C.c_void_p(stream))
         self._check(rc, "decode_scaled_device")
 
+    def decode_scaled_region(self, packed, scale_log2, x, y, w, h, out=None):
+        """Rectangle (x, y, w, h) of the picture at 1/2 (scale_log2 = 1) or 1/4 (2) scale, in that
+        picture's coordinates (himg_hip_decode_scaled_region_to), as an (h, w, C) uint8 array: sample
+        (i, j) is sample (y + i, x + j) of decode_scaled().  Only the stream's head and the block
+        rows the rectangle touches are uploaded (scaled_region_peek)."""
+        packed = _as_u8(packed)
+        wo, ho, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+        if lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK:
+            n = max(int(w), 0) * max(int(h), 0) * cc.value
+            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
+                out = np.empty(max(n, 1), np.uint8)
+            dst, cap = out.ctypes.data, n
+        rc = lib().himg_hip_decode_scaled_region_to(self._ctx, packed.ctypes.data, packed.nbytes, int(scale_log2), int(x),
+                                                    int(y), int(w), int(h), dst, cap, C.byref(wo), C.byref(ho),
+                                                    C.byref(c))
+        self._check(rc, "decode_scaled_region")
+        return out.ravel()[: ho.value * wo.value * c.value].reshape(ho.value, wo.value, c.value)
+
+    def decode_scaled_regions(self, streams, scale_log2, rects, outs=None):
+        """himg_hip_decode_scaled_regions_batch: rectangle rects[i] = (x, y, w, h) of stream i's
+        picture at 1/2 or 1/4 scale, as one (h_i, w_i, C_i) uint8 array per frame (frames that share
+        the geometry and the window size share device launches of up to 256 frames; only each
+        stream's head and the block rows its rectangle touches are uploaded).  `outs` (optional) are
+        reusable uint8 buffers."""
+        streams = [_as_u8(s_) for s_ in streams]
+        n = len(streams)
+        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
+        if outs is None:
+            outs = []
+            for s_, (_, _, w, h) in zip(streams, rc_):
+                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
+                ok = lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK
+                outs.append(np.empty(max(max(int(w), 0) * max(int(h), 0) * cc.value, 1) if ok else 1, np.uint8))
+        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
+        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        rc = lib().himg_hip_decode_scaled_regions_batch(self._ctx, src, szs, n, int(scale_log2), rc_.ctypes.data, dst,
+                                                        caps, ws, hs, cs)
+        self._check(rc, "decode_scaled_regions")
+        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+    def decode_scaled_regions_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, scale_log2,
+                                     origins, w, h, d_out, d_status, stream=0):
+        """himg_hip_decode_scaled_regions_device: the contract of decode_regions_device at a scale --
+        the window w x h at origin (x_f, y_f) = origins[f] of frame f's scaled picture (origins:
+        (batch, 2) int32, on the host); d_out holds batch x h x w x C bytes (frame f at f * h * w * C)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_decode_scaled_regions_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch,
+                                                         width, height, channels, int(scale_log2), org.ctypes.data,
+                                                         int(w), int(h), _ptr(d_out), _ptr(d_status),
+                                                         C.c_void_p(stream))
+        self._check(rc, "decode_scaled_regions_device")
+
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""
         opt = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}[option] if isinstance(option, str) else int(option)
@@ -767,6 +829,20 @@ def region_peek(packed, x, y, w, h, fix_t2=False):
                                     C.byref(plan))
     if rc != 0:
         raise HimgError(rc, "region_peek")
+    return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
+
+
+def scaled_region_peek(packed, scale_log2, x, y, w, h, fix_t2=False):
+    """himg_hip_scaled_region_peek (no GPU): the plan of rectangle (x, y, w, h) of the picture at
+    1/2 (scale_log2 = 1) or 1/4 (2) scale, as region_peek's dict: it is region_peek of the
+    full-resolution rectangle (F x, F y, min(F w, W - F x), min(F h, H - F y)), F = 2 ** scale_log2.
+    Raises HimgError (HIMG_ERR_ARG for a bad rectangle or another scale, else as region_peek)."""
+    a = _as_u8(packed)
+    plan = RegionPlan()
+    rc = lib().himg_hip_scaled_region_peek(a.ctypes.data, a.nbytes, 1 if fix_t2 else 0, int(scale_log2), int(x),
+                                           int(y), int(w), int(h), C.byref(plan))
+    if rc != 0:
+        raise HimgError(rc, "scaled_region_peek")
     return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
 
 

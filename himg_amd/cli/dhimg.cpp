@@ -7,6 +7,11 @@
 // through FreeImage, which this image does not have).
 // One addition: an optional leading "-s2" / "-s4" writes the picture at 1/2 / 1/4 scale
 // (himg_hip_decode_scaled_to: the decode the format defines at that scale).
+// Another: an optional "-r x,y,w,h" behind it writes only that rectangle -- of the scaled picture
+// with a scale (himg_hip_decode_scaled_region_to), of the full-resolution picture on its own
+// (himg_hip_decode_region_to).  The rectangle is in the coordinates of the picture as the decoder
+// returns it (row 0 = the first decoded row); the window then goes through the same row flip
+// and channel swap as a whole picture.  A malformed rectangle is a bad argument (usage, exit 0).
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -33,20 +38,36 @@ int main(int argc, const char **argv) {
   int scale_log2 = 0;
   if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
   else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
-  const char *in_path = argv[scale_log2 ? 2 : 1], *out_path = argv[scale_log2 ? 3 : 2];
+  int arg = scale_log2 ? 2 : 1;
+  bool region = false;
+  int rx = 0, ry = 0, rw = 0, rh = 0;
+  if (argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
+    char tail = 0;
+    if (std::sscanf(argv[arg + 1], "%d,%d,%d,%d%c", &rx, &ry, &rw, &rh, &tail) != 4) {
+      printf("Usage: %s image outfile\n", argv[0]);
+      return 0;
+    }
+    region = true;
+    arg += 2;
+  }
+  const char *in_path = argv[arg], *out_path = argv[arg + 1];
 
   std::vector<uint8_t> stream;
   if (!pnm::slurp(in_path, &stream)) return fail("Unable to read file", in_path);
   printf("File size: %zu\n", stream.size());
   fflush(stdout);   // the library reports through std::cout
 
-  if (scale_log2) {
+  if (scale_log2 || region) {
     himg_hip_ctx *ctx = nullptr;
     if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
     pnm::Image picture;
     int w = 0, h = 0, c = 0;
     std::vector<uint8_t> pixels;
-    int rc = himg_hip_decode_scaled_to(ctx, stream.data(), stream.size(), scale_log2, nullptr, 0, &w, &h, &c);
+    int rc;
+    if (!region) rc = himg_hip_decode_scaled_to(ctx, stream.data(), stream.size(), scale_log2, nullptr, 0, &w, &h, &c);
+    else if (scale_log2)
+      rc = himg_hip_decode_scaled_region_to(ctx, stream.data(), stream.size(), scale_log2, rx, ry, rw, rh, nullptr, 0, &w, &h, &c);
+    else rc = himg_hip_decode_region_to(ctx, stream.data(), stream.size(), rx, ry, rw, rh, nullptr, 0, &w, &h, &c);
     if (rc == HIMG_ERR_CAPACITY) {
       size_t n = 0;
       pixels.resize(static_cast<size_t>(w) * h * c);

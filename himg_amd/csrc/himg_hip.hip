@@ -1665,6 +1665,20 @@ static bool region_ok(int W, int H, int x, int y, int w, int h) {
   return w >= 1 && h >= 1 && x >= 0 && y >= 0 && (long long)x + w <= W && (long long)y + h <= H;
 }
 
+// A rectangle R of the picture at scale 2^-sl (sl = 0: the full-resolution picture, sl = 1, 2: the
+// scaled decode's, ceil(W / F) x ceil(H / F)): false when R does not lie inside it.  up[4]: the
+// full-resolution rectangle R covers, (F x, F y, min(F w, W - F x), min(F h, H - F y)) -- the one
+// whose block rows, verdict and bytes used are R's.
+static bool rect_up(int W, int H, int sl, int x, int y, int w, int h, int up[4]) {
+  const int F = 1 << sl;
+  const int ow = (int)(((long long)W + F - 1) / F), oh = (int)(((long long)H + F - 1) / F);
+  if (!region_ok(ow, oh, x, y, w, h)) return false;
+  up[0] = F * x; up[1] = F * y;
+  up[2] = (long long)F * w < W - up[0] ? F * w : W - up[0];
+  up[3] = (long long)F * h < H - up[1] ? F * h : H - up[1];
+  return true;
+}
+
 // himg_hip_index_host bounded at the rectangle's last block row: the chunk search, the length of
 // the FRES tree, the row headers of rows 0 .. row1-1 (to the end of the chunk when row1 is the
 // last row: the reference's Init walks them all).  row_index (2 x rows words, or nullptr): the
@@ -1742,14 +1756,23 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
 // The device launch behind every region entry point: the window w x h at frame f's origin
 // (h_org[2 f], h_org[2 f + 1]); every origin is checked before anything is launched.
 // d_row_index: the host's index, 2 x rows words per frame (rows r0_f .. r1_f - 1 filled).
+// scale_log2 = 1, 2: the window and the origins are those of the scaled picture (launch_scaled_region);
+// what reaches the device are the origins of the full-resolution rectangles the windows cover.
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                          int width, int height, int num_channels, const int32_t *h_org, int w, int h,
-                         const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream) {
+                         const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0) {
   Geom g;
+  if (scale_log2 < 0 || scale_log2 > 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
   if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
   apply_settings(ctx, &g);
-  for (int f = 0; f < batch; ++f)
-    if (!region_ok(width, height, h_org[2 * f], h_org[2 * f + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  std::vector<int32_t> up_org;
+  if (scale_log2) up_org.resize(2 * (size_t)batch);
+  for (int f = 0; f < batch; ++f) {
+    int up[4];
+    if (!rect_up(width, height, scale_log2, h_org[2 * f], h_org[2 * f + 1], w, h, up)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+    if (scale_log2) { up_org[2 * f] = up[0]; up_org[2 * f + 1] = up[1]; }
+  }
+  if (scale_log2) h_org = up_org.data();
   if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
   if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
     return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
@@ -1761,9 +1784,14 @@ static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stri
   rc = stage_sizes(ctx, h_sizes, batch, s, h_org);   // (the origins ride with the sizes: no extra copy, no wait)
   if (rc) return rc;
   const uint32_t *d_sizes = (const uint32_t *)ctx->d_sizes.p;
-  launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
-                (const int32_t *)(d_sizes + batch), w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                ctx->opts.use_side ? &ctx->dstr : nullptr);
+  if (scale_log2)
+    launch_scaled_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
+                         (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
+                         ctx->opts.use_side ? &ctx->dstr : nullptr);
+  else
+    launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
+                  (const int32_t *)(d_sizes + batch), w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
+                  ctx->opts.use_side ? &ctx->dstr : nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -1818,15 +1846,17 @@ static int region_status_error(himg_hip_ctx *ctx, int32_t st) {
   return code;
 }
 
-extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
-                                         int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height,
-                                         int *channels) {
+// himg_hip_decode_region_to (scale_log2 = 0) and himg_hip_decode_scaled_region_to (1, 2: the rectangle
+// in the scaled picture, planned as the full-resolution rectangle it covers).
+static int region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2, int x, int y,
+                     int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels) {
   if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
   int W = 0, H = 0, C = 0;
   if (const char *msg = parse_header(packed, packed_size, &W, &H, &C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
   Geom g;
   if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-  if (!region_ok(W, H, x, y, w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  int up[4];
+  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->host_bytes = 0;
   const size_t in_cap = round_up(packed_size + 16, 256);
@@ -1841,7 +1871,7 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   himg_hip_region_plan plan = himg_hip_region_plan();
   // The host walks the headers up to row1 and uploads the head and the touched rows, each at its
   // offset; a stream it does not index goes up whole and takes the device walk, which words the verdict.
-  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, x, y, w, h, &plan, ctx->hp_index) == HIMG_OK;
+  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, up[0], up[1], up[2], up[3], &plan, ctx->hp_index) == HIMG_OK;
   if (indexed) {
     HIP_TRY(ctx, hipMemcpyAsync(in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
     HIP_TRY(ctx, hipMemcpyAsync(in + plan.rows_begin, packed + plan.rows_begin, plan.rows_end - plan.rows_begin,
@@ -1854,7 +1884,7 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   const int32_t org[2] = {x, y};   // (a batch of one)
   int rc = region_launch(ctx, in, in_cap, &sz32, 1, W, H, C, org, w, h,
                          indexed ? (const uint32_t *)ctx->h_index.p : nullptr, ctx->h_out.p,
-                         (int32_t *)ctx->h_status.p, nullptr);
+                         (int32_t *)ctx->h_status.p, nullptr, scale_log2);
   if (rc) {
     (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffer
     return rc;
@@ -1867,6 +1897,12 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
+                                         int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height,
+                                         int *channels) {
+  return region_to(ctx, packed, packed_size, 0, x, y, w, h, dst, dst_cap, width, height, channels);
 }
 
 // decode_regions_batch's launches: at most kRegionLaunch frames (the grids take batch x C <= 65535),
@@ -1882,7 +1918,7 @@ constexpr size_t kRegionStageBytes = (size_t)1 << 30;
 static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
                          const int32_t *rects, const std::vector<int> &grp, size_t stride, int W, int H, int C,
                          uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights, int *channels,
-                         int *first_err) {
+                         int *first_err, int scale_log2) {
   const int m = (int)grp.size(), w = rects[4 * (size_t)grp[0] + 2], h = rects[4 * (size_t)grp[0] + 3];
   const int rows = (H + 7) / 8;
   const size_t n_idx = 2 * (size_t)rows * m, out_bytes = (size_t)w * h * C;
@@ -1897,8 +1933,10 @@ static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const 
     const int i = grp[k];
     const int32_t *R = rects + 4 * (size_t)i;
     himg_hip_region_plan plan = himg_hip_region_plan();
-    (void)region_index(packed[i], packed_sizes[i], ctx->fix_t2, R[0], R[1], R[2], R[3], &plan,
-                       ctx->hp_index + (size_t)k * 2 * rows);   // (it passed when the frame was planned)
+    int up[4];
+    (void)rect_up(W, H, scale_log2, R[0], R[1], R[2], R[3], up);
+    (void)region_index(packed[i], packed_sizes[i], ctx->fix_t2, up[0], up[1], up[2], up[3], &plan,
+                       ctx->hp_index + (size_t)k * 2 * rows);   // (both passed when the frame was planned)
     uint8_t *d = in + (size_t)k * stride;
     HIP_TRY(ctx, hipMemcpyAsync(d, packed[i], plan.head_bytes, hipMemcpyHostToDevice, nullptr));
     HIP_TRY(ctx, hipMemcpyAsync(d + plan.rows_begin, packed[i] + plan.rows_begin, plan.rows_end - plan.rows_begin,
@@ -1909,7 +1947,7 @@ static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const 
   }
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
   int rc = region_launch(ctx, in, stride, sz.data(), m, W, H, C, org.data(), w, h, (const uint32_t *)ctx->h_index.p,
-                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
+                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr, scale_log2);
   if (rc) {
     (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
     return rc;
@@ -1929,10 +1967,10 @@ static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const 
   return HIMG_OK;
 }
 
-extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
-                                             const size_t *packed_sizes, int n, const int32_t *rects,
-                                             uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights,
-                                             int *channels) {
+// himg_hip_decode_regions_batch (scale_log2 = 0) and himg_hip_decode_scaled_regions_batch (1, 2).
+static int regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes, int n,
+                         int scale_log2, const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap, int *widths,
+                         int *heights, int *channels) {
   if (!ctx || !packed || !packed_sizes || !rects || !dst || !dst_cap || !widths || !heights || !channels || n < 0)
     return HIMG_ERR_ARG;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -1942,27 +1980,27 @@ extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *c
     widths[i] = heights[i] = channels[i] = 0;
     const int32_t *R = rects + 4 * (size_t)i;
     Geom g;
-    int err = HIMG_OK;
+    int err = HIMG_OK, up[4];
     if (const char *msg = packed[i] ? parse_header(packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i]) : "Not a RIFF HIMG file.\n")
       err = fail(ctx, HIMG_ERR_FORMAT, msg);
     else if (!make_geom(W[i], H[i], Cc[i], Cc[i], 1, &g))
       err = fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-    else if (!region_ok(W[i], H[i], R[0], R[1], R[2], R[3]))
+    else if (!rect_up(W[i], H[i], scale_log2, R[0], R[1], R[2], R[3], up))
       err = fail(ctx, HIMG_ERR_ARG, "bad rectangle");
     if (err) {
       if (!first_err) first_err = err;
       continue;
     }
     himg_hip_region_plan plan = himg_hip_region_plan();
-    if (g.rows >= 2 && region_index(packed[i], packed_sizes[i], ctx->fix_t2, R[0], R[1], R[2], R[3], &plan, nullptr) == HIMG_OK) {
+    if (g.rows >= 2 && region_index(packed[i], packed_sizes[i], ctx->fix_t2, up[0], up[1], up[2], up[3], &plan, nullptr) == HIMG_OK) {
       done[i] = 0;   // planned: it goes through a shared launch below
       continue;
     }
     // A stream the host does not index goes through decode_region_to's own path (uploaded whole, the
     // device walk words the verdict), so that its status and message are that call's.
     int w = 0, h = 0, c = 0;
-    const int rc = himg_hip_decode_region_to(ctx, packed[i], packed_sizes[i], R[0], R[1], R[2], R[3], dst[i], dst_cap[i],
-                                             &w, &h, &c);
+    const int rc = region_to(ctx, packed[i], packed_sizes[i], scale_log2, R[0], R[1], R[2], R[3], dst[i], dst_cap[i],
+                             &w, &h, &c);
     if (rc == HIMG_ERR_HIP) return rc;
     if (rc) { if (!first_err) first_err = rc; continue; }
     widths[i] = w; heights[i] = h; channels[i] = c;
@@ -1985,10 +2023,17 @@ extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *c
       done[i] = 1;
     }
     const int rc = regions_group(ctx, packed, packed_sizes, rects, grp, stride, W[i0], H[i0], Cc[i0], dst, dst_cap,
-                                 widths, heights, channels, &first_err);
+                                 widths, heights, channels, &first_err, scale_log2);
     if (rc) return rc;
   }
   return first_err;
+}
+
+extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                             const size_t *packed_sizes, int n, const int32_t *rects,
+                                             uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights,
+                                             int *channels) {
+  return regions_batch(ctx, packed, packed_sizes, n, 0, rects, dst, dst_cap, widths, heights, channels);
 }
 
 // ---------------------------------------------------------------------------
@@ -2156,6 +2201,51 @@ extern "C" int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *co
     HIP_TRY(ctx, hipStreamSynchronize(nullptr));
   }
   return first_err;
+}
+
+// ---------------------------------------------------------------------------
+// Scaled region decode: a window of the picture at 1/2 or 1/4 scale (kernels_dec.hip,
+// launch_scaled_region).  A rectangle of the scaled picture is planned, walked, counted and judged as
+// the full-resolution rectangle it covers (rect_up); the entries are the region decode's with a scale.
+// ---------------------------------------------------------------------------
+extern "C" int himg_hip_scaled_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int scale_log2, int x,
+                                           int y, int w, int h, himg_hip_region_plan *plan) {
+  if (!packed || !plan || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
+  *plan = himg_hip_region_plan();
+  int W = 0, H = 0, C = 0, up[4];
+  if (int rc = himg_hip_peek(packed, packed_size, &W, &H, &C)) return rc;
+  plan->width = W; plan->height = H; plan->num_channels = C;
+  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return HIMG_ERR_ARG;
+  return region_index(packed, packed_size, fix_t2, up[0], up[1], up[2], up[3], plan, nullptr);
+}
+
+extern "C" int himg_hip_decode_scaled_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                                int scale_log2, int x, int y, int w, int h, uint8_t *dst,
+                                                size_t dst_cap, int *width, int *height, int *channels) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  return region_to(ctx, packed, packed_size, scale_log2, x, y, w, h, dst, dst_cap, width, height, channels);
+}
+
+extern "C" int himg_hip_decode_scaled_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                     const uint32_t *h_sizes, int batch, int width, int height,
+                                                     int num_channels, int scale_log2, const int32_t *h_origins,
+                                                     int w, int h, void *d_out, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_origins || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
+                       d_out, d_status, stream, scale_log2);
+}
+
+extern "C" int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                                    const size_t *packed_sizes, int n, int scale_log2,
+                                                    const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
+                                                    int *widths, int *heights, int *channels) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  return regions_batch(ctx, packed, packed_sizes, n, scale_log2, rects, dst, dst_cap, widths, heights, channels);
 }
 
 // ---------------------------------------------------------------------------

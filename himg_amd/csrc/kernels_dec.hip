@@ -4179,6 +4179,10 @@ struct ScaledArgs {
   int ow, oh;      // the output's size, ceil(W / F) x ceil(H / F)
   uint8_t *out;    // frame f's samples at out + f * oh * ow * C
 };
+// One frame's window in the scaled picture (scaled_tile_rows_crop).
+struct ScaledCrop {
+  int x, y, w, h;
+};
 
 template <int S>
 __host__ __device__ inline RegionLayout scaled_layout(int C, int sw) {
@@ -4322,73 +4326,7 @@ template <int S, int Y0, int NY>
 __device__ __forceinline__ void scaled_tile_rows(const Geom &g, int sstride, int cstride, const uint8_t *sym, const uint8_t *low,
                                                   const int16_t *s_unmap, const uint8_t *s_shift, int ycbcr, int u,
                                                   int v, const ScaledArgs &sa, uint8_t *img) {
-  constexpr int F = 8 / S, LG = S == 4 ? 1 : 2;
-  const int cols = g.cols, C = g.C;
-  const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
-  uint32_t q[NY * S];   // [(Y - Y0) * S + X]: the pixel's channels in bytes 0..3
-#pragma unroll
-  for (int i = 0; i < NY * S; ++i) q[i] = 0u;
-#pragma unroll 1
-  for (int c = 0; c < C; ++c) {   // (not unrolled: four planes' loads in flight at once cost registers)
-    const uint8_t *m = low + (size_t)c * g.rows * cols;
-    const int chroma = (ycbcr && (c == 1 || c == 2)) ? 1 : 0;  // decoder.cpp:376
-    const uint8_t *sh = s_shift + chroma * 64;
-    // quantize.cpp:153-165 on the top-left S x S: d[j][i], row j, column i.
-    int d[S][S];
-#pragma unroll
-    for (int k = 0; k < S * S; ++k) {
-      const int pos = kScanD[k], j = pos >> 3, i = pos & 7;
-      const uint32_t code = sym[(size_t)c * cstride + (size_t)k * sstride];
-      d[j][i] = (int)(int16_t)(uint16_t)((uint32_t)(int)s_unmap[code] << sh[pos]);
-    }
-#pragma unroll
-    for (int j = 0; j < S; ++j) iwht_short<S>(d[j]);   // rows: d[j][X]
-    int p[S][S];
-#pragma unroll
-    for (int X = 0; X < S; ++X) {
-      int col[S];
-#pragma unroll
-      for (int j = 0; j < S; ++j) col[j] = d[j][X];
-      iwht_short<S>(col);
-#pragma unroll
-      for (int Y = 0; Y < S; ++Y) p[Y][X] = col[Y];
-    }
-    // The low-res block (downsampled.cpp:130-169) and its F x F box means, an output row at a time.
-    // The left and the right column are interpolated together, one in each half of a register
-    // (values below 256: the bit a half's sum hands down is masked away).
-    uint32_t lr[9];
-    lr[0] = (uint32_t)m[(size_t)v * cols + u] | ((uint32_t)m[(size_t)v * cols + u2] << 16);
-    lr[8] = (uint32_t)m[(size_t)v2 * cols + u] | ((uint32_t)m[(size_t)v2 * cols + u2] << 16);
-    interp9pk(lr);
-#pragma unroll
-    for (int Y = Y0; Y < Y0 + NY; ++Y) {
-      int acc[S];
-#pragma unroll
-      for (int X = 0; X < S; ++X) acc[X] = F * F / 2;
-#pragma unroll
-      for (int y = Y * F; y < Y * F + F; ++y) {
-        int a[9];
-        a[0] = (int)(lr[y] & 0xffffu);
-        a[8] = (int)(lr[y] >> 16);
-        interp9d(a);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) acc[x / F] += a[x];
-      }
-#pragma unroll
-      for (int X = 0; X < S; ++X) {
-        const int smp = clamp255d((int)(int16_t)(p[Y][X] + (acc[X] >> (2 * LG))));   // decoder.cpp:36-75
-        q[(Y - Y0) * S + X] |= (uint32_t)smp << (8 * c);
-      }
-    }
-  }
-  if (ycbcr) {
-#pragma unroll
-    for (int i = 0; i < NY * S; ++i) {
-      uint32_t c0 = q[i] & 255u, c1 = (q[i] >> 8) & 255u, c2 = (q[i] >> 16) & 255u;
-      ycc_to_rgb(c0, c1, c2);   // ycbcr.cpp:54-82
-      q[i] = (q[i] & 0xff000000u) | c0 | (c1 << 8) | (c2 << 16);
-    }
-  }
+#include "dec_body_scaled_tile.inc"
   const int x0 = S * u;
 #pragma unroll
   for (int Y = Y0; Y < Y0 + NY; ++Y) {
@@ -4417,6 +4355,41 @@ __device__ __forceinline__ void scaled_tile_rows(const Geom &g, int sstride, int
   }
 }
 
+// The same tile for the scaled region decode: the stores cropped to the frame's window (img = the window's
+// sample (0, 0), row pitch w * C).
+template <int S, int Y0, int NY>
+__device__ __forceinline__ void scaled_tile_rows_crop(const Geom &g, int sstride, int cstride, const uint8_t *sym, const uint8_t *low,
+                                                  const int16_t *s_unmap, const uint8_t *s_shift, int ycbcr, int u,
+                                                  int v, const ScaledCrop &sa, uint8_t *img) {
+#include "dec_body_scaled_tile.inc"
+  const int px0 = S * u - sa.x;
+#pragma unroll
+  for (int Y = Y0; Y < Y0 + NY; ++Y) {
+    const int py = S * v + Y - sa.y;
+    if (py < 0 || py >= sa.h) continue;
+    const uint32_t *qr = q + (Y - Y0) * S;
+    uint8_t *d = img + ((long long)py * sa.w + px0) * C;
+    if (C == 4) {
+      if (px0 >= 0 && px0 + S <= sa.w && ((uintptr_t)d & (uintptr_t)(4 * S - 1)) == 0) {
+        if (S == 4) *reinterpret_cast<uint4 *>(d) = make_uint4(qr[0], qr[1], qr[2], qr[3]);
+        else *reinterpret_cast<uint2 *>(d) = make_uint2(qr[0], qr[1]);
+      } else {
+#pragma unroll
+        for (int X = 0; X < S; ++X)
+          if (px0 + X >= 0 && px0 + X < sa.w) reinterpret_cast<uint32_t *>(d)[X] = qr[X];   // (4 w per row: dword aligned)
+      }
+    } else {
+#pragma unroll
+      for (int X = 0; X < S; ++X) {
+        if (px0 + X < 0 || px0 + X >= sa.w) continue;
+        d[X * C] = (uint8_t)qr[X];
+        if (C > 1) d[X * C + 1] = (uint8_t)(qr[X] >> 8);
+        if (C > 2) d[X * C + 2] = (uint8_t)(qr[X] >> 16);
+      }
+    }
+  }
+}
+
 // S = 4: the tile in two halves of two output rows, each gathering and transforming the tile again
 // (sixteen symbols per plane) -- one pass keeps 16 + 16 + 16 values live beside the low-res block and
 // does not fit the 64 registers that let two workgroups share a CU.
@@ -4430,6 +4403,19 @@ __device__ __forceinline__ void scaled_tile_store(const Geom &g, int sstride, in
     scaled_tile_rows<S, S / 2, S / 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
   } else {
     scaled_tile_rows<S, 0, S>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+  }
+}
+
+template <int S>
+__device__ __forceinline__ void scaled_tile_store_crop(const Geom &g, int sstride, int cstride, const uint8_t *sym,
+                                                       const uint8_t *low, const int16_t *s_unmap, const uint8_t *s_shift,
+                                                       int ycbcr, int u, int v, const ScaledCrop &sa, uint8_t *img) {
+  if (S == 4) {
+    scaled_tile_rows_crop<S, 0, S / 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+    asm volatile("" ::: "memory");   // (the second half reads the symbols again)
+    scaled_tile_rows_crop<S, S / 2, S / 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+  } else {
+    scaled_tile_rows_crop<S, 0, S>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
   }
 }
 
@@ -4530,6 +4516,126 @@ __global__ __launch_bounds__(kDecThreads, 8) void k_dec_scaled(Geom g, DecWs ws,
                          s_shift, ycbcr, su0 + ul, r, sa, img);
 }
 
+// ---------------------------------------------------------------------------
+// k_dec_scaled_region<S>: the window w x h of the 1/2-scale (S = 4) or 1/4-scale (S = 2) picture
+// at frame f's own origin -- k_dec_scaled<S, false> over the block rows and tile columns a
+// window touches, as k_dec_region is to the full decode.  The origins are those of the full-resolution
+// rectangle the window covers, (F x_f, F y_f) with F = 8 / S: the region walk and count kernels
+// read the same array with the height F h, and touch exactly the window's block rows
+// r0_f = y_f / S .. r1_f = ceil((y_f + h) / S) (<= rows, because y_f + h <= ceil(H / F)).
+// A workgroup per (column strip of sw tiles from u0_f = x_f / S on, touched block row, frame); one
+// past its frame's last row or last tile returns first thing.  LDS: scaled_layout<S> -- C x S * S
+// segments of the strip's tiles.  The write pass is k_dec_scaled's with ScaledWin<S> bounded to
+// the window's tile columns: a lane whose recorded symbols hold no needed symbol of the window
+// does not walk, one that does stops behind its last (both off under the `strict` tree rule); the
+// completing lane and the no-record fallback walk the whole range with the reference's checks.
+// The transform is scaled_tile_rows' (the same included body), a lane per tile, its stores cropped to the window.
+// ---------------------------------------------------------------------------
+struct ScaledRegionArgs {
+  const int32_t *org;  // frame f's origin in full-resolution pixels (F x_f, F y_f) at org[2 f], org[2 f + 1]
+  int sw;              // tiles per column strip (blockIdx.x = strip, from u0_f on)
+  int w, h;            // the window, in samples of the scaled picture
+  uint8_t *out;        // frame f's samples at out + f * h * w * C
+};
+
+template <int S>
+__global__ __launch_bounds__(kDecThreads, 8) void k_dec_scaled_region(Geom g, DecWs ws, const uint8_t *packed,
+                                                                     size_t in_stride, const uint32_t *sizes,
+                                                                     ScaledRegionArgs sa) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  constexpr int LG = S == 4 ? 1 : 2;
+  const RegionLayout L = scaled_layout<S>(g.C, sa.sw);
+  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
+  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
+  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift: contiguous
+  const uint8_t *s_shift = smem + L.rowtab + 512;
+  uint8_t *sym = smem + L.sym;
+  const int tid = threadIdx.x, f = blockIdx.z;
+  // The frame's own window: its rows and tile columns; a workgroup past either has nothing to do.
+  ScaledCrop rr;
+  rr.x = sa.org[2 * f] >> LG; rr.y = sa.org[2 * f + 1] >> LG; rr.w = sa.w; rr.h = sa.h;
+  const int r = rr.y / S + (int)blockIdx.y, u1 = (rr.x + rr.w + S - 1) / S;
+  const int su0 = rr.x / S + (int)blockIdx.x * sa.sw;
+  if (r >= (rr.y + rr.h + S - 1) / S || su0 >= u1) return;
+  const int ww = min(sa.sw, u1 - su0);
+  DecFrame *df = ws.frames + f;
+  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
+  __syncthreads();
+  if (sh->flag) return;
+  load_dec_tables(ws, df, f, 1, &T);
+  if (tid < kRowTabWords / 4)
+    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
+  const uint32_t nsym16 = (L.seg * (uint32_t)(S * S) * (uint32_t)g.C + 15u) / 16u;
+  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
+  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
+  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
+  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+
+  const size_t ri = (size_t)f * g.rows + (size_t)r;
+  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
+  const GrpTables tb = tables_of(&T);
+  ScaledWin<S> win;
+  win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
+  win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
+  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
+  const uint32_t valid = po[kDecThreads + 2];
+  const bool rec = valid != 0 && pay_len != 0;
+  const unsigned long long P1 = 8ull * pay_len;
+  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
+  bool ok = true;
+  if (pay_len != 0) {
+    GReader rd;
+    rel0 = rd.attach(p, end, 8ull * pay_off);
+    const uint32_t rel_end = rel0 + (uint32_t)P1;
+    if (rec) {
+      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
+      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
+      tot = po[kDecThreads];
+      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
+      const uint32_t cnt = nxt - off;
+      if (off + cnt < out_size) {
+        // The lane's last needed symbol of the window (stop), if its symbols [off, off + cnt) hold one.
+        uint32_t stop = ~0u;
+        bool walk = true;
+        if (!strict) {
+          const long long last = cnt ? scaled_last_needed<S>(off + cnt - 1u, (uint32_t)g.cols, (uint32_t)su0, (uint32_t)ww) : -1;
+          walk = cnt != 0 && last >= (long long)off;
+          stop = walk ? (uint32_t)last : 0u;
+        }
+        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
+      } else if (off < out_size) {
+        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
+      }
+    } else if (tid == 0) {
+      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
+    }
+  }
+  if (!ok) sh->err = 1;
+  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
+  __syncthreads();
+  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
+  int bad = sh->err || pay_len == 0;
+  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
+  const unsigned long long E = sh->endbit;
+  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
+  if (bad) {
+    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+    return;
+  }
+  // ---- the strip's tiles: a lane per tile, the stores cropped to the window ----
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  uint8_t *img = sa.out + (size_t)f * ((size_t)sa.h * sa.w * g.C);
+  const int ycbcr = df->ycbcr;
+#pragma unroll 1
+  for (int ul = tid; ul < ww; ul += kDecThreads)
+    scaled_tile_store_crop<S>(g, (int)L.seg, S * S * (int)L.seg, sym + 4 + ul, low, s_unmap, s_shift, ycbcr, su0 + ul,
+                              r, rr, img);
+}
+
 #define HIMG_LAUNCH(name, grid, block, ...)                    \
   do {                                                         \
     prof_begin(prof, #name, stream);                           \
@@ -4568,7 +4674,8 @@ hipError_t dec_set_kernel_attrs() {
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(kLdsMax - fa.sharedSizeBytes));
   const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
-                          reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>)};
+                          reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>),
+                          reinterpret_cast<const void *>(&k_dec_scaled_region<4>), reinterpret_cast<const void *>(&k_dec_scaled_region<2>)};
   for (const void *k : scaled) {
     if (e == hipSuccess) e = hipFuncGetAttributes(&fa, k);
     if (e == hipSuccess)
@@ -4631,25 +4738,15 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 
-void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
-                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds) {
-  DecWs ws = ws_in;
-  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
-  // The batch's largest row and tile counts (the grids) and its touched rows (the count kernels' rule);
-  // for a fixed w x h a frame's counts are within one of these.
-  int nrows = 0, ntiles = 0;
-  bool stop_early = false;   // a frame whose walk stops before the last row
-  long long all_rows = 0;
-  for (int f = 0; f < batch; ++f) {
-    const int x = h_org[2 * f], y = h_org[2 * f + 1];
-    const int r0 = y / 8, r1 = (y + h + 7) / 8, nt = (x + w + 7) / 8 - x / 8;
-    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
-    ntiles = nt > ntiles ? nt : ntiles;
-    stop_early |= r1 < g.rows;
-    all_rows += r1 - r0;
-  }
+// What launch_region and launch_scaled_region share, everything in front of the row kernel: the
+// head phase, each frame's header walk to its r1_f and the counts over its rows [r0_f, r1_f), derived on
+// the device from d_org (full-resolution origins) and the full-resolution height h.  nrows: the batch's
+// largest touched-row count (the grids), all_rows: its touched rows (the count kernels' rule),
+// stop_early: a frame whose walk stops before the last row.
+static void launch_region_front(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                                const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *d_org, int h,
+                                int nrows, long long all_rows, bool stop_early, hipStream_t stream, Profiler *prof,
+                                const DecStreams *ds) {
   const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
   const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
   prof_begin(prof, "memset", stream);
@@ -4691,6 +4788,29 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
     HIMG_LAUNCH(k_region_count, dim3((nrows + rpc - 1) / rpc, batch), dim3(kDecThreads), gc, ws, d_packed, in_stride,
                 d_sizes, d_org, h, rpc);
   }
+}
+
+void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
+                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
+                   const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
+  // The batch's largest row and tile counts (the grids) and its touched rows (the count kernels' rule);
+  // for a fixed w x h a frame's counts are within one of these.
+  int nrows = 0, ntiles = 0;
+  bool stop_early = false;   // a frame whose walk stops before the last row
+  long long all_rows = 0;
+  for (int f = 0; f < batch; ++f) {
+    const int x = h_org[2 * f], y = h_org[2 * f + 1];
+    const int r0 = y / 8, r1 = (y + h + 7) / 8, nt = (x + w + 7) / 8 - x / 8;
+    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
+    ntiles = nt > ntiles ? nt : ntiles;
+    stop_early |= r1 < g.rows;
+    all_rows += r1 - r0;
+  }
+  launch_region_front(g, ws, batch, d_packed, in_stride, d_sizes, d_row_index, d_org, h, nrows, all_rows, stop_early,
+                      stream, prof, ds);
   RegionArgs ra;
   ra.org = d_org;
   const int smax = region_strip_tiles(g), nstrip = (ntiles + smax - 1) / smax;
@@ -4699,6 +4819,46 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   prof_begin(prof, "k_dec_region", stream);
   hipLaunchKernelGGL(k_dec_region, dim3(nstrip, nrows, batch), dim3(kDecThreads), region_layout(g.C, ra.sw).total, stream,
                      g, ws, d_packed, in_stride, d_sizes, ra);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+// The window w x h of the picture at scale 2^-scale_log2, frame f's origin (x_f, y_f) in that picture.
+// h_org / d_org hold the origins of the full-resolution rectangles the windows cover, (F x_f, F y_f):
+// with the height F h the region walk and count kernels touch rows y_f / S .. ceil((y_f + h) / S), which
+// stays within the frame's block rows because y_f + h <= ceil(H / F) (checked by the caller).
+void launch_scaled_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                          const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org,
+                          const int32_t *d_org, int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status,
+                          hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
+  const int F = 1 << scale_log2, S = 8 / F;
+  int nrows = 0, ntiles = 0;
+  bool stop_early = false;
+  long long all_rows = 0;
+  for (int f = 0; f < batch; ++f) {
+    const int x = h_org[2 * f] / F, y = h_org[2 * f + 1] / F;
+    const int r0 = y / S, r1 = (y + h + S - 1) / S, nt = (x + w + S - 1) / S - x / S;
+    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
+    ntiles = nt > ntiles ? nt : ntiles;
+    stop_early |= r1 < g.rows;
+    all_rows += r1 - r0;
+  }
+  launch_region_front(g, ws, batch, d_packed, in_stride, d_sizes, d_row_index, d_org, F * h, nrows, all_rows,
+                      stop_early, stream, prof, ds);
+  ScaledRegionArgs sa;
+  sa.org = d_org;
+  const int smax = scaled_strip_tiles(g, scale_log2), nstrip = (ntiles + smax - 1) / smax;
+  sa.sw = (ntiles + nstrip - 1) / nstrip;   // (strips of equal width)
+  sa.w = w; sa.h = h; sa.out = d_out;
+  prof_begin(prof, "k_dec_scaled_region", stream);
+  if (scale_log2 == 1)
+    hipLaunchKernelGGL(k_dec_scaled_region<4>, dim3(nstrip, nrows, batch), dim3(kDecThreads),
+                       scaled_layout<4>(g.C, sa.sw).total, stream, g, ws, d_packed, in_stride, d_sizes, sa);
+  else
+    hipLaunchKernelGGL(k_dec_scaled_region<2>, dim3(nstrip, nrows, batch), dim3(kDecThreads),
+                       scaled_layout<2>(g.C, sa.sw).total, stream, g, ws, d_packed, in_stride, d_sizes, sa);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }

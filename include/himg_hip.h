@@ -355,6 +355,58 @@ int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *const *packed
                                  int n, int scale_log2, uint8_t *const *dst, const size_t *dst_cap,
                                  int *widths, int *heights, int *channels);
 
+/* ---- scaled region decode: rectangles of the picture at 1/2 and 1/4 scale ---------- */
+/*
+ * scale_log2 = 1 or 2 (any other scale: HIMG_ERR_ARG), F = 2^scale_log2, S = 8 / F, ow = ceil(W / F),
+ * oh = ceil(H / F) as in himg_hip_scaled_size.  A rectangle R = (x, y, w, h) IN THE COORDINATES OF THE
+ * SCALED PICTURE, with w, h >= 1, x, y >= 0, x + w <= ow and y + h <= oh (any other rectangle:
+ * HIMG_ERR_ARG).  Output: h rows x w columns x C channels, interleaved u8, tightly packed; sample
+ * (i, j) is byte for byte sample (y + i, x + j) of himg_hip_decode_scaled_*'s output for the same
+ * stream, scale and HIMG_OPT_FIX_T2 setting.  No arithmetic of its own: the four steps of the scaled
+ * section above are the definition.
+ * R touches block rows r0 = y / S .. r1 = ceil((y + h) / S) and tile columns x / S ..
+ * ceil((x + w) / S): the rows and columns of the full-resolution rectangle it covers,
+ *   R^ = (F x, F y, min(F w, W - F x), min(F h, H - F y)).
+ * Verdict and bytes used: exactly those of the region decode of R^ (the region section above) --
+ * container stages, FRES chunk and tree, the size headers of rows 0 .. r1-1 (to the end of the chunk
+ * when r1 is the last row), the entropy decode of rows r0 .. r1-1 with each row's end-of-block checks;
+ * the same code and the same himg_hip_last_error wording.  A whole-picture rectangle therefore gets
+ * himg_hip_decode's verdict.  Every load stays inside the stream.
+ */
+/* Host only, no GPU: validates R against FRMT and fills the plan; it equals himg_hip_region_peek
+ * of R^ (a bounded himg_hip_index_host, error codes as there). */
+int himg_hip_scaled_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int scale_log2, int x,
+                                int y, int w, int h, himg_hip_region_plan *plan);
+/* R of one host stream into caller-owned host memory: himg_hip_decode_region_to at a scale.  The host
+ * indexes; only [0, head_bytes) and [rows_begin, rows_end) of the plan are uploaded; the capacity
+ * protocol of himg_hip_decode_to (HIMG_ERR_CAPACITY with *width = w, *height = h, *channels = C set;
+ * himg_hip_fetch_last copies the resident result).  Stands in for Decoder::Decode
+ * (decoder.cpp:95-135) followed by a shrink and a crop. */
+int himg_hip_decode_scaled_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                     int scale_log2, int x, int y, int w, int h, uint8_t *dst, size_t dst_cap,
+                                     int *width, int *height, int *channels);
+/* The window w x h at origin (x_f, y_f) = h_origins[2f], h_origins[2f+1] of frame f's scaled picture,
+ * streams of a batch in HBM: himg_hip_decode_regions_device at a scale, with its contract --
+ * h_origins a HOST array of 2 x batch values riding behind the sizes, every rectangle checked on the
+ * host before anything is launched (one outside its frame's ow x oh: HIMG_ERR_ARG, neither d_out nor
+ * d_status written), d_out = batch x h x w x C bytes, frame f at f * h * w * C with no alignment
+ * asked of a frame's start, asynchronous, the same grid limits.  One shared origin is the caller
+ * repeating it. */
+int himg_hip_decode_scaled_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                          const uint32_t *h_sizes, int batch, int width, int height,
+                                          int num_channels, int scale_log2, const int32_t *h_origins, int w,
+                                          int h, void *d_out, int32_t *d_status, void *stream);
+/* n host streams at one scale, rectangle i = rects[4i .. 4i+3] = {x, y, w, h} of frame i's scaled
+ * picture: the contract of himg_hip_decode_regions_batch (a failing frame gets widths[i] =
+ * heights[i] = channels[i] = 0 and does not stop the others, the first error is returned; frames
+ * that share (W, H, C, w, h) go through launches of at most 256 frames and 1 GiB of staging; only
+ * the planned bytes are uploaded; a stream the host cannot plan goes through
+ * himg_hip_decode_scaled_region_to's own path). */
+int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                         const size_t *packed_sizes, int n, int scale_log2,
+                                         const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
+                                         int *widths, int *heights, int *channels);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
