@@ -28,7 +28,7 @@ SYNTH = {"grad": 0, "gradn": 1, "rand": 2, "randtile": 3}
 DBG = {
     "avg": 0, "lowres": 1, "lres_sym": 2, "fres_sym": 3, "lres_hist": 4, "fres_hist": 5,
     "lres_len": 6, "fres_len": 7, "lres_code": 8, "fres_code": 9, "fres_row_bytes": 10,
-    "dec_stats": 11, "parse_stats": 12, "rowcount_stats": 13, "loop_counts": 14, "fres_tok_sym": 15,
+    "dec_stats": 11, "parse_stats": 12, "rowcount_stats": 13, "loop_counts": 14, "fres_tok_sym": 15, "tok_cnt": 16,
 }
 DBG_DECODER = 0x100
 
@@ -66,6 +66,7 @@ def lib():
     L.himg_hip_last_error.restype = C.c_char_p
     L.himg_hip_max_packed_size.argtypes = [i32, i32, i32]
     L.himg_hip_max_packed_size.restype = sz
+    L.himg_hip_tok_layout.argtypes = [i32, i32, i32, i32, i32, i32, P(i32)]
     L.himg_hip_encode.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, P(vp), P(sz)]
     L.himg_hip_decode.argtypes = [vp, vp, sz, P(vp), P(i32), P(i32), P(i32)]
     L.himg_hip_encode_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, sz, P(sz)]
@@ -166,6 +167,17 @@ def fnv1a64(buf):
 
 def max_packed_size(width, height, channels):
     return int(lib().himg_hip_max_packed_size(width, height, channels))
+
+
+def tok_layout(width, height, channels=4, pixel_stride=None, row_tokens=-1, batch=1):
+    """The encoder's token-stream layout for a geometry (himg_hip_tok_layout; no GPU needed): symbols per
+    segment, segments per block row, slots a segment owns, the slots half an iteration of k_tok can
+    stage and the slots its stage holds, and whether such an encode takes the token stream."""
+    out = (C.c_int32 * 6)()
+    rc = lib().himg_hip_tok_layout(width, height, pixel_stride or channels, channels, row_tokens, batch, out)
+    if rc != 0:
+        raise ValueError("himg_hip_tok_layout: %d" % rc)
+    return {"seg": out[0], "nseg": out[1], "cap": out[2], "stage_need": out[3], "stage": out[4], "tokens": bool(out[5])}
 
 
 def pinned_empty(nbytes):

@@ -77,7 +77,34 @@ struct EncWs {
 constexpr uint32_t kTokRunMark = 0x0100u;
 constexpr int kTokMaxRun = 255;          // zeros a literal slot can carry
 constexpr int kTokIter = 2048;           // symbols per wavefront iteration of the tokeniser (32 per lane)
-constexpr int kTokSegPad = 64;           // slots a segment can need beyond its symbol count (runs on their own, padding)
+constexpr int kTokRunPiece = 16662;      // zeros of one run on its own (the reference's greedy split: three slots each)
+constexpr int kTokStage = 1152;          // slots of a wavefront's staging buffer in k_tok (2.25 KiB: eight workgroups per CU)
+// How many slots a stretch of n symbols of a row can need, whatever the row holds.  Its slots are
+// L + 3 P: L non-zero symbols, P pieces of runs on their own.  Such a run is a lead of more than
+// 255 zeros in front of a literal of the stretch, or the row's trailing zeros (at least one).
+//   * A lead that began in front of the stretch (at most one) costs the stretch no symbol; every
+//     other lead has its 256 zeros and more inside, the trailing run at least one: with k and t of
+//     them L <= n - 256 k - t, and the R <= 1 + k + t runs give L + 3 R <= n + 3 - 253 k + 2 t <= n + 5.
+//   * A run of z zeros is ceil(z / 16662) <= 1 + floor(z / 16662) pieces, the runs are disjoint and
+//     runs never cross block rows: P <= R + floor(Z / 16662), Z <= row_block the zeros they cover.
+// So the stretch needs at most n + 5 + 3 floor(row_block / 16662) slots (tests/tok_model.py counts
+// them by k_tok's rules; tests/test_tok_capacity.py holds the two against each other).
+inline int tok_slots_beyond(int zeros_max) { return 5 + 3 * (zeros_max / kTokRunPiece); }
+// Slots a segment owns beyond its symbol count: that bound, whole 16-byte pieces (the tail of a
+// segment is padded to one); never less than the 64 every row below 333 240 symbols had before.
+inline int tok_seg_pad(int row_block) {
+  const int pad = (tok_slots_beyond(row_block) + 7) & ~7;
+  return pad > 64 ? pad : 64;
+}
+// Slots k_tok can have in a wavefront's stage at once.  An iteration that fits with what is
+// carried over is staged whole (the split test); otherwise half by half: n = 1024 symbols and
+// c < 8 slots carried over from the segment's earlier symbols.  c > 0 means the segment has a
+// non-zero symbol in front of the half, so every run the half emits lies inside the segment.
+inline int tok_stage_need(int row_block, int seg) {
+  const int alone = 1024 + tok_slots_beyond(row_block);
+  const int carried = 7 + 1024 + tok_slots_beyond(seg < row_block ? seg : row_block);
+  return alone > carried ? alone : carried;
+}
 
 // Container bytes that do not depend on the pixel data, built on the host.
 struct StaticChunks {
@@ -184,6 +211,8 @@ struct Profiler;  // host-side, see himg_hip.hip
 bool enc_uses_row_tokens(const Geom &g, int batch);
 // Symbols per token segment for this geometry (a multiple of kTokIter).
 int enc_tok_seg(const Geom &g);
+// Can k_tok take this geometry's rows at all (half an iteration's slots fit a wavefront's stage)?
+inline bool enc_tok_stage_fits(const Geom &g) { return tok_stage_need(g.row_block, enc_tok_seg(g)) <= kTokStage; }
 // Debug: expand frame `frame`'s token stream into symbols again (dst: fres_size bytes).
 void launch_tok_expand(const Geom &g, const EncWs &ws, int frame, uint8_t *dst, hipStream_t stream);
 

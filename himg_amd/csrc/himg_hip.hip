@@ -452,6 +452,21 @@ static int build_static(const Geom &g, int quality, StaticChunks *sc, ShiftTable
   return HIMG_OK;
 }
 
+extern "C" int himg_hip_tok_layout(int width, int height, int pixel_stride, int num_channels, int row_tokens,
+                                   int batch, int out[6]) {
+  Geom g;
+  if (!out || batch < 1 || !make_geom(width, height, pixel_stride, num_channels, 1, &g)) return HIMG_ERR_ARG;
+  g.row_tokens = row_tokens;
+  const int seg = himg_dev::enc_tok_seg(g);
+  out[0] = seg;
+  out[1] = (g.row_block + seg - 1) / seg;
+  out[2] = seg + himg_dev::tok_seg_pad(g.row_block);
+  out[3] = himg_dev::tok_stage_need(g.row_block, seg);
+  out[4] = himg_dev::kTokStage;
+  out[5] = himg_dev::enc_uses_row_tokens(g, batch) ? 1 : 0;
+  return HIMG_OK;
+}
+
 // ---------------------------------------------------------------------------
 // Workspaces.
 // ---------------------------------------------------------------------------
@@ -495,10 +510,10 @@ static int ensure_enc_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool allow
   const int nsp = g.lres_spans + g.rows;
   // FRES rows as a token stream between the tokeniser and the bit packer (batches): 16-bit slots,
   // worst case 2 bytes per symbol (+ padding per segment), ~0.7 in use.
-  const bool row_tok = allow_row_tokens && (force_row_tokens || himg_dev::enc_uses_row_tokens(g, batch));
+  const bool row_tok = allow_row_tokens && (force_row_tokens ? himg_dev::enc_tok_stage_fits(g) : himg_dev::enc_uses_row_tokens(g, batch));
   const int tok_seg = row_tok ? himg_dev::enc_tok_seg(g) : 0;
   const int tok_nseg = row_tok ? (g.row_block + tok_seg - 1) / tok_seg : 0;
-  const int tok_cap = tok_seg + himg_dev::kTokSegPad;
+  const int tok_cap = tok_seg + himg_dev::tok_seg_pad(g.row_block);   // (no content needs more: himg_dev.h)
   if (!ctx->e_planes.reserve(2 * plane * batch) || !ctx->e_lres.reserve(lres * batch) ||
       !ctx->e_fres.reserve(fres * batch) ||
       (row_tok && !ctx->e_tok.reserve((size_t)batch * g.rows * tok_nseg * ((size_t)tok_cap * 2 + 4))))
@@ -2405,6 +2420,9 @@ extern "C" int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void 
         HIP_TRY(ctx, hipDeviceSynchronize());
         src = ctx->e_tokx.p; n = (size_t)g.fres_size; break;
       }
+      case HIMG_DBG_TOK_CNT:
+        if (!w.tok) return HIMG_ERR_ARG;
+        src = w.tok_cnt + (size_t)frame * g.rows * w.tok_nseg; n = (size_t)g.rows * w.tok_nseg * 4; break;
       case HIMG_DBG_LRES_HIST: src = w.hist + ((size_t)frame * 2 + 0) * kHistStride; n = kNumSym * 4; break;
       case HIMG_DBG_FRES_HIST: src = w.hist + ((size_t)frame * 2 + 1) * kHistStride; n = kNumSym * 4; break;
       case HIMG_DBG_LRES_LEN: src = w.lens + ((size_t)frame * 2 + 0) * kHistStride; n = kNumSym * 4; break;

@@ -2847,6 +2847,12 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   uint32_t st0 = 0;
   if (tid == 0) st0 = df->status;
   if constexpr (COLS != 512) {
+    // A persistent workgroup's next row: the row before may have ended on a verdict read from the
+    // LDS with no barrier behind the read (sh->flag of a failed frame just below, sh->err of a
+    // failed row) -- a slow wavefront that has not read it yet must not meet this row's flag, or
+    // it stays in a row the others have left and its barriers pair with the wrong ones.  This is
+    // also the barrier in front of the LDS writes below (4096-pixel rows have it there).
+    if (again) __syncthreads();
     if (tid == 0) sh->flag = st0;
     __syncthreads();
     if (sh->flag) return;
@@ -2875,7 +2881,8 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   const int nr = COLS == 512 ? 1 : min(rpw, r1 - rb);
   // A persistent workgroup's next row: the loads above are in flight while the slowest wavefront
   // still transforms the row before; nothing of the LDS is written before it is done.
-  if (again) __syncthreads();
+  // (Other widths: that barrier stands in front of the flag store above.)
+  if (COLS == 512 && again) __syncthreads();
   {
     uint4 z;
     z.x = z.y = z.z = z.w = 0;
@@ -2994,6 +3001,13 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
                                             COLS == 512 ? pre_lr : nullptr, in_row, pf_on && it == tid, pf_a);
   }
   HIMG_SPAN_END("dec.transform");
+  // A wavefront without a transform iteration (per_row * nr < 1024: narrow rows in a frame's last
+  // workgroup) has not met the wait for its touch load: it waits here, the register its own up to
+  // the wait, before the persistent loop hands it the next row.  (4096-pixel rows: every lane
+  // has an iteration.)
+  if constexpr (COLS != 512) {
+    if (pf_on && tid >= per_row * nr) asm volatile("s_waitcnt vmcnt(0)" ::"v"(pf_a) : "memory");
+  }
   // Cycle stamps: the slowest wave counts (the SIMDs issue oldest-first, so the
   // first wave finishes long before the last one).
   if ((tid & 63) == 0) {

@@ -1514,7 +1514,7 @@ __global__ __launch_bounds__(NT) void k_tok_hist(Geom g, EncWs ws, int sp0) {
 // ---------------------------------------------------------------------------
 constexpr int kTokThreads = 256;
 constexpr int kTokWaves = kTokThreads / 64;
-constexpr int kTokStage = 1152;            // slots of a wavefront's staging buffer (a half's worst case: 1024 + runs on their own + < 8 carried over)
+// (kTokStage, the slots of a wavefront's staging buffer: himg_dev.h, with the bound on what a half can stage)
 
 __device__ __forceinline__ int run_token_symbol(int len) {   // huffman_enc.cpp:111-141
   return len == 1 ? 0 : len == 2 ? 256 : len <= 6 ? 257 : len <= 22 ? 258 : len <= 278 ? 259 : 260;
@@ -2982,6 +2982,9 @@ static void launch_emit(const Geom &g, const EncWs &ws, uint8_t *d_out, size_t o
 // ---- FRES rows through the token stream (k_tok + k_emit_tok) ----
 bool enc_uses_row_tokens(const Geom &g, int batch) {
   if (g.row_tokens == 0 || g.row_block % 64 != 0) return false;
+  // Rows so wide that half an iteration's slots could outgrow a wavefront's stage (runs on their own
+  // grow with the row: tok_stage_need) keep the kernels over the dense plane, forced or not.
+  if (!enc_tok_stage_fits(g)) return false;
   // (a single frame keeps the latency-tuned kernels: its 512 rows are a quarter of the chip's slots)
   return g.row_tokens > 0 || (long long)g.rows * batch >= 8192;
 }

@@ -63,6 +63,8 @@ const char *himg_hip_last_error(const himg_hip_ctx *ctx);
  *   HIMG_OPT_ROW_TOKENS  encoder: FRES rows go from the tokeniser to the bit packer as a stream of 16-bit
  *                        tokens (k_tok / k_emit_tok) instead of both walking the dense symbol plane (batches);
  *                        value 2 = on, and the bit packer takes its spelled-out path on every step (a test knob)
+ *                        Rows so wide that k_tok's stage could overflow (himg_hip_tok_layout: above 21 864
+ *                        RGBA pixels) keep the dense plane whatever the value.
  *                                                                      [env HIMG_ROW_TOKENS]
  *   HIMG_OPT_FRONT       encoder, full RGBA8 frames with rows of at most 512 tiles: box averages, low-res
  *                        plane and pixel stage in ONE pass over the pixels (k_front) instead of three
@@ -608,6 +610,9 @@ enum {
   HIMG_DBG_FRES_TOK_SYM = 15 /* encoder, after a batch encode that went through the token stream (HIMG_OPT_ROW_TOKENS):
                                 u8 [rows][C][64][cols], the slots of k_tok expanded into symbols again; status 7 is
                                 raised when a row's slots do not cover it exactly */
+  ,
+  HIMG_DBG_TOK_CNT = 16 /* encoder, after such an encode: u32 [rows][segments] the slots k_tok wrote per token
+                           segment of every block row (before the padding of the tail; himg_hip_tok_layout) */
 };
 int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void *host_dst,
                         size_t dst_bytes, size_t *bytes_written);
@@ -623,6 +628,15 @@ int himg_hip_profile_read(himg_hip_ctx *ctx, int *n_stages,
                           double ms[HIMG_MAX_STAGES], int launches[HIMG_MAX_STAGES]);
 
 /* ---- host utilities (no GPU needed) -------------------------------------- */
+
+/* The token-stream layout of the encoder's FRES rows for a geometry (k_tok -> k_emit_tok):
+ * out[0] symbols per segment, out[1] segments per block row, out[2] 16-bit slots a segment owns
+ * (its capacity: no content needs more -- the bound of himg_dev.h), out[3] the slots half an
+ * iteration of k_tok can stage at most, out[4] the slots its stage holds, out[5] whether an
+ * encode of `batch` frames with HIMG_OPT_ROW_TOKENS = row_tokens (-1, 0, 1, 2) takes the token
+ * stream: never when out[3] > out[4].  Returns HIMG_ERR_ARG for a geometry the encoder refuses. */
+int himg_hip_tok_layout(int width, int height, int pixel_stride, int num_channels, int row_tokens, int batch,
+                        int out[6]);
 
 /* Synthetic RGBA generators of SURVEY.md Appendix C.1. */
 enum { HIMG_SYNTH_GRAD = 0, HIMG_SYNTH_GRADN = 1, HIMG_SYNTH_RAND = 2, HIMG_SYNTH_RANDTILE = 3 };

@@ -8,6 +8,7 @@ import pytest
 
 import himg_amd
 import oracle_lib as ol
+import tok_model as tm
 
 pytestmark = pytest.mark.gpu
 
@@ -39,6 +40,7 @@ def test_token_stream_encode_matches_oracle(w, h):
             sym = eng.debug_read("fres_tok_sym", 0, tr["fres_sym"].size)
             assert np.array_equal(sym, tr["fres_sym"]), (name, q, ycc, "slots expanded")
             assert np.array_equal(eng.debug_read("fres_hist", 0, 261 * 4, np.uint32), tr["fres_hist"]), (name, q, ycc)
+            _check_slots(eng, 0, tr, w, h, (name, q, ycc))
     eng.close()
 
 
@@ -86,6 +88,123 @@ def test_token_stream_is_what_batches_take():
     torch.cuda.synchronize()
     stages = eng.profile_read()
     assert "k_tok" not in stages and "k_emit" in stages, sorted(stages)
+    eng.close()
+
+
+def _model_counts(tr, w, h, ch=4):
+    lay = himg_amd.tok_layout(w, h, ch, row_tokens=1)
+    counts, worst = tm.frame_demand(tr["fres_sym"], tr["rows"], lay["seg"], lay["nseg"], lay["stage"])
+    assert tm.padded(counts).max() <= lay["cap"] and worst <= lay["stage"], (w, h, "the model outgrows the product's bound")
+    return counts
+
+
+def _check_slots(eng, frame, tr, w, h, what):
+    """What k_tok left for one frame of the last encode: the slots expanded into symbols again, and the
+    slot count of every segment against the model's (tests/tok_model.py) -- slot for slot."""
+    sym = eng.debug_read("fres_tok_sym", frame, tr["fres_sym"].size)
+    assert np.array_equal(sym, tr["fres_sym"]), (what, "slots expanded")
+    counts = _model_counts(tr, w, h)
+    cnt = eng.debug_read("tok_cnt", frame, counts.size * 4, np.uint32)
+    assert np.array_equal(cnt.reshape(counts.shape), counts), (what, "tok_cnt")
+
+
+WIDE_SHAPES = [(8192, 24), (16384, 24)]
+
+
+@pytest.mark.parametrize("w,h", WIDE_SHAPES)
+def test_token_stream_wide_rows_match_oracle(w, h):
+    """The file's pictures at widths nothing forced the token stream at before (a row of the all-zero
+    picture is 16 and 32 pieces of a run; the lone column sits behind runs of tens of thousands)."""
+    eng = himg_amd.Engine(0)
+    eng.profile(True)
+    for name, img in _images(w, h):
+        for q, ycc in ((50, True), (90, False), (100, True), (10, True)):
+            want, tr = ol.oracle_encode(img, q, ycc, trace=True)
+            for mode in (1, 2):
+                eng.set_option("row_tokens", mode)
+                eng.profile_reset()
+                got = eng.encode(img, q, ycc)
+                stages = eng.profile_read()
+                assert "k_tok" in stages and "k_emit_tok" in stages and "k_tok_hist" not in stages, sorted(stages)
+                assert got.size == want.size and np.array_equal(got, want), (name, q, ycc, mode)
+            _check_slots(eng, 0, tr, w, h, (name, q, ycc))
+            assert np.array_equal(eng.debug_read("fres_hist", 0, 261 * 4, np.uint32), tr["fres_hist"]), (name, q, ycc)
+    eng.close()
+
+
+CRAFTED_WIDTHS = [12288, 16384, 20480, 32768]
+
+
+@pytest.mark.parametrize("w", CRAFTED_WIDTHS)
+@pytest.mark.parametrize("variant", tm.VARIANTS)
+def test_crafted_wide_rows_match_oracle(variant, w):
+    """The pictures of tests/tok_model.py: block rows whose one dense segment sits behind a run of most of a
+    row, so that it needs its symbol count plus three slots per 16 662 zeros in front -- more than the 64
+    spare slots a segment had whatever the width (16384 pixels: 65 620 against 65 600; 12288 pixels:
+    exactly the 49 216).  Forced through the token stream, both paths of the bit packer; a width whose
+    half-iteration could outgrow k_tok's stage (himg_dev.h tok_stage_need: 32768 pixels) keeps the kernels
+    over the dense plane, forced or not.  Stream, symbols, histogram and the slot counts against the
+    oracle and the model; then a device batch of three -- the picture, an ordinary frame, the picture --
+    so that slots written past a segment would have a neighbour (the next frame's rows, tok_cnt) to damage;
+    then the decode: the reference rejects its own streams of these pictures (trap T2), and so must the
+    engine, and with fix_t2 it gives the oracle's pixels."""
+    import torch
+    h = tm.crafted_height(w)
+    img = tm.crafted(variant, w, h)
+    lay = himg_amd.tok_layout(w, h, 4, row_tokens=1)
+    assert lay["tokens"] == (w <= 20480)
+    want, tr = ol.oracle_encode(img, 100, False, trace=True)
+    eng = himg_amd.Engine(0)
+    eng.profile(True)
+    for mode in (1, 2):
+        eng.set_option("row_tokens", mode)
+        eng.profile_reset()
+        got = eng.encode(img, 100, False)
+        stages = eng.profile_read()
+        if lay["tokens"]:
+            assert "k_tok" in stages and "k_emit_tok" in stages and "k_tok_hist" not in stages, sorted(stages)
+        else:
+            assert "k_tok_hist" in stages and "k_emit" in stages, sorted(stages)
+            assert "k_tok" not in stages and "k_emit_tok" not in stages, sorted(stages)
+        assert got.size == want.size and np.array_equal(got, want), (variant, w, mode)
+        if lay["tokens"]:
+            _check_slots(eng, 0, tr, w, h, (variant, w, mode))
+        assert np.array_equal(eng.debug_read("fres_sym", 0, tr["fres_sym"].size), tr["fres_sym"]), (variant, w, mode)
+        assert np.array_equal(eng.debug_read("fres_hist", 0, 261 * 4, np.uint32), tr["fres_hist"]), (variant, w, mode)
+    # a device batch: picture, neighbour, picture
+    other = himg_amd.synth("randtile", 5, w, h)
+    want_o, tr_o = ol.oracle_encode(other, 100, False, trace=True)
+    frames = np.stack([img, other, img])
+    d_frames = torch.from_numpy(frames).cuda()
+    cap = himg_amd.max_packed_size(w, h, 4)
+    d_out = torch.zeros((3, cap), dtype=torch.uint8, device="cuda")
+    d_sizes = torch.zeros(3, dtype=torch.int32, device="cuda")
+    d_st = torch.ones(3, dtype=torch.int32, device="cuda")
+    eng.set_option("row_tokens", 1)
+    eng.encode_device(d_frames, 3, w, h, 4, 4, 100, False, d_out, cap, d_sizes, d_st)
+    torch.cuda.synchronize()
+    assert not d_st.cpu().numpy().any()
+    sizes = d_sizes.cpu().numpy()
+    for f, (wb, trf) in enumerate(((want, tr), (want_o, tr_o), (want, tr))):
+        assert int(sizes[f]) == wb.size and np.array_equal(d_out[f, : wb.size].cpu().numpy(), wb), (variant, w, "batch", f)
+        if lay["tokens"]:
+            _check_slots(eng, f, trf, w, h, (variant, w, "batch", f))
+        assert np.array_equal(eng.debug_read("fres_hist", f, 261 * 4, np.uint32), trf["fres_hist"]), (variant, w, "batch", f)
+    del d_frames, d_out
+    # the decode
+    rc, _ = ol.oracle_decode(want)
+    assert rc == -7, rc
+    rc, px = ol.oracle_decode(want, fix_t2=True)
+    assert rc == 0
+    with pytest.raises(himg_amd.HimgError) as ei:
+        eng.decode(want)
+    assert ei.value.code == himg_amd.HIMG_ERR_FORMAT
+    eng.set_option("fix_t2", 1)
+    assert np.array_equal(eng.decode(want), px), (variant, w, "pixels")
+    eng.set_option("fix_t2", 0)
+    with pytest.raises(himg_amd.HimgError) as ei:
+        eng.decode(want)
+    assert ei.value.code == himg_amd.HIMG_ERR_FORMAT
     eng.close()
 
 
