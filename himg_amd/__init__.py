@@ -234,6 +234,22 @@ class Engine:
         if rc:
             raise HimgError(rc, "%s: %s" % (what, lib().himg_hip_last_error(self._ctx).decode()))
 
+    def _batch(self, fn, what, streams, outs, frame_bytes, *mid):
+        """What the batch decodes share: streams and output buffers into ctypes arrays, the call
+        fn(ctx, streams, sizes, n, *mid, outs, capacities, widths, heights, channels), the results as
+        (h, w, c) views of the buffers.  frame_bytes(i, stream): the size of a missing buffer (0 for a
+        stream that cannot be sized: its frame fails in the call)."""
+        n = len(streams)
+        if outs is None:
+            outs = [np.empty(max(frame_bytes(i, s_) or 0, 1), np.uint8) for i, s_ in enumerate(streams)]
+        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
+        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
+        self._check(fn(self._ctx, src, szs, n, *mid, dst, caps, ws, hs, cs), what)
+        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
     # host-buffer API ---------------------------------------------------------
     def encode(self, img, quality=50, use_ycbcr=True, channels=None, pixel_stride=None):
         """himg_hip_encode_to + himg_hip_fetch_last: the stream is fetched into an
@@ -257,10 +273,9 @@ class Engine:
         packed = np.ascontiguousarray(np.frombuffer(packed, np.uint8) if isinstance(packed, (bytes, bytearray)) else packed)
         w, h, c = C.c_int(), C.c_int(), C.c_int()
         dst, cap = None, 0
-        if lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(w), C.byref(h), C.byref(c)) == HIMG_OK:
-            n = w.value * h.value * c.value
-            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
-                out = np.empty(n, np.uint8)
+        geom = _peek(packed)
+        if geom:
+            out = _out_buffer(out, geom[0] * geom[1] * geom[2])
             dst, cap = out.ctypes.data, out.nbytes
         rc = lib().himg_hip_decode_to(self._ctx, packed.ctypes.data, packed.nbytes, dst, cap,
                                       C.byref(w), C.byref(h), C.byref(c))
@@ -292,21 +307,11 @@ class Engine:
         reusable uint8 buffers large enough for the pixels."""
         streams = [np.ascontiguousarray(np.frombuffer(s, np.uint8) if isinstance(s, (bytes, bytearray)) else s)
                    for s in streams]
-        n = len(streams)
-        if outs is None:
-            outs = []
-            for s_ in streams:
-                w, h, c = C.c_int(), C.c_int(), C.c_int()
-                ok = lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(w), C.byref(h), C.byref(c)) == HIMG_OK
-                outs.append(np.empty(w.value * h.value * c.value if ok else 1, np.uint8))
-        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
-        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = lib().himg_hip_decode_batch(self._ctx, src, szs, n, dst, caps, ws, hs, cs)
-        self._check(rc, "decode_batch")
-        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+
+        def frame_bytes(i, s_):
+            geom = _peek(s_)
+            return geom and geom[0] * geom[1] * geom[2]
+        return self._batch(lib().himg_hip_decode_batch, "decode_batch", streams, outs, frame_bytes)
 
     def preview(self, packed, out=None, packed_size=None):
         """1/8-scale preview (himg_hip_preview_to): the low-res picture at the front of the
@@ -320,9 +325,7 @@ class Engine:
         rc = lib().himg_hip_preview_peek(packed.ctypes.data, packed.nbytes, size, C.byref(pw), C.byref(ph), C.byref(c),
                                          C.byref(hb))
         if rc == HIMG_OK:
-            n = pw.value * ph.value * c.value
-            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
-                out = np.empty(n, np.uint8)
+            out = _out_buffer(out, pw.value * ph.value * c.value)
             dst, cap = out.ctypes.data, out.nbytes
         elif rc != HIMG_ERR_FORMAT:
             # himg_hip_preview_to reads head_bytes from `packed` (its precondition): an array that
@@ -340,24 +343,14 @@ class Engine:
     def preview_batch(self, streams, outs=None):
         """himg_hip_preview_batch: the previews of several streams (frames of one geometry
         share device launches of up to 256 frames); `outs` (optional) are reusable uint8 buffers."""
-        streams = [_as_u8(s_) for s_ in streams]
-        n = len(streams)
-        if outs is None:
-            outs = []
-            for s_ in streams:
-                try:
-                    pw, ph, c, _ = preview_peek(s_)
-                    outs.append(np.empty(pw * ph * c, np.uint8))
-                except HimgError:
-                    outs.append(np.empty(1, np.uint8))
-        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
-        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = lib().himg_hip_preview_batch(self._ctx, src, szs, n, dst, caps, ws, hs, cs)
-        self._check(rc, "preview_batch")
-        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+        def frame_bytes(i, s_):
+            try:
+                pw, ph, c, _ = preview_peek(s_)
+                return pw * ph * c
+            except HimgError:
+                return 0
+        return self._batch(lib().himg_hip_preview_batch, "preview_batch", [_as_u8(s_) for s_ in streams], outs,
+                           frame_bytes)
 
     def preview_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_out,
                        d_status, stream=0):
@@ -376,12 +369,11 @@ class Engine:
         packed = _as_u8(packed)
         wo, ho, c = C.c_int(), C.c_int(), C.c_int()
         dst, cap = None, 0
-        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-        if lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK:
-            n = max(int(w), 0) * max(int(h), 0) * cc.value
-            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
-                out = np.empty(max(n, 1), np.uint8)
-            dst, cap = out.ctypes.data, n
+        geom = _peek(packed)
+        if geom:
+            cap = max(int(w), 0) * max(int(h), 0) * geom[2]
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
         rc = lib().himg_hip_decode_region_to(self._ctx, packed.ctypes.data, packed.nbytes, int(x), int(y), int(w), int(h),
                                              dst, cap, C.byref(wo), C.byref(ho), C.byref(c))
         self._check(rc, "decode_region")
@@ -403,22 +395,9 @@ class Engine:
         the window size share device launches of up to 256 frames; only each stream's head and the
         block rows its rectangle touches are uploaded).  `outs` (optional) are reusable uint8 buffers."""
         streams = [_as_u8(s_) for s_ in streams]
-        n = len(streams)
-        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
-        if outs is None:
-            outs = []
-            for s_, (_, _, w, h) in zip(streams, rc_):
-                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-                ok = lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK
-                outs.append(np.empty(max(max(int(w), 0) * max(int(h), 0) * cc.value, 1) if ok else 1, np.uint8))
-        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
-        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = lib().himg_hip_decode_regions_batch(self._ctx, src, szs, n, rc_.ctypes.data, dst, caps, ws, hs, cs)
-        self._check(rc, "decode_regions")
-        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(len(streams), 4))
+        return self._batch(lib().himg_hip_decode_regions_batch, "decode_regions", streams, outs, _window_bytes(rc_),
+                           rc_.ctypes.data)
 
     def decode_regions_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, origins, w, h,
                               d_out, d_status, stream=0):
@@ -439,14 +418,12 @@ class Engine:
         packed = _as_u8(packed)
         wo, ho, c = C.c_int(), C.c_int(), C.c_int()
         dst, cap = None, 0
-        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-        if (scale_log2 in (1, 2) and
-                lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK):
-            ow, oh = scaled_size(ww.value, hh.value, scale_log2)
-            n = ow * oh * cc.value
-            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
-                out = np.empty(max(n, 1), np.uint8)
-            dst, cap = out.ctypes.data, n
+        geom = _peek(packed) if scale_log2 in (1, 2) else None
+        if geom:
+            ow, oh = scaled_size(geom[0], geom[1], scale_log2)
+            cap = ow * oh * geom[2]
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
         rc = lib().himg_hip_decode_scaled_to(self._ctx, packed.ctypes.data, packed.nbytes, int(scale_log2), dst, cap,
                                              C.byref(wo), C.byref(ho), C.byref(c))
         self._check(rc, "decode_scaled")
@@ -456,25 +433,14 @@ class Engine:
         """himg_hip_decode_scaled_batch: several streams at 1/2 or 1/4 scale (frames of one
         geometry share device launches of up to 256 frames); `outs` (optional) are reusable uint8
         buffers."""
-        streams = [_as_u8(s_) for s_ in streams]
-        n = len(streams)
-        if outs is None:
-            outs = []
-            for s_ in streams:
-                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-                ok = (scale_log2 in (1, 2) and
-                      lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK)
-                if ok:
-                    ow, oh = scaled_size(ww.value, hh.value, scale_log2)
-                outs.append(np.empty(max(ow * oh * cc.value, 1) if ok else 1, np.uint8))
-        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
-        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = lib().himg_hip_decode_scaled_batch(self._ctx, src, szs, n, int(scale_log2), dst, caps, ws, hs, cs)
-        self._check(rc, "decode_scaled_batch")
-        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+        def frame_bytes(i, s_):
+            geom = _peek(s_) if scale_log2 in (1, 2) else None
+            if not geom:
+                return 0
+            ow, oh = scaled_size(geom[0], geom[1], scale_log2)
+            return ow * oh * geom[2]
+        return self._batch(lib().himg_hip_decode_scaled_batch, "decode_scaled_batch", [_as_u8(s_) for s_ in streams],
+                           outs, frame_bytes, int(scale_log2))
 
     def decode_scaled_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, scale_log2,
                              d_out, d_status, stream=0):
@@ -494,12 +460,11 @@ class Engine:
         packed = _as_u8(packed)
         wo, ho, c = C.c_int(), C.c_int(), C.c_int()
         dst, cap = None, 0
-        ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-        if lib().himg_hip_peek(packed.ctypes.data, packed.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK:
-            n = max(int(w), 0) * max(int(h), 0) * cc.value
-            if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
-                out = np.empty(max(n, 1), np.uint8)
-            dst, cap = out.ctypes.data, n
+        geom = _peek(packed)
+        if geom:
+            cap = max(int(w), 0) * max(int(h), 0) * geom[2]
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
         rc = lib().himg_hip_decode_scaled_region_to(self._ctx, packed.ctypes.data, packed.nbytes, int(scale_log2), int(x),
                                                     int(y), int(w), int(h), dst, cap, C.byref(wo), C.byref(ho),
                                                     C.byref(c))
@@ -513,23 +478,9 @@ class Engine:
         stream's head and the block rows its rectangle touches are uploaded).  `outs` (optional) are
         reusable uint8 buffers."""
         streams = [_as_u8(s_) for s_ in streams]
-        n = len(streams)
-        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(n, 4))
-        if outs is None:
-            outs = []
-            for s_, (_, _, w, h) in zip(streams, rc_):
-                ww, hh, cc = C.c_int(), C.c_int(), C.c_int()
-                ok = lib().himg_hip_peek(s_.ctypes.data, s_.nbytes, C.byref(ww), C.byref(hh), C.byref(cc)) == HIMG_OK
-                outs.append(np.empty(max(max(int(w), 0) * max(int(h), 0) * cc.value, 1) if ok else 1, np.uint8))
-        src = (C.c_void_p * n)(*[s_.ctypes.data for s_ in streams])
-        szs = (C.c_size_t * n)(*[s_.nbytes for s_ in streams])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        ws, hs, cs = (C.c_int * n)(), (C.c_int * n)(), (C.c_int * n)()
-        rc = lib().himg_hip_decode_scaled_regions_batch(self._ctx, src, szs, n, int(scale_log2), rc_.ctypes.data, dst,
-                                                        caps, ws, hs, cs)
-        self._check(rc, "decode_scaled_regions")
-        return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
+        rc_ = np.ascontiguousarray(np.asarray(rects, np.int32).reshape(len(streams), 4))
+        return self._batch(lib().himg_hip_decode_scaled_regions_batch, "decode_scaled_regions", streams, outs,
+                           _window_bytes(rc_), int(scale_log2), rc_.ctypes.data)
 
     def decode_scaled_regions_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, scale_log2,
                                      origins, w, h, d_out, d_status, stream=0):
@@ -860,6 +811,29 @@ def scaled_region_peek(packed, scale_log2, x, y, w, h, fix_t2=False):
 
 def _as_u8(x):
     return np.ascontiguousarray(np.frombuffer(x, np.uint8) if isinstance(x, (bytes, bytearray)) else x, np.uint8)
+
+
+def _peek(a):
+    """himg_hip_peek of a uint8 array: (width, height, channels), or None for a stream it rejects."""
+    w, h, c = C.c_int(), C.c_int(), C.c_int()
+    if lib().himg_hip_peek(a.ctypes.data, a.nbytes, C.byref(w), C.byref(h), C.byref(c)) != HIMG_OK:
+        return None
+    return w.value, h.value, c.value
+
+
+def _out_buffer(out, n):
+    """The output buffer of a single-stream decode of n bytes: `out` when it fits, else a new array."""
+    if out is None or out.nbytes != n or not out.flags["C_CONTIGUOUS"] or out.dtype != np.uint8:
+        out = np.empty(max(n, 1), np.uint8)
+    return out
+
+
+def _window_bytes(rects):
+    """frame_bytes (Engine._batch) of window decodes: rects[i] = (x, y, w, h)."""
+    def frame_bytes(i, s_):
+        geom = _peek(s_)
+        return geom and max(int(rects[i][2]), 0) * max(int(rects[i][3]), 0) * geom[2]
+    return frame_bytes
 
 
 def index_host(packed, fix_t2=False):

@@ -265,18 +265,24 @@ constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                     const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
                     hipStream_t stream, Profiler *prof);
-// The region decode (k_dec_region): the window w x h at frame f's own origin (x_f, y_f) =
-// org[2 f], org[2 f + 1] (h_org on the host, d_org the same on the device, both in range), every
-// frame of the batch.  The head phase of the full decode (zeroing, k_dec_parse, the LRES chain),
+// The region decode (scale_log2 = 0, k_dec_region): the window w x h at frame f's own origin
+// (x_f, y_f) = org[2 f], org[2 f + 1] (h_org on the host, d_org the same on the device, both in range),
+// every frame of the batch.  The head phase of the full decode (zeroing, k_dec_parse, the LRES chain),
 // each frame's row index up to its block row r1_f = ceil((y_f + h) / 8) (d_row_index: given for
 // rows [y_f / 8, r1_f) of each frame at 2 f rows words, k_region_set_index; else k_region_rowwalk
 // stopping there, or walking on to the end of the chunk when r1_f is the last row; on ds->side
 // beside the head phase when ds is given), the counts of each frame's rows [y_f / 8, r1_f), then
 // the region kernel: batch x h x w x C interleaved bytes at d_out (frame f at f h w C).  No FRES
 // symbol plane, no quarter records.
+// The scaled region decode (scale_log2 = 1, 2, k_dec_scaled_region): the window w x h of the picture
+// at 1 / 2^scale_log2, frame f's window at its own origin (x_f, y_f) in that picture.  h_org / d_org:
+// the origins of the full-resolution rectangles the windows cover, (F x_f, F y_f), F = 2^scale_log2 --
+// what the walk and count kernels take, here with the height F h; the caller has checked
+// x_f + w <= ceil(W / F) and y_f + h <= ceil(H / F).  The same head phase, walk and counts, then the
+// scaled kernel over the touched block rows and tile columns.
 void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
-                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
+                   int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
                    const DecStreams *ds);
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
@@ -291,17 +297,6 @@ void launch_scaled(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
 // Widest column strip of the scaled kernel, in tiles (its LDS holds C x S x S segments of a strip).
 int scaled_strip_tiles(const Geom &g, int scale_log2);
-// The scaled region decode (k_dec_scaled_region): the window w x h of the picture at
-// 1 / 2^scale_log2 (1 or 2), frame f's window at its own origin (x_f, y_f) in that picture.
-// h_org / d_org: the origins of the full-resolution rectangles the windows cover, (F x_f, F y_f),
-// F = 2^scale_log2 -- what launch_region's walk and count kernels take, here with the height F h;
-// the caller has checked x_f + w <= ceil(W / F) and y_f + h <= ceil(H / F).  launch_region's
-// head phase, walk (d_row_index as there) and counts, then the scaled kernel over the touched
-// block rows and tile columns: batch x h x w x C interleaved bytes at d_out (frame f at f h w C).
-void launch_scaled_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
-                          const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org,
-                          const int32_t *d_org, int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status,
-                          hipStream_t stream, Profiler *prof, const DecStreams *ds);
 // The row-header walk of one frame alone (row-sharded decode: beside the head phase).
 void launch_rowwalk_only(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
                          const uint32_t *d_sizes, hipStream_t stream);

@@ -574,7 +574,9 @@ static int wide_q_hint(const Geom &g, uint32_t max_packed_size) {
 // the LRES stream's tables only; d_sizes holds the packed sizes, then where each LRES chunk ends.
 // region (the region decode): no FRES symbol plane and no quarter records either; d_sizes holds the
 // packed sizes, then each frame's origin (x, y).
-static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool head_only = false, bool region = false) {
+enum DecWsKind { kWsFull, kWsHead, kWsRegion };
+static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind kind) {
+  const bool head_only = kind == kWsHead, region = kind == kWsRegion;
   DecWs &w = ctx->dec_ws;
   ctx->head.valid = false;   // whatever decode this is, it overwrites what a head phase left
   const size_t plane = round_up((size_t)g.C * g.rows * g.cols, 256);
@@ -677,9 +679,61 @@ static int status_to_code(int32_t st) {
   }
 }
 
+// A device status as the host API reports it: the reference's message for a format error, else `what`.
+static int status_error(himg_hip_ctx *ctx, int32_t st, const char *what = "device decode reported an error") {
+  const int code = status_to_code(st);
+  if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
+  else fail(ctx, code, what);
+  return code;
+}
+
 // ---------------------------------------------------------------------------
 // Device-resident API.
 // ---------------------------------------------------------------------------
+// The preamble of every decode entry point, in two steps: the checks, which touch nothing, then the
+// reservation.  (Two, because decode_device and decode_walk_ranges_device have a check of their own
+// between them: nothing is reserved before every check has passed.)
+//
+// The checks: the geometry with the context's settings, the grid limit (kWsHead: the preview's, whose
+// grids are the low-res plane's) and the alignment rule -- in_stride given: a batch at that stride,
+// else one stream.  bad: what the call site found wrong with its own arguments (a row range, a
+// rectangle), reported behind a bad geometry.
+static int decode_args(himg_hip_ctx *ctx, int width, int height, int num_channels, int batch, DecWsKind kind,
+                       const void *d_packed, const void *d_out, const size_t *in_stride, const char *bad, Geom *g) {
+  if (!make_geom(width, height, num_channels, num_channels, 1, g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  apply_settings(ctx, g);
+  if (bad) return fail(ctx, HIMG_ERR_ARG, bad);
+  if ((kind == kWsHead ? g->mrows : g->rows + 1) > 65535 || batch * g->C > 65535)
+    return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if ((in_stride && (*in_stride & 3)) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
+    return fail(ctx, HIMG_ERR_ARG, in_stride ? "in_stride must be a multiple of 4; buffers 16-byte aligned"
+                                             : "buffers must be 16-byte aligned");
+  return HIMG_OK;
+}
+
+// The reservation: the device, the workspace, the caller's stream as the context's last one, and the
+// packed sizes (org: with each frame's origin, see stage_sizes) on their way to *d_sizes.
+static int decode_begin(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind kind, const uint32_t *h_sizes,
+                        void *stream, const uint32_t **d_sizes, const int32_t *org = nullptr) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (int rc = ensure_dec_ws(ctx, g, batch, kind)) return rc;
+  ctx->last_stream = (hipStream_t)stream;
+  if (int rc = stage_sizes(ctx, h_sizes, batch, ctx->last_stream, org)) return rc;
+  *d_sizes = (const uint32_t *)ctx->d_sizes.p;
+  return HIMG_OK;
+}
+
+static int stride_covers(himg_hip_ctx *ctx, const uint32_t *h_sizes, int batch, size_t in_stride) {
+  for (int i = 0; i < batch; ++i)
+    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
+      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
+  return HIMG_OK;
+}
+
+static const char *bad_row_range(int height, int row0, int row1) {
+  return row0 < 0 || row1 < row0 || row1 > ((height + 7) >> 3) ? "bad row range" : nullptr;
+}
+
 __global__ void k_copy_status(const int32_t *src, int32_t *dst, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) dst[i] = src[i];
@@ -724,27 +778,14 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
-  if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
-    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
-  for (int i = 0; i < batch; ++i)
-    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
-      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, batch);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, h_sizes, batch, s);
-  if (rc) return rc;
-  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride,
-                (const uint32_t *)ctx->d_sizes.p, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0,
-                g.rows);
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
+  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
+                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -755,27 +796,17 @@ extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_pack
                                            void *stream) {
   if (!ctx || !d_packed || !d_out_rows || !d_status) return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, d_out_rows, nullptr,
+                           bad_row_range(height, row0, row1), &g))
+    return rc;
   g.wide_q = wide_q_hint(g, packed_size);
-  if (row0 < 0 || row1 < row0 || row1 > g.rows) return fail(ctx, HIMG_ERR_ARG, "bad row range");
-  if (g.rows + 1 > 65535 || g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out_rows & 15))
-    return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   // The kernels address pixel rows of the whole frame; hand them a virtual frame
   // base so that block row row0 lands at the start of d_out_rows.
   uint8_t *base = (uint8_t *)d_out_rows - (size_t)8 * row0 * g.W * g.C;
-  launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->opts,
-                ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1);
+  launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4, d_sizes, base, d_status,
+                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -790,20 +821,13 @@ extern "C" int himg_hip_decode_index_device(himg_hip_ctx *ctx, const void *d_pac
                                             int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !d_row_index || !d_rows_first || !d_status) return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, nullptr, nullptr, nullptr, &g))
+    return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->opts,
+                d_sizes, nullptr, d_status, s, &ctx->prof, ctx->opts,
                 nullptr, 0, g.rows, nullptr, true);
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index, ctx->dec_ws.row_off, (size_t)g.rows * 4, hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index + g.rows, ctx->dec_ws.row_len, (size_t)g.rows * 4,
@@ -820,25 +844,16 @@ static int decode_rows_indexed(himg_hip_ctx *ctx, const void *d_packed, uint32_t
                                int height, int num_channels, int row0, int row1, const uint32_t *d_row_index,
                                void *d_out_rows, int32_t *d_status, void *stream, int phase) {
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, d_out_rows, nullptr,
+                           bad_row_range(height, row0, row1), &g))
+    return rc;
   g.wide_q = wide_q_hint(g, packed_size);
-  if (row0 < 0 || row1 < row0 || row1 > g.rows) return fail(ctx, HIMG_ERR_ARG, "bad row range");
-  if (g.rows + 1 > 65535 || g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if (((uintptr_t)d_packed & 15) || ((uintptr_t)d_out_rows & 15))
-    return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   uint8_t *base = d_out_rows ? (uint8_t *)d_out_rows - (size_t)8 * row0 * g.W * g.C : nullptr;
-  launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, base, d_status, s, &ctx->prof, ctx->opts,
-                ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1, d_row_index, false, phase);
+  launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4, d_sizes, base, d_status,
+                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, row0, row1,
+                d_row_index, false, phase);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -900,25 +915,18 @@ extern "C" int himg_hip_decode_walk_device(himg_hip_ctx *ctx, const void *d_pack
                                            uint32_t *d_rows_first, int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !d_row_index || !d_rows_first || !d_status) return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, nullptr, nullptr, nullptr, &g))
+    return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
   hipStream_t w = ctx->opts.use_side ? ctx->dstr.side : s;
   if (w != s) {
     HIP_TRY(ctx, hipEventRecord(ctx->dstr.ev_fork, s));
     HIP_TRY(ctx, hipStreamWaitEvent(w, ctx->dstr.ev_fork, 0));
   }
   himg_dev::launch_rowwalk_only(g, ctx->dec_ws, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                                (const uint32_t *)ctx->d_sizes.p, w);
+                                d_sizes, w);
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index, ctx->dec_ws.row_off, (size_t)g.rows * 4, hipMemcpyDeviceToDevice, w));
   HIP_TRY(ctx, hipMemcpyAsync(d_row_index + g.rows, ctx->dec_ws.row_len, (size_t)g.rows * 4, hipMemcpyDeviceToDevice, w));
   HIP_TRY(ctx, hipMemcpyAsync(d_rows_first, &ctx->dec_ws.frames[0].rows_first, 4, hipMemcpyDeviceToDevice, w));
@@ -935,22 +943,15 @@ extern "C" int himg_hip_decode_walk_ranges_device(himg_hip_ctx *ctx, const void 
       n_ranges > HIMG_MAX_WALK_RANGES)
     return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, nullptr, nullptr, nullptr, &g))
+    return rc;
   for (int k = 0; k < n_ranges; ++k)
     if (range_end[k] < 0 || (k && range_end[k] < range_end[k - 1])) return fail(ctx, HIMG_ERR_ARG, "range ends must ascend");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   for (int k = 0; k < n_ranges; ++k)
     if (!ctx->ev_range[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_range[k], hipEventDisableTiming));
   hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
   hipStream_t w = ctx->opts.use_side ? ctx->dstr.side : s;
   if (w != s) {
     HIP_TRY(ctx, hipEventRecord(ctx->dstr.ev_fork, s));
@@ -961,7 +962,7 @@ extern "C" int himg_hip_decode_walk_ranges_device(himg_hip_ctx *ctx, const void 
     const bool last = k + 1 == n_ranges || range_end[k] >= g.rows;
     const int upto = last ? g.rows : range_end[k];
     himg_dev::launch_rowwalk_range(g, ctx->dec_ws, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                                   (const uint32_t *)ctx->d_sizes.p, last ? 0x7fffffff : upto, k > 0, w);
+                                   d_sizes, last ? 0x7fffffff : upto, k > 0, w);
     if (upto > done) {
       HIP_TRY(ctx, hipMemcpyAsync(d_row_index + done, ctx->dec_ws.row_off + done, (size_t)(upto - done) * 4, hipMemcpyDeviceToDevice, w));
       HIP_TRY(ctx, hipMemcpyAsync(d_row_index + g.rows + done, ctx->dec_ws.row_len + done, (size_t)(upto - done) * 4, hipMemcpyDeviceToDevice, w));
@@ -1007,20 +1008,13 @@ extern "C" int himg_hip_decode_first_device(himg_hip_ctx *ctx, const void *d_pac
                                             int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !d_rows_first || !d_status) return HIMG_ERR_ARG;
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows + 1 > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((uintptr_t)d_packed & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, 1);
-  if (rc) return rc;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, 1, kWsFull, d_packed, nullptr, nullptr, nullptr, &g))
+    return rc;
+  if (int rc = decode_begin(ctx, g, 1, kWsFull, &packed_size, stream, &d_sizes)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, &packed_size, 1, s);
-  if (rc) return rc;
   launch_decode(g, ctx->dec_ws, 1, (const uint8_t *)d_packed, ((size_t)packed_size + 3) / 4 * 4,
-                (const uint32_t *)ctx->d_sizes.p, nullptr, d_status, s, &ctx->prof, ctx->opts,
+                d_sizes, nullptr, d_status, s, &ctx->prof, ctx->opts,
                 nullptr, 0, 0, nullptr, true);
   HIP_TRY(ctx, hipMemcpyAsync(d_rows_first, &ctx->dec_ws.frames[0].rows_first, 4, hipMemcpyDeviceToDevice, s));
   HIP_TRY(ctx, hipGetLastError());
@@ -1044,14 +1038,12 @@ static bool host_find_chunk(const uint8_t *p, size_t n, size_t *idx, uint32_t ta
   }
 }
 
-extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, int fix_t2, int *width,
-                                   int *height, int *num_channels, uint32_t *row_index,
-                                   size_t index_rows, uint32_t *rows_first) {
-  if (!packed || !width || !height || !num_channels || !rows_first) return HIMG_ERR_ARG;
-  int rc = himg_hip_peek(packed, packed_size, width, height, num_channels);
-  if (rc) return rc;
-  const size_t rows = ((size_t)*height + 7) / 8;
-  if (!row_index || index_rows < rows) return HIMG_ERR_CAPACITY;
+// The walk behind every host index and region plan: the chunk search to FRES, the length of the
+// serialised tree, then the row headers of rows 0 .. row1-1 (to the end of the chunk when row1 is the
+// last row: the reference's Init walks them all).  plan: head_bytes, and rows_begin / rows_end of rows
+// row0 .. row1-1; row_index (2 x rows words, or nullptr): their offsets and lengths.
+static int host_walk(const uint8_t *packed, size_t packed_size, int fix_t2, int rows, int row0, int row1,
+                     himg_hip_region_plan *plan, uint32_t *row_index) {
   static const uint32_t tags[6] = {0x544d5246u, 0x50414d4cu, 0x5345524cu, 0x47464351u, 0x50414d46u, 0x53455246u};
   size_t idx = 12;
   uint32_t sz = 0;
@@ -1079,15 +1071,16 @@ extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, in
   }
   size_t q = coff + ((bit + 7) >> 3);
   if (q >= end) return HIMG_ERR_FORMAT;
-  *rows_first = (uint32_t)q;
-  if (fix_t2 && rows == 1) {
-    row_index[0] = (uint32_t)q;
-    row_index[rows] = (uint32_t)(end - q);
+  plan->head_bytes = q;
+  if (fix_t2 && rows == 1) {   // one block row without a size header
+    plan->rows_begin = q; plan->rows_end = end;
+    if (row_index) { row_index[0] = (uint32_t)q; row_index[rows] = (uint32_t)(end - q); }
     return HIMG_OK;
   }
-  size_t r = 0;
-  while (q != end) {
+  int r = 0;
+  while (q != end && (r < row1 || row1 == rows)) {
     if (q + 2 > end) return HIMG_ERR_FORMAT;
+    const size_t hdr = q;
     uint32_t len = packed[q] | (packed[q + 1] << 8);
     q += 2;
     if (len & 0x8000u) {
@@ -1096,11 +1089,27 @@ extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, in
       q += 2;
     }
     if (len > end - q) return HIMG_ERR_FORMAT;
-    if (r < rows) { row_index[r] = (uint32_t)q; row_index[rows + r] = len; }
+    if (r == row0) plan->rows_begin = hdr;
+    if (r == row1 - 1) plan->rows_end = q + len;
+    if (row_index && r >= row0 && r < row1) { row_index[r] = (uint32_t)q; row_index[rows + r] = len; }
     ++r;
     q += len;
   }
-  return r < rows ? HIMG_ERR_FORMAT : HIMG_OK;
+  return r < row1 || (row1 == rows && r < rows) ? HIMG_ERR_FORMAT : HIMG_OK;
+}
+
+extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, int fix_t2, int *width,
+                                   int *height, int *num_channels, uint32_t *row_index,
+                                   size_t index_rows, uint32_t *rows_first) {
+  if (!packed || !width || !height || !num_channels || !rows_first) return HIMG_ERR_ARG;
+  int rc = himg_hip_peek(packed, packed_size, width, height, num_channels);
+  if (rc) return rc;
+  const int rows = (*height + 7) / 8;
+  if (!row_index || index_rows < (size_t)rows) return HIMG_ERR_CAPACITY;
+  himg_hip_region_plan plan = himg_hip_region_plan();
+  rc = host_walk(packed, packed_size, fix_t2, rows, 0, rows, &plan, row_index);   // (the whole frame)
+  if (plan.head_bytes) *rows_first = (uint32_t)plan.head_bytes;
+  return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -1218,13 +1227,41 @@ extern "C" int himg_hip_peek(const uint8_t *packed, size_t packed_size, int *wid
   return HIMG_OK;
 }
 
+// What the host entry points check of a stream (nullptr: a batch's missing one) before they plan its
+// decode: the header, with the reference's message, and the engine's limits.  The host only needs the
+// geometry to size the launch; every check is repeated on the device (k_dec_parse).
+static int stream_geom(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int *W, int *H, int *C, Geom *g) {
+  if (const char *msg = packed ? parse_header(packed, packed_size, W, H, C) : "Not a RIFF HIMG file.\n")
+    return fail(ctx, HIMG_ERR_FORMAT, msg);
+  if (!make_geom(*W, *H, *C, *C, 1, g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  return HIMG_OK;
+}
+
+// The pinned staging of host row indices (decode_core, staged_launch), n_idx dwords.
+static int reserve_hp_index(himg_hip_ctx *ctx, size_t n_idx) {
+  if (ctx->hp_index_cap >= n_idx) return HIMG_OK;
+  if (ctx->hp_index) hipHostFree(ctx->hp_index);
+  ctx->hp_index = nullptr;
+  ctx->hp_index_cap = 0;
+  if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
+    return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
+  ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
+  return HIMG_OK;
+}
+
+// A stream (or its first n bytes) into the staging slot [d, d + slot): the row kernels read whole dwords
+// and a few dwords ahead, so nothing of a stream staged before may lie behind this one -- zeros from
+// the last 16-byte boundary to the end of the slot, then the bytes.  On the null stream.
+static int upload_zero_tail(himg_hip_ctx *ctx, uint8_t *d, size_t slot, const uint8_t *src, size_t n) {
+  HIP_TRY(ctx, hipMemsetAsync(d + (n & ~(size_t)15), 0, slot - (n & ~(size_t)15), nullptr));
+  HIP_TRY(ctx, hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, nullptr));
+  return HIMG_OK;
+}
+
 static int decode_core(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int *W, int *H,
                        int *C) {
-  // The host only needs the geometry to size the launch; every check is repeated
-  // on the device (k_dec_parse).
-  if (const char *msg = parse_header(packed, packed_size, W, H, C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
   Geom g;
-  if (!make_geom(*W, *H, *C, *C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  if (int rc = stream_geom(ctx, packed, packed_size, W, H, C, &g)) return rc;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t in_cap = round_up(packed_size + 16, 256);
   const size_t out_bytes = (size_t)*W * *H * *C;
@@ -1232,43 +1269,27 @@ static int decode_core(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_s
       !ctx->h_status.reserve(256))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   ctx->host_bytes = 0;
-  // (The row kernels read whole dwords and a few dwords ahead: nothing of the stream decoded
-  // before may lie behind this one.)
-  // (Everything below is ordered on the null stream, which the decode runs on; the one wait of
-  // this call is the read of the verdict at the end.)
-  HIP_TRY(ctx, hipMemsetAsync((uint8_t *)ctx->h_in.p + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_in.p, packed, packed_size, hipMemcpyHostToDevice, nullptr));
-  const uint32_t sz32 = (uint32_t)packed_size;
   // The stream is in host memory: the FRES rows are indexed HERE -- the walk over the row
   // size headers (huffman_dec.cpp:232-248) is a chain of dependent reads, microseconds on
   // a CPU and 0.24 ms of a 0.41 ms decode as k_dec_rowwalk's 512 dependent HBM loads -- and
-  // the index goes up with the stream.  A stream the host walk does not accept (damaged
-  // headers, a geometry it does not index) takes the device walk, which words the verdict.
+  // the index goes up with the stream, from a pinned buffer the context keeps (this call returns
+  // only after the decode that reads its copy has finished).  A stream the host walk does not
+  // accept (damaged headers, a geometry it does not index) takes the device walk, which words the
+  // verdict.
+  const size_t n_idx = 2 * (size_t)g.rows;
+  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  // (Everything below is ordered on the null stream, which the decode runs on; the one wait of
+  // this call is the read of the verdict at the end.)
+  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
+  const uint32_t sz32 = (uint32_t)packed_size;
   int rc = -1;
-  {
-    // The index is written into a pinned buffer the context keeps (this call returns only after
-    // the decode that reads its copy has finished) and goes up asynchronously.
-    const size_t n_idx = 2 * (size_t)g.rows;
-    if (ctx->hp_index_cap < n_idx) {
-      if (ctx->hp_index) hipHostFree(ctx->hp_index);
-      ctx->hp_index = nullptr;
-      ctx->hp_index_cap = 0;
-      // (An error return from here on first waits for the uploads above: the caller may free or
-      // overwrite `packed` the moment this call returns.)
-      if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess) {
-        (void)hipStreamSynchronize(nullptr);
-        return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
-      }
-      ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
-    }
-    uint32_t first = 0;
-    int w2 = 0, h2 = 0, c2 = 0;
-    if (g.rows >= 2 && ctx->h_index.reserve(round_up(n_idx * 4, 256)) &&
-        himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows, &first) == HIMG_OK) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-      rc = himg_hip_decode_rows_indexed_device(ctx, ctx->h_in.p, sz32, *W, *H, *C, 0, g.rows, (const uint32_t *)ctx->h_index.p,
-                                               ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
-    }
+  uint32_t first = 0;
+  int w2 = 0, h2 = 0, c2 = 0;
+  if (g.rows >= 2 && ctx->h_index.reserve(round_up(n_idx * 4, 256)) &&
+      himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows, &first) == HIMG_OK) {
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+    rc = himg_hip_decode_rows_indexed_device(ctx, ctx->h_in.p, sz32, *W, *H, *C, 0, g.rows, (const uint32_t *)ctx->h_index.p,
+                                             ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
   }
   if (rc == -1)
     rc = himg_hip_decode_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, *W, *H, *C, ctx->h_out.p,
@@ -1279,14 +1300,7 @@ static int decode_core(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_s
   }
   int32_t st = 0;
   HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) {
-    const int code = status_to_code(st);
-    if (code == HIMG_ERR_FORMAT) {
-      ctx->err = format_message(st);
-      return code;
-    }
-    return fail(ctx, code, "device decode reported an error");
-  }
+  if (st) return status_error(ctx, st);
   ctx->host_bytes = out_bytes;
   return HIMG_OK;
 }
@@ -1416,9 +1430,7 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
       const int32_t st = (int32_t)p.h_meta[slot * 4 + 1];
       int err = HIMG_OK;
       if (st) {
-        err = status_to_code(st);
-        if (err == HIMG_ERR_FORMAT) ctx->err = format_message(st);
-        else fail(ctx, err, "device decode reported an error");
+        err = status_error(ctx, st);
       } else if (!dst[j] || dst_cap[j] < out_bytes[j]) {
         err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
       }
@@ -1536,20 +1548,12 @@ static int preview_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_str
                           int batch, int width, int height, int num_channels, void *d_out, int32_t *d_status,
                           void *stream) {
   Geom g;
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.mrows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
-    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, batch, true);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, h_sizes, batch, s);
-  if (rc) return rc;
-  launch_preview(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
-                 (uint32_t *)ctx->d_sizes.p + batch, (uint8_t *)d_out, d_status, s, &ctx->prof);
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsHead, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  if (int rc = decode_begin(ctx, g, batch, kWsHead, h_sizes, stream, &d_sizes)) return rc;
+  launch_preview(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint32_t *)ctx->d_sizes.p + batch,
+                 (uint8_t *)d_out, d_status, (hipStream_t)stream, &ctx->prof);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -1558,119 +1562,8 @@ extern "C" int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, 
                                        const uint32_t *h_sizes, int batch, int width, int height, int num_channels,
                                        void *d_out, int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
-  for (int i = 0; i < batch; ++i)
-    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
-      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return preview_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream);
-}
-
-// Host streams -> staging (their heads only, zero-padded to the stride) -> one device launch.
-static int preview_staged(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *heads, const uint32_t *sizes,
-                          int n, int W, int H, int C, int32_t *h_status) {
-  size_t stride = 0;
-  for (int i = 0; i < n; ++i) stride = heads[i] > stride ? heads[i] : stride;
-  stride = round_up(stride + 16, 256);
-  const size_t out_bytes = (size_t)((W + 7) / 8) * ((H + 7) / 8) * C;
-  if (!ctx->h_in.reserve(stride * n) || !ctx->h_out.reserve(round_up(out_bytes * n, 256)) ||
-      !ctx->h_status.reserve(round_up((size_t)n * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  uint8_t *in = (uint8_t *)ctx->h_in.p;
-  for (int i = 0; i < n; ++i) {
-    const size_t lo = heads[i] & ~(size_t)15;
-    HIP_TRY(ctx, hipMemsetAsync(in + (size_t)i * stride + lo, 0, stride - lo, nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(in + (size_t)i * stride, packed[i], heads[i], hipMemcpyHostToDevice, nullptr));
-  }
-  int rc = preview_launch(ctx, in, stride, sizes, n, W, H, C, ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
-  if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's buffers
-    return rc;
-  }
-  HIP_TRY(ctx, hipMemcpy(h_status, ctx->h_status.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-  return HIMG_OK;
-}
-
-static int status_error(himg_hip_ctx *ctx, int32_t st) {
-  const int code = status_to_code(st);
-  if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
-  else fail(ctx, code, "device preview reported an error");
-  return code;
-}
-
-extern "C" int himg_hip_preview_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
-                                   size_t dst_cap, int *pw, int *ph, int *channels) {
-  if (!ctx || !packed || !pw || !ph || !channels) return HIMG_ERR_ARG;
-  int W = 0, H = 0, C = 0;
-  size_t head = 0;
-  const char *msg = nullptr;
-  // (avail = packed_size: the walk stops at the end of LRES, so the caller's bytes behind it are never read)
-  int rc = preview_walk(packed, packed_size, packed_size, &W, &H, &C, &head, &msg);
-  if (rc == HIMG_ERR_FORMAT) return fail(ctx, rc, msg ? msg : "Error decoding low-res data.\n");
-  if (rc == HIMG_ERR_UNSUPPORTED) return fail(ctx, rc, "unsupported geometry");
-  if (rc) return fail(ctx, rc, "bad stream");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  const uint32_t sz32 = (uint32_t)packed_size;
-  int32_t st = 0;
-  rc = preview_staged(ctx, &packed, &head, &sz32, 1, W, H, C, &st);
-  if (rc) return rc;
-  if (st) return status_error(ctx, st);
-  *pw = (W + 7) / 8; *ph = (H + 7) / 8; *channels = C;
-  ctx->host_bytes = (size_t)*pw * *ph * C;
-  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
-}
-
-extern "C" int himg_hip_preview_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
-                                      int n, uint8_t *const *dst, const size_t *dst_cap, int *pw, int *ph,
-                                      int *channels) {
-  if (!ctx || !packed || !packed_sizes || !dst || !dst_cap || !pw || !ph || !channels || n < 0) return HIMG_ERR_ARG;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  int first_err = HIMG_OK;
-  std::vector<int> W(n), H(n), Cc(n), done(n, 0);
-  std::vector<size_t> head(n);
-  for (int i = 0; i < n; ++i) {
-    pw[i] = ph[i] = channels[i] = 0;
-    const char *msg = nullptr;
-    const int rc = packed[i] ? preview_walk(packed[i], packed_sizes[i], packed_sizes[i], &W[i], &H[i], &Cc[i], &head[i], &msg)
-                             : (msg = "Not a RIFF HIMG file.\n", HIMG_ERR_FORMAT);
-    if (rc) {
-      done[i] = 1;
-      if (!first_err) first_err = fail(ctx, rc, msg ? msg : rc == HIMG_ERR_UNSUPPORTED ? "unsupported geometry" : "bad stream");
-    }
-  }
-  // Frames that share a geometry: one launch (in the order of their first frame) of at most
-  // kPreviewLaunch frames -- the grids of the LRES kernels take batch x C <= 65535, and the staging
-  // holds one launch's heads and previews.
-  constexpr int kPreviewLaunch = 256;
-  for (int i0 = 0; i0 < n; ++i0) {
-    if (done[i0]) continue;
-    std::vector<int> grp;
-    const int lim = kPreviewLaunch < 65535 / Cc[i0] ? kPreviewLaunch : 65535 / Cc[i0];
-    for (int i = i0; i < n && (int)grp.size() < lim; ++i)
-      if (!done[i] && W[i] == W[i0] && H[i] == H[i0] && Cc[i] == Cc[i0]) { grp.push_back(i); done[i] = 1; }
-    const int m = (int)grp.size();
-    std::vector<const uint8_t *> src(m);
-    std::vector<size_t> hd(m);
-    std::vector<uint32_t> sz(m);
-    std::vector<int32_t> st(m);
-    for (int k = 0; k < m; ++k) { src[k] = packed[grp[k]]; hd[k] = head[grp[k]]; sz[k] = (uint32_t)packed_sizes[grp[k]]; }
-    const int rc = preview_staged(ctx, src.data(), hd.data(), sz.data(), m, W[i0], H[i0], Cc[i0], st.data());
-    if (rc) return rc;
-    const size_t bytes = (size_t)((W[i0] + 7) / 8) * ((H[i0] + 7) / 8) * Cc[i0];
-    for (int k = 0; k < m; ++k) {
-      const int i = grp[k];
-      int err = HIMG_OK;
-      if (st[k]) err = status_error(ctx, st[k]);
-      else if (!dst[i] || dst_cap[i] < bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-      if (err) { if (!first_err) first_err = err; continue; }
-      HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * bytes, bytes, hipMemcpyDeviceToHost, nullptr));
-      pw[i] = (W[i0] + 7) / 8; ph[i] = (H[i0] + 7) / 8; channels[i] = Cc[i0];
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-  }
-  return first_err;
 }
 
 // ---------------------------------------------------------------------------
@@ -1694,10 +1587,7 @@ static bool rect_up(int W, int H, int sl, int x, int y, int w, int h, int up[4])
   return true;
 }
 
-// himg_hip_index_host bounded at the rectangle's last block row: the chunk search, the length of
-// the FRES tree, the row headers of rows 0 .. row1-1 (to the end of the chunk when row1 is the
-// last row: the reference's Init walks them all).  row_index (2 x rows words, or nullptr): the
-// offsets and lengths of rows row0 .. row1-1.
+// The plan of rectangle (x, y, w, h): host_walk bounded at the rectangle's last block row.
 static int region_index(const uint8_t *packed, size_t packed_size, int fix_t2, int x, int y, int w, int h,
                         himg_hip_region_plan *plan, uint32_t *row_index) {
   int W = 0, H = 0, C = 0;
@@ -1705,60 +1595,8 @@ static int region_index(const uint8_t *packed, size_t packed_size, int fix_t2, i
   if (rc) return rc;
   plan->width = W; plan->height = H; plan->num_channels = C;
   if (!region_ok(W, H, x, y, w, h)) return HIMG_ERR_ARG;
-  const int rows = (H + 7) / 8, r0 = y / 8, r1 = (y + h + 7) / 8;
-  plan->row0 = r0; plan->row1 = r1;
-  static const uint32_t tags[6] = {0x544d5246u, 0x50414d4cu, 0x5345524cu, 0x47464351u, 0x50414d46u, 0x53455246u};
-  size_t idx = 12;
-  uint32_t sz = 0;
-  for (int t = 0; t < 6; ++t) {
-    if (!host_find_chunk(packed, packed_size, &idx, tags[t], &sz)) return HIMG_ERR_FORMAT;
-    if (t < 5) idx += sz;
-  }
-  const size_t coff = idx, end = idx + sz;
-  size_t bit = 0;
-  {
-    const size_t bit_end = 8 * (size_t)(sz < (uint32_t)kTreeStride ? sz : (uint32_t)kTreeStride);
-    int open = 1, count = 0;
-    while (open > 0) {
-      if (count >= 2 * kNumSym - 1 || bit >= bit_end) return HIMG_ERR_FORMAT;
-      ++count;
-      if ((packed[coff + (bit >> 3)] >> (bit & 7)) & 1) {
-        if (bit + 10 > bit_end) return HIMG_ERR_FORMAT;
-        bit += 10;
-        --open;
-      } else {
-        bit += 1;
-        ++open;
-      }
-    }
-  }
-  size_t q = coff + ((bit + 7) >> 3);
-  if (q >= end) return HIMG_ERR_FORMAT;
-  plan->head_bytes = q;
-  if (fix_t2 && rows == 1) {   // one block row without a size header
-    plan->rows_begin = q; plan->rows_end = end;
-    if (row_index) { row_index[0] = (uint32_t)q; row_index[rows] = (uint32_t)(end - q); }
-    return HIMG_OK;
-  }
-  int r = 0;
-  while (q != end && (r < r1 || r1 == rows)) {
-    if (q + 2 > end) return HIMG_ERR_FORMAT;
-    const size_t hdr = q;
-    uint32_t len = packed[q] | (packed[q + 1] << 8);
-    q += 2;
-    if (len & 0x8000u) {
-      if (q + 2 > end) return HIMG_ERR_FORMAT;
-      len = (len & 0x7fffu) | ((uint32_t)(packed[q] | (packed[q + 1] << 8)) << 15);
-      q += 2;
-    }
-    if (len > end - q) return HIMG_ERR_FORMAT;
-    if (r == r0) plan->rows_begin = hdr;
-    if (r == r1 - 1) plan->rows_end = q + len;
-    if (row_index && r >= r0 && r < r1) { row_index[r] = (uint32_t)q; row_index[rows + r] = len; }
-    ++r;
-    q += len;
-  }
-  return r < r1 || (r1 == rows && r < rows) ? HIMG_ERR_FORMAT : HIMG_OK;
+  plan->row0 = y / 8; plan->row1 = (y + h + 7) / 8;
+  return host_walk(packed, packed_size, fix_t2, (H + 7) / 8, plan->row0, plan->row1, plan, row_index);
 }
 
 extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int x, int y, int w, int h,
@@ -1771,50 +1609,31 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
 // The device launch behind every region entry point: the window w x h at frame f's origin
 // (h_org[2 f], h_org[2 f + 1]); every origin is checked before anything is launched.
 // d_row_index: the host's index, 2 x rows words per frame (rows r0_f .. r1_f - 1 filled).
-// scale_log2 = 1, 2: the window and the origins are those of the scaled picture (launch_scaled_region);
+// scale_log2 = 1, 2: the window and the origins are those of the scaled picture (k_dec_scaled_region);
 // what reaches the device are the origins of the full-resolution rectangles the windows cover.
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                          int width, int height, int num_channels, const int32_t *h_org, int w, int h,
                          const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0) {
-  Geom g;
   if (scale_log2 < 0 || scale_log2 > 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
   std::vector<int32_t> up_org;
   if (scale_log2) up_org.resize(2 * (size_t)batch);
-  for (int f = 0; f < batch; ++f) {
+  const char *bad = nullptr;
+  for (int f = 0; f < batch && !bad; ++f) {
     int up[4];
-    if (!rect_up(width, height, scale_log2, h_org[2 * f], h_org[2 * f + 1], w, h, up)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
-    if (scale_log2) { up_org[2 * f] = up[0]; up_org[2 * f + 1] = up[1]; }
+    if (!rect_up(width, height, scale_log2, h_org[2 * f], h_org[2 * f + 1], w, h, up)) bad = "bad rectangle";
+    else if (scale_log2) { up_org[2 * f] = up[0]; up_org[2 * f + 1] = up[1]; }
   }
   if (scale_log2) h_org = up_org.data();
-  if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
-    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, batch, false, true);
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, h_sizes, batch, s, h_org);   // (the origins ride with the sizes: no extra copy, no wait)
-  if (rc) return rc;
-  const uint32_t *d_sizes = (const uint32_t *)ctx->d_sizes.p;
-  if (scale_log2)
-    launch_scaled_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
-                         (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                         ctx->opts.use_side ? &ctx->dstr : nullptr);
-  else
-    launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
-                  (const int32_t *)(d_sizes + batch), w, h, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                  ctx->opts.use_side ? &ctx->dstr : nullptr);
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, bad, &g))
+    return rc;
+  // (the origins ride with the sizes: no extra copy, no wait)
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org)) return rc;
+  launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
+                (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, (hipStream_t)stream,
+                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
   HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
-}
-
-static int region_device_args(himg_hip_ctx *ctx, const uint32_t *h_sizes, int batch, size_t in_stride) {
-  for (int i = 0; i < batch; ++i)
-    if (((size_t)h_sizes[i] + 3) / 4 * 4 > in_stride)
-      return fail(ctx, HIMG_ERR_ARG, "in_stride must cover every stream rounded up to 4 bytes");
   return HIMG_OK;
 }
 
@@ -1823,7 +1642,7 @@ extern "C" int himg_hip_decode_region_device(himg_hip_ctx *ctx, const void *d_pa
                                              int num_channels, int x, int y, int w, int h, void *d_out,
                                              int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
-  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   std::vector<int32_t> org(2 * (size_t)batch);
   for (int f = 0; f < batch; ++f) { org[2 * f] = x; org[2 * f + 1] = y; }
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, org.data(), w, h, nullptr,
@@ -1836,82 +1655,291 @@ extern "C" int himg_hip_decode_regions_device(himg_hip_ctx *ctx, const void *d_p
                                               int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !h_sizes || !h_origins || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
-  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
                        d_out, d_status, stream);
 }
 
-// The pinned staging of host row indices (decode_region_to, decode_regions_batch), n_idx dwords.
-static int reserve_hp_index(himg_hip_ctx *ctx, size_t n_idx) {
-  if (ctx->hp_index_cap >= n_idx) return HIMG_OK;
-  if (ctx->hp_index) hipHostFree(ctx->hp_index);
-  ctx->hp_index = nullptr;
-  ctx->hp_index_cap = 0;
-  if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
-    return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
-  ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
+// The scaled region decode's device entry: a window of the picture at 1/2 or 1/4 scale.  A rectangle of
+// the scaled picture is planned, walked, counted and judged as the full-resolution rectangle it covers
+// (rect_up); the entries are the region decode's with a scale.
+extern "C" int himg_hip_decode_scaled_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                     const uint32_t *h_sizes, int batch, int width, int height,
+                                                     int num_channels, int scale_log2, const int32_t *h_origins,
+                                                     int w, int h, void *d_out, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_origins || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
+                       d_out, d_status, stream, scale_log2);
+}
+
+extern "C" int himg_hip_scaled_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int scale_log2, int x,
+                                           int y, int w, int h, himg_hip_region_plan *plan) {
+  if (!packed || !plan || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
+  *plan = himg_hip_region_plan();
+  int W = 0, H = 0, C = 0, up[4];
+  if (int rc = himg_hip_peek(packed, packed_size, &W, &H, &C)) return rc;
+  plan->width = W; plan->height = H; plan->num_channels = C;
+  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return HIMG_ERR_ARG;
+  return region_index(packed, packed_size, fix_t2, up[0], up[1], up[2], up[3], plan, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Scaled decode: the picture at 1/2 and 1/4 scale (kernels_dec.hip, launch_scaled).
+// ---------------------------------------------------------------------------
+extern "C" int himg_hip_scaled_size(int width, int height, int scale_log2, int *ow, int *oh) {
+  if (!ow || !oh || width < 1 || height < 1 || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
+  const int F = 1 << scale_log2;
+  *ow = (int)(((long long)width + F - 1) / F);
+  *oh = (int)(((long long)height + F - 1) / F);
   return HIMG_OK;
 }
 
-// A device status as decode_region_to reports it.
-static int region_status_error(himg_hip_ctx *ctx, int32_t st) {
-  const int code = status_to_code(st);
-  if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
-  else fail(ctx, code, "device decode reported an error");   // (himg_hip_decode's wording)
-  return code;
+// The device launch behind every scaled entry point.  d_row_index: the host's index (one frame).
+static int scaled_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
+                         int width, int height, int num_channels, int scale_log2, const uint32_t *d_row_index,
+                         void *d_out, int32_t *d_status, void *stream) {
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  // (the region decode's workspace: no FRES plane)
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes)) return rc;
+  launch_scaled(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, scale_log2,
+                (uint8_t *)d_out, d_status, (hipStream_t)stream, &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
 }
 
-// himg_hip_decode_region_to (scale_log2 = 0) and himg_hip_decode_scaled_region_to (1, 2: the rectangle
-// in the scaled picture, planned as the full-resolution rectangle it covers).
-static int region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2, int x, int y,
-                     int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels) {
-  if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
-  int W = 0, H = 0, C = 0;
-  if (const char *msg = parse_header(packed, packed_size, &W, &H, &C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
-  Geom g;
-  if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-  int up[4];
-  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  const size_t in_cap = round_up(packed_size + 16, 256);
-  const size_t out_bytes = (size_t)w * h * C;
-  const size_t n_idx = 2 * (size_t)g.rows;
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256) ||
-      !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+extern "C" int himg_hip_decode_scaled_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_sizes, int batch, int width, int height,
+                                             int num_channels, int scale_log2, void *d_out, int32_t *d_status,
+                                             void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  return scaled_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, scale_log2, nullptr, d_out,
+                       d_status, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Preview, region and scaled decodes of streams in host memory: streams of one geometry go through the
+// staging into one of the device launches above.
+// ---------------------------------------------------------------------------
+// A launch takes at most kStageLaunch frames (the grids take batch x C <= 65535); the region and scaled
+// batches keep its staging within kRegionStageBytes (one frame at least).  A stream occupies its whole
+// size there, rounded up to the launch's stride (the largest of its streams): of a region's stream only
+// the plan is uploaded, but the kernels bound their reads by the stream's size, so the rest of it must
+// be addressable.  Windows near the bottom of large frames are what fill it: their plans end near the
+// end of the stream.
+constexpr int kStageLaunch = 256;
+constexpr size_t kRegionStageBytes = (size_t)1 << 30;
+
+// What the staged entry points differ in, and one call's streams by frame.
+struct Staged {
+  enum Kind { kPreview, kRegion, kScaled } kind;
+  int scale_log2;       // kRegion: 0 (full resolution), 1, 2; kScaled: 1, 2
+  bool index;           // the host's row index goes up with the streams (kRegion: and of a stream only its plan)
+  const uint8_t *const *packed;
+  const size_t *packed_sizes;
+  const size_t *heads;    // kPreview: the bytes of a stream that go up (else all of it)
+  const int32_t *rects;   // kRegion: (x, y, w, h), in the picture at the scale
+};
+
+// A frame's output size: of geometry W x H, for kRegion the window of frame i.
+static void staged_dims(const Staged &c, int W, int H, int i, int *ow, int *oh) {
+  if (c.kind == Staged::kRegion) { *ow = c.rects[4 * (size_t)i + 2]; *oh = c.rects[4 * (size_t)i + 3]; }
+  else if (c.kind == Staged::kScaled) (void)himg_hip_scaled_size(W, H, c.scale_log2, ow, oh);
+  else { *ow = (W + 7) / 8; *oh = (H + 7) / 8; }
+}
+
+static int staged_error(himg_hip_ctx *ctx, const Staged &c, int32_t st) {
+  return status_error(ctx, st, c.kind == Staged::kPreview ? "device preview reported an error"
+                                                          : "device decode reported an error");
+}
+
+// Frames grp[0 .. m) -- one geometry, for kRegion one window size, every rectangle checked -- into the
+// staging at a stride, one device launch, their statuses to st.  A stream goes up to its head (kPreview)
+// or whole, the rest of its slot zeroed; with the host's index a region's stream only as its plan (the
+// head and the touched rows, each at its offset).  A stream the host does not index (a call of its own:
+// the batches plan their frames first) goes up whole and takes the device walk, which words the verdict.
+static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C, const int *grp, int m, int32_t *st) {
+  const int rows = (H + 7) / 8;
+  int ow = 0, oh = 0;
+  staged_dims(c, W, H, grp[0], &ow, &oh);
+  size_t stride = 0;
+  for (int k = 0; k < m; ++k) {
+    const size_t n = c.heads ? c.heads[grp[k]] : c.packed_sizes[grp[k]];
+    stride = n > stride ? n : stride;
+  }
+  stride = round_up(stride + 16, 256);
+  const size_t n_idx = c.index ? 2 * (size_t)rows * m : 0, out_bytes = (size_t)ow * oh * C;
+  if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
+      !ctx->h_status.reserve(round_up((size_t)m * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
   uint8_t *in = (uint8_t *)ctx->h_in.p;
-  const uint32_t sz32 = (uint32_t)packed_size;
-  himg_hip_region_plan plan = himg_hip_region_plan();
-  // The host walks the headers up to row1 and uploads the head and the touched rows, each at its
-  // offset; a stream it does not index goes up whole and takes the device walk, which words the verdict.
-  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, up[0], up[1], up[2], up[3], &plan, ctx->hp_index) == HIMG_OK;
-  if (indexed) {
-    HIP_TRY(ctx, hipMemcpyAsync(in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(in + plan.rows_begin, packed + plan.rows_begin, plan.rows_end - plan.rows_begin,
-                                hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-  } else {
-    HIP_TRY(ctx, hipMemsetAsync(in + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(in, packed, packed_size, hipMemcpyHostToDevice, nullptr));
+  std::vector<uint32_t> sz(m);
+  std::vector<int32_t> org(2 * (size_t)m);
+  bool indexed = c.index && rows >= 2;
+  for (int k = 0; k < m; ++k) {
+    const int i = grp[k];
+    uint8_t *d = in + (size_t)k * stride;
+    sz[k] = (uint32_t)c.packed_sizes[i];
+    int up[4] = {0, 0, W, H};   // (kScaled: every row, the whole frame as a rectangle)
+    if (c.rects) {
+      const int32_t *R = c.rects + 4 * (size_t)i;
+      (void)rect_up(W, H, c.scale_log2, R[0], R[1], R[2], R[3], up);
+      org[2 * k] = R[0];
+      org[2 * k + 1] = R[1];
+    }
+    himg_hip_region_plan plan = himg_hip_region_plan();
+    indexed = indexed && region_index(c.packed[i], c.packed_sizes[i], ctx->fix_t2, up[0], up[1], up[2], up[3], &plan,
+                                      ctx->hp_index + (size_t)k * 2 * rows) == HIMG_OK;
+    if (indexed && c.kind == Staged::kRegion) {
+      HIP_TRY(ctx, hipMemcpyAsync(d, c.packed[i], plan.head_bytes, hipMemcpyHostToDevice, nullptr));
+      HIP_TRY(ctx, hipMemcpyAsync(d + plan.rows_begin, c.packed[i] + plan.rows_begin, plan.rows_end - plan.rows_begin,
+                                  hipMemcpyHostToDevice, nullptr));
+    } else if (int rc = upload_zero_tail(ctx, d, stride, c.packed[i], c.heads ? c.heads[i] : c.packed_sizes[i])) {
+      return rc;
+    }
   }
-  const int32_t org[2] = {x, y};   // (a batch of one)
-  int rc = region_launch(ctx, in, in_cap, &sz32, 1, W, H, C, org, w, h,
-                         indexed ? (const uint32_t *)ctx->h_index.p : nullptr, ctx->h_out.p,
-                         (int32_t *)ctx->h_status.p, nullptr, scale_log2);
+  if (indexed) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  const uint32_t *d_index = indexed ? (const uint32_t *)ctx->h_index.p : nullptr;
+  int32_t *d_status = (int32_t *)ctx->h_status.p;
+  int rc;
+  if (c.kind == Staged::kPreview)
+    rc = preview_launch(ctx, in, stride, sz.data(), m, W, H, C, ctx->h_out.p, d_status, nullptr);
+  else if (c.kind == Staged::kScaled)
+    rc = scaled_launch(ctx, in, stride, sz.data(), m, W, H, C, c.scale_log2, d_index, ctx->h_out.p, d_status, nullptr);
+  else
+    rc = region_launch(ctx, in, stride, sz.data(), m, W, H, C, org.data(), ow, oh, d_index, ctx->h_out.p, d_status, nullptr,
+                       c.scale_log2);
   if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffer
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
     return rc;
   }
-  int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) return region_status_error(ctx, st);
-  ctx->host_bytes = out_bytes;
-  *width = w; *height = h; *channels = C;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(st, d_status, (size_t)m * 4, hipMemcpyDeviceToHost));
   return HIMG_OK;
+}
+
+// A *_to call is a launch of one stream (the arrays of c hold that one) whose result stays resident for
+// himg_hip_fetch_last; the dimensions are reported even where dst is too small.
+static int staged_to(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C, uint8_t *dst, size_t dst_cap, int *width,
+                     int *height, int *channels) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  const int frame = 0;
+  int32_t st = 0;
+  if (int rc = staged_launch(ctx, c, W, H, C, &frame, 1, &st)) return rc;
+  if (st) return staged_error(ctx, c, st);
+  staged_dims(c, W, H, 0, width, height);
+  *channels = C;
+  ctx->host_bytes = (size_t)*width * *height * C;
+  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+// The launches of a batch call.  Frames not yet done that share (W, H, C) -- for kRegion the window size
+// too -- go through one launch, in the order of their first frame: at most kStageLaunch of them, whose
+// streams, each at the launch's largest size, fit byte_cap (0: no limit).  A failing frame fails alone:
+// its dimensions stay zero and the call's first error is kept in *first_err.
+static int staged_batch(himg_hip_ctx *ctx, const Staged &c, int n, const int *W, const int *H, const int *C,
+                        std::vector<int> &done, size_t byte_cap, uint8_t *const *dst, const size_t *dst_cap, int *widths,
+                        int *heights, int *channels, int *first_err) {
+  for (int i0 = 0; i0 < n; ++i0) {
+    if (done[i0]) continue;
+    int ow = 0, oh = 0;
+    staged_dims(c, W[i0], H[i0], i0, &ow, &oh);
+    const int lim = kStageLaunch < 65535 / C[i0] ? kStageLaunch : 65535 / C[i0];
+    std::vector<int> grp;
+    size_t stride = 0;
+    for (int i = i0; i < n && (int)grp.size() < lim; ++i) {
+      int wi = ow, hi = oh;
+      if (c.rects) staged_dims(c, W[i], H[i], i, &wi, &hi);
+      if (done[i] || W[i] != W[i0] || H[i] != H[i0] || C[i] != C[i0] || wi != ow || hi != oh) continue;
+      const size_t si = round_up(c.packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
+      if (byte_cap && !grp.empty() && s2 * (grp.size() + 1) > byte_cap) break;
+      stride = s2;
+      grp.push_back(i);
+      done[i] = 1;
+    }
+    const int m = (int)grp.size();
+    const size_t out_bytes = (size_t)ow * oh * C[i0];
+    std::vector<int32_t> st(m);
+    if (int rc = staged_launch(ctx, c, W[i0], H[i0], C[i0], grp.data(), m, st.data())) return rc;
+    for (int k = 0; k < m; ++k) {
+      const int i = grp[k];
+      int err = HIMG_OK;
+      if (st[k]) err = staged_error(ctx, c, st[k]);
+      else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+      if (err) { if (!*first_err) *first_err = err; continue; }
+      HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
+                                  hipMemcpyDeviceToHost, nullptr));
+      widths[i] = ow; heights[i] = oh; channels[i] = C[i0];
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+  }
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_preview_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
+                                   size_t dst_cap, int *pw, int *ph, int *channels) {
+  if (!ctx || !packed || !pw || !ph || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  size_t head = 0;
+  const char *msg = nullptr;
+  // (avail = packed_size: the walk stops at the end of LRES, so the caller's bytes behind it are never read)
+  const int rc = preview_walk(packed, packed_size, packed_size, &W, &H, &C, &head, &msg);
+  if (rc == HIMG_ERR_FORMAT) return fail(ctx, rc, msg ? msg : "Error decoding low-res data.\n");
+  if (rc == HIMG_ERR_UNSUPPORTED) return fail(ctx, rc, "unsupported geometry");
+  if (rc) return fail(ctx, rc, "bad stream");
+  const Staged c = {Staged::kPreview, 0, false, &packed, &packed_size, &head, nullptr};
+  return staged_to(ctx, c, W, H, C, dst, dst_cap, pw, ph, channels);
+}
+
+extern "C" int himg_hip_preview_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
+                                      int n, uint8_t *const *dst, const size_t *dst_cap, int *pw, int *ph,
+                                      int *channels) {
+  if (!ctx || !packed || !packed_sizes || !dst || !dst_cap || !pw || !ph || !channels || n < 0) return HIMG_ERR_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  int first_err = HIMG_OK;
+  std::vector<int> W(n), H(n), Cc(n), done(n, 0);
+  std::vector<size_t> head(n);
+  for (int i = 0; i < n; ++i) {
+    pw[i] = ph[i] = channels[i] = 0;
+    const char *msg = nullptr;
+    const int rc = packed[i] ? preview_walk(packed[i], packed_sizes[i], packed_sizes[i], &W[i], &H[i], &Cc[i], &head[i], &msg)
+                             : (msg = "Not a RIFF HIMG file.\n", HIMG_ERR_FORMAT);
+    if (rc) {
+      done[i] = 1;
+      if (!first_err) first_err = fail(ctx, rc, msg ? msg : rc == HIMG_ERR_UNSUPPORTED ? "unsupported geometry" : "bad stream");
+    }
+  }
+  // (the staging holds one launch's heads and previews: no byte limit)
+  const Staged c = {Staged::kPreview, 0, false, packed, packed_sizes, head.data(), nullptr};
+  if (int rc = staged_batch(ctx, c, n, W.data(), H.data(), Cc.data(), done, 0, dst, dst_cap, pw, ph, channels, &first_err))
+    return rc;
+  return first_err;
+}
+
+// himg_hip_decode_region_to (scale_log2 = 0) and himg_hip_decode_scaled_region_to (1, 2: the rectangle
+// in the scaled picture, planned as the full-resolution rectangle it covers).  The host walks the headers
+// up to the rectangle's last row and uploads the head and the touched rows.
+static int region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2, int x, int y,
+                     int w, int h, uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels) {
+  if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0, up[4];
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  const int32_t R[4] = {x, y, w, h};
+  const Staged c = {Staged::kRegion, scale_log2, true, &packed, &packed_size, nullptr, R};
+  return staged_to(ctx, c, W, H, C, dst, dst_cap, width, height, channels);
 }
 
 extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int x, int y,
@@ -1920,66 +1948,12 @@ extern "C" int himg_hip_decode_region_to(himg_hip_ctx *ctx, const uint8_t *packe
   return region_to(ctx, packed, packed_size, 0, x, y, w, h, dst, dst_cap, width, height, channels);
 }
 
-// decode_regions_batch's launches: at most kRegionLaunch frames (the grids take batch x C <= 65535),
-// whose staging stays within kRegionStageBytes (one frame at least).  A stream occupies its whole size
-// there, rounded up to the launch's stride (the largest of its streams): only its plan is uploaded, but
-// the kernels bound their reads by the stream's size, so the rest of it must be addressable.  Windows
-// near the bottom of large frames are what fill it: their plans end near the end of the stream.
-constexpr int kRegionLaunch = 256;
-constexpr size_t kRegionStageBytes = (size_t)1 << 30;
-
-// One launch of decode_regions_batch: frames grp (one geometry and window size, each planned on the
-// host) at `stride` in the staging, their plans and host indices uploaded.
-static int regions_group(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
-                         const int32_t *rects, const std::vector<int> &grp, size_t stride, int W, int H, int C,
-                         uint8_t *const *dst, const size_t *dst_cap, int *widths, int *heights, int *channels,
-                         int *first_err, int scale_log2) {
-  const int m = (int)grp.size(), w = rects[4 * (size_t)grp[0] + 2], h = rects[4 * (size_t)grp[0] + 3];
-  const int rows = (H + 7) / 8;
-  const size_t n_idx = 2 * (size_t)rows * m, out_bytes = (size_t)w * h * C;
-  if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
-      !ctx->h_status.reserve(round_up((size_t)m * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
-  uint8_t *in = (uint8_t *)ctx->h_in.p;
-  std::vector<uint32_t> sz(m);
-  std::vector<int32_t> org(2 * (size_t)m), st(m);
-  for (int k = 0; k < m; ++k) {
-    const int i = grp[k];
-    const int32_t *R = rects + 4 * (size_t)i;
-    himg_hip_region_plan plan = himg_hip_region_plan();
-    int up[4];
-    (void)rect_up(W, H, scale_log2, R[0], R[1], R[2], R[3], up);
-    (void)region_index(packed[i], packed_sizes[i], ctx->fix_t2, up[0], up[1], up[2], up[3], &plan,
-                       ctx->hp_index + (size_t)k * 2 * rows);   // (both passed when the frame was planned)
-    uint8_t *d = in + (size_t)k * stride;
-    HIP_TRY(ctx, hipMemcpyAsync(d, packed[i], plan.head_bytes, hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(d + plan.rows_begin, packed[i] + plan.rows_begin, plan.rows_end - plan.rows_begin,
-                                hipMemcpyHostToDevice, nullptr));
-    sz[k] = (uint32_t)packed_sizes[i];
-    org[2 * k] = R[0];
-    org[2 * k + 1] = R[1];
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-  int rc = region_launch(ctx, in, stride, sz.data(), m, W, H, C, org.data(), w, h, (const uint32_t *)ctx->h_index.p,
-                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr, scale_log2);
-  if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
-    return rc;
-  }
-  HIP_TRY(ctx, hipMemcpy(st.data(), ctx->h_status.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-  for (int k = 0; k < m; ++k) {
-    const int i = grp[k];
-    int err = HIMG_OK;
-    if (st[k]) err = region_status_error(ctx, st[k]);
-    else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-    if (err) { if (!*first_err) *first_err = err; continue; }
-    HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
-                                hipMemcpyDeviceToHost, nullptr));
-    widths[i] = w; heights[i] = h; channels[i] = C;
-  }
-  HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-  return HIMG_OK;
+extern "C" int himg_hip_decode_scaled_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                                int scale_log2, int x, int y, int w, int h, uint8_t *dst,
+                                                size_t dst_cap, int *width, int *height, int *channels) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  return region_to(ctx, packed, packed_size, scale_log2, x, y, w, h, dst, dst_cap, width, height, channels);
 }
 
 // himg_hip_decode_regions_batch (scale_log2 = 0) and himg_hip_decode_scaled_regions_batch (1, 2).
@@ -1995,13 +1969,9 @@ static int regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const 
     widths[i] = heights[i] = channels[i] = 0;
     const int32_t *R = rects + 4 * (size_t)i;
     Geom g;
-    int err = HIMG_OK, up[4];
-    if (const char *msg = packed[i] ? parse_header(packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i]) : "Not a RIFF HIMG file.\n")
-      err = fail(ctx, HIMG_ERR_FORMAT, msg);
-    else if (!make_geom(W[i], H[i], Cc[i], Cc[i], 1, &g))
-      err = fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-    else if (!rect_up(W[i], H[i], scale_log2, R[0], R[1], R[2], R[3], up))
-      err = fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+    int up[4];
+    int err = stream_geom(ctx, packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i], &g);
+    if (!err && !rect_up(W[i], H[i], scale_log2, R[0], R[1], R[2], R[3], up)) err = fail(ctx, HIMG_ERR_ARG, "bad rectangle");
     if (err) {
       if (!first_err) first_err = err;
       continue;
@@ -2021,26 +1991,10 @@ static int regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const 
     widths[i] = w; heights[i] = h; channels[i] = c;
   }
   ctx->host_bytes = 0;   // (nothing resident for himg_hip_fetch_last, as in himg_hip_decode_batch)
-  // Frames that share (W, H, C, w, h): one launch, in the order of their first frame.
-  for (int i0 = 0; i0 < n; ++i0) {
-    if (done[i0]) continue;
-    const int32_t *R0 = rects + 4 * (size_t)i0;
-    const int lim = kRegionLaunch < 65535 / Cc[i0] ? kRegionLaunch : 65535 / Cc[i0];
-    std::vector<int> grp;
-    size_t stride = 0;
-    for (int i = i0; i < n && (int)grp.size() < lim; ++i) {
-      const int32_t *R = rects + 4 * (size_t)i;
-      if (done[i] || W[i] != W[i0] || H[i] != H[i0] || Cc[i] != Cc[i0] || R[2] != R0[2] || R[3] != R0[3]) continue;
-      const size_t si = round_up(packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
-      if (!grp.empty() && s2 * (grp.size() + 1) > kRegionStageBytes) break;
-      stride = s2;
-      grp.push_back(i);
-      done[i] = 1;
-    }
-    const int rc = regions_group(ctx, packed, packed_sizes, rects, grp, stride, W[i0], H[i0], Cc[i0], dst, dst_cap,
-                                 widths, heights, channels, &first_err, scale_log2);
-    if (rc) return rc;
-  }
+  const Staged c = {Staged::kRegion, scale_log2, true, packed, packed_sizes, nullptr, rects};
+  if (int rc = staged_batch(ctx, c, n, W.data(), H.data(), Cc.data(), done, kRegionStageBytes, dst, dst_cap, widths,
+                            heights, channels, &first_err))
+    return rc;
   return first_err;
 }
 
@@ -2051,96 +2005,29 @@ extern "C" int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *c
   return regions_batch(ctx, packed, packed_sizes, n, 0, rects, dst, dst_cap, widths, heights, channels);
 }
 
-// ---------------------------------------------------------------------------
-// Scaled decode: the picture at 1/2 and 1/4 scale (kernels_dec.hip, launch_scaled).
-// ---------------------------------------------------------------------------
-extern "C" int himg_hip_scaled_size(int width, int height, int scale_log2, int *ow, int *oh) {
-  if (!ow || !oh || width < 1 || height < 1 || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
-  const int F = 1 << scale_log2;
-  *ow = (int)(((long long)width + F - 1) / F);
-  *oh = (int)(((long long)height + F - 1) / F);
-  return HIMG_OK;
-}
-
-// The device launch behind every scaled entry point.  d_row_index: the host's index (one frame).
-static int scaled_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
-                         int width, int height, int num_channels, int scale_log2, const uint32_t *d_row_index,
-                         void *d_out, int32_t *d_status, void *stream) {
-  Geom g;
+extern "C" int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
+                                                    const size_t *packed_sizes, int n, int scale_log2,
+                                                    const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
+                                                    int *widths, int *heights, int *channels) {
+  if (!ctx) return HIMG_ERR_ARG;
   if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  if (!make_geom(width, height, num_channels, num_channels, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows + 1 > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((in_stride & 3) || ((uintptr_t)d_packed & 15) || ((uintptr_t)d_out & 15))
-    return fail(ctx, HIMG_ERR_ARG, "in_stride must be a multiple of 4; buffers 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_dec_ws(ctx, g, batch, false, true);   // (the region decode's workspace: no FRES plane)
-  if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  rc = stage_sizes(ctx, h_sizes, batch, s);
-  if (rc) return rc;
-  launch_scaled(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (const uint32_t *)ctx->d_sizes.p,
-                d_row_index, scale_log2, (uint8_t *)d_out, d_status, s, &ctx->prof,
-                ctx->opts.use_side ? &ctx->dstr : nullptr);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return regions_batch(ctx, packed, packed_sizes, n, scale_log2, rects, dst, dst_cap, widths, heights, channels);
 }
 
-extern "C" int himg_hip_decode_scaled_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
-                                             const uint32_t *h_sizes, int batch, int width, int height,
-                                             int num_channels, int scale_log2, void *d_out, int32_t *d_status,
-                                             void *stream) {
-  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
-  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
-  return scaled_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, scale_log2, nullptr, d_out,
-                       d_status, stream);
-}
-
+// The host walks every row header (the whole frame as a rectangle) and the index goes up with the
+// stream; a stream it does not index takes the device walk, which words the verdict.
 extern "C" int himg_hip_decode_scaled_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int scale_log2,
                                          uint8_t *dst, size_t dst_cap, int *width, int *height, int *channels) {
   if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
   if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
   int W = 0, H = 0, C = 0;
-  if (const char *msg = parse_header(packed, packed_size, &W, &H, &C)) return fail(ctx, HIMG_ERR_FORMAT, msg);
   Geom g;
-  if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-  int ow = 0, oh = 0;
-  (void)himg_hip_scaled_size(W, H, scale_log2, &ow, &oh);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  const size_t in_cap = round_up(packed_size + 16, 256);
-  const size_t out_bytes = (size_t)ow * oh * C;
-  const size_t n_idx = 2 * (size_t)g.rows;
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256) ||
-      !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
-  uint8_t *in = (uint8_t *)ctx->h_in.p;
-  const uint32_t sz32 = (uint32_t)packed_size;
-  // The host walks every row header (the whole frame as a rectangle); a stream it does not index
-  // takes the device walk, which words the verdict.
-  himg_hip_region_plan plan = himg_hip_region_plan();
-  const bool indexed = g.rows >= 2 && region_index(packed, packed_size, ctx->fix_t2, 0, 0, W, H, &plan, ctx->hp_index) == HIMG_OK;
-  HIP_TRY(ctx, hipMemsetAsync(in + (packed_size & ~(size_t)15), 0, in_cap - (packed_size & ~(size_t)15), nullptr));
-  HIP_TRY(ctx, hipMemcpyAsync(in, packed, packed_size, hipMemcpyHostToDevice, nullptr));
-  if (indexed) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-  int rc = scaled_launch(ctx, in, in_cap, &sz32, 1, W, H, C, scale_log2, indexed ? (const uint32_t *)ctx->h_index.p : nullptr,
-                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
-  if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffer
-    return rc;
-  }
-  int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) return region_status_error(ctx, st);
-  ctx->host_bytes = out_bytes;
-  *width = ow; *height = oh; *channels = C;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  const Staged c = {Staged::kScaled, scale_log2, true, &packed, &packed_size, nullptr, nullptr};
+  return staged_to(ctx, c, W, H, C, dst, dst_cap, width, height, channels);
 }
 
+// (Every frame's rows are walked on the device: launch_scaled takes the host's index of one frame only.)
 extern "C" int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *const *packed, const size_t *packed_sizes,
                                             int n, int scale_log2, uint8_t *const *dst, const size_t *dst_cap,
                                             int *widths, int *heights, int *channels) {
@@ -2154,113 +2041,16 @@ extern "C" int himg_hip_decode_scaled_batch(himg_hip_ctx *ctx, const uint8_t *co
   for (int i = 0; i < n; ++i) {
     widths[i] = heights[i] = channels[i] = 0;
     Geom g;
-    int err = HIMG_OK;
-    if (const char *msg = packed[i] ? parse_header(packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i]) : "Not a RIFF HIMG file.\n")
-      err = fail(ctx, HIMG_ERR_FORMAT, msg);
-    else if (!make_geom(W[i], H[i], Cc[i], Cc[i], 1, &g))
-      err = fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-    if (err) {
+    if (const int err = stream_geom(ctx, packed[i], packed_sizes[i], &W[i], &H[i], &Cc[i], &g)) {
       done[i] = 1;
       if (!first_err) first_err = err;
     }
   }
-  // Frames that share a geometry: one launch (in the order of their first frame) of at most
-  // kRegionLaunch frames whose streams, each at the launch's largest size, fit kRegionStageBytes.
-  for (int i0 = 0; i0 < n; ++i0) {
-    if (done[i0]) continue;
-    const int lim = kRegionLaunch < 65535 / Cc[i0] ? kRegionLaunch : 65535 / Cc[i0];
-    std::vector<int> grp;
-    size_t stride = 0;
-    for (int i = i0; i < n && (int)grp.size() < lim; ++i) {
-      if (done[i] || W[i] != W[i0] || H[i] != H[i0] || Cc[i] != Cc[i0]) continue;
-      const size_t si = round_up(packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
-      if (!grp.empty() && s2 * (grp.size() + 1) > kRegionStageBytes) break;
-      stride = s2;
-      grp.push_back(i);
-      done[i] = 1;
-    }
-    const int m = (int)grp.size();
-    int ow = 0, oh = 0;
-    (void)himg_hip_scaled_size(W[i0], H[i0], scale_log2, &ow, &oh);
-    const size_t out_bytes = (size_t)ow * oh * Cc[i0];
-    if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
-        !ctx->h_status.reserve(round_up((size_t)m * 4, 256)))
-      return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-    uint8_t *in = (uint8_t *)ctx->h_in.p;
-    std::vector<uint32_t> sz(m);
-    std::vector<int32_t> st(m);
-    for (int k = 0; k < m; ++k) {
-      const int i = grp[k];
-      const size_t lo = packed_sizes[i] & ~(size_t)15;
-      HIP_TRY(ctx, hipMemsetAsync(in + (size_t)k * stride + lo, 0, stride - lo, nullptr));
-      HIP_TRY(ctx, hipMemcpyAsync(in + (size_t)k * stride, packed[i], packed_sizes[i], hipMemcpyHostToDevice, nullptr));
-      sz[k] = (uint32_t)packed_sizes[i];
-    }
-    int rc = scaled_launch(ctx, in, stride, sz.data(), m, W[i0], H[i0], Cc[i0], scale_log2, nullptr, ctx->h_out.p,
-                           (int32_t *)ctx->h_status.p, nullptr);
-    if (rc) {
-      (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's buffers
-      return rc;
-    }
-    HIP_TRY(ctx, hipMemcpy(st.data(), ctx->h_status.p, (size_t)m * 4, hipMemcpyDeviceToHost));
-    for (int k = 0; k < m; ++k) {
-      const int i = grp[k];
-      int err = HIMG_OK;
-      if (st[k]) err = region_status_error(ctx, st[k]);
-      else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-      if (err) { if (!first_err) first_err = err; continue; }
-      HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
-                                  hipMemcpyDeviceToHost, nullptr));
-      widths[i] = ow; heights[i] = oh; channels[i] = Cc[i0];
-    }
-    HIP_TRY(ctx, hipStreamSynchronize(nullptr));
-  }
+  const Staged c = {Staged::kScaled, scale_log2, false, packed, packed_sizes, nullptr, nullptr};
+  if (int rc = staged_batch(ctx, c, n, W.data(), H.data(), Cc.data(), done, kRegionStageBytes, dst, dst_cap, widths,
+                            heights, channels, &first_err))
+    return rc;
   return first_err;
-}
-
-// ---------------------------------------------------------------------------
-// Scaled region decode: a window of the picture at 1/2 or 1/4 scale (kernels_dec.hip,
-// launch_scaled_region).  A rectangle of the scaled picture is planned, walked, counted and judged as
-// the full-resolution rectangle it covers (rect_up); the entries are the region decode's with a scale.
-// ---------------------------------------------------------------------------
-extern "C" int himg_hip_scaled_region_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int scale_log2, int x,
-                                           int y, int w, int h, himg_hip_region_plan *plan) {
-  if (!packed || !plan || (scale_log2 != 1 && scale_log2 != 2)) return HIMG_ERR_ARG;
-  *plan = himg_hip_region_plan();
-  int W = 0, H = 0, C = 0, up[4];
-  if (int rc = himg_hip_peek(packed, packed_size, &W, &H, &C)) return rc;
-  plan->width = W; plan->height = H; plan->num_channels = C;
-  if (!rect_up(W, H, scale_log2, x, y, w, h, up)) return HIMG_ERR_ARG;
-  return region_index(packed, packed_size, fix_t2, up[0], up[1], up[2], up[3], plan, nullptr);
-}
-
-extern "C" int himg_hip_decode_scaled_region_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
-                                                int scale_log2, int x, int y, int w, int h, uint8_t *dst,
-                                                size_t dst_cap, int *width, int *height, int *channels) {
-  if (!ctx) return HIMG_ERR_ARG;
-  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  return region_to(ctx, packed, packed_size, scale_log2, x, y, w, h, dst, dst_cap, width, height, channels);
-}
-
-extern "C" int himg_hip_decode_scaled_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
-                                                     const uint32_t *h_sizes, int batch, int width, int height,
-                                                     int num_channels, int scale_log2, const int32_t *h_origins,
-                                                     int w, int h, void *d_out, int32_t *d_status, void *stream) {
-  if (!ctx || !d_packed || !h_sizes || !h_origins || !d_out || !d_status || batch < 1 || batch > 65535)
-    return HIMG_ERR_ARG;
-  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  if (int rc = region_device_args(ctx, h_sizes, batch, in_stride)) return rc;
-  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
-                       d_out, d_status, stream, scale_log2);
-}
-
-extern "C" int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
-                                                    const size_t *packed_sizes, int n, int scale_log2,
-                                                    const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
-                                                    int *widths, int *heights, int *channels) {
-  if (!ctx) return HIMG_ERR_ARG;
-  if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  return regions_batch(ctx, packed, packed_sizes, n, scale_log2, rects, dst, dst_cap, widths, heights, channels);
 }
 
 // ---------------------------------------------------------------------------

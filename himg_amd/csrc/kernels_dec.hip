@@ -4736,15 +4736,36 @@ static void launch_lres_chain(const Geom &g, const DecWs &ws, int batch, const u
               dim3(64 * kUnpredWaves), g, ws);
 }
 
+// In front of every head phase: the diagnostics (the row counts' where the workspace has them) and the
+// LRES symbols (k_lres_write stores the non-zero ones only) are cleared.
+static void launch_zero(const Geom &g, const DecWs &ws, int batch, hipStream_t stream, Profiler *prof) {
+  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);   // (the stride is a multiple of 256)
+  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
+  prof_begin(prof, "memset", stream);
+  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
+                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
+  prof_end(prof, stream);
+}
+
+// The count kernel of a launch over all_rows block rows.  wave: one wavefront per row (k_row_count_w) --
+// from 8192 rows per call, below that the 1024-lane kernel keeps the GPU busier (HIMG_OPT_COUNT_WAVE
+// forces either); rpc: rows per workgroup of the 1024-lane kernel, which loads the decode tables once
+// for its rows -- a single frame has too few rows to fill the CUs that way.  g: the geometry the count
+// kernel takes.  one_record (the region and scaled decodes, whose row kernels have no parallel path for
+// a row in chunks): no limit on a lane's share of the row (max_sub; the full decode splits longer rows),
+// so that every row gets one record -- the lanes' ranges are 32-bit bit positions: any row a stream holds.
+struct CountRule { bool wave; int rpc; Geom g; };
+static CountRule count_rule(const Geom &g, long long all_rows, bool one_record) {
+  CountRule c = {g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192,
+                 all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount, g};
+  if (one_record) c.g.max_sub = 0x7fffffff;
+  return c;
+}
+
 void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                     const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
                     hipStream_t stream, Profiler *prof) {
-  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
-  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8);
-  prof_begin(prof, "memset", stream);
-  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
-                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, nullptr, 0u);
-  prof_end(prof, stream);
+  launch_zero(g, ws, batch, stream, prof);
   HIMG_LAUNCH(k_dec_parse_head, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes, d_head_sizes);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_head_sizes, stream, prof);
   const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
@@ -4752,21 +4773,39 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 
-// What launch_region and launch_scaled_region share, everything in front of the row kernel: the
-// head phase, each frame's header walk to its r1_f and the counts over its rows [r0_f, r1_f), derived on
-// the device from d_org (full-resolution origins) and the full-resolution height h.  nrows: the batch's
-// largest touched-row count (the grids), all_rows: its touched rows (the count kernels' rule),
-// stop_early: a frame whose walk stops before the last row.
-static void launch_region_front(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
-                                const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *d_org, int h,
-                                int nrows, long long all_rows, bool stop_early, hipStream_t stream, Profiler *prof,
-                                const DecStreams *ds) {
-  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
-  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
-  prof_begin(prof, "memset", stream);
-  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
-                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
-  prof_end(prof, stream);
+// The batch's largest touched-row and tile-column counts (the grids; for a fixed w x h a frame's counts
+// are within one of these), its touched rows (the count kernels' rule) and whether a frame's walk stops
+// before the last row.  h_org: full-resolution origins; w x h: the window in the picture whose tiles are
+// S x S (8, or 4 and 2 at 1/2 and 1/4 scale).
+struct WindowExtents { int nrows = 0, ntiles = 0; long long all_rows = 0; bool stop_early = false; };
+static WindowExtents window_extents(const Geom &g, int batch, const int32_t *h_org, int S, int w, int h) {
+  WindowExtents e;
+  const int F = 8 / S;
+  for (int f = 0; f < batch; ++f) {
+    const int x = h_org[2 * f] / F, y = h_org[2 * f + 1] / F;
+    const int r0 = y / S, r1 = (y + h + S - 1) / S, nt = (x + w + S - 1) / S - x / S;
+    e.nrows = r1 - r0 > e.nrows ? r1 - r0 : e.nrows;
+    e.ntiles = nt > e.ntiles ? nt : e.ntiles;
+    e.stop_early |= r1 < g.rows;
+    e.all_rows += r1 - r0;
+  }
+  return e;
+}
+
+// scale_log2 = 0: the region decode.  1, 2: the window w x h of the picture at scale 2^-scale_log2, frame
+// f's origin (x_f, y_f) in that picture; h_org / d_org hold the origins of the full-resolution rectangles
+// the windows cover, (F x_f, F y_f): with the height F h the walk and count kernels, which derive a
+// frame's rows on the device from d_org and that height, touch rows y_f / S .. ceil((y_f + h) / S), which
+// stays within the frame's block rows because y_f + h <= ceil(H / F) (checked by the caller).
+void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
+                   int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
+                   const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
+  const int F = 1 << scale_log2, hf = F * h;
+  const WindowExtents e = window_extents(g, batch, h_org, 8 / F, w, h);
+  launch_zero(g, ws, batch, stream, prof);
   // Each frame's row headers up to its r1_f (all of them for the whole frame's last row: the full decode's
   // verdict), on the side stream beside k_dec_parse and the LRES chain where there is one (launch_decode's
   // fork: the serial walk to a row deep in a 16384^2 frame is as long as the LRES chain).
@@ -4777,102 +4816,47 @@ static void launch_region_front(const Geom &g, const DecWs &ws, int batch, const
   }
   prof_begin(prof, d_row_index ? "k_region_set_index" : "k_region_rowwalk", ws_);
   if (d_row_index)
-    hipLaunchKernelGGL(k_region_set_index, dim3(batch), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, d_org, h);
+    hipLaunchKernelGGL(k_region_set_index, dim3(batch), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, d_org, hf);
   else
-    hipLaunchKernelGGL(k_region_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, d_org, h);
+    hipLaunchKernelGGL(k_region_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, d_org, hf);
   prof_end(prof, ws_);
   if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
   HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
   if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
-  if (!d_row_index && stop_early)
-    HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), g, ws, d_packed, in_stride, d_org, h, batch);
-  const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // (launch_decode's rule)
+  if (!d_row_index && e.stop_early)
+    HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), g, ws, d_packed, in_stride, d_org, hf, batch);
   // Every touched row gets a record: the count kernels that read the payload in place (k_row_count<true>
-  // gives up on rows beyond its LDS staging buffer, 36 KiB -- a 4096-pixel row above q50), and no limit on
-  // a lane's share of the row (max_sub: the full decode splits longer rows into chunks, which k_dec_region
-  // has no parallel path for).  The lanes' ranges are 32-bit bit positions: any row a stream holds.
-  Geom gc = g;
-  gc.max_sub = 0x7fffffff;
-  if (count_wave) {
-    HIMG_LAUNCH(k_region_count_w, dim3((nrows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), gc, ws,
-                d_packed, in_stride, d_sizes, d_org, h);
+  // gives up on rows beyond its LDS staging buffer, 36 KiB -- a 4096-pixel row above q50).
+  const CountRule cr = count_rule(g, e.all_rows, true);
+  if (cr.wave) {
+    HIMG_LAUNCH(k_region_count_w, dim3((e.nrows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
+                d_packed, in_stride, d_sizes, d_org, hf);
   } else {
-    const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
-    HIMG_LAUNCH(k_region_count, dim3((nrows + rpc - 1) / rpc, batch), dim3(kDecThreads), gc, ws, d_packed, in_stride,
-                d_sizes, d_org, h, rpc);
+    HIMG_LAUNCH(k_region_count, dim3((e.nrows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
+                in_stride, d_sizes, d_org, hf, cr.rpc);
   }
-}
-
-void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                   const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
-                   int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds) {
-  DecWs ws = ws_in;
-  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
-  // The batch's largest row and tile counts (the grids) and its touched rows (the count kernels' rule);
-  // for a fixed w x h a frame's counts are within one of these.
-  int nrows = 0, ntiles = 0;
-  bool stop_early = false;   // a frame whose walk stops before the last row
-  long long all_rows = 0;
-  for (int f = 0; f < batch; ++f) {
-    const int x = h_org[2 * f], y = h_org[2 * f + 1];
-    const int r0 = y / 8, r1 = (y + h + 7) / 8, nt = (x + w + 7) / 8 - x / 8;
-    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
-    ntiles = nt > ntiles ? nt : ntiles;
-    stop_early |= r1 < g.rows;
-    all_rows += r1 - r0;
+  // The row kernel over the touched block rows and tile columns, in strips of equal width.
+  const int smax = scale_log2 ? scaled_strip_tiles(g, scale_log2) : region_strip_tiles(g);
+  const int nstrip = (e.ntiles + smax - 1) / smax, sw = (e.ntiles + nstrip - 1) / nstrip;
+  const dim3 grid(nstrip, e.nrows, batch);
+  if (!scale_log2) {
+    RegionArgs ra;
+    ra.org = d_org; ra.sw = sw; ra.w = w; ra.h = h; ra.out = d_out;
+    prof_begin(prof, "k_dec_region", stream);
+    hipLaunchKernelGGL(k_dec_region, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, g, ws, d_packed,
+                       in_stride, d_sizes, ra);
+  } else {
+    ScaledRegionArgs sa;
+    sa.org = d_org; sa.sw = sw; sa.w = w; sa.h = h; sa.out = d_out;
+    prof_begin(prof, "k_dec_scaled_region", stream);
+    if (scale_log2 == 1)
+      hipLaunchKernelGGL(k_dec_scaled_region<4>, grid, dim3(kDecThreads), scaled_layout<4>(g.C, sw).total, stream, g, ws,
+                         d_packed, in_stride, d_sizes, sa);
+    else
+      hipLaunchKernelGGL(k_dec_scaled_region<2>, grid, dim3(kDecThreads), scaled_layout<2>(g.C, sw).total, stream, g, ws,
+                         d_packed, in_stride, d_sizes, sa);
   }
-  launch_region_front(g, ws, batch, d_packed, in_stride, d_sizes, d_row_index, d_org, h, nrows, all_rows, stop_early,
-                      stream, prof, ds);
-  RegionArgs ra;
-  ra.org = d_org;
-  const int smax = region_strip_tiles(g), nstrip = (ntiles + smax - 1) / smax;
-  ra.sw = (ntiles + nstrip - 1) / nstrip;   // (strips of equal width)
-  ra.w = w; ra.h = h; ra.out = d_out;
-  prof_begin(prof, "k_dec_region", stream);
-  hipLaunchKernelGGL(k_dec_region, dim3(nstrip, nrows, batch), dim3(kDecThreads), region_layout(g.C, ra.sw).total, stream,
-                     g, ws, d_packed, in_stride, d_sizes, ra);
-  prof_end(prof, stream);
-  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
-}
-
-// The window w x h of the picture at scale 2^-scale_log2, frame f's origin (x_f, y_f) in that picture.
-// h_org / d_org hold the origins of the full-resolution rectangles the windows cover, (F x_f, F y_f):
-// with the height F h the region walk and count kernels touch rows y_f / S .. ceil((y_f + h) / S), which
-// stays within the frame's block rows because y_f + h <= ceil(H / F) (checked by the caller).
-void launch_scaled_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                          const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org,
-                          const int32_t *d_org, int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status,
-                          hipStream_t stream, Profiler *prof, const DecStreams *ds) {
-  DecWs ws = ws_in;
-  ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
-  const int F = 1 << scale_log2, S = 8 / F;
-  int nrows = 0, ntiles = 0;
-  bool stop_early = false;
-  long long all_rows = 0;
-  for (int f = 0; f < batch; ++f) {
-    const int x = h_org[2 * f] / F, y = h_org[2 * f + 1] / F;
-    const int r0 = y / S, r1 = (y + h + S - 1) / S, nt = (x + w + S - 1) / S - x / S;
-    nrows = r1 - r0 > nrows ? r1 - r0 : nrows;
-    ntiles = nt > ntiles ? nt : ntiles;
-    stop_early |= r1 < g.rows;
-    all_rows += r1 - r0;
-  }
-  launch_region_front(g, ws, batch, d_packed, in_stride, d_sizes, d_row_index, d_org, F * h, nrows, all_rows,
-                      stop_early, stream, prof, ds);
-  ScaledRegionArgs sa;
-  sa.org = d_org;
-  const int smax = scaled_strip_tiles(g, scale_log2), nstrip = (ntiles + smax - 1) / smax;
-  sa.sw = (ntiles + nstrip - 1) / nstrip;   // (strips of equal width)
-  sa.w = w; sa.h = h; sa.out = d_out;
-  prof_begin(prof, "k_dec_scaled_region", stream);
-  if (scale_log2 == 1)
-    hipLaunchKernelGGL(k_dec_scaled_region<4>, dim3(nstrip, nrows, batch), dim3(kDecThreads),
-                       scaled_layout<4>(g.C, sa.sw).total, stream, g, ws, d_packed, in_stride, d_sizes, sa);
-  else
-    hipLaunchKernelGGL(k_dec_scaled_region<2>, dim3(nstrip, nrows, batch), dim3(kDecThreads),
-                       scaled_layout<2>(g.C, sa.sw).total, stream, g, ws, d_packed, in_stride, d_sizes, sa);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
@@ -4884,13 +4868,7 @@ void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_row_count<false>)
   const int F = 1 << scale_log2;
-  const long long all_rows = (long long)batch * g.rows;
-  const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);
-  const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
-  prof_begin(prof, "memset", stream);
-  hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
-                     reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
-  prof_end(prof, stream);
+  launch_zero(g, ws, batch, stream, prof);
   // launch_decode's order: the whole row index on the side stream beside k_dec_parse, the counts
   // behind both on the side stream beside the LRES chain, the row kernel behind the join.
   hipStream_t side = ds ? ds->side : stream;
@@ -4902,21 +4880,16 @@ void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
       hipLaunchKernelGGL(k_dec_rowwalk, dim3(batch), dim3(64), 0, s, g, ws, d_packed, in_stride, d_sizes, kWalkAll, 0);
     prof_end(prof, s);
   };
-  // Every row gets one record: the count kernels that read the payload in place, and no limit on a
-  // lane's share of the row (launch_region's reasons).
-  Geom gc = g;
-  gc.max_sub = 0x7fffffff;
-  const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // (launch_decode's rule)
+  // Every row gets one record: the count kernels that read the payload in place (launch_region's reasons).
+  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
   auto row_count = [&](hipStream_t s) {
     prof_begin(prof, "k_row_count", s);
-    if (count_wave) {
-      hipLaunchKernelGGL(k_row_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s, gc,
+    if (cr.wave)
+      hipLaunchKernelGGL(k_row_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s, cr.g,
                          ws, d_packed, in_stride, d_sizes, 0, g.rows);
-    } else {
-      const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
-      hipLaunchKernelGGL(k_row_count<false>, dim3((g.rows + rpc - 1) / rpc, batch), dim3(kDecThreads), 0, s, gc, ws,
-                         d_packed, in_stride, d_sizes, 0, g.rows, rpc);
-    }
+    else
+      hipLaunchKernelGGL(k_row_count<false>, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), 0, s, cr.g, ws,
+                         d_packed, in_stride, d_sizes, 0, g.rows, cr.rpc);
     prof_end(prof, s);
   };
   if (ds) {
@@ -4979,10 +4952,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   // Block rows [r0, r1) only (row-sharded decode: every rank decodes the small
   // LRES stream and walks all row headers, then its own FRES rows).
   const int nrows = r1 - r0;
-  // Rows per k_row_count workgroup: a workgroup loads the decode tables once for its rows; a
-  // single frame has too few rows to fill the CUs that way.
-  const long long all_rows = (long long)batch * nrows;
-  const int rpc = all_rows <= 512 ? 1 : all_rows <= 1024 ? 2 : kRowsPerCount;
+  const CountRule cr = count_rule(g, (long long)batch * nrows, false);
   const unsigned gx = (unsigned)((((g.cols + 31) / 32) * 64 + 255) / 256);   // k_tile_inv: two lanes per tile, 32 tiles per wave
   // Fused row kernel when the row's symbols and the decode tables fit the 160 KiB
   // LDS (width <= 4352 for RGBA); the payload is read in place from L2.
@@ -5003,14 +4973,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   auto seg_lo = [&](int k) { return r0 + (int)((long long)nrows * k / nseg); };
   // Diagnostics and the LRES symbols (k_lres_write stores the non-zero ones only) are
   // cleared up front: k_row_count may start as soon as the parse and the walk are done.
-  if (do_head) {
-    const uint32_t n16 = (uint32_t)(((size_t)batch * ws.lres_stride + 15) / 16);   // (the stride is a multiple of 256)
-    const uint32_t ns = (uint32_t)((size_t)batch * (g.rows + 1) * 8), nr = ws.rc_stats ? (uint32_t)((size_t)batch * g.rows * 8) : 0u;
-    prof_begin(prof, "memset", stream);
-    hipLaunchKernelGGL(k_dec_zero, dim3((n16 + 256 * 4 - 1) / (256 * 4)), dim3(256), 0, stream,
-                       reinterpret_cast<uint4 *>(ws.lres_sym), n16, ws.stats, ns, ws.rc_stats, nr);
-    prof_end(prof, stream);
-  }
+  if (do_head) launch_zero(g, ws, batch, stream, prof);
   // Fork: the serial FRES row-header walk runs on the side stream beside k_dec_parse.
   if (ds && do_rows) {
     (void)hipEventRecord(ds->ev_fork, stream);
@@ -5034,26 +4997,24 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   // The FRES counts need the decode tables (parse) and the row index (walk); their
   // stream joins this one again before the FRES row kernels.
   // (ds == nullptr: everything in line.)
-  // Batches: one wavefront per row (k_row_count_w) -- from 8192 rows per call, below that
-  // the 1024-lane kernel keeps the GPU busier (HIMG_COUNT_WAVE=0 / 1 forces either).
-  const bool count_wave = g.count_wave >= 0 ? g.count_wave != 0 : all_rows >= 8192;   // HIMG_OPT_COUNT_WAVE
+  // (Which count kernel: count_rule.)
   auto row_count = [&](hipStream_t s, int a, int b) {
     if (b <= a) return;
     prof_begin(prof, "k_row_count", s);
-    if (count_wave)
+    if (cr.wave)
       hipLaunchKernelGGL(k_row_count_w, dim3((b - a + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s,
                          g, ws, d_packed, in_stride, d_sizes, a, b);
     else if (wps)
-      hipLaunchKernelGGL(k_row_count<true>, dim3((b - a + rpc - 1) / rpc, batch), dim3(kDecThreads), 0, s, g, ws,
-                         d_packed, in_stride, d_sizes, a, b, rpc);
+      hipLaunchKernelGGL(k_row_count<true>, dim3((b - a + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), 0, s, g, ws,
+                         d_packed, in_stride, d_sizes, a, b, cr.rpc);
     else if (ws.lane_q && g.wide_q && g.count_wave < 0 && (g.row_block % 16) == 0)
       // Rows that go through windows, at a bit rate the staged reader takes (the host's estimate
       // from the stream's size; a row beyond it is left to k_dec_huff): four records per lane
       // from 4096 sub-sequences.  HIMG_OPT_COUNT_WAVE = 0 / 1 force the other two forms.
       hipLaunchKernelGGL(k_row_count_q, dim3(b - a, batch), dim3(kDecThreads), 0, s, g, ws, d_packed, in_stride, d_sizes, a);
     else
-      hipLaunchKernelGGL(k_row_count<false>, dim3((b - a + rpc - 1) / rpc, batch), dim3(kDecThreads), 0, s, g, ws,
-                         d_packed, in_stride, d_sizes, a, b, rpc);
+      hipLaunchKernelGGL(k_row_count<false>, dim3((b - a + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), 0, s, g, ws,
+                         d_packed, in_stride, d_sizes, a, b, cr.rpc);
     prof_end(prof, s);
   };
   // The entropy pass of rows that do not fit the LDS, rows [a, b): every 128 KiB window of a
