@@ -85,6 +85,12 @@ def lib():
     L.himg_hip_host_free.restype = None
     L.himg_hip_encode_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
     L.himg_hip_decode_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_encode_device_q.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp]
+    L.himg_hip_encode_sizes_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+    L.himg_hip_budget_probes.argtypes = [i32, i32]
+    L.himg_hip_encode_budget_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp]
+    L.himg_hip_encode_budget_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, sz, vp, sz, P(sz), P(i32)]
+    L.himg_hip_encode_budget_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.himg_hip_decode_rows_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_index_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_rows_indexed_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
@@ -167,6 +173,15 @@ def fnv1a64(buf):
 
 def max_packed_size(width, height, channels):
     return int(lib().himg_hip_max_packed_size(width, height, channels))
+
+
+def budget_probes(qmin=0, qmax=100):
+    """himg_hip_budget_probes (no GPU): the size probes an encode to a byte budget makes for the
+    quality range [qmin, qmax].  Raises HimgError (HIMG_ERR_ARG) unless 0 <= qmin <= qmax <= 100."""
+    n = lib().himg_hip_budget_probes(int(qmin), int(qmax))
+    if n < 0:
+        raise HimgError(n, "budget_probes")
+    return n
 
 
 def tok_layout(width, height, channels=4, pixel_stride=None, row_tokens=-1, batch=1):
@@ -301,6 +316,50 @@ class Engine:
                                          dst, caps, sizes)
         self._check(rc, "encode_batch")
         return [o[: sizes[i]] for i, o in enumerate(outs)]
+
+    def encode_budget(self, img, budget, qmin=0, qmax=100, use_ycbcr=True, channels=None, pixel_stride=None):
+        """himg_hip_encode_budget_to + himg_hip_fetch_last: (stream, quality) -- the stream of at most
+        `budget` bytes at the quality the search of include/himg_hip.h finds in [qmin, qmax].  Raises
+        HimgError (HIMG_ERR_CAPACITY, its `quality` -1) when the stream at qmin is larger than the budget."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape[:2]
+        ch = channels if channels is not None else (img.shape[2] if img.ndim == 3 else 1)
+        stride = pixel_stride if pixel_stride is not None else (img.shape[2] if img.ndim == 3 else 1)
+        n, q = C.c_size_t(), C.c_int(-1)
+        rc = lib().himg_hip_encode_budget_to(self._ctx, img.ctypes.data, w, h, stride, ch, int(qmin), int(qmax),
+                                             1 if use_ycbcr else 0, max(int(budget), 0), None, 0, C.byref(n), C.byref(q))
+        if rc != HIMG_ERR_CAPACITY or n.value == 0:
+            e = HimgError(rc if rc != HIMG_OK else HIMG_ERR_ARG,
+                          "encode_budget: %s" % lib().himg_hip_last_error(self._ctx).decode())
+            e.quality = q.value
+            raise e
+        out = np.empty(n.value, np.uint8)
+        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode_budget")
+        return out, q.value
+
+    def encode_budget_batch(self, frames, budgets, qmin=0, qmax=100, use_ycbcr=True, outs=None):
+        """himg_hip_encode_budget_batch: frames of one geometry, frame i within budgets[i] bytes.
+        Returns (streams, qualities, rc): a frame whose budget is below its size at qmin (or that
+        failed otherwise) has an empty stream and, for the budget, quality -1; rc is the first such
+        error, HIMG_OK if there was none."""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        n = len(frames)
+        h, w = frames[0].shape[:2]
+        ch = frames[0].shape[2] if frames[0].ndim == 3 else 1
+        cap = max_packed_size(w, h, ch)
+        if outs is None:
+            outs = [np.empty(cap, np.uint8) for _ in range(n)]
+        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        bud = (C.c_size_t * n)(*[max(int(b), 0) for b in budgets])
+        sizes = (C.c_size_t * n)()
+        quals = (C.c_int * n)()
+        rc = lib().himg_hip_encode_budget_batch(self._ctx, src, n, w, h, ch, ch, int(qmin), int(qmax),
+                                                1 if use_ycbcr else 0, bud, dst, caps, sizes, quals)
+        if rc not in (HIMG_OK, HIMG_ERR_CAPACITY):
+            self._check(rc, "encode_budget_batch")
+        return [o[: sizes[i]] for i, o in enumerate(outs)], [quals[i] for i in range(n)], rc
 
     def decode_batch(self, streams, outs=None):
         """himg_hip_decode_batch: returns the decoded frames; `outs` (optional) are
@@ -518,6 +577,38 @@ class Engine:
                                           _ptr(d_out), out_stride, _ptr(d_sizes), _ptr(d_status),
                                           C.c_void_p(stream))
         self._check(rc, "encode_device")
+
+    def encode_device_q(self, d_frames, batch, width, height, pixel_stride, channels, qualities,
+                        use_ycbcr, d_out, out_stride, d_sizes, d_status, stream=0):
+        """himg_hip_encode_device_q: encode_device with a quality per frame (qualities: `batch` values
+        in [0, 100], on the host)."""
+        q = np.ascontiguousarray(np.asarray(qualities, np.int32).reshape(batch))
+        rc = lib().himg_hip_encode_device_q(self._ctx, _ptr(d_frames), batch, width, height, pixel_stride, channels,
+                                            q.ctypes.data, 1 if use_ycbcr else 0, _ptr(d_out), out_stride,
+                                            _ptr(d_sizes), _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_device_q")
+
+    def encode_sizes_device(self, d_frames, batch, width, height, pixel_stride, channels, qualities,
+                            use_ycbcr, d_sizes, d_status, stream=0):
+        """himg_hip_encode_sizes_device: every frame's exact stream size at its quality into d_sizes,
+        without writing a stream."""
+        q = np.ascontiguousarray(np.asarray(qualities, np.int32).reshape(batch))
+        rc = lib().himg_hip_encode_sizes_device(self._ctx, _ptr(d_frames), batch, width, height, pixel_stride,
+                                                channels, q.ctypes.data, 1 if use_ycbcr else 0, _ptr(d_sizes),
+                                                _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_sizes_device")
+
+    def encode_budget_device(self, d_frames, batch, width, height, pixel_stride, channels, qmin, qmax,
+                             use_ycbcr, budgets, d_out, out_stride, d_sizes, d_quality, d_status, stream=0):
+        """himg_hip_encode_budget_device: every frame at the quality the search finds for its budget
+        (budgets: `batch` byte counts, on the host); d_quality receives the qualities (-1: the
+        frame's stream at qmin is larger than its budget)."""
+        b = np.ascontiguousarray(np.minimum(np.asarray(budgets, np.uint64), 0xffffffff).astype(np.uint32).reshape(batch))
+        rc = lib().himg_hip_encode_budget_device(self._ctx, _ptr(d_frames), batch, width, height, pixel_stride,
+                                                 channels, int(qmin), int(qmax), 1 if use_ycbcr else 0,
+                                                 b.ctypes.data, _ptr(d_out), out_stride, _ptr(d_sizes),
+                                                 _ptr(d_quality), _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_budget_device")
 
     def decode_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_out,
                       d_status, stream=0):

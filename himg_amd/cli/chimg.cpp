@@ -4,6 +4,9 @@
 // (src/chimg.cpp:36-169): "chimg [-q N] [-rgb] image outfile"; exit 0 after the
 // usage text, -1 when the input cannot be read or the output cannot be written.
 // Input: binary PGM / PPM / PAM (pnm_io.h) instead of the formats FreeImage reads.
+// Beyond the reference: "-b <bytes>" encodes to a byte budget through the C ABI
+// (himg_hip_encode_budget_to, qualities 0 .. the -q value, 100 without one) and prints
+// the quality it chose.
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +14,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "himg_hip.h"
 #include "pnm_io.h"
 
 namespace {
@@ -18,6 +22,8 @@ namespace {
 struct Request {
   int quality = 50;        // the reference's default (src/chimg.cpp:22)
   bool ycbcr = true;
+  bool have_quality = false;
+  long long budget = -1;   // -b: at most this many bytes (-1: not given)
   const char *input = nullptr;
   const char *output = nullptr;
 };
@@ -46,6 +52,21 @@ bool parse(int argc, const char **argv, Request *rq) {
         printf("Invalid quality level: %d\n", rq->quality);
         return false;
       }
+      rq->have_quality = true;
+    } else if (!strcmp(a, "-b")) {
+      if (++i >= argc) return false;
+      char *end = nullptr;
+      errno = 0;
+      const long long v = strtoll(argv[i], &end, 10);
+      if (end == argv[i] || *end) {
+        printf("Invalid integer expression: %s\n", argv[i]);
+        return false;
+      }
+      if (v < 0 || errno == ERANGE) {
+        printf("Invalid byte budget: %s\n", argv[i]);
+        return false;
+      }
+      rq->budget = v;
     } else {
       printf("Invalid option: %s\n", a);
       return false;
@@ -62,7 +83,8 @@ int main(int argc, const char **argv) {
     printf("Usage: %s [options] image outfile\n"
            "Options:\n"
            " -q <quality> Set the quality (0-100)\n"
-           " -rgb         Use RGB color space (instead of YCbCr)\n",
+           " -rgb         Use RGB color space (instead of YCbCr)\n"
+           " -b <bytes>   Fit the file into a byte budget (-q: the highest quality to try)\n",
            argv[0]);
     return 0;
   }
@@ -78,9 +100,37 @@ int main(int argc, const char **argv) {
   std::vector<uint8_t> pixels(picture.data.size());
   pnm::flip_and_swap(picture.data.data(), pixels.data(), picture.width, picture.height, picture.channels);
 
+  const int c = picture.channels;
+  if (rq.budget >= 0) {
+    himg_hip_ctx *ctx = nullptr;
+    const size_t cap = himg_hip_max_packed_size(picture.width, picture.height, c);
+    std::vector<uint8_t> packed(cap);
+    size_t n = 0;
+    int quality = -1;
+    int rc = himg_hip_create(0, &ctx);
+    if (rc == HIMG_OK)
+      rc = himg_hip_encode_budget_to(ctx, pixels.data(), picture.width, picture.height, c, c, 0,
+                                     rq.have_quality ? rq.quality : 100, rq.ycbcr ? 1 : 0,
+                                     static_cast<size_t>(rq.budget), packed.data(), packed.size(), &n, &quality);
+    himg_hip_destroy(ctx);
+    if (rc == HIMG_ERR_CAPACITY && quality < 0) {
+      fprintf(stderr, "%s does not fit %lld bytes at quality 0\n", rq.input, rq.budget);
+      return -1;
+    }
+    if (rc != HIMG_OK) {
+      fprintf(stderr, "Unable to encode %s\n", rq.input);
+      return -1;
+    }
+    printf("Quality: %d\n", quality);
+    printf("Compressed size: %d\n", static_cast<int>(n));
+    FILE *f = fopen(rq.output, "wb");
+    const bool ok = f && fwrite(packed.data(), 1, n, f) == n;
+    if (f) fclose(f);
+    return ok ? 0 : -1;
+  }
+
   fflush(stdout);   // the library reports through std::cout
   himg::Encoder encoder;
-  const int c = picture.channels;
   if (!encoder.Encode(pixels.data(), picture.width, picture.height, c, c, rq.quality, rq.ycbcr)) {
     fprintf(stderr, "Unable to encode %s\n", rq.input);   // no GPU engine: there is no CPU fallback
     return -1;

@@ -122,6 +122,22 @@ struct LresTables {
   uint8_t code[512];  // code[delta + 255] for delta in [-255, 255]
 };
 
+// Everything of the encoder that depends on the quality, for ONE quality (encode with a quality per
+// frame, encode to a byte budget): a context holds 101 of them in HBM, and the quality-indexed
+// forms of the kernels read entry quality[frame] where the others read their kernel arguments.
+struct QualTab {
+  uint32_t pq[3][2][64];  // the pixel stage's quantiser words (PixQuant: rr, kk, ss x luma / chroma x scan position)
+  ShiftTables st;
+  LresTables lt;
+  uint8_t lmap[128];      // the LMAP chunk's payload (StaticChunks::head + 39)
+  uint8_t qcfg[64];       // the QCFG chunk's payload, luma then chroma (StaticChunks::mid + 8; 32 bytes without chroma)
+};
+constexpr int kQualities = 101;
+struct QualSel {
+  const QualTab *tab;       // [kQualities]
+  const int32_t *quality;   // [frame], each in [0, 100]
+};
+
 // ---- decoder ---------------------------------------------------------------
 
 constexpr int kLutBits = 11;  // width of the Huffman decode group table
@@ -221,6 +237,34 @@ void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_f
                    const StaticChunks &sc, const ShiftTables &st, const LresTables &lt,
                    const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
                    hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
+
+// One quality's entry of the table, from what build_static makes for that quality (host).
+void enc_fill_qual_tab(const StaticChunks &sc, const ShiftTables &st, const LresTables &lt, QualTab *qt);
+// launch_encode with frame f's tables taken from qs.tab[qs.quality[f]] (sc: build_static's for any
+// quality; its LMAP / QCFG payloads are not used).  d_out == nullptr: the size-only pass -- everything
+// up to k_span_bits, then the sizes alone to d_sizes: no byte of a stream is written, out_stride is
+// not looked at, and only the histograms and status words are zeroed in front of it.
+void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                     uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                     const StaticChunks &sc, const QualSel &qs,
+                     const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                     hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
+// The search of himg_hip_encode_budget_device (include/himg_hip.h), per frame on the device.
+struct BudgetState {
+  int32_t *quality;         // [f] the quality of the next probe / of the final encode
+  const uint32_t *budget;   // [f] bytes
+  int32_t *lo, *hi;         // [f] the bisection's bounds
+  int32_t *state;           // [f] kBudget*
+  int32_t *err;             // [f] a probe's own failure (an encoder status), kept through the later passes
+};
+enum { kBudgetSearch = 0, kBudgetFound = 1, kBudgetTooSmall = 2, kBudgetError = 3 };
+// Behind probe `probe` (0: at qmin, 1: at qmax, then the midpoints) of `probes`: advance every frame.
+// The last one leaves quality[f] = the result (qmin for a frame without one) and d_quality[f] (-1).
+void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
+                        const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof);
+// Behind the final encode: d_status[f] (the encode's own, or the search's failure) and d_sizes[f] = 0 for a failed frame.
+void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
+                          hipStream_t stream, Profiler *prof);
 
 // The decoder's helper streams and events (owned by the context).
 constexpr int kWalkSegs = 4;   // single large frames: at most this many row ranges whose walk / count / row kernels overlap

@@ -132,6 +132,10 @@ struct himg_hip_ctx {
 
   // Encoder workspace.
   DevBuf e_planes, e_lres, e_fres, e_small, e_spanhist, e_tok, e_tokx;
+  // Quality per frame / encode to a byte budget: the tables of all 101 qualities (built on first
+  // use) and the per-frame words of a launch (BudgetState's arrays, the quality first).
+  DevBuf e_qtab, e_bud;
+  bool qtab_ready = false;
   Geom enc_geom{};
   EncWs enc_ws{};
   int enc_batch = 0;
@@ -362,7 +366,7 @@ extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
     hipHostFree(ctx->pipe.h_meta);
   }
   DevBuf *all[] = {&ctx->fmap_lut, &ctx->e_planes, &ctx->e_lres, &ctx->e_fres, &ctx->e_small,
-                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
+                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_bud, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
                    &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->h_in,
                    &ctx->h_out, &ctx->h_sizes, &ctx->h_status, &ctx->h_index};
   for (DevBuf *b : all) b->release();
@@ -470,15 +474,15 @@ extern "C" int himg_hip_tok_layout(int width, int height, int pixel_stride, int 
 // ---------------------------------------------------------------------------
 // Workspaces.
 // ---------------------------------------------------------------------------
-// Copy `n` packed sizes into the next pinned slot and start the H2D copy from there.  org (the
-// region decode): n origins (x, y) follow the sizes, in the same slot and the same copy.
-static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s, const int32_t *org = nullptr) {
+// Copy the na words at a, then the nb words at b, into the next pinned slot and start the H2D copy
+// from there to d_dst.
+static int stage_words(himg_hip_ctx *ctx, void *d_dst, const void *a, size_t na, const void *b, size_t nb, hipStream_t s) {
   auto &r = ctx->sizes_ring;
   const int k = r.next;
   r.next = (k + 1) % himg_hip_ctx::SizeRing::kSlots;
   if (!r.ev[k]) HIP_TRY(ctx, hipEventCreateWithFlags(&r.ev[k], hipEventDisableTiming));
   if (r.busy[k]) HIP_TRY(ctx, hipEventSynchronize(r.ev[k]));
-  const size_t words = (size_t)n * (org ? 3 : 1);
+  const size_t words = na + nb;
   if (r.cap[k] < words) {
     if (r.h[k]) hipHostFree(r.h[k]);
     r.h[k] = nullptr;
@@ -487,12 +491,17 @@ static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_
     HIP_TRY(ctx, hipHostMalloc((void **)&r.h[k], want * 4, hipHostMallocDefault));
     r.cap[k] = want;
   }
-  memcpy(r.h[k], src, (size_t)n * 4);
-  if (org) memcpy(r.h[k] + n, org, (size_t)n * 8);
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sizes.p, r.h[k], words * 4, hipMemcpyHostToDevice, s));
+  memcpy(r.h[k], a, na * 4);
+  if (nb) memcpy(r.h[k] + na, b, nb * 4);
+  HIP_TRY(ctx, hipMemcpyAsync(d_dst, r.h[k], words * 4, hipMemcpyHostToDevice, s));
   HIP_TRY(ctx, hipEventRecord(r.ev[k], s));
   r.busy[k] = true;
   return HIMG_OK;
+}
+// `n` packed sizes on their way to the decoder's d_sizes.  org (the region decode): n origins
+// (x, y) follow the sizes, in the same slot and the same copy.
+static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s, const int32_t *org = nullptr) {
+  return stage_words(ctx, ctx->d_sizes.p, src, (size_t)n, org, org ? (size_t)n * 2 : 0, s);
 }
 
 static int ensure_enc_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool allow_row_tokens = true, bool force_row_tokens = false) {
@@ -767,6 +776,151 @@ extern "C" int himg_hip_encode_device(himg_hip_ctx *ctx, const void *d_frames, i
   if (d_status)
     hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, s, ctx->enc_ws.status,
                        d_status, batch);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+// ---- quality per frame, size-only pass, encode to a byte budget ----------------------------
+
+// The tables of every quality, in HBM: built on the context's first such call (the one place where
+// these calls wait for the device).
+static int ensure_qual_tab(himg_hip_ctx *ctx) {
+  if (ctx->qtab_ready) return HIMG_OK;
+  Geom g;
+  if (!make_geom(8, 8, 4, 4, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");   // (any geometry with a chroma table)
+  std::vector<QualTab> tabs(kQualities);
+  for (int q = 0; q < kQualities; ++q) {
+    StaticChunks sc;
+    ShiftTables st;
+    LresTables lt;
+    const int rc = build_static(g, q, &sc, &st, &lt);
+    if (rc) return fail(ctx, rc, "unsupported table configuration");
+    himg_dev::enc_fill_qual_tab(sc, st, lt, &tabs[q]);
+  }
+  if (!ctx->e_qtab.reserve(round_up(tabs.size() * sizeof(QualTab), 256)))
+    return fail(ctx, HIMG_ERR_HIP, "quality table allocation failed");
+  HIP_TRY(ctx, hipMemcpy(ctx->e_qtab.p, tabs.data(), tabs.size() * sizeof(QualTab), hipMemcpyHostToDevice));
+  ctx->qtab_ready = true;
+  return HIMG_OK;
+}
+
+struct EncQ {
+  Geom g;
+  StaticChunks sc;   // (the container's quality-independent bytes; LMAP / QCFG come from the table)
+  QualSel qs;
+  BudgetState bs;
+  hipStream_t s;
+};
+// What the three entry points share: the checks of himg_hip_encode_device (need_out: with its
+// output buffer's), the workspace, the table, and where the per-frame words live.
+static int enc_q_begin(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height, int pixel_stride,
+                       int num_channels, int use_ycbcr, bool need_out, const void *d_out, size_t out_stride,
+                       const uint32_t *d_sizes, void *stream, EncQ *e) {
+  if (!d_frames || !d_sizes || (need_out && !d_out) || batch < 1 || batch > 65535) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &e->g))
+    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
+  Geom &g = e->g;
+  apply_settings(ctx, &g);
+  if (g.rows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if (need_out && ((out_stride & 255) || out_stride < 1024 || ((uintptr_t)d_out & 15)))
+    return fail(ctx, HIMG_ERR_ARG, "out_stride must be a multiple of 256; buffers 16-byte aligned");
+  if ((uintptr_t)d_frames & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int rc = ensure_enc_ws(ctx, g, batch);
+  if (rc) return rc;
+  if ((rc = ensure_qual_tab(ctx))) return rc;
+  if (!ctx->e_bud.reserve(round_up((size_t)batch * 6 * 4, 256))) return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
+  ShiftTables st;
+  LresTables lt;
+  rc = build_static(g, 50, &e->sc, &st, &lt);
+  if (rc) return fail(ctx, rc, "unsupported table configuration");
+  int32_t *w = (int32_t *)ctx->e_bud.p;
+  e->qs.tab = (const QualTab *)ctx->e_qtab.p;
+  e->qs.quality = w;
+  e->bs.quality = w; e->bs.budget = (const uint32_t *)(w + batch);
+  e->bs.lo = w + 2 * (size_t)batch; e->bs.hi = w + 3 * (size_t)batch;
+  e->bs.state = w + 4 * (size_t)batch; e->bs.err = w + 5 * (size_t)batch;
+  e->s = (hipStream_t)stream;
+  ctx->last_stream = e->s;
+  return HIMG_OK;
+}
+static void enc_q_launch(himg_hip_ctx *ctx, const EncQ &e, int batch, const void *d_frames, void *d_out, size_t out_stride,
+                         uint32_t *d_sizes) {
+  launch_encode_q(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, (uint8_t *)d_out, out_stride, d_sizes, e.sc, e.qs,
+                  (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof, ctx->opts.use_side ? ctx->side_enc : nullptr,
+                  ctx->ev_fork_e, ctx->ev_join_e);
+}
+static bool qualities_ok(const int32_t *h_quality, int batch) {
+  if (!h_quality) return false;
+  for (int i = 0; i < batch; ++i)
+    if (h_quality[i] < 0 || h_quality[i] > 100) return false;
+  return true;
+}
+
+extern "C" int himg_hip_encode_device_q(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                        int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
+                                        void *d_out, size_t out_stride, uint32_t *d_sizes, int32_t *d_status,
+                                        void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
+  EncQ e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
+                       d_sizes, stream, &e);
+  if (rc) return rc;
+  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
+  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
+  if (d_status)
+    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_sizes_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                            int pixel_stride, int num_channels, const int32_t *h_quality,
+                                            int use_ycbcr, uint32_t *d_sizes, int32_t *d_status, void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
+  EncQ e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, false, nullptr, 0,
+                       d_sizes, stream, &e);
+  if (rc) return rc;
+  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
+  enc_q_launch(ctx, e, batch, d_frames, nullptr, 0, d_sizes);
+  if (d_status)
+    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_budget_probes(int qmin, int qmax) {
+  if (qmin < 0 || qmax > 100 || qmin > qmax) return HIMG_ERR_ARG;
+  if (qmin == qmax) return 1;
+  int n = 2;
+  for (int d = qmax - qmin; d > 1; d = (d + 1) >> 1) ++n;   // + ceil(log2(qmax - qmin))
+  return n;
+}
+
+extern "C" int himg_hip_encode_budget_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                             int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                             const uint32_t *h_budgets, void *d_out, size_t out_stride,
+                                             uint32_t *d_sizes, int32_t *d_quality, int32_t *d_status, void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  const int probes = himg_hip_budget_probes(qmin, qmax);
+  if (probes < 0) return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  if (!h_budgets || !d_quality) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  EncQ e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
+                       d_sizes, stream, &e);
+  if (rc) return rc;
+  // The first probe's qualities (qmin) and the budgets, in one copy: BudgetState's first two arrays.
+  std::vector<int32_t> q0((size_t)batch, qmin);
+  if ((rc = stage_words(ctx, e.bs.quality, q0.data(), (size_t)batch, h_budgets, (size_t)batch, e.s))) return rc;
+  for (int p = 0; p < probes; ++p) {
+    enc_q_launch(ctx, e, batch, d_frames, nullptr, 0, d_sizes);   // (every probe zeroes its own histograms and status words)
+    launch_budget_step(e.bs, ctx->enc_ws, batch, p, probes, qmin, qmax, d_sizes, d_quality, e.s, &ctx->prof);
+  }
+  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
+  launch_budget_finish(e.bs, ctx->enc_ws, batch, d_sizes, d_status, e.s, &ctx->prof);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -1119,9 +1273,20 @@ extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, in
 // The stream / the pixels of the last host call stay resident in ctx->h_out; the
 // entry points differ only in where they copy them to.
 
+// The budget forms of the host API: the quality range with each frame's budget, and where the chosen
+// quality goes (-1 for a frame whose budget is below its size at qmin).
+struct HostBudget {
+  int qmin, qmax;
+  const size_t *budgets;
+  int *qualities;
+};
+static uint32_t budget_u32(size_t b) { return b > 0xffffffffull ? 0xffffffffu : (uint32_t)b; }
+static const char *const kBudgetBelowQmin = "the budget is below the stream's size at qmin";
+
+// bud: the budget form (`quality` is then not used).
 static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
                        int pixel_stride, int num_channels, int quality, int use_ycbcr,
-                       uint32_t *n_out) {
+                       uint32_t *n_out, const HostBudget *bud = nullptr) {
   Geom g;
   if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
@@ -1132,14 +1297,27 @@ static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int he
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   ctx->host_bytes = 0;
   HIP_TRY(ctx, hipMemcpy(ctx->h_in.p, data, (size_t)g.frame_bytes, hipMemcpyHostToDevice));
-  int rc = himg_hip_encode_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels,
-                                  quality, use_ycbcr, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
-                                  (int32_t *)ctx->h_status.p, nullptr);
+  int rc;
+  if (bud) {
+    const uint32_t b = budget_u32(bud->budgets[0]);
+    rc = himg_hip_encode_budget_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels, bud->qmin,
+                                       bud->qmax, use_ycbcr, &b, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
+                                       (int32_t *)ctx->h_status.p + 1, (int32_t *)ctx->h_status.p, nullptr);
+  } else {
+    rc = himg_hip_encode_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels,
+                                quality, use_ycbcr, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
+                                (int32_t *)ctx->h_status.p, nullptr);
+  }
   if (rc) return rc;
   uint32_t n = 0;
-  int32_t st = 0;
+  int32_t st2[2] = {0, 0};   // the status, then (budget form) the quality
   HIP_TRY(ctx, hipMemcpy(&n, ctx->h_sizes.p, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(st2, ctx->h_status.p, bud ? 8 : 4, hipMemcpyDeviceToHost));
+  const int32_t st = st2[0];
+  if (bud) {
+    bud->qualities[0] = st2[1];
+    if (st == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
+  }
   if (st) return fail(ctx, status_to_code(st), "device encode reported an error");
   ctx->host_bytes = n;
   *n_out = n;
@@ -1170,6 +1348,24 @@ extern "C" int himg_hip_encode_to(himg_hip_ctx *ctx, const uint8_t *data, int wi
   *out_size = 0;
   uint32_t n = 0;
   const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, quality, use_ycbcr, &n);
+  if (rc) return rc;
+  *out_size = n;
+  if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, n, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
+                                         int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                         size_t budget, uint8_t *dst, size_t dst_cap, size_t *out_size, int *quality) {
+  if (!ctx || !data || !out_size || !quality) return HIMG_ERR_ARG;
+  *out_size = 0;
+  *quality = -1;
+  if (himg_hip_budget_probes(qmin, qmax) < 0)
+    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  uint32_t n = 0;
+  const HostBudget bud = {qmin, qmax, &budget, quality};
+  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, 0, use_ycbcr, &n, &bud);
   if (rc) return rc;
   *out_size = n;
   if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
@@ -1353,10 +1549,12 @@ static int pipe_init(himg_hip_ctx *ctx) {
   return HIMG_OK;
 }
 
-extern "C" int himg_hip_encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
-                                     int height, int pixel_stride, int num_channels, int quality,
-                                     int use_ycbcr, uint8_t *const *dst, const size_t *dst_cap,
-                                     size_t *out_sizes) {
+// himg_hip_encode_batch, and with bud its budget form (frame i: budget bud->budgets[i], the chosen
+// quality to bud->qualities[i]).
+static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                        int height, int pixel_stride, int num_channels, int quality,
+                        int use_ycbcr, uint8_t *const *dst, const size_t *dst_cap,
+                        size_t *out_sizes, const HostBudget *bud) {
   if (!ctx || !frames || !dst || !dst_cap || !out_sizes || n < 0) return HIMG_ERR_ARG;
   Geom g;
   if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
@@ -1379,7 +1577,9 @@ extern "C" int himg_hip_encode_batch(himg_hip_ctx *ctx, const uint8_t *const *fr
     const uint32_t nbytes = p.h_meta[slot * 4 + 0];
     const int32_t st = (int32_t)p.h_meta[slot * 4 + 1];
     int err = HIMG_OK;
-    if (st) err = fail(ctx, status_to_code(st), "device encode reported an error");
+    if (bud) bud->qualities[j] = (int32_t)p.h_meta[slot * 4 + 2];
+    if (bud && st == HIMG_ERR_CAPACITY) err = fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
+    else if (st) err = fail(ctx, status_to_code(st), "device encode reported an error");
     else if (!dst[j] || dst_cap[j] < nbytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
     if (!err) {
       HIP_TRY(ctx, hipMemcpyAsync(dst[j], p.out[slot].p, nbytes, hipMemcpyDeviceToHost, p.s_out));
@@ -1397,17 +1597,45 @@ extern "C" int himg_hip_encode_batch(himg_hip_ctx *ctx, const uint8_t *const *fr
     HIP_TRY(ctx, hipMemcpyAsync(p.in[slot].p, frames[i], (size_t)g.frame_bytes, hipMemcpyHostToDevice, p.s_in));
     HIP_TRY(ctx, hipEventRecord(p.ev_in[slot], p.s_in));
     HIP_TRY(ctx, hipStreamWaitEvent(p.s_comp, p.ev_in[slot], 0));
-    rc = himg_hip_encode_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, quality,
-                                use_ycbcr, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
-                                (int32_t *)p.meta[slot].p + 1, p.s_comp);
+    if (bud) {
+      const uint32_t b = budget_u32(bud->budgets[i]);
+      rc = himg_hip_encode_budget_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, bud->qmin,
+                                         bud->qmax, use_ycbcr, &b, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
+                                         (int32_t *)p.meta[slot].p + 2, (int32_t *)p.meta[slot].p + 1, p.s_comp);
+    } else {
+      rc = himg_hip_encode_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, quality,
+                                  use_ycbcr, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
+                                  (int32_t *)p.meta[slot].p + 1, p.s_comp);
+    }
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + slot * 4, p.meta[slot].p, 8, hipMemcpyDeviceToHost, p.s_comp));
+    HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + slot * 4, p.meta[slot].p, bud ? 12 : 8, hipMemcpyDeviceToHost, p.s_comp));
     HIP_TRY(ctx, hipEventRecord(p.ev_k[slot], p.s_comp));
     if (i >= 1 && (rc = finish(i - 1))) return rc;
   }
   if (n >= 1 && (rc = finish(n - 1))) return rc;
   HIP_TRY(ctx, hipStreamSynchronize(p.s_out));
   return first_err;
+}
+
+extern "C" int himg_hip_encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                                     int height, int pixel_stride, int num_channels, int quality,
+                                     int use_ycbcr, uint8_t *const *dst, const size_t *dst_cap,
+                                     size_t *out_sizes) {
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, quality, use_ycbcr, dst, dst_cap,
+                      out_sizes, nullptr);
+}
+
+extern "C" int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                                            int height, int pixel_stride, int num_channels, int qmin, int qmax,
+                                            int use_ycbcr, const size_t *budgets, uint8_t *const *dst,
+                                            const size_t *dst_cap, size_t *out_sizes, int *qualities) {
+  if (!ctx || !budgets || !qualities || n < 0) return HIMG_ERR_ARG;
+  for (int i = 0; i < n; ++i) qualities[i] = -1;
+  if (himg_hip_budget_probes(qmin, qmax) < 0)
+    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  const HostBudget bud = {qmin, qmax, budgets, qualities};
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, 0, use_ycbcr, dst, dst_cap, out_sizes,
+                      &bud);
 }
 
 extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,

@@ -18,7 +18,10 @@
 #include "himg_dev.h"
 #include "loop_counts.h"
 
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
+#include <type_traits>
 #include <utility>
 
 namespace himg_dev {
@@ -35,6 +38,18 @@ static constexpr uint8_t kScanHost[64] = {HIMG_SCAN_ORDER};   // the same for ho
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 __device__ __forceinline__ int clamp255(int x) { return x < 0 ? 0 : (x > 255 ? 255 : x); }
+
+// Wave-uniform read-only words -- the kernel-argument segment, or a table in HBM that no kernel of
+// the launch writes: a load through this address space at a uniform address is a scalar load.
+typedef const __attribute__((address_space(4))) uint32_t *KargWords;
+__device__ __forceinline__ KargWords uniform_words(const void *p) { return (KargWords)(uintptr_t)p; }
+// The quality-indexed forms of the kernels (QI, a compile-time parameter) take a QualSel where the
+// others take their tables as kernel arguments.  The frame index is uniform per workgroup: the
+// frame's quality is one scalar load, and its entry of the table a base address in scalar registers.
+template <bool QI, class T> using QualArg = std::conditional_t<QI, QualSel, T>;
+__device__ __forceinline__ const QualTab *qual_entry(const QualSel &qs, int f) {
+  return qs.tab + __builtin_amdgcn_readfirstlane((int)uniform_words(qs.quality)[f]);
+}
 
 // Colour lift of one pixel (ycbcr.cpp:32-37).
 __device__ __forceinline__ void lift_fwd(int &c0, int &c1, int &c2) {
@@ -184,9 +199,11 @@ __device__ __forceinline__ int predict(int s1, int s2, int s3, int p) {
 //     the 256-step serial chain is run as 31 anti-diagonal wavefronts, lane =
 //     row of the macro block, reconstructed samples exchanged through LDS.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_lres_predict(Geom g, const uint8_t *low,
-                                                     size_t plane_stride, uint8_t *lres_sym,
-                                                     size_t lres_stride, LresTables lt) {
+// QI: the companding tables of the frame's own quality.
+template <bool QI>
+__global__ __launch_bounds__(64) void k_lres_predict_t(Geom g, const uint8_t *low,
+                                                       size_t plane_stride, uint8_t *lres_sym,
+                                                       size_t lres_stride, QualArg<QI, LresTables> lt) {
   // FOUR macro blocks per wavefront, 16 lanes each (lane & 15 = row of the block):
   // the delta chain only ever has 16 rows to work on, so one block per wave left
   // three quarters of it idle -- and a 4096x4096 frame is 4096 blocks per channel.
@@ -200,8 +217,15 @@ __global__ __launch_bounds__(64) void k_lres_predict(Geom g, const uint8_t *low,
   const int lane = threadIdx.x, b = lane >> 4, dv = lane & 15;
   const int mu = blockIdx.x * 4 + b, mv = blockIdx.y;
   const int f = blockIdx.z / g.C, c = blockIdx.z % g.C;
-  for (int k = lane; k < 128; k += 64) s_tab[k] = lt.tab[k];
-  for (int k = lane; k < 512; k += 64) s_code[k] = lt.code[k];
+  if constexpr (QI) {
+    // (the frame's entry: a uniform base, the lanes' own elements of it on their way into the LDS)
+    const LresTables *__restrict__ q = &qual_entry(lt, f)->lt;
+    for (int k = lane; k < 128; k += 64) s_tab[k] = q->tab[k];
+    for (int k = lane; k < 512; k += 64) s_code[k] = q->code[k];
+  } else {
+    for (int k = lane; k < 128; k += 64) s_tab[k] = lt.tab[k];
+    for (int k = lane; k < 512; k += 64) s_code[k] = lt.code[k];
+  }
   const uint8_t *m = low + (size_t)f * plane_stride + (size_t)c * g.rows * g.cols;
   const bool live = mu < g.mcols;
   const int u0 = mu * 16, v0 = mv * 16;
@@ -314,6 +338,8 @@ __global__ __launch_bounds__(64) void k_lres_predict(Geom g, const uint8_t *low,
     __syncthreads();
   }
 }
+static constexpr auto k_lres_predict = &k_lres_predict_t<false>;
+static constexpr auto k_lres_predict_q = &k_lres_predict_t<true>;
 
 // ---------------------------------------------------------------------------
 // Tile helpers.
@@ -398,12 +424,13 @@ __device__ __forceinline__ void residual_full_tile(const uint8_t *row0, size_t p
 // FAST: every tile is full and pixels are packed RGBA8 (the BASELINE configs);
 // otherwise the generic path handles ragged edges, other channel counts and
 // pixel strides.
-template <bool FAST, int COLS>
+// QI: the shift tables of the frame's own quality (scalar loads of the table's words).
+template <bool FAST, int COLS, bool QI = false>
 __global__ __launch_bounds__(kTileThreads) void k_tile_fwd(Geom g, const uint8_t *frames,
                                                   const uint8_t *low, size_t plane_stride,
                                                   uint8_t *fres_sym, size_t fres_stride,
                                                   const uint8_t *__restrict__ fmap_lut,
-                                                  ShiftTables st, int v0) {
+                                                  QualArg<QI, ShiftTables> st, int v0) {
   const int u = blockIdx.x * blockDim.x + threadIdx.x;
   const int v = blockIdx.y + v0, f = blockIdx.z;
   if (u >= g.cols) return;
@@ -459,13 +486,18 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_fwd(Geom g, const uint8_t
       wht8(b[x], b[8 + x], b[16 + x], b[24 + x], b[32 + x], b[40 + x], b[48 + x], b[56 + x]);
 
     const bool chroma = g.ycbcr && (c == 1 || c == 2);  // encoder.cpp:284
-    const uint8_t *shift = st.s[chroma ? 1 : 0];
+    const uint8_t *shift = nullptr;
+    KargWords shift_w = nullptr;
+    if constexpr (QI) shift_w = uniform_words(qual_entry(st, f)->st.s[chroma ? 1 : 0]);
+    else shift = st.s[chroma ? 1 : 0];
     const int cols = COLS ? COLS : g.cols;  // compile-time stride -> no 64 live store addresses
     uint8_t *dst = dst_row + (size_t)c * 64 * cols;
 #pragma unroll
     for (int i = 0; i < 64; ++i) {
       const int pos = kScan[i];
-      const int s = shift[pos];
+      int s;
+      if constexpr (QI) s = (int)((shift_w[pos >> 2] >> (8 * (pos & 3))) & 255u);
+      else s = shift[pos];
       const int x = (int)(int16_t)b[pos];  // the reference's int16 wrap
       // Sign-magnitude rounding shift (quantize.cpp:135-148).
       const int r = s ? (1 << (s - 1)) : 0;
@@ -608,12 +640,13 @@ static PixQuant make_pix_quant(const ShiftTables &st) {
   return pq;
 }
 
-template <bool YCBCR, int COLS, bool FULL>
+// QI: the quantiser's words of the frame's own quality, scalar loads from its entry of the table.
+template <bool YCBCR, int COLS, bool FULL, bool QI = false>
 __global__ __launch_bounds__(kPixThreads, 2) void k_pix_fwd(Geom g, const uint8_t *frames,
                                                             const uint8_t *low, size_t plane_stride,
                                                             uint8_t *fres_sym, size_t fres_stride,
                                                             const uint8_t *__restrict__ fmap_lut,
-                                                            PixQuant pq, int v0) {
+                                                            QualArg<QI, PixQuant> pq, int v0) {
   // Companding LUT for magnitudes below kPixLut (every larger one maps to 127:
   // the full-res table tops out at 8039, mapper.cpp:54-71,159-182).
   __shared__ __attribute__((aligned(16))) uint8_t s_lut[kPixLut];
@@ -624,6 +657,8 @@ __global__ __launch_bounds__(kPixThreads, 2) void k_pix_fwd(Geom g, const uint8_
   const int u = blockIdx.x * kPixThreads + threadIdx.x;
   const int v = blockIdx.y + v0, f = blockIdx.z;
   if ((int)(blockIdx.x * kPixThreads + (threadIdx.x & ~63)) >= cols) return;   // the whole wave is beyond the row
+  KargWords qw = nullptr;   // QI: [rr, kk, ss][luma / chroma][coefficient], as k_front indexes PixQuant
+  if constexpr (QI) qw = uniform_words(qual_entry(pq, f)->pq);
   // FULL: cols is a multiple of 64, every lane of a live wave owns a tile.
   const bool valid = FULL || u < cols;
   const int uc = valid ? u : cols - 1;
@@ -711,8 +746,14 @@ __global__ __launch_bounds__(kPixThreads, 2) void k_pix_fwd(Geom g, const uint8_
         const pk16 x = b[pos];
         const pk16 fifteen = {15, 15};
         const pk16 sign = x >> fifteen;                       // 0 or -1 per half
-        const pk16 rr = __builtin_bit_cast(pk16, pq.rr[qt][i]), kk = __builtin_bit_cast(pk16, pq.kk[qt][i]);
-        const pk16 ss = __builtin_bit_cast(pk16, pq.ss[qt][i]);
+        pk16 rr, kk, ss;
+        if constexpr (QI) {
+          rr = __builtin_bit_cast(pk16, qw[(0 * 2 + qt) * 64 + i]); kk = __builtin_bit_cast(pk16, qw[(1 * 2 + qt) * 64 + i]);
+          ss = __builtin_bit_cast(pk16, qw[(2 * 2 + qt) * 64 + i]);
+        } else {
+          rr = __builtin_bit_cast(pk16, pq.rr[qt][i]); kk = __builtin_bit_cast(pk16, pq.kk[qt][i]);
+          ss = __builtin_bit_cast(pk16, pq.ss[qt][i]);
+        }
         q[k] = (sign * kk + x + rr) >> ss;
         const upk16 fifty = {50, 50};
         top = __builtin_elementwise_max(top, (upk16)(__builtin_bit_cast(upk16, q[k]) + fifty));
@@ -809,7 +850,8 @@ __device__ __forceinline__ uint32_t front_blend(uint32_t a11, uint32_t a12, uint
 
 // (One argument block: the quantiser's tables are read through the kernel-argument segment at
 // offsetof(FrontArgs, pq) -- see the walk below.)
-struct FrontArgs {
+template <bool QI>
+struct FrontArgsT {
   Geom g;
   const uint8_t *frames;
   uint8_t *avg, *low;
@@ -818,12 +860,14 @@ struct FrontArgs {
   size_t fres_stride;
   const uint8_t *fmap_lut;
   int chunk_rows;
-  PixQuant pq;
+  QualArg<QI, PixQuant> pq;
 };
-typedef const __attribute__((address_space(4))) uint32_t *KargWords;
+typedef FrontArgsT<false> FrontArgs;
 
-template <bool YCBCR, int COLS>
-__global__ __launch_bounds__(512) void k_front(FrontArgs a) {
+// QI: the quantiser's words come from the frame's entry of the per-quality table instead -- the same
+// scalar loads at their uses, from a base in HBM.
+template <bool YCBCR, int COLS, bool QI = false>
+__global__ __launch_bounds__(512) void k_front(FrontArgsT<QI> a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const Geom &g = a.g;
   const uint8_t *frames = a.frames, *fmap_lut = a.fmap_lut;
@@ -873,6 +917,8 @@ __global__ __launch_bounds__(512) void k_front(FrontArgs a) {
 
   const int t_begin = max(v0 - 2, 0), t_end = v1;   // rows whose sums this chunk needs (t_end == rows: nothing to load)
   load_row(t_begin);
+  KargWords qbase = nullptr;
+  if constexpr (QI) qbase = uniform_words(qual_entry(a.pq, f)->pq);
   const pk16 zero2 = {0, 0};
   pk16 bl_prev[2] = {zero2, zero2}, brl_prev[2] = {zero2, zero2};   // BL(u, t-1), BR(u-1, t-1)
   uint32_t avg_prev[3] = {0, 0, 0};    // averages of row t - 1 at u - 1, u, u + 1 (clipped)
@@ -883,8 +929,10 @@ __global__ __launch_bounds__(512) void k_front(FrontArgs a) {
     // The quantiser's 384 words are scalar loads from the kernel arguments AT THEIR USES, as in
     // k_pix_fwd: through a pointer the compiler cannot see through, or it hoists all of them out
     // of this loop (370 scalar registers spilled).
-    KargWords qw = (KargWords)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
-                               offsetof(FrontArgs, pq));
+    KargWords qw;
+    if constexpr (QI) qw = qbase;
+    else qw = (KargWords)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
+                          offsetof(FrontArgs, pq));
     asm volatile("" : "+s"(qw));
     const bool have = t < g.rows;
     uint32_t low_cur[2] = {low_prev[0], low_prev[1]};   // (t == rows: the row below the last one is the last one)
@@ -2116,12 +2164,16 @@ __global__ __launch_bounds__(256) void k_span_bits(Geom g, EncWs ws, int sp0, in
 // this identically and emits its rows at the same relative offsets.
 // [hr0, hr1): the rows whose size headers this call stores (a rank's own rows when `out`
 // is shared with other ranks / devices: nobody else's bytes are touched).
-__global__ __launch_bounds__(256) void k_sizes(Geom g, EncWs ws, StaticChunks sc, uint8_t *out,
-                                               size_t out_stride, uint32_t *sizes,
-                                               const uint32_t *row_bits_in, int fres_rel, int hr0, int hr1) {
+// QI: the LMAP and QCFG payloads of the frame's own quality (qs) replace sc's.
+// SIZES: the size-only pass -- sizes[f] and nothing else: no byte of a stream (out is not looked at),
+// no out_stride in the fit test; status 5 only where no out_stride could help (2 GiB, the LRES bound).
+template <bool QI, bool SIZES>
+__device__ __forceinline__ void sizes_body(const Geom &g, const EncWs &ws, const StaticChunks &sc, const QualSel &qs,
+                                           uint8_t *out, size_t out_stride, uint32_t *sizes,
+                                           const uint32_t *row_bits_in, int fres_rel, int hr0, int hr1) {
   __shared__ uint32_t sm[4];
   const int f = blockIdx.x, tid = threadIdx.x;
-  uint8_t *o = out + (size_t)f * out_stride;
+  uint8_t *o = SIZES ? nullptr : out + (size_t)f * out_stride;
   const int nsp = g.lres_spans + g.rows;
   uint64_t *bit0 = ws.span_bit0 + (size_t)f * nsp;
   uint32_t *nbits = ws.span_bits + (size_t)f * nsp;
@@ -2160,7 +2212,7 @@ __global__ __launch_bounds__(256) void k_sizes(Geom g, EncWs ws, StaticChunks sc
       const unsigned long long p = pos + ex + hdr;  // first payload byte
       bit0[g.lres_spans + r] = 8ull * p;
       nbits[g.lres_spans + r] = b;
-      if (p + nbytes <= out_stride && r >= hr0 && r < hr1) {
+      if (!SIZES && p + nbytes <= out_stride && r >= hr0 && r < hr1) {
         if (hdr == 2) {
           o[p - 2] = (uint8_t)(nbytes & 255); o[p - 1] = (uint8_t)(nbytes >> 8);
         } else if (hdr == 4) {
@@ -2178,22 +2230,26 @@ __global__ __launch_bounds__(256) void k_sizes(Geom g, EncWs ws, StaticChunks sc
   // + 64 bytes from kHeadLen & ~3 (launch_encode); a payload beyond it (more than
   // 8 bits per symbol on average) would be OR-ed onto stale bytes.
   const bool lres_fits = fres_rel || (unsigned long long)lres_bytes + 8ull <= (unsigned long long)g.lres_size + kTreeStride + 64ull;
-  const bool fits = total <= out_stride && total < 0x7fffffffull && lres_fits;
+  const bool fits = (SIZES || total <= out_stride) && total < 0x7fffffffull && lres_fits;
   if (tid == 0) {
     if (!fits) atomicMax(&ws.status[f], 5);
     sizes[f] = (fits && ws.status[f] == 0) ? (uint32_t)total : 0u;
   }
-  if (!fits || fres_rel) return;
+  if (!fits || fres_rel || SIZES) return;
 
+  const QualTab *__restrict__ qt = nullptr;
+  if constexpr (QI) qt = qual_entry(qs, f);
   // Static container bytes with the data-dependent size fields patched in.
   for (int k = tid; k < kHeadLen; k += 256) {
     uint8_t b = sc.head[k];
+    if constexpr (QI) { if (k >= 39 && k < 39 + 128) b = qt->lmap[k - 39]; }
     if (k >= 4 && k < 8) b = (uint8_t)(((uint32_t)total - 8u) >> (8 * (k - 4)));
     if (k >= kHeadLen - 4) b = (uint8_t)(lres_bytes >> (8 * (k - (kHeadLen - 4))));
     o[k] = b;
   }
   for (int k = tid; k < sc.mid_len; k += 256) {
     uint8_t b = sc.mid[k];
+    if constexpr (QI) { if (k >= 8 && k < 8 + (g.ycbcr ? 64 : 32)) b = qt->qcfg[k - 8]; }
     if (k >= sc.mid_len - 4) b = (uint8_t)(fres_bytes >> (8 * (k - (sc.mid_len - 4))));
     o[kHeadLen + lres_bytes + k] = b;
   }
@@ -2201,6 +2257,66 @@ __global__ __launch_bounds__(256) void k_sizes(Geom g, EncWs ws, StaticChunks sc
   const uint8_t *tf = ws.tree + ((size_t)f * 2 + 1) * kTreeStride;
   for (int k = tid; k < (int)tree_l; k += 256) o[kHeadLen + k] = tl[k];
   for (int k = tid; k < (int)tree_f; k += 256) o[fres_base + k] = tf[k];
+}
+__global__ __launch_bounds__(256) void k_sizes(Geom g, EncWs ws, StaticChunks sc, uint8_t *out,
+                                               size_t out_stride, uint32_t *sizes,
+                                               const uint32_t *row_bits_in, int fres_rel, int hr0, int hr1) {
+  sizes_body<false, false>(g, ws, sc, QualSel{}, out, out_stride, sizes, row_bits_in, fres_rel, hr0, hr1);
+}
+__global__ __launch_bounds__(256) void k_sizes_q(Geom g, EncWs ws, StaticChunks sc, QualSel qs, uint8_t *out,
+                                                 size_t out_stride, uint32_t *sizes) {
+  sizes_body<true, false>(g, ws, sc, qs, out, out_stride, sizes, nullptr, 0, 0, g.rows);
+}
+// (sc: for the length of the QCFG / FMAP part; a stream's size does not depend on what those chunks hold)
+__global__ __launch_bounds__(256) void k_sizes_only(Geom g, EncWs ws, StaticChunks sc, uint32_t *sizes) {
+  sizes_body<false, true>(g, ws, sc, QualSel{}, nullptr, 0, sizes, nullptr, 0, 0, g.rows);
+}
+
+// ---------------------------------------------------------------------------
+// k_budget_step: the search of himg_hip_encode_budget_device between two size probes, one lane per
+// frame.  Probe 0 was at qmin, probe 1 at qmax, every later one at the midpoint the step before
+// chose; sizes[f] / ws.status[f] are the probe's.  A settled frame's quality stays where it is (its
+// later probes repeat), so that behind the last step quality[f] is what the final encode takes.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_budget_step(BudgetState bs, const int32_t *probe_status, const uint32_t *sizes,
+                                                    int batch, int probe, int last, int qmin, int qmax,
+                                                    int32_t *d_quality) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  int state = probe == 0 ? (int)kBudgetSearch : bs.state[f];
+  int lo = probe == 0 ? qmin : bs.lo[f], hi = probe == 0 ? qmax : bs.hi[f];
+  int err = probe == 0 ? 0 : bs.err[f];
+  if (state == kBudgetSearch) {
+    const int32_t st = probe_status[f];
+    const bool fit = sizes[f] <= bs.budget[f];
+    if (st != 0) { state = kBudgetError; err = st; }
+    else if (probe == 0) {
+      if (!fit) state = kBudgetTooSmall;
+      else if (qmax == qmin) state = kBudgetFound;
+    } else if (probe == 1) {
+      if (fit) { lo = qmax; state = kBudgetFound; }
+    } else {
+      const int mid = (lo + hi) >> 1;   // (what this probe was at)
+      if (fit) lo = mid; else hi = mid;
+    }
+    if (state == kBudgetSearch && probe >= 1 && hi - lo <= 1) state = kBudgetFound;
+  }
+  const bool found = state == kBudgetFound;
+  // The next probe: qmax behind the first, then the midpoint; a settled frame: its result (qmin without one).
+  bs.quality[f] = state == kBudgetSearch ? (probe == 0 ? qmax : (lo + hi) >> 1) : (found ? lo : qmin);
+  bs.lo[f] = lo; bs.hi[f] = hi; bs.state[f] = state; bs.err[f] = err;
+  if (last) d_quality[f] = found ? lo : -1;
+}
+
+// Behind the final encode: a frame without a result keeps the search's verdict, whatever its
+// encode at qmin said; the others get the encode's own status.
+__global__ __launch_bounds__(64) void k_budget_finish(BudgetState bs, const int32_t *enc_status, int batch,
+                                                      uint32_t *sizes, int32_t *d_status) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  const int state = bs.state[f];
+  if (state != kBudgetFound) sizes[f] = 0;
+  if (d_status) d_status[f] = state == kBudgetFound ? enc_status[f] : state == kBudgetTooSmall ? -5 /* HIMG_ERR_CAPACITY */ : bs.err[f];
 }
 
 // ---------------------------------------------------------------------------
@@ -2846,6 +2962,24 @@ static bool use_pix_path(const Geom &g) {
   return g.W % 8 == 0 && g.H % 8 == 0 && g.stride == 4 && g.C == 4;
 }
 
+// The same launch with the quantiser of every frame's own quality (the COLS = 0 forms serve every width).
+static void launch_pix_q(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const QualSel &qs,
+                         const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof) {
+  const unsigned gxt = (unsigned)((g.cols + kPixThreads - 1) / kPixThreads);
+  const dim3 grid(gxt, g.rows, batch), block(kPixThreads);
+#define HIMG_PIX_Q(Y, COLS, FULL)                                                                          \
+  HIMG_LAUNCH((k_pix_fwd<Y, COLS, FULL, true>), grid, block, g, d_frames, ws.low, ws.plane_stride, ws.fres_sym, \
+              ws.fres_stride, d_fmap_lut, qs, 0)
+  const bool full = g.cols % 64 == 0;
+  if (g.ycbcr) {
+    if (g.cols == 512) HIMG_PIX_Q(true, 512, true);
+    else if (full) HIMG_PIX_Q(true, 0, true);
+    else HIMG_PIX_Q(true, 0, false);
+  }
+  else { if (full) HIMG_PIX_Q(false, 0, true); else HIMG_PIX_Q(false, 0, false); }
+#undef HIMG_PIX_Q
+}
+
 static void launch_pix(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const ShiftTables &st,
                        const uint8_t *d_fmap_lut, int r0, int n, int batch, hipStream_t stream,
                        Profiler *prof) {
@@ -2880,8 +3014,10 @@ static bool use_front(const Geom &g, int batch) {
   // (256 x 1024^2: 97 against 109 Gpx/s with the three kernels).
   return g.cols > 192 && (long long)g.rows * batch >= 8192;
 }
-static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const ShiftTables &st,
-                         const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof) {
+// qs (else st): the quality-indexed form.
+static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const ShiftTables *st,
+                         const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof,
+                         const QualSel *qs = nullptr) {
   const int wpr = (g.cols + 63) / 64, nt = 64 * wpr;
   // ~64 block rows per workgroup (a chunk re-reads two tile rows above it), more chunks when the batch
   // alone does not give every CU two rounds of workgroups; never fewer than 16 rows.
@@ -2892,10 +3028,24 @@ static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames
   const int chunk = (g.rows + nchunks - 1) / nchunks;
   const size_t lds = (size_t)nt * 256 + kPixLut + (size_t)kFrontExch * nt * 4;
   const dim3 grid((unsigned)((g.rows + chunk - 1) / chunk), (unsigned)batch), block((unsigned)nt);
+  auto fill = [&](auto &fa) {
+    fa.g = g; fa.frames = d_frames; fa.avg = ws.avg; fa.low = ws.low; fa.plane_stride = ws.plane_stride;
+    fa.fres_sym = ws.fres_sym; fa.fres_stride = ws.fres_stride; fa.fmap_lut = d_fmap_lut; fa.chunk_rows = chunk;
+  };
+  if (qs) {
+    FrontArgsT<true> fq;
+    fill(fq);
+    fq.pq = *qs;
+    prof_begin(prof, "k_front", stream);
+    if (g.ycbcr && g.cols == 512) hipLaunchKernelGGL((k_front<true, 512, true>), grid, block, lds, stream, fq);
+    else if (g.ycbcr) hipLaunchKernelGGL((k_front<true, 0, true>), grid, block, lds, stream, fq);
+    else hipLaunchKernelGGL((k_front<false, 0, true>), grid, block, lds, stream, fq);
+    prof_end(prof, stream);
+    return;
+  }
   FrontArgs fa;
-  fa.g = g; fa.frames = d_frames; fa.avg = ws.avg; fa.low = ws.low; fa.plane_stride = ws.plane_stride;
-  fa.fres_sym = ws.fres_sym; fa.fres_stride = ws.fres_stride; fa.fmap_lut = d_fmap_lut; fa.chunk_rows = chunk;
-  fa.pq = make_pix_quant(st);
+  fill(fa);
+  fa.pq = make_pix_quant(*st);
   static_assert(sizeof(((PixQuant *)0)->rr) == 2 * 64 * 4 && offsetof(PixQuant, kk) == 512 && offsetof(PixQuant, ss) == 1024,
                 "k_front indexes the quantiser's words as [table][luma / chroma][coefficient]");
 #define HIMG_FRONT(Y, COLS)                                                                               \
@@ -2920,7 +3070,10 @@ hipError_t enc_set_kernel_attrs() {
                          reinterpret_cast<const void *>(&k_front<true, 256>),
                          reinterpret_cast<const void *>(&k_front<true, 240>),
                          reinterpret_cast<const void *>(&k_front<true, 0>),
-                         reinterpret_cast<const void *>(&k_front<false, 0>)};
+                         reinterpret_cast<const void *>(&k_front<false, 0>),
+                         reinterpret_cast<const void *>(&k_front<true, 512, true>),
+                         reinterpret_cast<const void *>(&k_front<true, 0, true>),
+                         reinterpret_cast<const void *>(&k_front<false, 0, true>)};
   for (const void *k : front) {
     const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
@@ -3022,19 +3175,29 @@ void launch_tok_expand(const Geom &g, const EncWs &ws, int frame, uint8_t *dst, 
 
 int loop_counts_read_enc(unsigned long long *out) { return loop_counts_read(out); }
 
-void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
-                   uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
-                   const StaticChunks &sc, const ShiftTables &st, const LresTables &lt,
-                   const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
-                   hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+// The launch sequence of an encode.  st / lt: the tables of the launch's one quality as kernel
+// arguments (launch_encode); qs instead: the quality-indexed forms of the five kernels that read
+// them (launch_encode_q), and with d_out == nullptr its size-only pass.
+static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                            uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                            const StaticChunks &sc, const ShiftTables *st, const LresTables *lt, const QualSel *qs,
+                            const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                            hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
   const int nsp = g.lres_spans + g.rows;
   const dim3 b256(256);
   const unsigned gx = (unsigned)((g.cols + 255) / 256);
+  const bool sizes_only = d_out == nullptr;
 
   prof_begin(prof, "memset", stream);
-  // Histograms, status words and the LRES payload region -- pre-zeroed because span
-  // edges are OR-ed in (k_emit).
-  {
+  if (sizes_only) {
+    // (no stream, no LRES region: the histograms and the status words alone)
+    hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)((batch * 2 * kHistStride + 256 * 8 - 1) / (256 * 8)), 1), b256, 0, stream,
+                       reinterpret_cast<uint32_t *>(ws.hist), (size_t)0, 0u,
+                       reinterpret_cast<uint32_t *>(ws.hist), (uint32_t)(batch * 2 * kHistStride),
+                       reinterpret_cast<uint32_t *>(ws.status), (uint32_t)batch);
+  } else {
+    // Histograms, status words and the LRES payload region -- pre-zeroed because span
+    // edges are OR-ed in (k_emit).
     const size_t start = (size_t)(kHeadLen & ~3);
     size_t width = (size_t)g.lres_size + kTreeStride + 64;
     if (start + width > out_stride) width = out_stride - start;
@@ -3052,7 +3215,7 @@ void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_f
   // low-res plane and the symbols; the LRES branch then forks behind it and runs beside the tokeniser.
   const bool front = use_front(g, batch);
   if (front) {
-    launch_front(g, ws, d_frames, st, d_fmap_lut, batch, stream, prof);
+    launch_front(g, ws, d_frames, st, d_fmap_lut, batch, stream, prof, qs);
   } else {
     HIMG_LAUNCH(k_lowres_avg, dim3(gx, g.rows, batch), b256, g, d_frames, ws.avg, ws.plane_stride, 0);
     if ((g.cols & 3) == 0 && (ws.plane_stride & 3) == 0)
@@ -3074,8 +3237,12 @@ void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_f
   {
     hipStream_t stream_saved = stream;
     stream = ls;
-    HIMG_LAUNCH(k_lres_predict, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
-                ws.plane_stride, ws.lres_sym, ws.lres_stride, lt);
+    if (qs)
+      HIMG_LAUNCH(k_lres_predict_q, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
+                  ws.plane_stride, ws.lres_sym, ws.lres_stride, *qs);
+    else
+      HIMG_LAUNCH(k_lres_predict, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
+                  ws.plane_stride, ws.lres_sym, ws.lres_stride, *lt);
     HIMG_LAUNCH(k_lres_summary, dim3(g.lres_spans, batch), b256, g, ws);
     HIMG_LAUNCH(k_tok_hist<256>, dim3(g.lres_spans, batch), b256, g, ws, 0);
     stream = stream_saved;
@@ -3087,18 +3254,29 @@ void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_f
   if (front) {
     // (the symbols are there already)
   } else if (pix) {
-    launch_pix(g, ws, d_frames, st, d_fmap_lut, 0, g.rows, batch, stream, prof);
+    if (qs) launch_pix_q(g, ws, d_frames, *qs, d_fmap_lut, batch, stream, prof);
+    else launch_pix(g, ws, d_frames, *st, d_fmap_lut, 0, g.rows, batch, stream, prof);
+  } else if (qs) {
+    HIMG_LAUNCH((k_tile_fwd<false, 0, true>), dim3(gxt, g.rows, batch), dim3(kTileThreads), g, d_frames,
+                ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, *qs, 0);
   } else {
     HIMG_LAUNCH((k_tile_fwd<false, 0>), dim3(gxt, g.rows, batch), dim3(kTileThreads), g, d_frames,
-                ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, st, 0);
+                ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, *st, 0);
   }
   if (row_tok) launch_tok_rows(g, ws, 0, g.rows, batch, stream, prof);   // FRES rows: slots + histograms
   else launch_tok_hist_rows(g, ws, 0, g.rows, batch, stream, prof);
   if (side) (void)hipStreamWaitEvent(stream, ev_join, 0);
   HIMG_LAUNCH(k_tree, dim3(2, batch), dim3(kTreeThreads), ws, 0);
   HIMG_LAUNCH(k_span_bits, dim3((nsp + 3) / 4, batch), b256, g, ws, 0, nsp, (uint32_t *)nullptr);
-  HIMG_LAUNCH(k_sizes, dim3(batch), b256, g, ws, sc, d_out, out_stride, d_sizes,
-              (const uint32_t *)nullptr, 0, 0, g.rows);
+  if (sizes_only) {
+    HIMG_LAUNCH(k_sizes_only, dim3(batch), b256, g, ws, sc, d_sizes);
+    return;
+  }
+  if (qs)
+    HIMG_LAUNCH(k_sizes_q, dim3(batch), b256, g, ws, sc, *qs, d_out, out_stride, d_sizes);
+  else
+    HIMG_LAUNCH(k_sizes, dim3(batch), b256, g, ws, sc, d_out, out_stride, d_sizes,
+                (const uint32_t *)nullptr, 0, 0, g.rows);
   // The LRES spans' bit packing (1/64 of the symbols, 20 us of a single frame's 130) beside
   // the FRES rows': forked to the side stream again, joined behind the pad-bit fix-up.
   // (A single frame only: in a batch the LRES spans are thousands of workgroups of their own
@@ -3118,6 +3296,44 @@ void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_f
   HIMG_LAUNCH(k_padfix, dim3((g.rows + 3) / 4, batch), b256, g, ws, d_out, out_stride,
               d_sizes);
   if (lres_side) (void)hipStreamWaitEvent(stream, ev_join, 0);
+}
+
+void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                   uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                   const StaticChunks &sc, const ShiftTables &st, const LresTables &lt,
+                   const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                   hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  encode_launches(g, ws, batch, d_frames, d_out, out_stride, d_sizes, sc, &st, &lt, nullptr, d_fmap_lut, stream, prof,
+                  side, ev_fork, ev_join);
+}
+
+void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                     uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                     const StaticChunks &sc, const QualSel &qs,
+                     const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                     hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  encode_launches(g, ws, batch, d_frames, d_out, out_stride, d_sizes, sc, nullptr, nullptr, &qs, d_fmap_lut, stream, prof,
+                  side, ev_fork, ev_join);
+}
+
+void enc_fill_qual_tab(const StaticChunks &sc, const ShiftTables &st, const LresTables &lt, QualTab *qt) {
+  const PixQuant pq = make_pix_quant(st);
+  static_assert(sizeof(qt->pq) == sizeof(PixQuant), "the quantiser's words as one array");
+  memcpy(qt->pq, &pq, sizeof(pq));
+  qt->st = st;
+  qt->lt = lt;
+  memcpy(qt->lmap, sc.head + 39, sizeof(qt->lmap));
+  memcpy(qt->qcfg, sc.mid + 8, sizeof(qt->qcfg));   // (built with the chroma table: 64 bytes)
+}
+
+void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
+                        const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof) {
+  HIMG_LAUNCH(k_budget_step, dim3((batch + 63) / 64), dim3(64), bs, ws.status, d_sizes, batch, probe,
+              probe == probes - 1 ? 1 : 0, qmin, qmax, d_quality);
+}
+void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
+                          hipStream_t stream, Profiler *prof) {
+  HIMG_LAUNCH(k_budget_finish, dim3((batch + 63) / 64), dim3(64), bs, ws.status, batch, d_sizes, d_status);
 }
 
 // ---- row-sharded encode of ONE frame (see himg_hip.h, "row-sharded encode") ----

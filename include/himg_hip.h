@@ -176,6 +176,72 @@ int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_st
                            int num_channels, void *d_out, int32_t *d_status,
                            void *stream);
 
+/* ---- quality per frame, and encode to a byte budget --------------------------- */
+/*
+ * Quality enters the encoder only as small tables (the quantiser's shifts, the low-res companding
+ * table, the LMAP and QCFG chunks).  A context keeps them for all 101 qualities in HBM -- built on
+ * its first call of this section, the one place where these calls wait for the device -- and the
+ * kernels that read them pick frame f's by a quality index on the device.
+ */
+/* A quality per frame: h_quality is a HOST array of `batch` values in [0, 100] (any other value:
+ * HIMG_ERR_ARG, nothing launched, neither d_out nor d_status written); it reaches the device as
+ * h_sizes / h_origins do in the decode (no host synchronisation).  Otherwise the contract of
+ * himg_hip_encode_device; frame f's bytes are those of himg_hip_encode at quality h_quality[f]. */
+int himg_hip_encode_device_q(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                             int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
+                             void *d_out, size_t out_stride, uint32_t *d_sizes, int32_t *d_status,
+                             void *stream);
+/* The exact stream size of every frame at its quality, WITHOUT writing a stream: d_sizes[f] is what
+ * himg_hip_encode_device_q would report (for any out_stride that obeys its contract); no output
+ * buffer, no out_stride, no bit packing -- the size follows from the token histograms and the code
+ * lengths.  d_status[f]: a failure of the stages in front of the bit packer (d_sizes[f] is then 0). */
+int himg_hip_encode_sizes_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                 int pixel_stride, int num_channels, const int32_t *h_quality,
+                                 int use_ycbcr, uint32_t *d_sizes, int32_t *d_status, void *stream);
+/*
+ * Encode to a byte budget: "at most B bytes for this picture".  Per frame, frames independent of each
+ * other; size(q) is the frame's exact stream size at quality q (himg_hip_encode_sizes_device), B its
+ * budget in bytes (h_budgets: a HOST array of `batch` values, staged like h_quality):
+ *   1. probe qmin.  size(qmin) > B: the frame fails -- d_quality[f] = -1, d_sizes[f] = 0, d_status[f] =
+ *      HIMG_ERR_CAPACITY; its bytes in d_out are unspecified but stay inside its out_stride bytes.
+ *      The other frames go on.
+ *   2. if qmax > qmin, probe qmax.  It fits: the result is qmax.
+ *   3. otherwise lo = qmin, hi = qmax; while hi - lo > 1: mid = (lo + hi) >> 1; size(mid) <= B ?
+ *      lo = mid : hi = mid.  The result is lo.
+ * Every frame with a result is then encoded at it: d_quality[f] holds the result, d_out / d_sizes[f]
+ * exactly the bytes and the size of himg_hip_encode at that quality, d_status[f] that encode's status
+ * (d_quality[f] = -1 and d_sizes[f] = 0 as well where a probe or the encode itself failed).  The probe's
+ * size is exact, so d_sizes[f] <= B.
+ * The size is NOT monotone in the quality -- over q = 0 .. 100 most small test pictures have 2 to 17
+ * places where size(q + 1) < size(q): random noise shrinks from q = 95 upwards, gradients wobble below
+ * q = 30 (tests/test_budget_host.py holds the oracle to it) -- so this is THE SEARCH'S result, a
+ * deterministic quality that is guaranteed to fit, not the largest fitting one, which would take all
+ * 101 encodes.
+ * Asynchronous on the caller's stream, no host synchronisation: every frame takes the launch's fixed
+ * number of probes (himg_hip_budget_probes; a settled frame repeats its last one), lo / hi / the next
+ * quality live on the device and a small kernel advances them between two probes.  out_stride obeys
+ * the contract of himg_hip_encode_device (>= himg_hip_max_packed_size), so a chosen stream always fits.
+ */
+/* Host only, no GPU: the number of size probes the search makes for [qmin, qmax]: 1 when qmin == qmax,
+ * else 2 + ceil(log2(qmax - qmin)) (9 for 0 .. 100); HIMG_ERR_ARG unless 0 <= qmin <= qmax <= 100. */
+int himg_hip_budget_probes(int qmin, int qmax);
+int himg_hip_encode_budget_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                  int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                  const uint32_t *h_budgets, void *d_out, size_t out_stride,
+                                  uint32_t *d_sizes, int32_t *d_quality, int32_t *d_status, void *stream);
+/* The host forms: himg_hip_encode_to / himg_hip_encode_batch with a budget (in bytes; one above 2^32 - 1
+ * counts as that) -- the capacity protocol, himg_hip_fetch_last, a failing frame's out_sizes[i] = 0
+ * and the first error as the return value, as there.  *quality / qualities[i]: the chosen quality; -1
+ * for a frame whose budget is below size(qmin), for which the call returns HIMG_ERR_CAPACITY (the
+ * batch form: as that frame's error). */
+int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
+                              int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                              size_t budget, uint8_t *dst, size_t dst_cap, size_t *out_size, int *quality);
+int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                                 int height, int pixel_stride, int num_channels, int qmin, int qmax,
+                                 int use_ycbcr, const size_t *budgets, uint8_t *const *dst,
+                                 const size_t *dst_cap, size_t *out_sizes, int *qualities);
+
 /* ---- 1/8-scale preview: the low-res picture at the front of the stream ------ */
 /*
  * The LRES chunk holds one sample per 8x8 block and channel and comes
