@@ -21,6 +21,7 @@ HIMG_ERR_HIP = -2
 HIMG_ERR_UNSUPPORTED = -3
 HIMG_ERR_FORMAT = -4
 HIMG_ERR_CAPACITY = -5
+HIMG_ERR_TARGET = -6
 
 SYNTH = {"grad": 0, "gradn": 1, "rand": 2, "randtile": 3}
 
@@ -91,6 +92,12 @@ def lib():
     L.himg_hip_encode_budget_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp]
     L.himg_hip_encode_budget_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, sz, vp, sz, P(sz), P(i32)]
     L.himg_hip_encode_budget_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    u64 = C.c_uint64
+    L.himg_hip_encode_sse_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
+    L.himg_hip_encode_target_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.himg_hip_encode_target_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, vp, sz, P(sz), P(i32), P(u64)]
+    L.himg_hip_encode_target_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.himg_hip_psnr_to_sse.argtypes = [C.c_double, i32, i32, i32, P(u64)]
     L.himg_hip_decode_rows_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_index_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_rows_indexed_device.argtypes = [vp, vp, C.c_uint32, i32, i32, i32, i32, i32, vp, vp, vp, vp]
@@ -182,6 +189,17 @@ def budget_probes(qmin=0, qmax=100):
     if n < 0:
         raise HimgError(n, "budget_probes")
     return n
+
+
+def psnr_to_sse(psnr_db, width, height, channels):
+    """himg_hip_psnr_to_sse (no GPU): the largest sum of squared differences with which a width x
+    height x channels picture still has at least psnr_db dB (the target of Engine.encode_target).
+    Raises HimgError (HIMG_ERR_ARG) for a non-finite or negative dB or a bad geometry."""
+    v = C.c_uint64()
+    rc = lib().himg_hip_psnr_to_sse(float(psnr_db), int(width), int(height), int(channels), C.byref(v))
+    if rc:
+        raise HimgError(rc, "psnr_to_sse")
+    return v.value
 
 
 def tok_layout(width, height, channels=4, pixel_stride=None, row_tokens=-1, batch=1):
@@ -360,6 +378,54 @@ class Engine:
         if rc not in (HIMG_OK, HIMG_ERR_CAPACITY):
             self._check(rc, "encode_budget_batch")
         return [o[: sizes[i]] for i, o in enumerate(outs)], [quals[i] for i in range(n)], rc
+
+    def encode_target(self, img, max_sse, qmin=0, qmax=100, use_ycbcr=True, channels=None, pixel_stride=None):
+        """himg_hip_encode_target_to + himg_hip_fetch_last: (stream, quality, sse) -- the stream at the
+        quality the search of include/himg_hip.h finds in [qmin, qmax] for a sum of squared differences
+        of at most `max_sse` (psnr_to_sse turns a PSNR into one), and the sum it has.  Raises HimgError
+        (HIMG_ERR_TARGET, its `quality` -1 and its `sse` the sum at qmax) when qmax misses the target."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w = img.shape[:2]
+        ch = channels if channels is not None else (img.shape[2] if img.ndim == 3 else 1)
+        stride = pixel_stride if pixel_stride is not None else (img.shape[2] if img.ndim == 3 else 1)
+        n, q, sse = C.c_size_t(), C.c_int(-1), C.c_uint64()
+        rc = lib().himg_hip_encode_target_to(self._ctx, img.ctypes.data, w, h, stride, ch, int(qmin), int(qmax),
+                                             1 if use_ycbcr else 0, min(max(int(max_sse), 0), 2 ** 64 - 1), None, 0,
+                                             C.byref(n), C.byref(q), C.byref(sse))
+        if rc != HIMG_ERR_CAPACITY or n.value == 0:
+            e = HimgError(rc if rc != HIMG_OK else HIMG_ERR_ARG,
+                          "encode_target: %s" % lib().himg_hip_last_error(self._ctx).decode())
+            e.quality = q.value
+            e.sse = sse.value
+            raise e
+        out = np.empty(n.value, np.uint8)
+        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode_target")
+        return out, q.value, sse.value
+
+    def encode_target_batch(self, frames, max_sses, qmin=0, qmax=100, use_ycbcr=True, outs=None):
+        """himg_hip_encode_target_batch: frames of one geometry, frame i with a sum of squared
+        differences of at most max_sses[i].  Returns (streams, qualities, sses, rc): a frame that
+        misses its target at qmax (or that failed otherwise) has an empty stream and quality -1; rc is
+        the first such error, HIMG_OK if there was none."""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        n = len(frames)
+        h, w = frames[0].shape[:2]
+        ch = frames[0].shape[2] if frames[0].ndim == 3 else 1
+        cap = max_packed_size(w, h, ch)
+        if outs is None:
+            outs = [np.empty(cap, np.uint8) for _ in range(n)]
+        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        tgt = (C.c_uint64 * n)(*[min(max(int(t), 0), 2 ** 64 - 1) for t in max_sses])
+        sizes = (C.c_size_t * n)()
+        quals = (C.c_int * n)()
+        sses = (C.c_uint64 * n)()
+        rc = lib().himg_hip_encode_target_batch(self._ctx, src, n, w, h, ch, ch, int(qmin), int(qmax),
+                                                1 if use_ycbcr else 0, tgt, dst, caps, sizes, quals, sses)
+        if rc not in (HIMG_OK, HIMG_ERR_TARGET):
+            self._check(rc, "encode_target_batch")
+        return [o[: sizes[i]] for i, o in enumerate(outs)], [quals[i] for i in range(n)], [sses[i] for i in range(n)], rc
 
     def decode_batch(self, streams, outs=None):
         """himg_hip_decode_batch: returns the decoded frames; `outs` (optional) are
@@ -609,6 +675,29 @@ class Engine:
                                                  b.ctypes.data, _ptr(d_out), out_stride, _ptr(d_sizes),
                                                  _ptr(d_quality), _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "encode_budget_device")
+
+    def encode_sse_device(self, d_frames, batch, width, height, pixel_stride, channels, qualities,
+                          use_ycbcr, d_sse, d_status, stream=0):
+        """himg_hip_encode_sse_device: every frame's exact sum of squared differences between the
+        source and the decode of its encode at its quality into d_sse (`batch` 64-bit words), without
+        writing a stream."""
+        q = np.ascontiguousarray(np.asarray(qualities, np.int32).reshape(batch))
+        rc = lib().himg_hip_encode_sse_device(self._ctx, _ptr(d_frames), batch, width, height, pixel_stride,
+                                              channels, q.ctypes.data, 1 if use_ycbcr else 0, _ptr(d_sse),
+                                              _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_sse_device")
+
+    def encode_target_device(self, d_frames, batch, width, height, pixel_stride, channels, qmin, qmax,
+                             use_ycbcr, max_sses, d_out, out_stride, d_sizes, d_quality, d_sse, d_status, stream=0):
+        """himg_hip_encode_target_device: every frame at the quality the search finds for its target
+        (max_sses: `batch` sums of squared differences, on the host); d_quality receives the qualities
+        (-1: the frame misses its target at qmax), d_sse the sums reached."""
+        t = np.ascontiguousarray(np.array([min(max(int(x), 0), 2 ** 64 - 1) for x in max_sses], np.uint64).reshape(batch))
+        rc = lib().himg_hip_encode_target_device(self._ctx, _ptr(d_frames), batch, width, height, pixel_stride,
+                                                 channels, int(qmin), int(qmax), 1 if use_ycbcr else 0,
+                                                 t.ctypes.data, _ptr(d_out), out_stride, _ptr(d_sizes),
+                                                 _ptr(d_quality), _ptr(d_sse), _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_target_device")
 
     def decode_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_out,
                       d_status, stream=0):

@@ -6,8 +6,10 @@
 // Input: binary PGM / PPM / PAM (pnm_io.h) instead of the formats FreeImage reads.
 // Beyond the reference: "-b <bytes>" encodes to a byte budget through the C ABI
 // (himg_hip_encode_budget_to, qualities 0 .. the -q value, 100 without one) and prints
-// the quality it chose.
+// the quality it chose; "-p <dB>" encodes to a quality floor (himg_hip_encode_target_to with
+// himg_hip_psnr_to_sse's target) and prints the chosen quality and the PSNR reached.
 #include <cerrno>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -24,6 +26,7 @@ struct Request {
   bool ycbcr = true;
   bool have_quality = false;
   long long budget = -1;   // -b: at most this many bytes (-1: not given)
+  double psnr = -1.0;      // -p: at least this many dB (-1: not given)
   const char *input = nullptr;
   const char *output = nullptr;
 };
@@ -67,10 +70,27 @@ bool parse(int argc, const char **argv, Request *rq) {
         return false;
       }
       rq->budget = v;
+    } else if (!strcmp(a, "-p")) {
+      if (++i >= argc) return false;
+      char *end = nullptr;
+      const double v = strtod(argv[i], &end);
+      if (end == argv[i] || *end) {
+        printf("Invalid number: %s\n", argv[i]);
+        return false;
+      }
+      if (!std::isfinite(v) || v < 0.0) {
+        printf("Invalid PSNR: %s\n", argv[i]);
+        return false;
+      }
+      rq->psnr = v;
     } else {
       printf("Invalid option: %s\n", a);
       return false;
     }
+  }
+  if (rq->budget >= 0 && rq->psnr >= 0.0) {
+    printf("-b and -p exclude each other\n");
+    return false;
   }
   return nfiles == 2;
 }
@@ -84,7 +104,8 @@ int main(int argc, const char **argv) {
            "Options:\n"
            " -q <quality> Set the quality (0-100)\n"
            " -rgb         Use RGB color space (instead of YCbCr)\n"
-           " -b <bytes>   Fit the file into a byte budget (-q: the highest quality to try)\n",
+           " -b <bytes>   Fit the file into a byte budget (-q: the highest quality to try)\n"
+           " -p <dB>      Reach at least this PSNR in as few bytes as the search finds (-q: as for -b)\n",
            argv[0]);
     return 0;
   }
@@ -101,6 +122,39 @@ int main(int argc, const char **argv) {
   pnm::flip_and_swap(picture.data.data(), pixels.data(), picture.width, picture.height, picture.channels);
 
   const int c = picture.channels;
+  if (rq.psnr >= 0.0) {
+    himg_hip_ctx *ctx = nullptr;
+    const size_t cap = himg_hip_max_packed_size(picture.width, picture.height, c);
+    std::vector<uint8_t> packed(cap);
+    size_t n = 0;
+    int quality = -1;
+    uint64_t target = 0, sse = 0;
+    int rc = himg_hip_psnr_to_sse(rq.psnr, picture.width, picture.height, c, &target);
+    if (rc == HIMG_OK) rc = himg_hip_create(0, &ctx);
+    if (rc == HIMG_OK)
+      rc = himg_hip_encode_target_to(ctx, pixels.data(), picture.width, picture.height, c, c, 0,
+                                     rq.have_quality ? rq.quality : 100, rq.ycbcr ? 1 : 0, target, packed.data(),
+                                     packed.size(), &n, &quality, &sse);
+    himg_hip_destroy(ctx);
+    const double samples = (double)picture.width * picture.height * c;
+    const double reached = sse ? 10.0 * log10(255.0 * 255.0 * samples / (double)sse) : INFINITY;
+    if (rc == HIMG_ERR_TARGET) {
+      fprintf(stderr, "%s does not reach %g dB at quality %d (%.2f dB)\n", rq.input, rq.psnr,
+              rq.have_quality ? rq.quality : 100, reached);
+      return -1;
+    }
+    if (rc != HIMG_OK) {
+      fprintf(stderr, "Unable to encode %s\n", rq.input);
+      return -1;
+    }
+    printf("Quality: %d\n", quality);
+    printf("PSNR: %.2f\n", reached);
+    printf("Compressed size: %d\n", static_cast<int>(n));
+    FILE *f = fopen(rq.output, "wb");
+    const bool ok = f && fwrite(packed.data(), 1, n, f) == n;
+    if (f) fclose(f);
+    return ok ? 0 : -1;
+  }
   if (rq.budget >= 0) {
     himg_hip_ctx *ctx = nullptr;
     const size_t cap = himg_hip_max_packed_size(picture.width, picture.height, c);

@@ -266,6 +266,45 @@ void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int p
 void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
                           hipStream_t stream, Profiler *prof);
 
+// ---- the distortion probe (himg_hip_encode_sse_device, himg_hip_encode_target_device) ----
+// The decode-side tables of a stream of ONE quality, as k_dec_parse builds DecFrame::row_tabs from
+// the stream's FMAP and QCFG chunks: the code byte -> dequantised magnitude (int16 [256]), the shifts
+// (u8 [2][64]), the shifts as packed pairs in tile_plane's register order (u32 [2][32]) and the
+// identity-test words (u32 [4]).  A context holds kQualities of them in HBM beside the QualTab's.
+struct SseTab {
+  alignas(16) uint32_t w[128 + 32 + 64 + 4];
+};
+void sse_fill_tab(const int16_t fmap[128], const ShiftTables &st, SseTab *t);   // (host)
+struct SseArgs {
+  uint8_t *rec;          // [f] the reconstructed low-res plane, [C][rows][cols], EncWs::plane_stride apart
+  const SseTab *tab;     // [kQualities]
+  uint64_t *sse;         // [f] the result
+};
+// k_sse (kernels_dec.hip, beside the inverse transform it shares): frame f's symbols in ws.fres_sym
+// through the decoder's inverse path at quality qs.quality[f], compared with the source; the sums
+// are ADDED to sa.sse[f] (zeroed by the caller).
+void launch_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames, const QualSel &qs,
+                const SseArgs &sa, hipStream_t stream, Profiler *prof);
+// The probe's launch sequence: launch_encode_q's front (k_front, or the averages, the blend and the
+// pixel / tile stage), the low-res chain in the form that stores its reconstructed samples, k_sse.
+void launch_encode_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                       const StaticChunks &sc, const QualSel &qs, const SseArgs &sse,
+                       const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                       hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
+// The search of himg_hip_encode_target_device, per frame on the device (the states: kBudget*).
+struct TargetState {
+  int32_t *quality;          // [f] the quality of the next probe / of the final encode
+  const uint64_t *target;    // [f] the largest sse the frame may have
+  uint64_t *probe_sse;       // [f] the last probe's
+  uint64_t *best_sse;        // [f] the sse at hi
+  int32_t *lo, *hi, *state, *err;
+};
+// Behind probe `probe` (0: at qmax, 1: at qmin, then the midpoints) of `probes`.
+void launch_target_step(const TargetState &ts, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
+                        int32_t *d_quality, hipStream_t stream, Profiler *prof);
+void launch_target_finish(const TargetState &ts, const EncWs &ws, int batch, uint32_t *d_sizes, uint64_t *d_sse,
+                          int32_t *d_status, hipStream_t stream, Profiler *prof);
+
 // The decoder's helper streams and events (owned by the context).
 constexpr int kWalkSegs = 4;   // single large frames: at most this many row ranges whose walk / count / row kernels overlap
 struct DecStreams {

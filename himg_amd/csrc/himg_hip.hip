@@ -8,6 +8,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -135,6 +136,9 @@ struct himg_hip_ctx {
   // Quality per frame / encode to a byte budget: the tables of all 101 qualities (built on first
   // use) and the per-frame words of a launch (BudgetState's arrays, the quality first).
   DevBuf e_qtab, e_bud;
+  // The distortion probe: the decode-side tables of all 101 qualities (built with e_qtab) and the
+  // reconstructed low-res planes of a launch.
+  DevBuf e_stab, e_rec;
   bool qtab_ready = false;
   Geom enc_geom{};
   EncWs enc_ws{};
@@ -366,7 +370,7 @@ extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
     hipHostFree(ctx->pipe.h_meta);
   }
   DevBuf *all[] = {&ctx->fmap_lut, &ctx->e_planes, &ctx->e_lres, &ctx->e_fres, &ctx->e_small,
-                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_bud, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
+                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_bud, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
                    &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->h_in,
                    &ctx->h_out, &ctx->h_sizes, &ctx->h_status, &ctx->h_index};
   for (DevBuf *b : all) b->release();
@@ -789,6 +793,14 @@ static int ensure_qual_tab(himg_hip_ctx *ctx) {
   Geom g;
   if (!make_geom(8, 8, 4, 4, 1, &g)) return fail(ctx, HIMG_ERR_ARG, "bad geometry");   // (any geometry with a chroma table)
   std::vector<QualTab> tabs(kQualities);
+  std::vector<himg_dev::SseTab> stabs(kQualities);
+  // The magnitudes a decoder reads back from the FMAP chunk (serialised and parsed, as a stream carries them).
+  int16_t fmap[128], fmap_dec[128];
+  uint8_t fbuf[512];
+  himg_tables_fullres_map(fmap);
+  const int fn = himg_tables_mapping_function(fmap, fbuf);
+  if (fn <= 0 || fn > (int)sizeof(fbuf) || himg_tables_parse_mapping_function(fmap_dec, fbuf, fn) != 1)
+    return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported table configuration");
   for (int q = 0; q < kQualities; ++q) {
     StaticChunks sc;
     ShiftTables st;
@@ -796,10 +808,13 @@ static int ensure_qual_tab(himg_hip_ctx *ctx) {
     const int rc = build_static(g, q, &sc, &st, &lt);
     if (rc) return fail(ctx, rc, "unsupported table configuration");
     himg_dev::enc_fill_qual_tab(sc, st, lt, &tabs[q]);
+    himg_dev::sse_fill_tab(fmap_dec, st, &stabs[q]);
   }
-  if (!ctx->e_qtab.reserve(round_up(tabs.size() * sizeof(QualTab), 256)))
+  if (!ctx->e_qtab.reserve(round_up(tabs.size() * sizeof(QualTab), 256)) ||
+      !ctx->e_stab.reserve(round_up(stabs.size() * sizeof(himg_dev::SseTab), 256)))
     return fail(ctx, HIMG_ERR_HIP, "quality table allocation failed");
   HIP_TRY(ctx, hipMemcpy(ctx->e_qtab.p, tabs.data(), tabs.size() * sizeof(QualTab), hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->e_stab.p, stabs.data(), stabs.size() * sizeof(himg_dev::SseTab), hipMemcpyHostToDevice));
   ctx->qtab_ready = true;
   return HIMG_OK;
 }
@@ -829,7 +844,7 @@ static int enc_q_begin(himg_hip_ctx *ctx, const void *d_frames, int batch, int w
   int rc = ensure_enc_ws(ctx, g, batch);
   if (rc) return rc;
   if ((rc = ensure_qual_tab(ctx))) return rc;
-  if (!ctx->e_bud.reserve(round_up((size_t)batch * 6 * 4, 256))) return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
+  if (!ctx->e_bud.reserve(round_up((size_t)batch * 12 * 4 + 8, 256))) return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
   ShiftTables st;
   LresTables lt;
   rc = build_static(g, 50, &e->sc, &st, &lt);
@@ -922,6 +937,97 @@ extern "C" int himg_hip_encode_budget_device(himg_hip_ctx *ctx, const void *d_fr
   enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
   launch_budget_finish(e.bs, ctx->enc_ws, batch, d_sizes, d_status, e.s, &ctx->prof);
   HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+// ---- the distortion probe, encode to a distortion target ------------------------------------
+
+// The probe's own buffers: the reconstructed low-res planes beside the workspace's, and where the
+// per-frame words of the search live in e_bud (the quality first, as in EncQ::bs; the 64-bit
+// words behind an even number of them).
+static int sse_begin(himg_hip_ctx *ctx, const EncQ &e, int batch, himg_dev::SseArgs *sa, himg_dev::TargetState *ts) {
+  if (!ctx->e_rec.reserve(ctx->enc_ws.plane_stride * (size_t)batch))
+    return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
+  sa->rec = (uint8_t *)ctx->e_rec.p;
+  sa->tab = (const himg_dev::SseTab *)ctx->e_stab.p;
+  sa->sse = nullptr;
+  int32_t *w = (int32_t *)ctx->e_bud.p;
+  const size_t b = (size_t)batch, b2 = (b + 1) & ~(size_t)1;
+  ts->quality = w;
+  ts->target = (const uint64_t *)(w + b2);
+  ts->probe_sse = (uint64_t *)(w + b2 + 2 * b);
+  ts->best_sse = (uint64_t *)(w + b2 + 4 * b);
+  ts->lo = w + b2 + 6 * b; ts->hi = w + b2 + 7 * b; ts->state = w + b2 + 8 * b; ts->err = w + b2 + 9 * b;
+  return HIMG_OK;
+}
+static void sse_launch(himg_hip_ctx *ctx, const EncQ &e, int batch, const void *d_frames, const himg_dev::SseArgs &sa) {
+  himg_dev::launch_encode_sse(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, e.sc, e.qs, sa,
+                              (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof,
+                              ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
+}
+
+extern "C" int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                          int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
+                                          uint64_t *d_sse, int32_t *d_status, void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
+  if (!d_sse || ((uintptr_t)d_sse & 7)) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  EncQ e;
+  // (no sizes: d_sse stands in for the checks' result pointer)
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, false, nullptr, 0,
+                       (const uint32_t *)d_sse, stream, &e);
+  if (rc) return rc;
+  himg_dev::SseArgs sa;
+  himg_dev::TargetState ts;
+  if ((rc = sse_begin(ctx, e, batch, &sa, &ts))) return rc;
+  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
+  sa.sse = d_sse;
+  sse_launch(ctx, e, batch, d_frames, sa);
+  if (d_status)
+    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_target_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                             int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                             const uint64_t *h_max_sse, void *d_out, size_t out_stride,
+                                             uint32_t *d_sizes, int32_t *d_quality, uint64_t *d_sse, int32_t *d_status,
+                                             void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  const int probes = himg_hip_budget_probes(qmin, qmax);
+  if (probes < 0) return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  if (!h_max_sse || !d_quality || !d_sse || ((uintptr_t)d_sse & 7)) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  EncQ e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
+                       d_sizes, stream, &e);
+  if (rc) return rc;
+  himg_dev::SseArgs sa;
+  himg_dev::TargetState ts;
+  if ((rc = sse_begin(ctx, e, batch, &sa, &ts))) return rc;
+  // The first probe's qualities (qmax) and the targets, in one copy: TargetState's first two arrays.
+  const size_t b2 = ((size_t)batch + 1) & ~(size_t)1;
+  std::vector<int32_t> w0(b2 + 2 * (size_t)batch, qmax);
+  memcpy(w0.data() + b2, h_max_sse, (size_t)batch * 8);
+  if ((rc = stage_words(ctx, ts.quality, w0.data(), w0.size(), nullptr, 0, e.s))) return rc;
+  sa.sse = ts.probe_sse;
+  for (int p = 0; p < probes; ++p) {
+    sse_launch(ctx, e, batch, d_frames, sa);   // (every probe zeroes its own sums and status words)
+    himg_dev::launch_target_step(ts, ctx->enc_ws, batch, p, probes, qmin, qmax, d_quality, e.s, &ctx->prof);
+  }
+  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
+  himg_dev::launch_target_finish(ts, ctx->enc_ws, batch, d_sizes, d_sse, d_status, e.s, &ctx->prof);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int num_channels, uint64_t *max_sse) {
+  Geom g;
+  if (!max_sse || !std::isfinite(psnr_db) || psnr_db < 0.0 ||
+      !make_geom(width, height, num_channels, num_channels, 1, &g))
+    return HIMG_ERR_ARG;
+  const double n = (double)width * (double)height * (double)num_channels;
+  *max_sse = (uint64_t)floor(255.0 * 255.0 * n / pow(10.0, psnr_db / 10.0));
   return HIMG_OK;
 }
 
@@ -1279,7 +1385,12 @@ struct HostBudget {
   int qmin, qmax;
   const size_t *budgets;
   int *qualities;
+  // The distortion-target forms (himg_hip_encode_target_to / _batch) instead: each frame's largest
+  // sse, and where the sse reached goes; a frame that misses its target at qmax has quality -1.
+  const uint64_t *max_sse = nullptr;
+  uint64_t *sses = nullptr;
 };
+static const char *const kTargetAboveQmax = "the distortion at qmax is above the target";
 static uint32_t budget_u32(size_t b) { return b > 0xffffffffull ? 0xffffffffu : (uint32_t)b; }
 static const char *const kBudgetBelowQmin = "the budget is below the stream's size at qmin";
 
@@ -1298,7 +1409,12 @@ static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int he
   ctx->host_bytes = 0;
   HIP_TRY(ctx, hipMemcpy(ctx->h_in.p, data, (size_t)g.frame_bytes, hipMemcpyHostToDevice));
   int rc;
-  if (bud) {
+  if (bud && bud->max_sse) {
+    rc = himg_hip_encode_target_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels, bud->qmin,
+                                       bud->qmax, use_ycbcr, bud->max_sse, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
+                                       (int32_t *)ctx->h_status.p + 1, (uint64_t *)ctx->h_status.p + 1,
+                                       (int32_t *)ctx->h_status.p, nullptr);
+  } else if (bud) {
     const uint32_t b = budget_u32(bud->budgets[0]);
     rc = himg_hip_encode_budget_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels, bud->qmin,
                                        bud->qmax, use_ycbcr, &b, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
@@ -1310,13 +1426,16 @@ static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int he
   }
   if (rc) return rc;
   uint32_t n = 0;
-  int32_t st2[2] = {0, 0};   // the status, then (budget form) the quality
+  int32_t st2[4] = {0, 0, 0, 0};   // the status, then (budget form) the quality, then (target form) the sse
   HIP_TRY(ctx, hipMemcpy(&n, ctx->h_sizes.p, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(st2, ctx->h_status.p, bud ? 8 : 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(st2, ctx->h_status.p, bud ? (bud->max_sse ? 16 : 8) : 4, hipMemcpyDeviceToHost));
   const int32_t st = st2[0];
   if (bud) {
     bud->qualities[0] = st2[1];
-    if (st == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
+    if (bud->max_sse) {
+      memcpy(bud->sses, st2 + 2, 8);
+      if (st == HIMG_ERR_TARGET) return fail(ctx, HIMG_ERR_TARGET, kTargetAboveQmax);
+    } else if (st == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
   }
   if (st) return fail(ctx, status_to_code(st), "device encode reported an error");
   ctx->host_bytes = n;
@@ -1365,6 +1484,28 @@ extern "C" int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data,
     return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
   uint32_t n = 0;
   const HostBudget bud = {qmin, qmax, &budget, quality};
+  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, 0, use_ycbcr, &n, &bud);
+  if (rc) return rc;
+  *out_size = n;
+  if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, n, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_target_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
+                                         int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                         uint64_t max_sse, uint8_t *dst, size_t dst_cap, size_t *out_size, int *quality,
+                                         uint64_t *sse) {
+  if (!ctx || !data || !out_size || !quality || !sse) return HIMG_ERR_ARG;
+  *out_size = 0;
+  *quality = -1;
+  *sse = 0;
+  if (himg_hip_budget_probes(qmin, qmax) < 0)
+    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  uint32_t n = 0;
+  HostBudget bud = {qmin, qmax, nullptr, quality};
+  bud.max_sse = &max_sse;
+  bud.sses = sse;
   const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, 0, use_ycbcr, &n, &bud);
   if (rc) return rc;
   *out_size = n;
@@ -1578,7 +1719,9 @@ static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, 
     const int32_t st = (int32_t)p.h_meta[slot * 4 + 1];
     int err = HIMG_OK;
     if (bud) bud->qualities[j] = (int32_t)p.h_meta[slot * 4 + 2];
-    if (bud && st == HIMG_ERR_CAPACITY) err = fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
+    if (bud && bud->max_sse) memcpy(&bud->sses[j], p.h_meta + 10 + 2 * slot, 8);
+    if (bud && bud->max_sse && st == HIMG_ERR_TARGET) err = fail(ctx, HIMG_ERR_TARGET, kTargetAboveQmax);
+    else if (bud && !bud->max_sse && st == HIMG_ERR_CAPACITY) err = fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
     else if (st) err = fail(ctx, status_to_code(st), "device encode reported an error");
     else if (!dst[j] || dst_cap[j] < nbytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
     if (!err) {
@@ -1597,7 +1740,14 @@ static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, 
     HIP_TRY(ctx, hipMemcpyAsync(p.in[slot].p, frames[i], (size_t)g.frame_bytes, hipMemcpyHostToDevice, p.s_in));
     HIP_TRY(ctx, hipEventRecord(p.ev_in[slot], p.s_in));
     HIP_TRY(ctx, hipStreamWaitEvent(p.s_comp, p.ev_in[slot], 0));
-    if (bud) {
+    if (bud && bud->max_sse) {
+      // (meta: size, status, quality, -, then the sse as one 64-bit word; its pinned mirror: words 10 + 2 slot)
+      rc = himg_hip_encode_target_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, bud->qmin,
+                                         bud->qmax, use_ycbcr, bud->max_sse + i, p.out[slot].p, cap,
+                                         (uint32_t *)p.meta[slot].p, (int32_t *)p.meta[slot].p + 2,
+                                         (uint64_t *)p.meta[slot].p + 2, (int32_t *)p.meta[slot].p + 1, p.s_comp);
+      if (!rc) HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + 10 + 2 * slot, (uint32_t *)p.meta[slot].p + 4, 8, hipMemcpyDeviceToHost, p.s_comp));
+    } else if (bud) {
       const uint32_t b = budget_u32(bud->budgets[i]);
       rc = himg_hip_encode_budget_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, bud->qmin,
                                          bud->qmax, use_ycbcr, &b, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
@@ -1634,6 +1784,21 @@ extern "C" int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *co
   if (himg_hip_budget_probes(qmin, qmax) < 0)
     return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
   const HostBudget bud = {qmin, qmax, budgets, qualities};
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, 0, use_ycbcr, dst, dst_cap, out_sizes,
+                      &bud);
+}
+
+extern "C" int himg_hip_encode_target_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                                            int height, int pixel_stride, int num_channels, int qmin, int qmax,
+                                            int use_ycbcr, const uint64_t *max_sse, uint8_t *const *dst,
+                                            const size_t *dst_cap, size_t *out_sizes, int *qualities, uint64_t *sses) {
+  if (!ctx || !max_sse || !qualities || !sses || n < 0) return HIMG_ERR_ARG;
+  for (int i = 0; i < n; ++i) { qualities[i] = -1; sses[i] = 0; }
+  if (himg_hip_budget_probes(qmin, qmax) < 0)
+    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  HostBudget bud = {qmin, qmax, nullptr, qualities};
+  bud.max_sse = max_sse;
+  bud.sses = sses;
   return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, 0, use_ycbcr, dst, dst_cap, out_sizes,
                       &bud);
 }

@@ -2603,15 +2603,32 @@ __device__ __forceinline__ void tile_plane(const uint8_t *slot, int cols_rt, con
 __device__ __forceinline__ int pair_tile(int it) { return (it >> 6) * 32 + (it & 31); }
 __device__ __forceinline__ int pair_half(int it) { return (it >> 5) & 1; }
 
+// The squared differences of the four bytes of a and b, added to acc: the bytes as packed int16
+// pairs (even bytes, odd bytes), then v_dot2_i32_i16 of each difference with itself.
+__device__ __forceinline__ uint32_t sse_word(uint32_t a, uint32_t b, uint32_t acc) {
+  const uint32_t m = 0x00ff00ffu;
+  const dpk16 e = __builtin_bit_cast(dpk16, a & m) - __builtin_bit_cast(dpk16, b & m);
+  const dpk16 o = __builtin_bit_cast(dpk16, (a >> 8) & m) - __builtin_bit_cast(dpk16, (b >> 8) & m);
+  int r = __builtin_amdgcn_sdot2(e, e, (int)acc, false);
+  r = __builtin_amdgcn_sdot2(o, o, r, false);
+  return (uint32_t)r;
+}
+
 // FULL4: four channels, whole tiles only (W and H multiples of 8) -- the ragged-edge
 // stores and the channel-count tests are compiled out.
-template <int COLS, bool FULL4 = false>
-__device__ __forceinline__ void transform_store_pair(const Geom &g, int cols_rt, const uint8_t *sym,
+// SSE (k_sse, the encoder's distortion probe): nothing is stored -- the lane's four pixel rows are
+// compared with the source picture instead (src: the frame, sstride bytes per pixel of which the
+// first C count; FULL4: packed RGBA, two 16-byte loads per pixel row) and the sum of the squared
+// differences over the real pixels is returned (at most 4 * 8 * 4 * 255^2 < 2^24).
+template <int COLS, bool FULL4 = false, bool SSE = false>
+__device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols_rt, const uint8_t *sym,
                                                      const uint8_t *low, const int16_t *s_unmap,
                                                      const uint8_t *s_shift, const uint32_t *s_shiftp,
                                                      int ycbcr, int u, int s, int v, uint8_t *img,
                                                      const uint32_t *pre_lr = nullptr, bool store_ok = true,
-                                                     bool touched_on = false, uint32_t touched = 0) {
+                                                     bool touched_on = false, uint32_t touched = 0,
+                                                     const uint8_t *src = nullptr, int sstride = 0) {
+  uint32_t sse = 0;
   const int cols = COLS > 0 ? COLS : cols_rt;
   const int C = FULL4 ? 4 : g.C;
   const int v2 = min(v + 1, g.rows - 1);
@@ -2704,6 +2721,27 @@ __device__ __forceinline__ void transform_store_pair(const Geom &g, int cols_rt,
           px[4 * h + 3] = __builtin_amdgcn_perm(w1, t1, 0x07060302u);
         }
       }
+      if constexpr (SSE) {
+        if (FULL4 || y < bh) {
+          if (FULL4) {
+            const uint4 *sp = reinterpret_cast<const uint4 *>(src + ((size_t)(8 * v + y) * g.W + 8 * u) * 4);
+            const uint4 a0 = sp[0], a1 = sp[1];
+            sse = sse_word(px[0], a0.x, sse); sse = sse_word(px[1], a0.y, sse);
+            sse = sse_word(px[2], a0.z, sse); sse = sse_word(px[3], a0.w, sse);
+            sse = sse_word(px[4], a1.x, sse); sse = sse_word(px[5], a1.y, sse);
+            sse = sse_word(px[6], a1.z, sse); sse = sse_word(px[7], a1.w, sse);
+          } else {
+            const uint8_t *sp = src + ((size_t)(8 * v + y) * g.W + 8 * u) * sstride;
+#pragma unroll
+            for (int x = 0; x < 8; ++x)
+              if (x < bw)
+                for (int c = 0; c < C; ++c) {
+                  const int d = (int)((px[x] >> (8 * c)) & 255u) - (int)sp[x * sstride + c];
+                  sse += (uint32_t)(d * d);
+                }
+          }
+        }
+      } else
       if (store_ok && (FULL4 || y < bh)) {
         uint8_t *dst = img + ((size_t)(8 * v + y) * g.W + 8 * u) * C;
         if (FULL4 || (C == 4 && bw == 8)) {
@@ -2720,6 +2758,7 @@ __device__ __forceinline__ void transform_store_pair(const Geom &g, int cols_rt,
         }
       }
     }
+    return sse;
 }
 
 // tile_plane's identity test, by one wavefront (l = 0..63).  n = the largest code with
@@ -2779,6 +2818,49 @@ __global__ __launch_bounds__(256) void k_tile_inv(Geom g, DecWs ws, uint8_t *out
                           ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp,
                           df->ycbcr, pair_tile(it), pair_half(it), v,
                           out_frames + (size_t)f * ((size_t)g.W * g.H * g.C));
+}
+
+// ---------------------------------------------------------------------------
+// k_sse: the encoder's distortion probe (himg_hip_encode_sse_device).  k_tile_inv's transform on
+// the ENCODER's symbol plane (the same [rows][C][64][cols] layout) and its reconstructed low-res
+// plane, with the decode-side tables of the frame's quality from the context's per-quality table
+// instead of a parsed stream's -- and instead of storing the pixels it compares them with the
+// source and adds the squared differences up.  No entropy coder ran in either direction.
+// Two lanes per tile, 128 tiles per workgroup.  FAST: packed RGBA, whole tiles.
+// The sum: below 2^24 per lane, below 2^30 per wavefront (32 bits), 64 bits across the
+// workgroup's wavefronts, then ONE 64-bit vector atomic add per workgroup: integer adds, so the
+// result does not depend on their order.
+// ---------------------------------------------------------------------------
+template <bool FAST>
+__global__ __launch_bounds__(256) void k_sse(Geom g, const uint8_t *frames, const uint8_t *fres_sym, size_t fres_stride,
+                                             const uint8_t *rec, size_t plane_stride, const SseTab *tabs,
+                                             const int32_t *quality, unsigned long long *sse) {
+  __shared__ __attribute__((aligned(16))) uint32_t s_tab[kRowTabWords];
+  __shared__ unsigned long long s_part[4];
+  const int v = blockIdx.y, f = blockIdx.z, tid = threadIdx.x;
+  // (the frame index is uniform: its quality is one scalar load)
+  const int q = __builtin_amdgcn_readfirstlane(
+      ((const __attribute__((address_space(4))) int32_t *)(uintptr_t)quality)[f]);
+  if (tid < kRowTabWords / 4) reinterpret_cast<uint4 *>(s_tab)[tid] = reinterpret_cast<const uint4 *>(tabs[q].w)[tid];
+  __syncthreads();
+  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(s_tab);
+  const uint8_t *s_shift = reinterpret_cast<const uint8_t *>(s_tab + 128);
+  const uint32_t *s_shiftp = s_tab + 160;
+  const int it = blockIdx.x * 256 + tid;   // (tile, half): both lanes of a pair are in or out
+  uint32_t acc = 0;
+  if (pair_tile(it) < g.cols)
+    acc = transform_store_pair<(FAST ? -1 : 0), FAST, true>(
+        g, g.cols, fres_sym + (size_t)f * fres_stride + (size_t)v * g.row_block, rec + (size_t)f * plane_stride,
+        s_unmap, s_shift, s_shiftp, g.ycbcr, pair_tile(it), pair_half(it), v, nullptr, nullptr, true, false, 0,
+        frames + (size_t)f * (size_t)g.frame_bytes, g.stride);
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d);
+  if ((tid & 63) == 0) s_part[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned long long t = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    if (t) __hip_atomic_fetch_add(sse + f, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 // COLS > 0 fixes the tile count per block row at compile time (512 = 4096-pixel
@@ -5121,6 +5203,54 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     }
   }
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+// ---- the encoder's distortion probe ----------------------------------------------------
+void launch_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames, const QualSel &qs,
+                const SseArgs &sa, hipStream_t stream, Profiler *prof) {
+  const unsigned gx = (unsigned)((((g.cols + 31) / 32) * 64 + 255) / 256);   // two lanes per tile, 32 tiles per wave
+  const dim3 grid(gx, g.rows, batch);
+  if (g.C == 4 && g.stride == 4 && (g.W & 7) == 0 && (g.H & 7) == 0)
+    HIMG_LAUNCH(k_sse<true>, grid, dim3(256), g, d_frames, ws.fres_sym, ws.fres_stride, sa.rec, ws.plane_stride, sa.tab,
+                qs.quality, (unsigned long long *)sa.sse);
+  else
+    HIMG_LAUNCH(k_sse<false>, grid, dim3(256), g, d_frames, ws.fres_sym, ws.fres_stride, sa.rec, ws.plane_stride, sa.tab,
+                qs.quality, (unsigned long long *)sa.sse);
+}
+
+// DecFrame::row_tabs on the host (k_dec_parse, identity_test_words), from the tables a stream of
+// that quality carries.
+void sse_fill_tab(const int16_t fmap[128], const ShiftTables &st, SseTab *t) {
+  static_assert(sizeof(t->w) == kRowTabWords * 4, "DecFrame::row_tabs");
+  int16_t *um = reinterpret_cast<int16_t *>(t->w);
+  uint8_t *sh = reinterpret_cast<uint8_t *>(t->w + 128);
+  uint32_t *sp = t->w + 160;
+  for (int k = 0; k < 256; ++k) {
+    const int sc = (int8_t)k;
+    um[k] = (int16_t)(sc >= 0 ? fmap[sc] : (sc == -128 ? -fmap[127] : -fmap[-sc]));
+  }
+  for (int k = 0; k < 128; ++k) sh[k] = st.s[k >> 6][k & 63];
+  for (int k = 0; k < 64; ++k) {
+    const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
+    sp[k] = (uint32_t)st.s[ch][(2 * j) * 8 + x] | ((uint32_t)st.s[ch][(2 * j + 1) * 8 + x] << 16);
+  }
+  int n = 127;
+  for (int i = 0; i < 128; ++i)
+    if (fmap[i] != i) { n = i - 1; break; }
+  for (int l = 0; l < 2; ++l) {
+    int smax = 0;
+    for (int y = 2; y < 8; ++y)
+      for (int x = 1; x < 8; ++x) smax = st.s[l][y * 8 + x] > smax ? st.s[l][y * 8 + x] : smax;
+    int B = 0;
+    if (n >= 1) {
+      B = 1;
+      while (2 * B <= n) B *= 2;
+      while (B && ((long long)B << smax) > 2048) B >>= 1;
+    }
+    const uint32_t b16 = B ? (uint32_t)B : 0x4000u, m16 = B ? (uint32_t)(0xffffu & ~(2u * B - 1u)) : 0xffffu;
+    sp[64 + 2 * l] = b16 | (b16 << 16);
+    sp[64 + 2 * l + 1] = m16 | (m16 << 16);
+  }
 }
 
 }  // namespace himg_dev

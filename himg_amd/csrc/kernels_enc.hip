@@ -200,146 +200,28 @@ __device__ __forceinline__ int predict(int s1, int s2, int s3, int p) {
 //     row of the macro block, reconstructed samples exchanged through LDS.
 // ---------------------------------------------------------------------------
 // QI: the companding tables of the frame's own quality.
+// The body (enc_body_lres_predict.inc) is also k_lres_predict_rec's, the form of the distortion probe
+// (REC): quality-indexed, and it stores the reconstructed samples as well -- the plane the decoder's
+// k_lres_unpredict produces from these symbols, [C][rows][cols] like `low`.
 template <bool QI>
 __global__ __launch_bounds__(64) void k_lres_predict_t(Geom g, const uint8_t *low,
                                                        size_t plane_stride, uint8_t *lres_sym,
                                                        size_t lres_stride, QualArg<QI, LresTables> lt) {
-  // FOUR macro blocks per wavefront, 16 lanes each (lane & 15 = row of the block):
-  // the delta chain only ever has 16 rows to work on, so one block per wave left
-  // three quarters of it idle -- and a 4096x4096 frame is 4096 blocks per channel.
-  __shared__ __attribute__((aligned(4))) uint8_t mb[4][16][20];   // (rows dword aligned: the fast path stores them as dwords)
-  __shared__ uint8_t recp[4][17][18];   // the reconstructed block with a border row / column in front (see the chain below)
-  // The companding tables in LDS: the delta chain below looks them up twice per
-  // step, and out of the kernel-argument segment each lookup is a global load on
-  // the critical path of 31 dependent steps.
-  __shared__ int16_t s_tab[128];
-  __shared__ uint8_t s_code[512];
-  const int lane = threadIdx.x, b = lane >> 4, dv = lane & 15;
-  const int mu = blockIdx.x * 4 + b, mv = blockIdx.y;
-  const int f = blockIdx.z / g.C, c = blockIdx.z % g.C;
-  if constexpr (QI) {
-    // (the frame's entry: a uniform base, the lanes' own elements of it on their way into the LDS)
-    const LresTables *__restrict__ q = &qual_entry(lt, f)->lt;
-    for (int k = lane; k < 128; k += 64) s_tab[k] = q->tab[k];
-    for (int k = lane; k < 512; k += 64) s_code[k] = q->code[k];
-  } else {
-    for (int k = lane; k < 128; k += 64) s_tab[k] = lt.tab[k];
-    for (int k = lane; k < 512; k += 64) s_code[k] = lt.code[k];
-  }
-  const uint8_t *m = low + (size_t)f * plane_stride + (size_t)c * g.rows * g.cols;
-  const bool live = mu < g.mcols;
-  const int u0 = mu * 16, v0 = mv * 16;
-  const int bw = live ? min(16, g.cols - u0) : 0, bh = min(16, g.rows - v0);
-
-  int err[5] = {0, 0, 0, 0, 0};
-  // Four full blocks in rows of sixteen-byte-aligned samples (every block of the BASELINE frames
-  // but those at the right / bottom edge of odd sizes): the lane's row is ONE 16-byte load and stays
-  // in registers, the row above comes from the lane before by DPP (a block is a DPP row of 16
-  // lanes), and the predictors' squared errors are accumulated without a branch or an LDS read.
-  const bool fast = __all(live && bw == 16 && bh == 16) && (g.cols & 15) == 0;
-  if (fast) {
-    const uint4 q = *reinterpret_cast<const uint4 *>(m + (size_t)(v0 + dv) * g.cols + u0);
-    const uint32_t R[4] = {q.x, q.y, q.z, q.w};
-    uint32_t U[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      U[k] = dpp_row_shr1(R[k]);
-      *reinterpret_cast<uint32_t *>(&mb[b][dv][4 * k]) = R[k];
-    }
-    const bool up_ok1 = dv > 0;
-#pragma unroll
-    for (int du = 0; du < 16; ++du) {
-      const int actual = (int)((R[du >> 2] >> (8 * (du & 3))) & 255u);
-      const int up = (int)((U[du >> 2] >> (8 * (du & 3))) & 255u);
-      int s1, s2, s3;
-      if (du > 0) {
-        const int left = (int)((R[(du - 1) >> 2] >> (8 * ((du - 1) & 3))) & 255u);
-        const int ul = (int)((U[(du - 1) >> 2] >> (8 * ((du - 1) & 3))) & 255u);
-        s3 = left; s2 = up_ok1 ? up : left; s1 = up_ok1 ? ul : left;
-      } else {
-        s1 = s2 = s3 = up_ok1 ? up : 128;
-      }
-      const int t = s2 + s3;
-      const int pr[5] = {clamp255((3 * t - 2 * s1 + 2) >> 2), s2, s3, (t + 1) >> 1, clamp255(t - s1)};
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        const int dd = actual - pr[p];
-        err[p] += dd * dd;
-      }
-    }
-    __syncthreads();
-  } else {
-#pragma unroll
-  for (int du = 0; du < 16; ++du)
-    mb[b][dv][du] = (dv < bh && du < bw) ? m[(size_t)(v0 + dv) * g.cols + u0 + du] : 0;
-  __syncthreads();
-
-  if (dv < bh) {
-    for (int du = 0; du < bw; ++du) {
-      int s1, s2, s3;
-      if (du > 0 && dv > 0) { s1 = mb[b][dv - 1][du - 1]; s2 = mb[b][dv - 1][du]; s3 = mb[b][dv][du - 1]; }
-      else if (du > 0) { s1 = s2 = s3 = mb[b][dv][du - 1]; }
-      else if (dv > 0) { s1 = s2 = s3 = mb[b][dv - 1][du]; }
-      else { s1 = s2 = s3 = 128; }
-      const int actual = mb[b][dv][du];
-#pragma unroll
-      for (int p = 0; p < 5; ++p) {
-        const int d = actual - predict(s1, s2, s3, p);
-        err[p] += d * d;
-      }
-    }
-  }
-  }
-#pragma unroll
-  for (int p = 0; p < 5; ++p)
-    for (int d = 8; d >= 1; d >>= 1) err[p] += __shfl_xor(err[p], d);   // over the block's 16 lanes
-  int best = 0, best_err = err[0];
-#pragma unroll
-  for (int p = 1; p < 5; ++p)
-    if (err[p] < best_err) { best = p; best_err = err[p]; }
-
-  uint8_t *out = lres_sym + (size_t)f * lres_stride + (size_t)c * g.chan_size;
-  if (live && dv == 0) out[mv * g.mcols + mu] = (uint8_t)(best - 2);  // downsampled.cpp:33-35
-  // The stored byte is read back as (uint8 + 2) in int arithmetic
-  // (downsampled.cpp:37-39), so selections 0 and 1 both CODE with predictor 0.
-  const int pc = best <= 1 ? 0 : best;
-
-  uint8_t *dst = out + g.mrows * g.mcols + (size_t)v0 * g.cols + (size_t)bh * u0;
-  // The delta chain, branch free: the three reconstructed neighbours are read from a copy of the
-  // block with a border (index + 1: the reads of row / column -1 land on it, their values are
-  // not used), the cases of downsampled.cpp:263-281 are four selects (f = the neighbour that
-  // stands for all three at an edge), all five predictors are computed and the block's is
-  // selected -- the four blocks of a wavefront code with different predictors, and a switch ran
-  // every case taken by any of them.  (~100 -> ~45 instructions per anti-diagonal step.)
-  const bool row_live = dv < bh;
-  const bool up_ok = dv > 0;
-  uint8_t *rrow = &recp[b][dv + 1][1];          // rrow[du] = reconstructed sample (dv, du)
-  const uint8_t *urow = &recp[b][dv][1];        // the row above
-  for (int d = 0; d < 31; ++d) {
-    const int du = d - dv;
-    const bool active = row_live && du >= 0 && du < bw;
-    const int duc = active ? du : 0;
-    const int left = rrow[duc - 1], up = urow[duc], ul = urow[duc - 1];
-    const bool left_ok = duc > 0;
-    const int f = up_ok ? up : (left_ok ? left : 128);
-    const int s3 = left_ok ? left : f, s2 = f, s1 = (up_ok && left_ok) ? ul : f;
-    const int t = s2 + s3;
-    const int p0 = clamp255((3 * t - 2 * s1 + 2) >> 2), p3 = (t + 1) >> 1, p4 = clamp255(t - s1);
-    const int predicted = pc == 2 ? s3 : pc == 3 ? p3 : pc == 4 ? p4 : p0;   // (pc is 0, 2, 3 or 4: selections 0 and 1 both code with 0)
-    const int delta = (int)mb[b][dv][duc] - predicted;
-    const uint8_t code = s_code[delta + 255];
-    const int sc = (int8_t)code;
-    const int mag = s_tab[sc < 0 ? -sc : sc];
-    const int un = sc < 0 ? -mag : mag;
-    if (active) {
-      rrow[du] = (uint8_t)clamp255(predicted + un);
-      dst[dv * bw + du] = code;
-    }
-    __syncthreads();
-  }
+  constexpr bool REC = false;
+  uint8_t *const rec_plane = nullptr;
+#include "enc_body_lres_predict.inc"
+}
+// (a template like the other, so that the body's table branch stays a discarded statement)
+template <bool QI>
+__global__ __launch_bounds__(64) void k_lres_predict_rec_t(Geom g, const uint8_t *low, size_t plane_stride,
+                                                           uint8_t *lres_sym, size_t lres_stride,
+                                                           QualArg<QI, LresTables> lt, uint8_t *rec_plane) {
+  constexpr bool REC = true;
+#include "enc_body_lres_predict.inc"
 }
 static constexpr auto k_lres_predict = &k_lres_predict_t<false>;
 static constexpr auto k_lres_predict_q = &k_lres_predict_t<true>;
+static constexpr auto k_lres_predict_rec = &k_lres_predict_rec_t<true>;
 
 // ---------------------------------------------------------------------------
 // Tile helpers.
@@ -2320,6 +2202,58 @@ __global__ __launch_bounds__(64) void k_budget_finish(BudgetState bs, const int3
 }
 
 // ---------------------------------------------------------------------------
+// k_target_step: the search of himg_hip_encode_target_device between two distortion probes --
+// k_budget_step with the comparison and the roles of lo and hi turned round.  Probe 0 was at qmax,
+// probe 1 at qmin, every later one at the midpoint the step before chose; ts.probe_sse[f] /
+// probe_status[f] are the probe's.  best_sse[f] follows hi: the distortion at the quality that the
+// search would return now.  (The states are the budget's; kBudgetTooSmall: sse(qmax) misses the target.)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_target_step(TargetState ts, const int32_t *probe_status, int batch, int probe,
+                                                    int last, int qmin, int qmax, int32_t *d_quality) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  int state = probe == 0 ? (int)kBudgetSearch : ts.state[f];
+  int lo = probe == 0 ? qmin : ts.lo[f], hi = probe == 0 ? qmax : ts.hi[f];
+  int err = probe == 0 ? 0 : ts.err[f];
+  unsigned long long best = probe == 0 ? 0ull : ts.best_sse[f];
+  if (state == kBudgetSearch) {
+    const int32_t st = probe_status[f];
+    const unsigned long long sse = ts.probe_sse[f];
+    const bool meets = sse <= ts.target[f];
+    if (st != 0) { state = kBudgetError; err = st; }
+    else if (probe == 0) {
+      best = sse;
+      if (!meets) state = kBudgetTooSmall;
+      else if (qmax == qmin) state = kBudgetFound;
+    } else if (probe == 1) {
+      if (meets) { hi = qmin; best = sse; state = kBudgetFound; }
+    } else {
+      const int mid = (lo + hi) >> 1;   // (what this probe was at)
+      if (meets) { hi = mid; best = sse; } else lo = mid;
+    }
+    if (state == kBudgetSearch && probe >= 1 && hi - lo <= 1) state = kBudgetFound;
+  }
+  const bool found = state == kBudgetFound;
+  // The next probe: qmin behind the first, then the midpoint; a settled frame: its result (qmin without one).
+  ts.quality[f] = state == kBudgetSearch ? (probe == 0 ? qmin : (lo + hi) >> 1) : (found ? hi : qmin);
+  ts.lo[f] = lo; ts.hi[f] = hi; ts.state[f] = state; ts.err[f] = err; ts.best_sse[f] = best;
+  if (last) d_quality[f] = found ? hi : -1;
+}
+
+// Behind the final encode: a frame without a result keeps the search's verdict, whatever its
+// encode at qmin said; the others get the encode's own status.  d_sse[f]: the distortion at the
+// chosen quality (a frame that misses its target: at qmax).
+__global__ __launch_bounds__(64) void k_target_finish(TargetState ts, const int32_t *enc_status, int batch,
+                                                      uint32_t *sizes, unsigned long long *d_sse, int32_t *d_status) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  const int state = ts.state[f];
+  if (state != kBudgetFound) sizes[f] = 0;
+  d_sse[f] = state == kBudgetError ? 0ull : ts.best_sse[f];
+  if (d_status) d_status[f] = state == kBudgetFound ? enc_status[f] : state == kBudgetTooSmall ? -6 /* HIMG_ERR_TARGET */ : ts.err[f];
+}
+
+// ---------------------------------------------------------------------------
 // k_emit: RLE tokenise + Huffman bit pack of one span straight into its final
 // position.  Bits are assembled in an LDS staging buffer with ds atomics and
 // flushed as whole dwords; the dwords at the two ends of a span are shared
@@ -3177,19 +3111,27 @@ int loop_counts_read_enc(unsigned long long *out) { return loop_counts_read(out)
 
 // The launch sequence of an encode.  st / lt: the tables of the launch's one quality as kernel
 // arguments (launch_encode); qs instead: the quality-indexed forms of the five kernels that read
-// them (launch_encode_q), and with d_out == nullptr its size-only pass.
+// them (launch_encode_q), and with d_out == nullptr its size-only pass.  sse (with qs): the
+// distortion probe (launch_encode_sse) -- the front, the low-res chain in its storing form, then
+// k_sse; no token, tree, size or bit-packing kernel.
 static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
                             uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
                             const StaticChunks &sc, const ShiftTables *st, const LresTables *lt, const QualSel *qs,
                             const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
-                            hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+                            hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const SseArgs *sse = nullptr) {
   const int nsp = g.lres_spans + g.rows;
   const dim3 b256(256);
   const unsigned gx = (unsigned)((g.cols + 255) / 256);
   const bool sizes_only = d_out == nullptr;
 
   prof_begin(prof, "memset", stream);
-  if (sizes_only) {
+  if (sse) {
+    // (the sums -- k_sse adds into them -- and the status words)
+    hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)((batch * 2 + 256 * 8 - 1) / (256 * 8)), 1), b256, 0, stream,
+                       reinterpret_cast<uint32_t *>(sse->sse), (size_t)0, 0u,
+                       reinterpret_cast<uint32_t *>(sse->sse), (uint32_t)(batch * 2),
+                       reinterpret_cast<uint32_t *>(ws.status), (uint32_t)batch);
+  } else if (sizes_only) {
     // (no stream, no LRES region: the histograms and the status words alone)
     hipLaunchKernelGGL(k_zero_rows, dim3((unsigned)((batch * 2 * kHistStride + 256 * 8 - 1) / (256 * 8)), 1), b256, 0, stream,
                        reinterpret_cast<uint32_t *>(ws.hist), (size_t)0, 0u,
@@ -3237,14 +3179,19 @@ static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uin
   {
     hipStream_t stream_saved = stream;
     stream = ls;
-    if (qs)
+    if (sse)
+      HIMG_LAUNCH(k_lres_predict_rec, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
+                  ws.plane_stride, ws.lres_sym, ws.lres_stride, *qs, sse->rec);
+    else if (qs)
       HIMG_LAUNCH(k_lres_predict_q, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
                   ws.plane_stride, ws.lres_sym, ws.lres_stride, *qs);
     else
       HIMG_LAUNCH(k_lres_predict, dim3((g.mcols + 3) / 4, g.mrows, batch * g.C), dim3(64), g, ws.low,
                   ws.plane_stride, ws.lres_sym, ws.lres_stride, *lt);
-    HIMG_LAUNCH(k_lres_summary, dim3(g.lres_spans, batch), b256, g, ws);
-    HIMG_LAUNCH(k_tok_hist<256>, dim3(g.lres_spans, batch), b256, g, ws, 0);
+    if (!sse) {
+      HIMG_LAUNCH(k_lres_summary, dim3(g.lres_spans, batch), b256, g, ws);
+      HIMG_LAUNCH(k_tok_hist<256>, dim3(g.lres_spans, batch), b256, g, ws, 0);
+    }
     stream = stream_saved;
   }
   if (side) (void)hipEventRecord(ev_join, side);
@@ -3262,6 +3209,12 @@ static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uin
   } else {
     HIMG_LAUNCH((k_tile_fwd<false, 0>), dim3(gxt, g.rows, batch), dim3(kTileThreads), g, d_frames,
                 ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, *st, 0);
+  }
+  if (sse) {
+    // The symbols and the reconstructed low-res plane are there: decode-side transform and compare.
+    if (side) (void)hipStreamWaitEvent(stream, ev_join, 0);
+    launch_sse(g, ws, batch, d_frames, *qs, *sse, stream, prof);
+    return;
   }
   if (row_tok) launch_tok_rows(g, ws, 0, g.rows, batch, stream, prof);   // FRES rows: slots + histograms
   else launch_tok_hist_rows(g, ws, 0, g.rows, batch, stream, prof);
@@ -3316,6 +3269,14 @@ void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d
                   side, ev_fork, ev_join);
 }
 
+void launch_encode_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
+                       const StaticChunks &sc, const QualSel &qs, const SseArgs &sse,
+                       const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                       hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  encode_launches(g, ws, batch, d_frames, nullptr, 0, nullptr, sc, nullptr, nullptr, &qs, d_fmap_lut, stream, prof,
+                  side, ev_fork, ev_join, &sse);
+}
+
 void enc_fill_qual_tab(const StaticChunks &sc, const ShiftTables &st, const LresTables &lt, QualTab *qt) {
   const PixQuant pq = make_pix_quant(st);
   static_assert(sizeof(qt->pq) == sizeof(PixQuant), "the quantiser's words as one array");
@@ -3334,6 +3295,17 @@ void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int p
 void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
                           hipStream_t stream, Profiler *prof) {
   HIMG_LAUNCH(k_budget_finish, dim3((batch + 63) / 64), dim3(64), bs, ws.status, batch, d_sizes, d_status);
+}
+
+void launch_target_step(const TargetState &ts, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
+                        int32_t *d_quality, hipStream_t stream, Profiler *prof) {
+  HIMG_LAUNCH(k_target_step, dim3((batch + 63) / 64), dim3(64), ts, ws.status, batch, probe,
+              probe == probes - 1 ? 1 : 0, qmin, qmax, d_quality);
+}
+void launch_target_finish(const TargetState &ts, const EncWs &ws, int batch, uint32_t *d_sizes, uint64_t *d_sse,
+                          int32_t *d_status, hipStream_t stream, Profiler *prof) {
+  HIMG_LAUNCH(k_target_finish, dim3((batch + 63) / 64), dim3(64), ts, ws.status, batch, d_sizes,
+              (unsigned long long *)d_sse, d_status);
 }
 
 // ---- row-sharded encode of ONE frame (see himg_hip.h, "row-sharded encode") ----

@@ -31,6 +31,7 @@ extern "C" {
 #define HIMG_ERR_UNSUPPORTED (-3) /* geometry or stream outside the built scope */
 #define HIMG_ERR_FORMAT (-4)      /* decode: the reference would return false */
 #define HIMG_ERR_CAPACITY (-5)    /* output buffer too small */
+#define HIMG_ERR_TARGET (-6)      /* encode to a distortion target: not reached at the highest quality */
 
 typedef struct himg_hip_ctx himg_hip_ctx;
 
@@ -241,6 +242,67 @@ int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *const *frames
                                  int height, int pixel_stride, int num_channels, int qmin, int qmax,
                                  int use_ycbcr, const size_t *budgets, uint8_t *const *dst,
                                  const size_t *dst_cap, size_t *out_sizes, int *qualities);
+
+/* ---- the distortion of an encode, and encode to a distortion target ----------- */
+/*
+ * sse(q) of a frame: the sum over all H x W x C samples of (source - decoded)^2, where `decoded` is
+ * the decode of himg_hip_encode at quality q with HIMG_OPT_FIX_T2 on.  Only real pixels count (for
+ * W % 8 != 0 or H % 8 != 0 the clipped picture, as the decoder defines it), and of every pixel_stride
+ * bytes only the first num_channels.  An exact integer in a uint64_t (16384^2 RGBA: at most 7e13).
+ * Why the fixed decode: the reference decoder rejects many of its own encoder's streams (trap T2) --
+ * 327 of the 808 streams of eight small pictures over q = 0 .. 100 without the fix, none with it -- and
+ * wherever it accepts one its pixels equal the fixed decode's, so the fixed decode is the picture the
+ * stream defines.  The definition does not depend on the context's own HIMG_OPT_FIX_T2.
+ *
+ * The probe computes it without an entropy coder in either direction: the encoder's front stages
+ * leave every frame's quantised symbols and low-res plane on the device; the low-res chain stores
+ * the samples it reconstructs while it codes (what a decoder gets back), and one kernel sends the
+ * symbols through the decoder's dequantiser, inverse transform, low-res add, clamp and inverse
+ * colour transform and compares the result with the source.  d_sse: `batch` 8-byte aligned words on
+ * the device; d_status[f] (may be NULL): a failure of the front stages.  h_quality as in
+ * himg_hip_encode_device_q (a value outside [0, 100]: HIMG_ERR_ARG, nothing launched or written).
+ */
+int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                               int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
+                               uint64_t *d_sse, int32_t *d_status, void *stream);
+/*
+ * Encode to a distortion target: "at least this good, in as few bytes as the search finds".  Per
+ * frame, frames independent of each other; T its target (h_max_sse: a HOST array of `batch` values,
+ * staged like h_budgets):
+ *   1. probe qmax.  sse(qmax) > T: the frame fails -- d_quality[f] = -1, d_sizes[f] = 0, d_status[f] =
+ *      HIMG_ERR_TARGET, d_sse[f] = sse(qmax); its bytes in d_out are unspecified but stay inside its
+ *      out_stride bytes.  The other frames go on.
+ *   2. if qmin < qmax, probe qmin.  It meets T: the result is qmin.
+ *   3. otherwise lo = qmin, hi = qmax; while hi - lo > 1: mid = (lo + hi) >> 1; sse(mid) <= T ?
+ *      hi = mid : lo = mid.  The result is hi.
+ * Every frame with a result is then encoded at it (byte-identical to himg_hip_encode at that
+ * quality); d_sse[f] holds sse at the result -- exact, so d_sse[f] <= T.
+ * sse is NOT monotone in the quality: eight small test pictures have between 4 and 39 places in
+ * 0 .. 99 where sse(q + 1) > sse(q), and random noise (64 x 64 RGBA, YCbCr) has its minimum 47 717 at
+ * q = 86 and 66 146 at q = 100 (tests/test_target_host.py holds the oracle to both).  So this is THE
+ * SEARCH'S result, a deterministic quality that meets the target -- not the least such quality, and
+ * a target that some quality below qmax would meet fails when qmax itself does not.
+ * Asynchronous, no host synchronisation: himg_hip_budget_probes(qmin, qmax) probes for every frame.
+ * Argument checks as himg_hip_encode_budget_device.
+ */
+int himg_hip_encode_target_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                  int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                  const uint64_t *h_max_sse, void *d_out, size_t out_stride, uint32_t *d_sizes,
+                                  int32_t *d_quality, uint64_t *d_sse, int32_t *d_status, void *stream);
+/* The host forms, as himg_hip_encode_budget_to / _batch: *quality / qualities[i] = -1 and the error
+ * HIMG_ERR_TARGET for a frame that misses its target at qmax; *sse / sses[i]: the sse reached. */
+int himg_hip_encode_target_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
+                              int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                              uint64_t max_sse, uint8_t *dst, size_t dst_cap, size_t *out_size, int *quality,
+                              uint64_t *sse);
+int himg_hip_encode_target_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
+                                 int height, int pixel_stride, int num_channels, int qmin, int qmax,
+                                 int use_ycbcr, const uint64_t *max_sse, uint8_t *const *dst,
+                                 const size_t *dst_cap, size_t *out_sizes, int *qualities, uint64_t *sses);
+/* Host only, no GPU: the largest sse with which a W x H x C picture still has at least psnr_db dB,
+ * floor(255^2 W H C / 10^(dB / 10)) in double arithmetic.  HIMG_ERR_ARG for a non-finite or negative
+ * dB or a bad geometry; a dB so high that the result is 0 asks for a lossless result. */
+int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int num_channels, uint64_t *max_sse);
 
 /* ---- 1/8-scale preview: the low-res picture at the front of the stream ------ */
 /*
