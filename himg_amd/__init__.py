@@ -23,6 +23,10 @@ HIMG_ERR_FORMAT = -4
 HIMG_ERR_CAPACITY = -5
 HIMG_ERR_TARGET = -6
 
+HIMG_DT_F32 = 0
+HIMG_DT_F16 = 1
+HIMG_DT_BF16 = 2
+
 SYNTH = {"grad": 0, "gradn": 1, "rand": 2, "randtile": 3}
 
 # himg_hip_debug_read selectors (include/himg_hip.h)
@@ -114,6 +118,9 @@ def lib():
     L.himg_hip_decode_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_region_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.himg_hip_tensor_bytes.argtypes = [vp, i32, i32, i32, P(sz)]
+    L.himg_hip_decode_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.himg_hip_decode_regions_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_regions_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.himg_hip_scaled_size.argtypes = [i32, i32, i32, P(i32), P(i32)]
     L.himg_hip_decode_scaled_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -536,6 +543,18 @@ class Engine:
                                                   _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_regions_device")
 
+    def decode_regions_tensor_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, origins,
+                                     w, h, desc, d_out, d_status, stream=0):
+        """himg_hip_decode_regions_tensor_device: the contract of decode_regions_device with the
+        planar float output of `desc` (tensor_desc): d_out holds [batch][Co][h][w] elements."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_decode_regions_tensor_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch,
+                                                         width, height, channels, org.ctypes.data, int(w), int(h),
+                                                         C.byref(desc), _ptr(d_out), _ptr(d_status),
+                                                         C.c_void_p(stream))
+        self._check(rc, "decode_regions_tensor_device")
+
     def decode_scaled(self, packed, scale_log2, out=None):
         """The picture at 1/2 (scale_log2 = 1) or 1/4 (2) scale (himg_hip_decode_scaled_to) as a
         (ceil(H/F), ceil(W/F), C) uint8 array, F = 2 ** scale_log2: the decode the format defines
@@ -706,6 +725,16 @@ class Engine:
                                           batch, width, height, channels, _ptr(d_out),
                                           _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_device")
+
+    def decode_tensor_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, desc, d_out,
+                             d_status, stream=0):
+        """himg_hip_decode_tensor_device: the contract of decode_device with the planar float output
+        of `desc` (tensor_desc): d_out holds [batch][Co][H][W] elements of desc's type."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_tensor_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data,
+                                                 batch, width, height, channels, C.byref(desc), _ptr(d_out),
+                                                 _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_tensor_device")
 
     def decode_rows_device(self, d_packed, packed_size, width, height, channels, row0, row1,
                            d_out_rows, d_status, stream=0):
@@ -954,6 +983,59 @@ def scaled_size(w, h, scale_log2):
     if rc != 0:
         raise HimgError(rc, "scaled_size")
     return ow.value, oh.value
+
+
+class TensorDesc(C.Structure):
+    """himg_hip_tensor_desc."""
+    _fields_ = [("dtype", C.c_int), ("out_channels", C.c_int), ("scale", C.c_float * 4), ("bias", C.c_float * 4)]
+
+
+def _tensor_dtype(dtype):
+    if isinstance(dtype, (int, np.integer)):
+        return int(dtype)
+    import torch
+    table = {torch.float32: HIMG_DT_F32, torch.float16: HIMG_DT_F16, torch.bfloat16: HIMG_DT_BF16}
+    if dtype not in table:
+        raise ValueError("tensor_desc: dtype must be HIMG_DT_* or torch.float32 / float16 / bfloat16")
+    return table[dtype]
+
+
+def tensor_desc(dtype, out_channels, mean=None, std=None, scale=None, bias=None):
+    """A himg_hip_tensor_desc: element = cvt(fma(p, scale[c], bias[c])) of byte p, planar output of the
+    first out_channels channels.  dtype: HIMG_DT_* or torch.float32 / float16 / bfloat16.  With
+    mean / std (per channel, for pixels scaled to 0..1): scale = 1 / (255 std), bias = -mean / std,
+    computed in double and rounded once to float32.  Otherwise scale (default 1) and bias (default 0)
+    per channel.  The library validates the descriptor (tensor_bytes, the decode calls)."""
+    d = TensorDesc()
+    d.dtype = _tensor_dtype(dtype)
+    d.out_channels = int(out_channels)
+    n = min(max(d.out_channels, 0), 4)
+    if mean is not None or std is not None:
+        if scale is not None or bias is not None:
+            raise ValueError("tensor_desc: mean / std or scale / bias, not both")
+        m = [0.0] * n if mean is None else [float(v) for v in mean]
+        sd = [1.0] * n if std is None else [float(v) for v in std]
+        sc = [1.0 / (255.0 * sd[c]) for c in range(n)]
+        bi = [-m[c] / sd[c] for c in range(n)]
+    else:
+        sc = [1.0] * n if scale is None else [float(v) for v in scale]
+        bi = [0.0] * n if bias is None else [float(v) for v in bias]
+    for c in range(min(n, len(sc))):
+        d.scale[c] = float(np.float32(sc[c]))
+    for c in range(min(n, len(bi))):
+        d.bias[c] = float(np.float32(bi[c]))
+    return d
+
+
+def tensor_bytes(desc, channels, w, h):
+    """himg_hip_tensor_bytes (no GPU): bytes per frame of the [Co][h][w] output of `desc` for a
+    picture of `channels` channels.  Raises HimgError (HIMG_ERR_ARG) for a descriptor the decode
+    calls reject: an unknown dtype, out_channels outside 1..channels, a non-finite used scale / bias."""
+    n = C.c_size_t()
+    rc = lib().himg_hip_tensor_bytes(C.byref(desc), int(channels), int(w), int(h), C.byref(n))
+    if rc != 0:
+        raise HimgError(rc, "tensor_bytes")
+    return n.value
 
 
 class RegionPlan(C.Structure):

@@ -1,0 +1,106 @@
+// The body of k_dec_region and of its tensor form k_dec_region_t: one copy, included behind each
+// kernel's own parameters (g, ws, packed, in_stride, sizes, ra) with kRegionTens and td (the
+// descriptor, or nullptr) defined, so that k_dec_region keeps its code instruction for instruction.
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+  const RegionLayout L = region_layout(g.C, ra.sw);
+  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
+  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
+  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift, shiftp: contiguous
+  const uint8_t *s_shift = smem + L.rowtab + 512;
+  const uint32_t *s_shiftp = reinterpret_cast<const uint32_t *>(smem + L.rowtab + 640);
+  uint8_t *sym = smem + L.sym;
+  const int tid = threadIdx.x, f = blockIdx.z;
+  // The frame's own rectangle: its rows and tile columns; a workgroup past either has nothing to do.
+  RegionRect rr;
+  rr.x = ra.org[2 * f]; rr.y = ra.org[2 * f + 1]; rr.w = ra.w; rr.h = ra.h;
+  const int r = rr.y / 8 + (int)blockIdx.y, u1 = (rr.x + rr.w + 7) / 8;
+  const int su0 = rr.x / 8 + (int)blockIdx.x * ra.sw;
+  if (r >= (rr.y + rr.h + 7) / 8 || su0 >= u1) return;
+  const int ww = min(ra.sw, u1 - su0);
+  DecFrame *df = ws.frames + f;
+  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
+  __syncthreads();
+  if (sh->flag) return;
+  load_dec_tables(ws, df, f, 1, &T);
+  if (tid < kRowTabWords / 4)
+    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
+  const uint32_t nsym16 = (L.seg * 64u * (uint32_t)g.C + 15u) / 16u;
+  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
+  __syncthreads();
+  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
+  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
+  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
+  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+
+  const size_t ri = (size_t)f * g.rows + (size_t)r;
+  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
+  const GrpTables tb = tables_of(&T);
+  RegionWin win;
+  win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
+  win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
+  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
+  const uint32_t valid = po[kDecThreads + 2];
+  const bool rec = valid != 0 && pay_len != 0;
+  const unsigned long long P1 = 8ull * pay_len;
+  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
+  bool ok = true;
+  if (pay_len != 0) {
+    GReader rd;
+    rel0 = rd.attach(p, end, 8ull * pay_off);
+    const uint32_t rel_end = rel0 + (uint32_t)P1;
+    if (rec) {
+      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
+      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
+      tot = po[kDecThreads];
+      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
+      const uint32_t cnt = nxt - off;
+      if (off + cnt < out_size) {
+        // The lane's last strip symbol (stop), if its symbols [off, off + cnt) hold one.
+        uint32_t stop = ~0u;
+        bool walk = true;
+        if (!strict) {
+          const uint32_t e = off + cnt - 1u, se = e / (uint32_t)g.cols, ce = e - se * (uint32_t)g.cols;
+          long long last;
+          if (ce >= (uint32_t)(su0 + ww)) last = (long long)se * g.cols + su0 + ww - 1;
+          else if (ce >= (uint32_t)su0) last = e;
+          else last = se ? (long long)(se - 1u) * g.cols + su0 + ww - 1 : -1;
+          walk = cnt != 0 && last >= (long long)off;
+          stop = walk ? (uint32_t)last : 0u;
+        }
+        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
+      } else if (off < out_size) {
+        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
+      }
+    } else if (tid == 0) {
+      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
+    }
+  }
+  if (!ok) sh->err = 1;
+  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
+  __syncthreads();
+  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
+  int bad = sh->err || pay_len == 0;
+  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
+  const unsigned long long E = sh->endbit;
+  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
+  if (bad) {
+    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+    return;
+  }
+  // ---- the strip's tiles: transform, colour inverse, cropped stores ----
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  uint8_t *img;
+  if constexpr (kRegionTens) img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * (size_t)(td->co * tens_elem_size(td->dtype)));
+  else img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
+  const int ycbcr = df->ycbcr;
+  const int per_row = ((ww + 31) >> 5) * 64;   // whole wavefronts: both lanes of a pair are active
+#pragma unroll 1
+  for (int it = tid; it < per_row; it += kDecThreads) {
+    const int ul = pair_tile(it);
+    const bool in_strip = ul < ww;
+    const int uc = in_strip ? ul : ww - 1;
+    transform_store_region<kRegionTens>(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
+                                 pair_half(it), r, rr, img, in_strip, td);
+  }

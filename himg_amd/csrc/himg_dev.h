@@ -334,11 +334,24 @@ constexpr int kLoopCounters = 8;
 int loop_counts_read_enc(unsigned long long *out);
 int loop_counts_read_dec(unsigned long long *out);
 
+// The planar float output (himg_hip_tensor_desc as the kernels take it): element (f, c, i, j) of
+// [batch][co][H][W] is cvt(fma((float)p, scale[c], bias[c])) of byte (i, j, c) of the uint8 picture.
+// It travels in the kernel-argument segment of the tensor forms of the store kernels
+// (k_dec_row_fused_t, k_tile_inv_t, k_dec_region_t), which read scale / bias there at their use.
+struct TensDesc {
+  int dtype, co;   // HIMG_DT_*; the first co channels are stored
+  float scale[4], bias[4];
+};
+__host__ __device__ inline int tens_elem_size(int dtype) { return dtype == 0 ? 4 : 2; }
+
+// tens: the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W] elements);
+// everything in front of them is the same launch.
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
-                   const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3);
+                   const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3,
+                   const TensDesc *tens = nullptr);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 // The 1/8-scale preview: the zeroing of the LRES symbols, the container parse up to the end of
 // the LRES chunk (k_dec_parse_head, which writes where that chunk ends to d_head_sizes[f]), the
@@ -366,7 +379,7 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
 void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds);
+                   const DecStreams *ds, const TensDesc *tens = nullptr);   // (tens: scale_log2 = 0 only, [batch][co][h][w])
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
 // The scaled decode (k_dec_scaled): every frame of the batch at 1 / 2^scale_log2 (1 or 2) of its

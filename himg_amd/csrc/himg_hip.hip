@@ -1050,6 +1050,54 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
   return HIMG_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Tensor decode: the planar float output (include/himg_hip.h).  The descriptor is checked on the
+// host and rides in the kernel arguments of the store kernels.
+// ---------------------------------------------------------------------------
+static bool tensor_desc_ok(const himg_hip_tensor_desc *t, int C, himg_dev::TensDesc *td) {
+  if (!t || t->dtype < HIMG_DT_F32 || t->dtype > HIMG_DT_BF16 || t->out_channels < 1 || t->out_channels > C || C > 4)
+    return false;
+  himg_dev::TensDesc d = {};
+  d.dtype = t->dtype; d.co = t->out_channels;
+  for (int c = 0; c < t->out_channels; ++c) {
+    if (!std::isfinite(t->scale[c]) || !std::isfinite(t->bias[c])) return false;
+    d.scale[c] = t->scale[c]; d.bias[c] = t->bias[c];
+  }
+  if (td) *td = d;
+  return true;
+}
+
+extern "C" int himg_hip_tensor_bytes(const himg_hip_tensor_desc *t, int num_channels, int w, int h,
+                                     size_t *bytes_per_frame) {
+  Geom g;
+  if (!bytes_per_frame || !make_geom(w, h, num_channels, num_channels, 1, &g) || !tensor_desc_ok(t, num_channels, nullptr))
+    return HIMG_ERR_ARG;
+  *bytes_per_frame = (size_t)t->out_channels * (size_t)h * (size_t)w * (size_t)himg_dev::tens_elem_size(t->dtype);
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_tensor_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_sizes, int batch, int width, int height,
+                                             int num_channels, const himg_hip_tensor_desc *t, void *d_out,
+                                             int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !t || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  himg_dev::TensDesc td;
+  const char *bad = tensor_desc_ok(t, num_channels, &td) ? nullptr : "bad tensor descriptor";
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, bad, &g))
+    return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
+  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
+                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows,
+                nullptr, false, 3, &td);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
 extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_packed, uint32_t packed_size,
                                            int width, int height, int num_channels, int row0,
                                            int row1, void *d_out_rows, int32_t *d_status,
@@ -2006,8 +2054,11 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
 // what reaches the device are the origins of the full-resolution rectangles the windows cover.
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                          int width, int height, int num_channels, const int32_t *h_org, int w, int h,
-                         const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0) {
+                         const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0,
+                         const himg_hip_tensor_desc *tens = nullptr) {
   if (scale_log2 < 0 || scale_log2 > 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
+  himg_dev::TensDesc td;
+  if (tens && (scale_log2 || !tensor_desc_ok(tens, num_channels, &td))) return fail(ctx, HIMG_ERR_ARG, "bad tensor descriptor");
   std::vector<int32_t> up_org;
   if (scale_log2) up_org.resize(2 * (size_t)batch);
   const char *bad = nullptr;
@@ -2025,7 +2076,7 @@ static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stri
   if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org)) return rc;
   launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
                 (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, (hipStream_t)stream,
-                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr, tens ? &td : nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -2051,6 +2102,18 @@ extern "C" int himg_hip_decode_regions_device(himg_hip_ctx *ctx, const void *d_p
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
                        d_out, d_status, stream);
+}
+
+extern "C" int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                     const uint32_t *h_sizes, int batch, int width, int height,
+                                                     int num_channels, const int32_t *h_origins, int w, int h,
+                                                     const himg_hip_tensor_desc *t, void *d_out,
+                                                     int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_origins || !t || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
+                       d_out, d_status, stream, 0, t);
 }
 
 // The scaled region decode's device entry: a window of the picture at 1/2 or 1/4 scale.  A rectangle of

@@ -18,6 +18,10 @@
 //   k_dec_region, k_dec_scaled
 //                     a rectangle at full resolution; the picture at 1/2 and 1/4 scale from each
 //                     tile's lowest-sequency coefficients (no counterpart in the reference)
+//   k_dec_row_fused_t, k_tile_inv_t, k_dec_region_t
+//                     the tensor forms of the three kernels that write full-resolution pixels: a
+//                     planar, normalised float32 / float16 / bfloat16 output converted in the store
+//                     stage (TensDesc; include/himg_hip.h, "tensor decode")
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
 #include "loop_counts.h"
@@ -2614,20 +2618,119 @@ __device__ __forceinline__ uint32_t sse_word(uint32_t a, uint32_t b, uint32_t ac
   return (uint32_t)r;
 }
 
+// The planar float store form (TensDesc): the value of byte N of a packed word, one v_cvt_f32_ubyteN
+// and one v_fma_f32; pairs of them rounded to nearest even into a dword of two float16 / bfloat16
+// (v_cvt_pk_f16_f32 / v_cvt_pk_bf16_f32 -- never the round-toward-zero pack).  dtype is uniform
+// across the launch: a scalar branch at the conversion, not a template parameter.
+typedef const __attribute__((address_space(4))) TensDesc *TensK;   // in the kernel-argument segment
+typedef float tens_f2 __attribute__((ext_vector_type(2)));
+typedef _Float16 tens_h2 __attribute__((ext_vector_type(2)));
+typedef __bf16 tens_b2 __attribute__((ext_vector_type(2)));
+
+template <int N>
+__device__ __forceinline__ float tens_val(uint32_t w, float sc, float bi) {
+  return __builtin_fmaf((float)((w >> (8 * N)) & 255u), sc, bi);
+}
+__device__ __forceinline__ uint32_t tens_pack(float a, float b, int dtype) {
+  const tens_f2 v = {a, b};
+  if (dtype == 1) return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, tens_h2));
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, tens_b2));
+}
+// Eight consecutive elements of one plane row from the packed bytes w0 (x = 0..3) and w1 (x = 4..7):
+// one 16-byte store (float16 / bfloat16) or two (float32).  ALIGNED: dst is 16-byte aligned (the full
+// decode of whole tiles).  Otherwise dst is only element-aligned (ragged widths, a window's rows) and
+// elements [lo, hi) of the eight are real: all eight take the same 16-byte stores, which global memory
+// accepts at any alignment; a tile cut by an edge stores its real elements one by one, from the same
+// converted registers (dst itself may then lie in front of the buffer; nothing outside [lo, hi) is touched).
+template <bool ALIGNED = true>
+__device__ __forceinline__ void tens_store8(uint8_t *dst, uint32_t w0, uint32_t w1, float sc, float bi, int dtype,
+                                            int lo = 0, int hi = 8) {
+  const float v0 = tens_val<0>(w0, sc, bi), v1 = tens_val<1>(w0, sc, bi), v2 = tens_val<2>(w0, sc, bi),
+              v3 = tens_val<3>(w0, sc, bi), v4 = tens_val<0>(w1, sc, bi), v5 = tens_val<1>(w1, sc, bi),
+              v6 = tens_val<2>(w1, sc, bi), v7 = tens_val<3>(w1, sc, bi);
+  const bool whole = ALIGNED || (lo == 0 && hi == 8);
+  if (dtype == 0) {
+    const float4 a = make_float4(v0, v1, v2, v3), b = make_float4(v4, v5, v6, v7);
+    if (ALIGNED) {
+      reinterpret_cast<float4 *>(dst)[0] = a;
+      reinterpret_cast<float4 *>(dst)[1] = b;
+    } else if (whole) {
+      __builtin_memcpy(dst, &a, 16);
+      __builtin_memcpy(dst + 16, &b, 16);
+    } else {
+      const float v[8] = {v0, v1, v2, v3, v4, v5, v6, v7};
+#pragma unroll
+      for (int x = 0; x < 8; ++x)
+        if (x >= lo && x < hi) reinterpret_cast<float *>(dst)[x] = v[x];
+    }
+  } else {
+    uint4 o;
+    o.x = tens_pack(v0, v1, dtype); o.y = tens_pack(v2, v3, dtype);
+    o.z = tens_pack(v4, v5, dtype); o.w = tens_pack(v6, v7, dtype);
+    if (ALIGNED) {
+      *reinterpret_cast<uint4 *>(dst) = o;
+    } else if (whole) {
+      __builtin_memcpy(dst, &o, 16);
+    } else {
+      const uint32_t p[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+      for (int x = 0; x < 8; ++x)
+        if (x >= lo && x < hi) reinterpret_cast<uint16_t *>(dst)[x] = (uint16_t)(p[x >> 1] >> (16 * (x & 1)));
+    }
+  }
+}
+// The lane's packed bytes of one half row (q0..q3: channels 0..3, x = 4h..4h+3) as the channels the
+// picture has: the colour inverse of transform_store_pair (ycbcr.cpp:54-82, two pixels per packed
+// operation), its saturated pairs merged per channel instead of interleaved per pixel.
+__device__ __forceinline__ void tens_planes(uint32_t q0, uint32_t q1, uint32_t q2, uint32_t q3, int ycbcr,
+                                            uint32_t &p0, uint32_t &p1, uint32_t &p2, uint32_t &p3) {
+  if (ycbcr) {
+    uint32_t rs[2], gs[2], bs[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const uint32_t sel = k ? 0x0c030c02u : 0x0c010c00u;
+      const dpk16 yy = __builtin_bit_cast(dpk16, __builtin_amdgcn_perm(0u, q0, sel));
+      const dpk16 cbq = __builtin_bit_cast(dpk16, __builtin_amdgcn_perm(0u, q1, sel));
+      const dpk16 crq = __builtin_bit_cast(dpk16, __builtin_amdgcn_perm(0u, q2, sel));
+      const dpk16 c255 = {255, 255}, c254 = {254, 254}, one = {1, 1};
+      const dpk16 gg = yy - ((cbq + crq - c254) >> one);
+      const dpk16 g255 = gg - c255;
+      rs[k] = sat_pk_u8(pk_mad2(crq, g255));
+      gs[k] = sat_pk_u8(__builtin_bit_cast(uint32_t, gg));
+      bs[k] = sat_pk_u8(pk_mad2(cbq, g255));
+    }
+    p0 = __builtin_amdgcn_perm(rs[1], rs[0], 0x05040100u);
+    p1 = __builtin_amdgcn_perm(gs[1], gs[0], 0x05040100u);
+    p2 = __builtin_amdgcn_perm(bs[1], bs[0], 0x05040100u);
+  } else {
+    p0 = q0; p1 = q1; p2 = q2;
+  }
+  p3 = q3;
+}
 // FULL4: four channels, whole tiles only (W and H multiples of 8) -- the ragged-edge
 // stores and the channel-count tests are compiled out.
 // SSE (k_sse, the encoder's distortion probe): nothing is stored -- the lane's four pixel rows are
 // compared with the source picture instead (src: the frame, sstride bytes per pixel of which the
 // first C count; FULL4: packed RGBA, two 16-byte loads per pixel row) and the sum of the squared
 // differences over the real pixels is returned (at most 4 * 8 * 4 * 255^2 < 2^24).
-template <int COLS, bool FULL4 = false, bool SSE = false>
+// TENS (the tensor forms of the row kernels): the planar float output instead of the interleaved
+// bytes -- img is frame f's [co][H][W] elements, td the descriptor in the kernel-argument segment,
+// read here at its use.  The lane converts its four pixel rows from the per-channel packed bytes
+// (ch0..ch3, or the saturated r / g / b pairs behind the colour inverse) and never interleaves them:
+// FULL4 eight consecutive elements per channel and pixel row (adjacent lanes adjacent tiles: a
+// wavefront's stores are contiguous along the row), 16-byte aligned; otherwise the same stores at
+// element alignment for whole tiles and element stores for the ragged right edge (tens_store8), rows
+// masked to H and channels to co.
+// Channels from co on are neither converted nor stored.
+template <int COLS, bool FULL4 = false, bool SSE = false, bool TENS = false>
 __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols_rt, const uint8_t *sym,
                                                      const uint8_t *low, const int16_t *s_unmap,
                                                      const uint8_t *s_shift, const uint32_t *s_shiftp,
                                                      int ycbcr, int u, int s, int v, uint8_t *img,
                                                      const uint32_t *pre_lr = nullptr, bool store_ok = true,
                                                      bool touched_on = false, uint32_t touched = 0,
-                                                     const uint8_t *src = nullptr, int sstride = 0) {
+                                                     const uint8_t *src = nullptr, int sstride = 0,
+                                                     TensK td = nullptr) {
   uint32_t sse = 0;
   const int cols = COLS > 0 ? COLS : cols_rt;
   const int C = FULL4 ? 4 : g.C;
@@ -2687,6 +2790,27 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int y = 4 * s + rr;
+      if constexpr (TENS) {
+        uint32_t pc[4][2];   // [channel][h]: the bytes of x = 4h..4h+3
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const uint32_t q0 = ch0[rr * 2 + h], q1 = ch1[rr * 2 + h], q2 = ch2[rr * 2 + h], q3 = ch3[rr * 2 + h];
+          tens_planes(q0, q1, q2, q3, ycbcr, pc[0][h], pc[1][h], pc[2][h], pc[3][h]);
+        }
+        if (store_ok && (FULL4 || y < bh)) {
+          const int dtype = td->dtype, co = td->co;
+          const size_t es = (size_t)tens_elem_size(dtype);
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if (c < co) {
+              const float sc = td->scale[c], bi = td->bias[c];
+              const size_t e = ((size_t)c * g.H + (size_t)(8 * v + y)) * g.W + (size_t)(8 * u);
+              if (FULL4) tens_store8(img + e * es, pc[c][0], pc[c][1], sc, bi, dtype);
+              else tens_store8<false>(img + e * es, pc[c][0], pc[c][1], sc, bi, dtype, 0, bw);
+            }
+          }
+        }
+      } else {
       uint32_t px[8];
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
@@ -2757,6 +2881,7 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
               for (int c = 0; c < C; ++c) dst[x * C + c] = (uint8_t)(px[x] >> (8 * c));
         }
       }
+      }   // (!TENS)
     }
     return sse;
 }
@@ -2820,6 +2945,51 @@ __global__ __launch_bounds__(256) void k_tile_inv(Geom g, DecWs ws, uint8_t *out
                           out_frames + (size_t)f * ((size_t)g.W * g.H * g.C));
 }
 
+// k_tile_inv_t: k_tile_inv in its tensor form (TensDesc): frame f's [co][H][W] elements at
+// out_frames + f * co * H * W elements.  The arguments in one struct, so that the descriptor is
+// read from the kernel-argument segment where the stores use it.
+struct TileArgsT {
+  Geom g;
+  DecWs ws;
+  uint8_t *out_frames;
+  int v0;
+  TensDesc t;
+};
+template <bool FAST>
+__global__ __launch_bounds__(256) void k_tile_inv_t(TileArgsT a) {
+  __shared__ int16_t s_unmap[256];   // indexed by the code byte
+  __shared__ uint8_t s_shift[2][64];
+  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const TensK td = &((const __attribute__((address_space(4))) TileArgsT *)__builtin_amdgcn_kernarg_segment_ptr())->t;
+  const int v = blockIdx.y + a.v0, f = blockIdx.z;
+  const DecFrame *df = ws.frames + f;
+  __shared__ int s_status;
+  if (threadIdx.x == 0) s_status = df->status;
+  __syncthreads();
+  if (s_status) return;
+  {
+    const int k = threadIdx.x;
+    const int sc = (int8_t)k;
+    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
+    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
+    if (k < 64) {
+      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
+      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
+    }
+    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
+  }
+  __syncthreads();
+  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
+  if (pair_tile(it) >= g.cols) return;
+  const size_t frame_bytes = (size_t)g.W * g.H * (size_t)(td->co * tens_elem_size(td->dtype));
+  transform_store_pair<(FAST ? -1 : 0), FAST, false, true>(
+      g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
+      ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp, df->ycbcr, pair_tile(it),
+      pair_half(it), v, a.out_frames + (size_t)f * frame_bytes, nullptr, true, false, 0, nullptr, 0, td);
+}
+
 // ---------------------------------------------------------------------------
 // k_sse: the encoder's distortion probe (himg_hip_encode_sse_device).  k_tile_inv's transform on
 // the ENCODER's symbol plane (the same [rows][C][64][cols] layout) and its reconstructed low-res
@@ -2871,12 +3041,15 @@ __global__ __launch_bounds__(256) void k_sse(Geom g, const uint8_t *frames, cons
 // lanes without a tile in the transform (two lanes per tile: 480 lanes at 1920
 // pixels), so as many rows as fit the LDS -- and the lanes -- are entropy-decoded one
 // after the other (each by all 1024 lanes) and then transformed together.
-template <int COLS>
+// TENS: the planar float output (transform_store_pair's tensor form); out_frames is then the
+// [batch][co][H][W] buffer and td the descriptor in the kernel-argument segment.
+template <int COLS, bool TENS = false>
 __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &ws, const uint8_t *packed,
                                                    size_t in_stride, const uint32_t *sizes,
                                                    uint8_t *out_frames, int r0, int r1, int rpw,
                                                    const int bx, const int f, const int gx, const int gy,
-                                                   const uint32_t next_lin, const bool again, const bool same_tables) {
+                                                   const uint32_t next_lin, const bool again, const bool same_tables,
+                                                   TensK td = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   if (COLS == 512) rpw = 1;   // 4096-pixel rows: one row fills the lanes and the LDS (known at compile time)
   const FusedLayout L = fused_layout(g.row_block, rpw);
@@ -3068,7 +3241,9 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   // ---- phase 2: inverse transform, colour inverse and stores ----
   // Two adjacent lanes share a tile (transform_store_pair).  The decoded symbols
   // stay read-only in LDS: no barrier, no second pass over them.
-  uint8_t *img = out_frames + (size_t)f * ((size_t)g.W * g.H * g.C);
+  uint8_t *img;
+  if constexpr (TENS) img = out_frames + (size_t)f * ((size_t)g.W * g.H * (size_t)(td->co * tens_elem_size(td->dtype)));
+  else img = out_frames + (size_t)f * ((size_t)g.W * g.H * g.C);
   const int per_row = ((cols + 31) >> 5) * 64;   // whole wavefronts: a lane pair never straddles rows
   HIMG_SPAN_BEGIN("dec.transform");
 #pragma unroll 1
@@ -3078,9 +3253,10 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
     // transforms the last tile once more and stores nothing: no exec-masked region around
     // the transform (with compile-time strides it cost 50 VGPR spills at 1920 pixels).
     const bool in_row = pair_tile(il) < cols;
-    transform_store_pair<COLS, COLS != 0>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
+    transform_store_pair<COLS, COLS != 0, false, TENS>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
                                             in_row ? pair_tile(il) : cols - 1, pair_half(il), rb + i, img,
-                                            COLS == 512 ? pre_lr : nullptr, in_row, pf_on && it == tid, pf_a);
+                                            COLS == 512 ? pre_lr : nullptr, in_row, pf_on && it == tid, pf_a,
+                                            nullptr, 0, td);
   }
   HIMG_SPAN_END("dec.transform");
   // A wavefront without a transform iteration (per_row * nr < 1024: narrow rows in a frame's last
@@ -3155,6 +3331,41 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused(RowArgs) {
     const uint32_t nd = (uint32_t)ka->next_dist;
     dec_row_fused_body<COLS>(g, ws, ka->packed, ka->in_stride, ka->sizes, ka->out_frames, ka->r0, ka->r1, ka->rpw,
                              (int)(lin % (uint32_t)gx), f, gx, ka->gy, nd ? lin + nd : element(i + 1), again, f == f_prev);
+    again = true;
+    f_prev = f;
+  }
+}
+
+// k_dec_row_fused_t: the same kernel in its tensor form.  Its arguments are RowArgs -- unchanged, the
+// uint8 kernels keep their code -- followed by the descriptor, which stays in the kernel-argument
+// segment: the transform reads scale and bias there, per row and at the conversion, so that nothing
+// of it is live across the row loop or the entropy phase.
+struct RowArgsT {
+  RowArgs a;
+  TensDesc t;
+};
+template <int COLS>
+__global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_t(RowArgsT) {
+  typedef const __attribute__((address_space(4))) RowArgsT *KArgs;
+  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
+  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
+  bool again = false;
+  int f_prev = -1;
+#pragma unroll 1
+  for (uint32_t i = 0; i * S < total; ++i) {
+    const uint32_t lin = element(i);
+    if (lin >= total) break;   // (the last round is a partial one)
+    asm volatile("" : "+s"(ka));
+    Geom g;
+    DecWs ws;
+    karg_copy<uint32_t>(&g, &ka->a.g);
+    karg_copy<unsigned long long>(&ws, &ka->a.ws);
+    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
+    const uint32_t nd = (uint32_t)ka->a.next_dist;
+    dec_row_fused_body<COLS, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
+                                   ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
+                                   nd ? lin + nd : element(i + 1), again, f == f_prev, &ka->t);
     again = true;
     f_prev = f;
   }
@@ -3995,11 +4206,14 @@ __device__ __forceinline__ bool region_walk(GReader &rd, const GrpTables &t, uin
 // The transform of one tile half (transform_store_pair's lane pair, generic channel count) for the
 // region: the symbols at sym with segment stride `sstride`, the low-res corners from the frame's
 // planes at the global tile u, and the stores cropped to the rectangle (row pitch w * C).
+// TENS: the planar float output (TensDesc) -- img is frame f's [co][h][w] elements, row pitch w
+// elements per plane, element stores (a window's rows are only element-aligned).
+template <bool TENS = false>
 __device__ __forceinline__ void transform_store_region(const Geom &g, int sstride, const uint8_t *sym,
                                                        const uint8_t *low, const int16_t *s_unmap,
                                                        const uint8_t *s_shift, const uint32_t *s_shiftp, int ycbcr,
                                                        int u, int s, int v, const RegionRect &ra, uint8_t *img,
-                                                       bool store_ok) {
+                                                       bool store_ok, TensK td = nullptr) {
   const int cols = g.cols, C = g.C;
   const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
   uint32_t QA[16], QB[16];
@@ -4037,6 +4251,30 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
   for (int rr = 0; rr < 4; ++rr) {
     const int py = 8 * v + 4 * s + rr - ra.y;   // pixel row in the rectangle
     if (py < 0 || py >= ra.h) continue;
+    if constexpr (TENS) {
+      // A tile inside the window: eight consecutive elements per channel, one or two 16-byte stores at
+      // whatever alignment the window gives them; a tile the window's left or right edge cuts: its
+      // elements [lo, hi), one by one (tens_store8).
+      uint32_t pc[4][2];   // [channel][h]: the bytes of x = 4h..4h+3
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        tens_planes(ch0[rr * 2 + h], ch1[rr * 2 + h], ch2[rr * 2 + h], ch3[rr * 2 + h], ycbcr, pc[0][h], pc[1][h],
+                    pc[2][h], pc[3][h]);
+      const int dtype = td->dtype, co = td->co;
+      const size_t es = (size_t)tens_elem_size(dtype);
+      // (ternaries, not min / max: more callers of those shared inline functions and the compiler emits
+      // other code for the existing kernels that call them)
+      const int px0 = 8 * u - ra.x, lo = px0 < 0 ? -px0 : 0, hi = ra.w - px0 < 8 ? ra.w - px0 : 8;
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (c < co) {
+          const float sc = td->scale[c], bi = td->bias[c];
+          const long long e = ((long long)c * ra.h + py) * ra.w + px0;   // (px0 < 0 at the left edge: lo > 0)
+          tens_store8<false>(img + e * (long long)es, pc[c][0], pc[c][1], sc, bi, dtype, lo, hi);
+        }
+      }
+      continue;
+    }
     uint8_t *drow = img + (size_t)py * ra.w * C;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -4063,107 +4301,33 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
 
 __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, RegionArgs ra) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const RegionLayout L = region_layout(g.C, ra.sw);
-  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
-  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
-  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift, shiftp: contiguous
-  const uint8_t *s_shift = smem + L.rowtab + 512;
-  const uint32_t *s_shiftp = reinterpret_cast<const uint32_t *>(smem + L.rowtab + 640);
-  uint8_t *sym = smem + L.sym;
-  const int tid = threadIdx.x, f = blockIdx.z;
-  // The frame's own rectangle: its rows and tile columns; a workgroup past either has nothing to do.
-  RegionRect rr;
-  rr.x = ra.org[2 * f]; rr.y = ra.org[2 * f + 1]; rr.w = ra.w; rr.h = ra.h;
-  const int r = rr.y / 8 + (int)blockIdx.y, u1 = (rr.x + rr.w + 7) / 8;
-  const int su0 = rr.x / 8 + (int)blockIdx.x * ra.sw;
-  if (r >= (rr.y + rr.h + 7) / 8 || su0 >= u1) return;
-  const int ww = min(ra.sw, u1 - su0);
-  DecFrame *df = ws.frames + f;
-  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
-  __syncthreads();
-  if (sh->flag) return;
-  load_dec_tables(ws, df, f, 1, &T);
-  if (tid < kRowTabWords / 4)
-    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
-  const uint32_t nsym16 = (L.seg * 64u * (uint32_t)g.C + 15u) / 16u;
-  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
-  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
-  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
-  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+  constexpr bool kRegionTens = false;
+  const TensK td = nullptr;
+#include "dec_body_region.inc"
+}
 
-  const size_t ri = (size_t)f * g.rows + (size_t)r;
-  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
-  const GrpTables tb = tables_of(&T);
-  RegionWin win;
-  win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
-  win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
-  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
-  const uint32_t valid = po[kDecThreads + 2];
-  const bool rec = valid != 0 && pay_len != 0;
-  const unsigned long long P1 = 8ull * pay_len;
-  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
-  bool ok = true;
-  if (pay_len != 0) {
-    GReader rd;
-    rel0 = rd.attach(p, end, 8ull * pay_off);
-    const uint32_t rel_end = rel0 + (uint32_t)P1;
-    if (rec) {
-      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
-      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
-      tot = po[kDecThreads];
-      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
-      const uint32_t cnt = nxt - off;
-      if (off + cnt < out_size) {
-        // The lane's last strip symbol (stop), if its symbols [off, off + cnt) hold one.
-        uint32_t stop = ~0u;
-        bool walk = true;
-        if (!strict) {
-          const uint32_t e = off + cnt - 1u, se = e / (uint32_t)g.cols, ce = e - se * (uint32_t)g.cols;
-          long long last;
-          if (ce >= (uint32_t)(su0 + ww)) last = (long long)se * g.cols + su0 + ww - 1;
-          else if (ce >= (uint32_t)su0) last = e;
-          else last = se ? (long long)(se - 1u) * g.cols + su0 + ww - 1 : -1;
-          walk = cnt != 0 && last >= (long long)off;
-          stop = walk ? (uint32_t)last : 0u;
-        }
-        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
-      } else if (off < out_size) {
-        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
-      }
-    } else if (tid == 0) {
-      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
-    }
-  }
-  if (!ok) sh->err = 1;
-  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
-  __syncthreads();
-  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
-  int bad = sh->err || pay_len == 0;
-  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
-  const unsigned long long E = sh->endbit;
-  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
-  if (bad) {
-    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
-    return;
-  }
-  // ---- the strip's tiles: transform, colour inverse, cropped stores ----
-  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
-  uint8_t *img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
-  const int ycbcr = df->ycbcr;
-  const int per_row = ((ww + 31) >> 5) * 64;   // whole wavefronts: both lanes of a pair are active
-#pragma unroll 1
-  for (int it = tid; it < per_row; it += kDecThreads) {
-    const int ul = pair_tile(it);
-    const bool in_strip = ul < ww;
-    const int uc = in_strip ? ul : ww - 1;
-    transform_store_region(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
-                           pair_half(it), r, rr, img, in_strip);
-  }
+// k_dec_region_t: the same kernel in its tensor form -- frame f's [co][h][w] elements at
+// ra.out + f * co * h * w elements, the crop of the full decode's tensor.  The arguments in one
+// struct: the descriptor is read from the kernel-argument segment where the stores use it.
+struct RegionArgsT {
+  Geom g;
+  DecWs ws;
+  const uint8_t *packed;
+  size_t in_stride;
+  const uint32_t *sizes;
+  RegionArgs ra;
+  TensDesc t;
+};
+__global__ __launch_bounds__(kDecThreads) void k_dec_region_t(RegionArgsT a) {
+  constexpr bool kRegionTens = true;
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const uint8_t *packed = a.packed;
+  const size_t in_stride = a.in_stride;
+  const uint32_t *sizes = a.sizes;
+  const RegionArgs &ra = a.ra;
+  const TensK td = &((const __attribute__((address_space(4))) RegionArgsT *)__builtin_amdgcn_kernarg_segment_ptr())->t;
+#include "dec_body_region.inc"
 }
 
 // The region decode's per-frame forms of the kernels it shares with the full decode: frame f's
@@ -4752,7 +4916,10 @@ hipError_t dec_set_kernel_attrs() {
                          reinterpret_cast<const void *>(&k_dec_row_fused<256>),
                          reinterpret_cast<const void *>(&k_dec_row_fused<240>),
                          reinterpret_cast<const void *>(&k_dec_row_fused<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused<0>)};
+                         reinterpret_cast<const void *>(&k_dec_row_fused<0>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_t<512>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_t<-1>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_t<0>)};
   for (const void *k : fused) {
     // (the kernel's static LDS counts against the same 160 KiB)
     hipFuncAttributes fa;
@@ -4768,6 +4935,10 @@ hipError_t dec_set_kernel_attrs() {
   e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region));
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(kLdsMax - fa.sharedSizeBytes));
+  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region_t));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_t), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(kLdsMax - fa.sharedSizeBytes));
   const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
                           reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>),
@@ -4882,7 +5053,7 @@ static WindowExtents window_extents(const Geom &g, int batch, const int32_t *h_o
 void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds) {
+                   const DecStreams *ds, const TensDesc *tens) {
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
   const int F = 1 << scale_log2, hf = F * h;
@@ -4925,7 +5096,12 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   if (!scale_log2) {
     RegionArgs ra;
     ra.org = d_org; ra.sw = sw; ra.w = w; ra.h = h; ra.out = d_out;
-    prof_begin(prof, "k_dec_region", stream);
+    prof_begin(prof, tens ? "k_dec_region_t" : "k_dec_region", stream);
+    if (tens) {
+      RegionArgsT rt;
+      rt.g = g; rt.ws = ws; rt.packed = d_packed; rt.in_stride = in_stride; rt.sizes = d_sizes; rt.ra = ra; rt.t = *tens;
+      hipLaunchKernelGGL(k_dec_region_t, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, rt);
+    } else
     hipLaunchKernelGGL(k_dec_region, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, g, ws, d_packed,
                        in_stride, d_sizes, ra);
   } else {
@@ -5014,7 +5190,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
-                   const uint32_t *d_row_index, bool index_only, int phase) {
+                   const uint32_t *d_row_index, bool index_only, int phase, const TensDesc *tens) {
   // d_row_index: the FRES row index is given (k_dec_set_index instead of the serial
   // header walk; one frame).  index_only: container parse and row-header walk only --
   // the caller reads ws.row_off / ws.row_len / DecFrame::rows_first (rank 0 of a
@@ -5172,6 +5348,12 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     ra_.g = g; ra_.ws = ws; ra_.packed = d_packed; ra_.in_stride = in_stride; ra_.sizes = d_sizes; \
     ra_.out_frames = d_out; ra_.r0 = (A); ra_.r1 = (B); ra_.rpw = rpw; ra_.gx = gx_; ra_.gy = batch; \
     ra_.next_dist = pers_ ? 0 : n_cu * per_cu;                                                 \
+    if (tens) {                                                                                 \
+      RowArgsT rt_;                                                                             \
+      rt_.a = ra_; rt_.t = *tens;                                                               \
+      hipLaunchKernelGGL((k_dec_row_fused_t<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
+                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rt_); \
+    } else                                                                                      \
     hipLaunchKernelGGL((k_dec_row_fused<COLS>), dim3((unsigned)(pers_ ? slots_ : all_)),        \
                        dim3(kDecThreads), lds, stream, ra_);                                    \
   } while (0)
@@ -5180,8 +5362,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       if (ds) (void)hipStreamWaitEvent(stream, ds->ev_cnt[k], 0);
       else row_count(stream, a, b);
       if (b <= a) continue;
-      prof_begin(prof, "k_dec_row_fused", stream);
+      // (tensor forms: <512>, <-1> -- which also serves 2048 and 1920 -- and <0>)
       const bool whole4 = g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0;   // FULL4
+      // (the tensor forms carry their instantiation in the stage name: the tests assert which one ran)
+      prof_begin(prof, !tens ? "k_dec_row_fused" : g.W == 4096 && whole4 ? "k_dec_row_fused_t<512>"
+                                                 : whole4 ? "k_dec_row_fused_t<-1>" : "k_dec_row_fused_t<0>", stream);
       if (g.W == 4096 && whole4) HIMG_FUSED_LAUNCH(512, a, b);
       else if (g.W == 2048 && whole4) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
       else if (g.W == 1920 && whole4) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
@@ -5198,6 +5383,12 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       if (ds) (void)hipStreamWaitEvent(stream, ds->ev_win[k], 0);
       else { row_count(stream, a, b); window_pass(stream, a, b); }
       if (b <= a) continue;
+      if (tens) {
+        TileArgsT ta;
+        ta.g = g; ta.ws = ws; ta.out_frames = d_out; ta.v0 = a; ta.t = *tens;
+        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_t<true>, dim3(gx, b - a, batch), dim3(256), ta);
+        else HIMG_LAUNCH(k_tile_inv_t<false>, dim3(gx, b - a, batch), dim3(256), ta);
+      } else
       if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv<true>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
       else HIMG_LAUNCH(k_tile_inv<false>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
     }

@@ -434,6 +434,58 @@ int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packe
                                   uint8_t *const *dst, const size_t *dst_cap,
                                   int *widths, int *heights, int *channels);
 
+/* ---- tensor decode: planar, normalised float output ------------------------------ */
+/*
+ * The decode in the form a network takes: the first Co channels of the picture (3 of RGBA drops
+ * alpha), planar, cast and normalised -- instead of a second pass over the interleaved bytes.
+ * Output: [batch][Co][H][W] elements of the chosen type, tightly packed, frame f at element
+ * f * Co * H * W.  Element (f, c, i, j) = cvt(fma_f32((float)p, scale[c], bias[c])):
+ *   p        byte (i, j, c) of himg_hip_decode's output for that stream, under the same
+ *            HIMG_OPT_FIX_T2 setting;
+ *   fma_f32  ONE fused multiply-add in binary32, round to nearest even, denormals kept;
+ *   cvt      the identity for HIMG_DT_F32; for HIMG_DT_F16 / HIMG_DT_BF16 the conversion of that
+ *            binary32 value, round to nearest even (never a round-toward-zero pack).
+ * The value is fully determined: results are compared bit for bit, not within a tolerance.
+ * Descriptor errors: an unknown dtype, out_channels outside 1 .. C, or a non-finite scale / bias
+ * among the first Co -- HIMG_ERR_ARG, nothing launched, neither d_out nor d_status written.
+ * Entries of scale / bias from Co on are ignored.  d_out's base must be 16-byte aligned
+ * (HIMG_ERR_ARG otherwise); only the base is constrained.
+ * Not in this form (they keep their interleaved u8 output): the scaled, scaled-region and preview
+ * decodes, the host-memory entry points (_to, _batch), the row-sharded and multi-GPU paths and
+ * the command-line tools.  There is no NHWC float layout and no encode from float tensors.
+ */
+#define HIMG_DT_F32 0
+#define HIMG_DT_F16 1
+#define HIMG_DT_BF16 2
+typedef struct himg_hip_tensor_desc {
+  int dtype;            /* HIMG_DT_* */
+  int out_channels;     /* Co, 1..C: the first Co channels of the decoded picture (3 of RGBA drops alpha) */
+  float scale[4], bias[4];   /* per output channel; entries >= Co are ignored */
+} himg_hip_tensor_desc;
+/* Host only, no GPU: validates the descriptor against C = num_channels (the rules above) and the
+ * geometry, and sets *bytes_per_frame = Co * h * w * element size. */
+int himg_hip_tensor_bytes(const himg_hip_tensor_desc *t, int num_channels, int w, int h, size_t *bytes_per_frame);
+/* Streams of a batch in HBM: the argument, alignment, asynchrony and verdict contract of
+ * himg_hip_decode_device with the output above.  Frame f's status is exactly
+ * himg_hip_decode_device's; a failed frame's output is as unspecified as it is there, and its
+ * neighbours are unaffected.  The descriptor travels in the kernel arguments: no host
+ * synchronisation, no extra copy. */
+int himg_hip_decode_tensor_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                  const uint32_t *h_sizes, int batch, int width, int height,
+                                  int num_channels, const himg_hip_tensor_desc *t, void *d_out,
+                                  int32_t *d_status, void *stream);
+/* The window w x h at origin (x_f, y_f) of frame f (a data loader's random crop): the contract of
+ * himg_hip_decode_regions_device -- rectangles checked on the host before anything is launched,
+ * per-frame verdicts, bytes used, grid limits -- with the output [batch][Co][h][w]: element
+ * (f, c, i, j) is the formula above applied to pixel (y_f + i, x_f + j).  Windows are arbitrary:
+ * beyond the 16-byte aligned base the stores are only element-aligned, and nothing outside the
+ * batch * Co * h * w elements is written. */
+int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                          const uint32_t *h_sizes, int batch, int width, int height,
+                                          int num_channels, const int32_t *h_origins, int w, int h,
+                                          const himg_hip_tensor_desc *t, void *d_out,
+                                          int32_t *d_status, void *stream);
+
 /* ---- scaled decode: the picture at 1/2 and 1/4 scale ----------------------------- */
 /*
  * scale_log2 = 1 or 2: F = 2^scale_log2 pixels per output sample and side, S = 8 / F coefficients
