@@ -96,7 +96,6 @@ def lib():
     L.himg_hip_encode_budget_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp]
     L.himg_hip_encode_budget_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, sz, vp, sz, P(sz), P(i32)]
     L.himg_hip_encode_budget_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    u64 = C.c_uint64
     L.himg_hip_encode_sse_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
     L.himg_hip_encode_target_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp, vp]
     L.himg_hip_encode_target_to.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, u64, vp, sz, P(sz), P(i32), P(u64)]
@@ -243,6 +242,10 @@ def psnr(a, b):
 
 # ---- engine ------------------------------------------------------------------
 
+# himg_hip_get_option / himg_hip_set_option: the options by name (HIMG_OPT_*, include/himg_hip.h).
+_OPTIONS = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}
+
+
 class Engine:
     """One C-ABI context (one device).  Mirrors the reference's Encoder/Decoder
     pair: encode()/decode() take and return host buffers like
@@ -290,22 +293,51 @@ class Engine:
         self._check(fn(self._ctx, src, szs, n, *mid, dst, caps, ws, hs, cs), what)
         return [o.ravel()[: ws[i] * hs[i] * cs[i]].reshape(hs[i], ws[i], cs[i]) for i, o in enumerate(outs)]
 
+    def _encode_to(self, fn, what, img, channels, pixel_stride, mid, **results):
+        """What the single-frame encodes share: fn(ctx, pixels, w, h, stride, ch, *mid, None, 0, &size,
+        *&results) -- the call without a buffer, which reports the size with HIMG_ERR_CAPACITY -- then
+        himg_hip_fetch_last into an array of exactly that size (no intermediate copies).  Returns
+        (stream, *results); any other outcome raises HimgError with the results as attributes."""
+        img = np.ascontiguousarray(img, np.uint8)
+        h, w, ch, stride = _image_geom(img, channels, pixel_stride)
+        n = C.c_size_t()
+        rc = fn(self._ctx, img.ctypes.data, w, h, stride, ch, *mid, None, 0, C.byref(n),
+                *[C.byref(v) for v in results.values()])
+        if rc != HIMG_ERR_CAPACITY or n.value == 0:
+            e = HimgError(rc if rc != HIMG_OK else HIMG_ERR_ARG,
+                          "%s: %s" % (what, lib().himg_hip_last_error(self._ctx).decode()))
+            for name, v in results.items():
+                setattr(e, name, v.value)
+            raise e
+        out = np.empty(n.value, np.uint8)
+        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), what)
+        return (out, *[v.value for v in results.values()])
+
+    def _encode_batch(self, fn, what, frames, outs, mid, results=(), soft=()):
+        """What the batch encodes share: frames of one geometry and output buffers (`outs`: reusable
+        uint8 buffers of at least max_packed_size bytes, else new ones) into ctypes arrays, the call
+        fn(ctx, frames, n, w, h, stride, ch, *mid, outs, capacities, sizes, *results).  Returns (the
+        streams as views into the buffers, rc): rc other than HIMG_OK or one of `soft` raises."""
+        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+        n = len(frames)
+        h, w, ch, stride = _image_geom(frames[0])
+        if outs is None:
+            outs = [np.empty(max_packed_size(w, h, ch), np.uint8) for _ in range(n)]
+        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
+        sizes = (C.c_size_t * n)()
+        rc = fn(self._ctx, src, n, w, h, stride, ch, *mid, dst, caps, sizes, *results)
+        if rc not in (HIMG_OK, *soft):
+            self._check(rc, what)
+        return [o[: sizes[i]] for i, o in enumerate(outs)], rc
+
     # host-buffer API ---------------------------------------------------------
     def encode(self, img, quality=50, use_ycbcr=True, channels=None, pixel_stride=None):
         """himg_hip_encode_to + himg_hip_fetch_last: the stream is fetched into an
         array of exactly its size (no intermediate copies)."""
-        img = np.ascontiguousarray(img, np.uint8)
-        h, w = img.shape[:2]
-        ch = channels if channels is not None else (img.shape[2] if img.ndim == 3 else 1)
-        stride = pixel_stride if pixel_stride is not None else (img.shape[2] if img.ndim == 3 else 1)
-        n = C.c_size_t()
-        rc = lib().himg_hip_encode_to(self._ctx, img.ctypes.data, w, h, stride, ch, quality,
-                                      1 if use_ycbcr else 0, None, 0, C.byref(n))
-        if rc != HIMG_ERR_CAPACITY or n.value == 0:
-            self._check(rc if rc != HIMG_OK else HIMG_ERR_ARG, "encode")
-        out = np.empty(n.value, np.uint8)
-        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode")
-        return out
+        return self._encode_to(lib().himg_hip_encode_to, "encode", img, channels, pixel_stride,
+                               (quality, 1 if use_ycbcr else 0))[0]
 
     def decode(self, packed, out=None):
         """himg_hip_peek + himg_hip_decode_to straight into `out` (reused when it has
@@ -326,113 +358,50 @@ class Engine:
         """himg_hip_encode_batch: frames of one geometry, transfers overlapped with the
         kernels.  `outs` (optional) are reusable uint8 buffers of at least
         max_packed_size bytes; returns the streams (views into outs when given)."""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-        n = len(frames)
-        h, w = frames[0].shape[:2]
-        ch = frames[0].shape[2] if frames[0].ndim == 3 else 1
-        cap = max_packed_size(w, h, ch)
-        if outs is None:
-            outs = [np.empty(cap, np.uint8) for _ in range(n)]
-        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
-        sizes = (C.c_size_t * n)()
-        rc = lib().himg_hip_encode_batch(self._ctx, src, n, w, h, ch, ch, quality, 1 if use_ycbcr else 0,
-                                         dst, caps, sizes)
-        self._check(rc, "encode_batch")
-        return [o[: sizes[i]] for i, o in enumerate(outs)]
+        return self._encode_batch(lib().himg_hip_encode_batch, "encode_batch", frames, outs,
+                                  (quality, 1 if use_ycbcr else 0))[0]
 
     def encode_budget(self, img, budget, qmin=0, qmax=100, use_ycbcr=True, channels=None, pixel_stride=None):
         """himg_hip_encode_budget_to + himg_hip_fetch_last: (stream, quality) -- the stream of at most
         `budget` bytes at the quality the search of include/himg_hip.h finds in [qmin, qmax].  Raises
         HimgError (HIMG_ERR_CAPACITY, its `quality` -1) when the stream at qmin is larger than the budget."""
-        img = np.ascontiguousarray(img, np.uint8)
-        h, w = img.shape[:2]
-        ch = channels if channels is not None else (img.shape[2] if img.ndim == 3 else 1)
-        stride = pixel_stride if pixel_stride is not None else (img.shape[2] if img.ndim == 3 else 1)
-        n, q = C.c_size_t(), C.c_int(-1)
-        rc = lib().himg_hip_encode_budget_to(self._ctx, img.ctypes.data, w, h, stride, ch, int(qmin), int(qmax),
-                                             1 if use_ycbcr else 0, max(int(budget), 0), None, 0, C.byref(n), C.byref(q))
-        if rc != HIMG_ERR_CAPACITY or n.value == 0:
-            e = HimgError(rc if rc != HIMG_OK else HIMG_ERR_ARG,
-                          "encode_budget: %s" % lib().himg_hip_last_error(self._ctx).decode())
-            e.quality = q.value
-            raise e
-        out = np.empty(n.value, np.uint8)
-        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode_budget")
-        return out, q.value
+        return self._encode_to(lib().himg_hip_encode_budget_to, "encode_budget", img, channels, pixel_stride,
+                               (int(qmin), int(qmax), 1 if use_ycbcr else 0, max(int(budget), 0)), quality=C.c_int(-1))
 
     def encode_budget_batch(self, frames, budgets, qmin=0, qmax=100, use_ycbcr=True, outs=None):
         """himg_hip_encode_budget_batch: frames of one geometry, frame i within budgets[i] bytes.
         Returns (streams, qualities, rc): a frame whose budget is below its size at qmin (or that
         failed otherwise) has an empty stream and, for the budget, quality -1; rc is the first such
         error, HIMG_OK if there was none."""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
         n = len(frames)
-        h, w = frames[0].shape[:2]
-        ch = frames[0].shape[2] if frames[0].ndim == 3 else 1
-        cap = max_packed_size(w, h, ch)
-        if outs is None:
-            outs = [np.empty(cap, np.uint8) for _ in range(n)]
-        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
         bud = (C.c_size_t * n)(*[max(int(b), 0) for b in budgets])
-        sizes = (C.c_size_t * n)()
         quals = (C.c_int * n)()
-        rc = lib().himg_hip_encode_budget_batch(self._ctx, src, n, w, h, ch, ch, int(qmin), int(qmax),
-                                                1 if use_ycbcr else 0, bud, dst, caps, sizes, quals)
-        if rc not in (HIMG_OK, HIMG_ERR_CAPACITY):
-            self._check(rc, "encode_budget_batch")
-        return [o[: sizes[i]] for i, o in enumerate(outs)], [quals[i] for i in range(n)], rc
+        streams, rc = self._encode_batch(lib().himg_hip_encode_budget_batch, "encode_budget_batch", frames, outs,
+                                         (int(qmin), int(qmax), 1 if use_ycbcr else 0, bud), (quals,),
+                                         soft=(HIMG_ERR_CAPACITY,))
+        return streams, list(quals), rc
 
     def encode_target(self, img, max_sse, qmin=0, qmax=100, use_ycbcr=True, channels=None, pixel_stride=None):
         """himg_hip_encode_target_to + himg_hip_fetch_last: (stream, quality, sse) -- the stream at the
         quality the search of include/himg_hip.h finds in [qmin, qmax] for a sum of squared differences
         of at most `max_sse` (psnr_to_sse turns a PSNR into one), and the sum it has.  Raises HimgError
         (HIMG_ERR_TARGET, its `quality` -1 and its `sse` the sum at qmax) when qmax misses the target."""
-        img = np.ascontiguousarray(img, np.uint8)
-        h, w = img.shape[:2]
-        ch = channels if channels is not None else (img.shape[2] if img.ndim == 3 else 1)
-        stride = pixel_stride if pixel_stride is not None else (img.shape[2] if img.ndim == 3 else 1)
-        n, q, sse = C.c_size_t(), C.c_int(-1), C.c_uint64()
-        rc = lib().himg_hip_encode_target_to(self._ctx, img.ctypes.data, w, h, stride, ch, int(qmin), int(qmax),
-                                             1 if use_ycbcr else 0, min(max(int(max_sse), 0), 2 ** 64 - 1), None, 0,
-                                             C.byref(n), C.byref(q), C.byref(sse))
-        if rc != HIMG_ERR_CAPACITY or n.value == 0:
-            e = HimgError(rc if rc != HIMG_OK else HIMG_ERR_ARG,
-                          "encode_target: %s" % lib().himg_hip_last_error(self._ctx).decode())
-            e.quality = q.value
-            e.sse = sse.value
-            raise e
-        out = np.empty(n.value, np.uint8)
-        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode_target")
-        return out, q.value, sse.value
+        return self._encode_to(lib().himg_hip_encode_target_to, "encode_target", img, channels, pixel_stride,
+                               (int(qmin), int(qmax), 1 if use_ycbcr else 0, min(max(int(max_sse), 0), 2 ** 64 - 1)),
+                               quality=C.c_int(-1), sse=C.c_uint64())
 
     def encode_target_batch(self, frames, max_sses, qmin=0, qmax=100, use_ycbcr=True, outs=None):
         """himg_hip_encode_target_batch: frames of one geometry, frame i with a sum of squared
         differences of at most max_sses[i].  Returns (streams, qualities, sses, rc): a frame that
         misses its target at qmax (or that failed otherwise) has an empty stream and quality -1; rc is
         the first such error, HIMG_OK if there was none."""
-        frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
         n = len(frames)
-        h, w = frames[0].shape[:2]
-        ch = frames[0].shape[2] if frames[0].ndim == 3 else 1
-        cap = max_packed_size(w, h, ch)
-        if outs is None:
-            outs = [np.empty(cap, np.uint8) for _ in range(n)]
-        src = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
-        dst = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        caps = (C.c_size_t * n)(*[o.nbytes for o in outs])
         tgt = (C.c_uint64 * n)(*[min(max(int(t), 0), 2 ** 64 - 1) for t in max_sses])
-        sizes = (C.c_size_t * n)()
-        quals = (C.c_int * n)()
-        sses = (C.c_uint64 * n)()
-        rc = lib().himg_hip_encode_target_batch(self._ctx, src, n, w, h, ch, ch, int(qmin), int(qmax),
-                                                1 if use_ycbcr else 0, tgt, dst, caps, sizes, quals, sses)
-        if rc not in (HIMG_OK, HIMG_ERR_TARGET):
-            self._check(rc, "encode_target_batch")
-        return [o[: sizes[i]] for i, o in enumerate(outs)], [quals[i] for i in range(n)], [sses[i] for i in range(n)], rc
+        quals, sses = (C.c_int * n)(), (C.c_uint64 * n)()
+        streams, rc = self._encode_batch(lib().himg_hip_encode_target_batch, "encode_target_batch", frames, outs,
+                                         (int(qmin), int(qmax), 1 if use_ycbcr else 0, tgt), (quals, sses),
+                                         soft=(HIMG_ERR_TARGET,))
+        return streams, list(quals), list(sses), rc
 
     def decode_batch(self, streams, outs=None):
         """himg_hip_decode_batch: returns the decoded frames; `outs` (optional) are
@@ -641,7 +610,7 @@ class Engine:
 
     def get_option(self, option):
         """himg_hip_get_option: the option as the context holds it (names as in set_option)."""
-        opt = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}[option] if isinstance(option, str) else int(option)
+        opt = _OPTIONS[option] if isinstance(option, str) else int(option)
         v = C.c_int(0)
         self._check(lib().himg_hip_get_option(self._ctx, opt, C.byref(v)), "get_option")
         return v.value
@@ -649,7 +618,7 @@ class Engine:
     def set_option(self, option, value):
         """himg_hip_set_option; option names: "fix_t2", and the kernel-variant selectors
         "count_wave" / "emit_rows" (-1 = by launch size, 0 / 1 = force; see include/himg_hip.h)."""
-        opt = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}[option] if isinstance(option, str) else int(option)
+        opt = _OPTIONS[option] if isinstance(option, str) else int(option)
         self._check(lib().himg_hip_set_option(self._ctx, opt, int(value)), "set_option")
         if opt == 1:
             self.fix_t2 = bool(value)   # (the row-sharded decoder's host index follows it, sharded.py)
@@ -1069,6 +1038,12 @@ def scaled_region_peek(packed, scale_log2, x, y, w, h, fix_t2=False):
     if rc != 0:
         raise HimgError(rc, "scaled_region_peek")
     return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
+
+
+def _image_geom(img, channels=None, pixel_stride=None):
+    """(h, w, channels, pixel stride) of an image array: its last axis (1 without one) where not given."""
+    last = img.shape[2] if img.ndim == 3 else 1
+    return img.shape[0], img.shape[1], last if channels is None else channels, last if pixel_stride is None else pixel_stride
 
 
 def _as_u8(x):

@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "search_step.h"
+
 namespace himg_dev {
 
 constexpr int kNumSym = 261;      // huffman_common.h:18-20
@@ -249,22 +251,34 @@ void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d
                      const StaticChunks &sc, const QualSel &qs,
                      const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
                      hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
-// The search of himg_hip_encode_budget_device (include/himg_hip.h), per frame on the device.
-struct BudgetState {
-  int32_t *quality;         // [f] the quality of the next probe / of the final encode
-  const uint32_t *budget;   // [f] bytes
-  int32_t *lo, *hi;         // [f] the bisection's bounds
-  int32_t *state;           // [f] kBudget*
-  int32_t *err;             // [f] a probe's own failure (an encoder status), kept through the later passes
+// The quality searches of himg_hip_encode_budget_device and himg_hip_encode_target_device, per frame on
+// the device: a SearchFrame (search_step.h) per frame, one array per field.
+struct SearchState {
+  int32_t *quality;          // (first in the buffer: the per-quality forms keep their QualSel::quality there)
+  uint64_t *limit, *best;
+  uint64_t *value;           // [f] where a probe with 64-bit values leaves them (the distortion probe's sums)
+  int32_t *ok, *bad, *state, *err;
 };
-enum { kBudgetSearch = 0, kBudgetFound = 1, kBudgetTooSmall = 2, kBudgetError = 3 };
-// Behind probe `probe` (0: at qmin, 1: at qmax, then the midpoints) of `probes`: advance every frame.
-// The last one leaves quality[f] = the result (qmin for a frame without one) and d_quality[f] (-1).
-void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
-                        const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof);
-// Behind the final encode: d_status[f] (the encode's own, or the search's failure) and d_sizes[f] = 0 for a failed frame.
-void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
-                          hipStream_t stream, Profiler *prof);
+// The buffer behind a SearchState -- these two alone know its layout: the qualities (an even number of
+// words), the 64-bit arrays, the other words.  The qualities and the limits are adjacent: one copy stages both.
+inline size_t search_state_bytes(int batch) { return ((((size_t)batch + 1) & ~(size_t)1) + 10 * (size_t)batch) * 4; }
+inline SearchState search_state_carve(void *base, int batch) {
+  const size_t b = (size_t)batch;
+  int32_t *w = (int32_t *)base;
+  uint64_t *d = (uint64_t *)(w + ((b + 1) & ~(size_t)1));
+  int32_t *t = (int32_t *)(d + 3 * b);
+  return SearchState{w, d, d + b, d + 2 * b, t, t + b, t + 2 * b, t + 3 * b};
+}
+// Behind probe `probe` of `probes`: search_step for every frame, the probe's values from d_sizes, or
+// from ss.value when that is null.  The last one leaves quality[f] = the result (qmin for a frame
+// without one) and d_quality[f] (-1).
+void launch_search_step(const SearchState &ss, const EncWs &ws, int batch, int probe, int probes, int dir, int qmin,
+                        int qmax, const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof);
+// Behind the final encode: d_status[f] (the encode's own, or the search's failure: miss_code for a frame
+// whose first probe missed its limit, else the failed probe's status) and d_sizes[f] = 0 for a failed
+// frame; d_sse (may be null): the value at the chosen quality, at the first probe's for a miss, 0 after an error.
+void launch_search_finish(const SearchState &ss, const EncWs &ws, int batch, int miss_code, uint32_t *d_sizes,
+                          uint64_t *d_sse, int32_t *d_status, hipStream_t stream, Profiler *prof);
 
 // ---- the distortion probe (himg_hip_encode_sse_device, himg_hip_encode_target_device) ----
 // The decode-side tables of a stream of ONE quality, as k_dec_parse builds DecFrame::row_tabs from
@@ -291,19 +305,6 @@ void launch_encode_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t 
                        const StaticChunks &sc, const QualSel &qs, const SseArgs &sse,
                        const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
                        hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
-// The search of himg_hip_encode_target_device, per frame on the device (the states: kBudget*).
-struct TargetState {
-  int32_t *quality;          // [f] the quality of the next probe / of the final encode
-  const uint64_t *target;    // [f] the largest sse the frame may have
-  uint64_t *probe_sse;       // [f] the last probe's
-  uint64_t *best_sse;        // [f] the sse at hi
-  int32_t *lo, *hi, *state, *err;
-};
-// Behind probe `probe` (0: at qmax, 1: at qmin, then the midpoints) of `probes`.
-void launch_target_step(const TargetState &ts, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
-                        int32_t *d_quality, hipStream_t stream, Profiler *prof);
-void launch_target_finish(const TargetState &ts, const EncWs &ws, int batch, uint32_t *d_sizes, uint64_t *d_sse,
-                          int32_t *d_status, hipStream_t stream, Profiler *prof);
 
 // The decoder's helper streams and events (owned by the context).
 constexpr int kWalkSegs = 4;   // single large frames: at most this many row ranges whose walk / count / row kernels overlap

@@ -89,6 +89,21 @@ struct DevBuf {
 
 size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// What a host form reads back of a frame, as its device call writes it (the fields its form does not
+// have stay unwritten) and as one copy fetches it.
+struct HostResult {
+  uint32_t size;
+  int32_t status;
+  int32_t quality;
+  uint64_t sse;
+};
+// The batched host forms' pinned words: the mirrors of the two slots' results, and the packed sizes
+// their decodes are handed.
+struct PipeMeta {
+  HostResult res[2];
+  uint32_t dec_size[2];
+};
+
 }  // namespace
 
 struct himg_hip_ctx {
@@ -127,15 +142,15 @@ struct himg_hip_ctx {
     bool ready = false;
     hipStream_t s_in = nullptr, s_comp = nullptr, s_out = nullptr;
     hipEvent_t ev_in[2] = {nullptr, nullptr}, ev_k[2] = {nullptr, nullptr}, ev_out[2] = {nullptr, nullptr};
-    DevBuf in[2], out[2], meta[2];     // meta: u32 packed size, i32 status
-    uint32_t *h_meta = nullptr;        // pinned mirror of meta[2] (+ the decode sizes), 2 x 4 words
+    DevBuf in[2], out[2], meta[2];     // meta: the frame's HostResult
+    PipeMeta *h_meta = nullptr;        // pinned
   } pipe;
 
   // Encoder workspace.
   DevBuf e_planes, e_lres, e_fres, e_small, e_spanhist, e_tok, e_tokx;
-  // Quality per frame / encode to a byte budget: the tables of all 101 qualities (built on first
-  // use) and the per-frame words of a launch (BudgetState's arrays, the quality first).
-  DevBuf e_qtab, e_bud;
+  // Quality per frame and the searches: the tables of all 101 qualities (built on first use) and
+  // the per-frame words of a launch (a SearchState's arrays, the quality first).
+  DevBuf e_qtab, e_search;
   // The distortion probe: the decode-side tables of all 101 qualities (built with e_qtab) and the
   // reconstructed low-res planes of a launch.
   DevBuf e_stab, e_rec;
@@ -166,7 +181,7 @@ struct himg_hip_ctx {
   } head;
 
   // Staging for the host-buffer API.
-  DevBuf h_in, h_out, h_sizes, h_status, h_index;
+  DevBuf h_in, h_out, h_result, h_status, h_index;   // h_result: a HostResult (encode); h_status: status words (decode)
   uint32_t *hp_index = nullptr;          // pinned staging of the host row index (decode_core)
   size_t hp_index_cap = 0;               // in dwords
 
@@ -370,9 +385,9 @@ extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
     hipHostFree(ctx->pipe.h_meta);
   }
   DevBuf *all[] = {&ctx->fmap_lut, &ctx->e_planes, &ctx->e_lres, &ctx->e_fres, &ctx->e_small,
-                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_bud, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
+                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_search, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
                    &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->h_in,
-                   &ctx->h_out, &ctx->h_sizes, &ctx->h_status, &ctx->h_index};
+                   &ctx->h_out, &ctx->h_result, &ctx->h_status, &ctx->h_index};
   for (DevBuf *b : all) b->release();
   if (ctx->hp_index) hipHostFree(ctx->hp_index);
   delete ctx;
@@ -752,39 +767,68 @@ __global__ void k_copy_status(const int32_t *src, int32_t *dst, int n) {
   if (i < n) dst[i] = src[i];
 }
 
-extern "C" int himg_hip_encode_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width,
-                                      int height, int pixel_stride, int num_channels, int quality,
-                                      int use_ycbcr, void *d_out, size_t out_stride,
-                                      uint32_t *d_sizes, int32_t *d_status, void *stream) {
-  if (!ctx || !d_frames || !d_out || !d_sizes || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+// ---- the encode entry points -----------------------------------------------------------------
+
+struct Enc {
   Geom g;
-  if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
+  hipStream_t s;
+  // The per-quality forms (enc_q_begin):
+  StaticChunks sc;   // (the container's quality-independent bytes; LMAP / QCFG come from the table)
+  QualSel qs;
+  SearchState ss;    // the per-frame words of the launch in e_search; the plain per-quality forms use its qualities alone
+  himg_dev::SseArgs sa;
+};
+// What every encode entry point begins with: the checks (need_out: with the output buffer's), the
+// workspace, the caller's stream as the context's last one.
+static int enc_begin(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height, int pixel_stride,
+                     int num_channels, int use_ycbcr, bool need_out, const void *d_out, size_t out_stride,
+                     void *stream, Enc *e) {
+  if (!d_frames || (need_out && !d_out) || batch < 1 || batch > 65535) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &e->g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  apply_settings(ctx, &g);
-  if (g.rows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if ((out_stride & 255) || out_stride < 1024 || ((uintptr_t)d_out & 15) || ((uintptr_t)d_frames & 15))
+  apply_settings(ctx, &e->g);
+  if (e->g.rows > 65535 || batch * e->g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  if (need_out && ((out_stride & 255) || out_stride < 1024 || ((uintptr_t)d_out & 15)))
     return fail(ctx, HIMG_ERR_ARG, "out_stride must be a multiple of 256; buffers 16-byte aligned");
+  if ((uintptr_t)d_frames & 15)
+    return fail(ctx, HIMG_ERR_ARG, need_out ? "out_stride must be a multiple of 256; buffers 16-byte aligned"
+                                            : "buffers must be 16-byte aligned");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_enc_ws(ctx, g, batch);
-  if (rc) return rc;
-  StaticChunks sc;
-  ShiftTables st;
-  LresTables lt;
-  rc = build_static(g, quality, &sc, &st, &lt);
-  if (rc) return fail(ctx, rc, "unsupported table configuration");
-  hipStream_t s = (hipStream_t)stream;
-  ctx->last_stream = s;
-  launch_encode(g, ctx->enc_ws, batch, (const uint8_t *)d_frames, (uint8_t *)d_out, out_stride,
-                d_sizes, sc, st, lt, (const uint8_t *)ctx->fmap_lut.p, s, &ctx->prof,
-                ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
+  if (int rc = ensure_enc_ws(ctx, e->g, batch)) return rc;
+  e->s = (hipStream_t)stream;
+  ctx->last_stream = e->s;
+  return HIMG_OK;
+}
+// ... and ends with: the workspace's status words to d_status (the searches' finish kernel has written
+// them: nullptr), and whatever a launch has reported.
+static int enc_end(himg_hip_ctx *ctx, const Enc &e, int batch, int32_t *d_status) {
   if (d_status)
-    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, s, ctx->enc_ws.status,
-                       d_status, batch);
+    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
 
-// ---- quality per frame, size-only pass, encode to a byte budget ----------------------------
+extern "C" int himg_hip_encode_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width,
+                                      int height, int pixel_stride, int num_channels, int quality,
+                                      int use_ycbcr, void *d_out, size_t out_stride,
+                                      uint32_t *d_sizes, int32_t *d_status, void *stream) {
+  if (!ctx || !d_sizes) return HIMG_ERR_ARG;
+  Enc e;
+  int rc = enc_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
+                     stream, &e);
+  if (rc) return rc;
+  StaticChunks sc;
+  ShiftTables st;
+  LresTables lt;
+  rc = build_static(e.g, quality, &sc, &st, &lt);
+  if (rc) return fail(ctx, rc, "unsupported table configuration");
+  launch_encode(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, (uint8_t *)d_out, out_stride,
+                d_sizes, sc, st, lt, (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof,
+                ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
+  return enc_end(ctx, e, batch, d_status);
+}
+
+// ---- quality per frame, size-only pass, distortion probe, the searches ------------------------
 
 // The tables of every quality, in HBM: built on the context's first such call (the one place where
 // these calls wait for the device).
@@ -819,51 +863,42 @@ static int ensure_qual_tab(himg_hip_ctx *ctx) {
   return HIMG_OK;
 }
 
-struct EncQ {
-  Geom g;
-  StaticChunks sc;   // (the container's quality-independent bytes; LMAP / QCFG come from the table)
-  QualSel qs;
-  BudgetState bs;
-  hipStream_t s;
-};
-// What the three entry points share: the checks of himg_hip_encode_device (need_out: with its
-// output buffer's), the workspace, the table, and where the per-frame words live.
+// enc_begin for the forms that take their tables by each frame's quality: the table, the per-frame
+// words, and (sse: the distortion probe runs) the reconstructed low-res planes beside the workspace's.
 static int enc_q_begin(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height, int pixel_stride,
-                       int num_channels, int use_ycbcr, bool need_out, const void *d_out, size_t out_stride,
-                       const uint32_t *d_sizes, void *stream, EncQ *e) {
-  if (!d_frames || !d_sizes || (need_out && !d_out) || batch < 1 || batch > 65535) return fail(ctx, HIMG_ERR_ARG, "bad argument");
-  if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &e->g))
-    return fail(ctx, HIMG_ERR_ARG, "bad geometry");
-  Geom &g = e->g;
-  apply_settings(ctx, &g);
-  if (g.rows > 65535 || batch * g.C > 65535) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
-  if (need_out && ((out_stride & 255) || out_stride < 1024 || ((uintptr_t)d_out & 15)))
-    return fail(ctx, HIMG_ERR_ARG, "out_stride must be a multiple of 256; buffers 16-byte aligned");
-  if ((uintptr_t)d_frames & 15) return fail(ctx, HIMG_ERR_ARG, "buffers must be 16-byte aligned");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  int rc = ensure_enc_ws(ctx, g, batch);
+                       int num_channels, int use_ycbcr, bool need_out, const void *d_out, size_t out_stride, bool sse,
+                       void *stream, Enc *e) {
+  int rc = enc_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, need_out, d_out,
+                     out_stride, stream, e);
   if (rc) return rc;
   if ((rc = ensure_qual_tab(ctx))) return rc;
-  if (!ctx->e_bud.reserve(round_up((size_t)batch * 12 * 4 + 8, 256))) return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
+  if (!ctx->e_search.reserve(round_up(himg_dev::search_state_bytes(batch), 256)) ||
+      (sse && !ctx->e_rec.reserve(ctx->enc_ws.plane_stride * (size_t)batch)))
+    return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
   ShiftTables st;
   LresTables lt;
-  rc = build_static(g, 50, &e->sc, &st, &lt);
+  rc = build_static(e->g, 50, &e->sc, &st, &lt);
   if (rc) return fail(ctx, rc, "unsupported table configuration");
-  int32_t *w = (int32_t *)ctx->e_bud.p;
+  e->ss = himg_dev::search_state_carve(ctx->e_search.p, batch);
   e->qs.tab = (const QualTab *)ctx->e_qtab.p;
-  e->qs.quality = w;
-  e->bs.quality = w; e->bs.budget = (const uint32_t *)(w + batch);
-  e->bs.lo = w + 2 * (size_t)batch; e->bs.hi = w + 3 * (size_t)batch;
-  e->bs.state = w + 4 * (size_t)batch; e->bs.err = w + 5 * (size_t)batch;
-  e->s = (hipStream_t)stream;
-  ctx->last_stream = e->s;
+  e->qs.quality = e->ss.quality;
+  e->sa.rec = (uint8_t *)ctx->e_rec.p;
+  e->sa.tab = (const himg_dev::SseTab *)ctx->e_stab.p;
+  e->sa.sse = nullptr;   // (sse_launch: the caller's, or SearchState::value)
   return HIMG_OK;
 }
-static void enc_q_launch(himg_hip_ctx *ctx, const EncQ &e, int batch, const void *d_frames, void *d_out, size_t out_stride,
+static void enc_q_launch(himg_hip_ctx *ctx, const Enc &e, int batch, const void *d_frames, void *d_out, size_t out_stride,
                          uint32_t *d_sizes) {
   launch_encode_q(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, (uint8_t *)d_out, out_stride, d_sizes, e.sc, e.qs,
                   (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof, ctx->opts.use_side ? ctx->side_enc : nullptr,
                   ctx->ev_fork_e, ctx->ev_join_e);
+}
+static void sse_launch(himg_hip_ctx *ctx, const Enc &e, int batch, const void *d_frames, uint64_t *d_sse) {
+  himg_dev::SseArgs sa = e.sa;
+  sa.sse = d_sse;
+  himg_dev::launch_encode_sse(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, e.sc, e.qs, sa,
+                              (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof,
+                              ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
 }
 static bool qualities_ok(const int32_t *h_quality, int batch) {
   if (!h_quality) return false;
@@ -872,39 +907,44 @@ static bool qualities_ok(const int32_t *h_quality, int batch) {
   return true;
 }
 
+// The three forms with a quality per frame from the host: the streams (need_out), their sizes alone
+// (d_sizes without d_out), or their distortions (d_sse, no sizes).
+static int encode_q_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height, int pixel_stride,
+                           int num_channels, const int32_t *h_quality, int use_ycbcr, bool need_out, void *d_out,
+                           size_t out_stride, uint32_t *d_sizes, uint64_t *d_sse, int32_t *d_status, void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
+  if (d_sse ? ((uintptr_t)d_sse & 7) != 0 : !d_sizes) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  Enc e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, need_out, d_out,
+                       out_stride, d_sse != nullptr, stream, &e);
+  if (rc) return rc;
+  if ((rc = stage_words(ctx, e.ss.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
+  if (d_sse) sse_launch(ctx, e, batch, d_frames, d_sse);
+  else enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
+  return enc_end(ctx, e, batch, d_status);
+}
+
 extern "C" int himg_hip_encode_device_q(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
                                         int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
                                         void *d_out, size_t out_stride, uint32_t *d_sizes, int32_t *d_status,
                                         void *stream) {
-  if (!ctx) return HIMG_ERR_ARG;
-  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
-  EncQ e;
-  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
-                       d_sizes, stream, &e);
-  if (rc) return rc;
-  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
-  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
-  if (d_status)
-    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return encode_q_device(ctx, d_frames, batch, width, height, pixel_stride, num_channels, h_quality, use_ycbcr, true,
+                         d_out, out_stride, d_sizes, nullptr, d_status, stream);
 }
 
 extern "C" int himg_hip_encode_sizes_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
                                             int pixel_stride, int num_channels, const int32_t *h_quality,
                                             int use_ycbcr, uint32_t *d_sizes, int32_t *d_status, void *stream) {
-  if (!ctx) return HIMG_ERR_ARG;
-  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
-  EncQ e;
-  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, false, nullptr, 0,
-                       d_sizes, stream, &e);
-  if (rc) return rc;
-  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
-  enc_q_launch(ctx, e, batch, d_frames, nullptr, 0, d_sizes);
-  if (d_status)
-    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return encode_q_device(ctx, d_frames, batch, width, height, pixel_stride, num_channels, h_quality, use_ycbcr, false,
+                         nullptr, 0, d_sizes, nullptr, d_status, stream);
+}
+
+extern "C" int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
+                                          int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
+                                          uint64_t *d_sse, int32_t *d_status, void *stream) {
+  return encode_q_device(ctx, d_frames, batch, width, height, pixel_stride, num_channels, h_quality, use_ycbcr, false,
+                         nullptr, 0, nullptr, d_sse, d_status, stream);
 }
 
 extern "C" int himg_hip_budget_probes(int qmin, int qmax) {
@@ -915,78 +955,55 @@ extern "C" int himg_hip_budget_probes(int qmin, int qmax) {
   return n;
 }
 
+// A search over [qmin, qmax] on the device (himg_hip_encode_budget_device / _target_device).
+struct EncSearch {
+  int dir;           // kSearchFromMin / kSearchFromMax: the end the first probe is at
+  bool probe_sse;    // the probe: sse_launch, its values in SearchState::value; else the size-only enc_q_launch, in d_sizes
+  int miss_code;     // the status of a frame whose first probe misses its limit
+  uint64_t *d_sse;   // where the value at the chosen quality goes, or nullptr
+};
+// L: the limits as the ABI has them (32-bit budgets, 64-bit targets); the device takes 64-bit ones.
+template <typename L>
+static int encode_search_device(himg_hip_ctx *ctx, const EncSearch &k, const void *d_frames, int batch, int width,
+                                int height, int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
+                                const L *h_limits, void *d_out, size_t out_stride, uint32_t *d_sizes, int32_t *d_quality,
+                                int32_t *d_status, void *stream) {
+  if (!ctx) return HIMG_ERR_ARG;
+  const int probes = himg_hip_budget_probes(qmin, qmax);
+  if (probes < 0) return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  if (!h_limits || !d_sizes || !d_quality || (k.probe_sse && (!k.d_sse || ((uintptr_t)k.d_sse & 7))))
+    return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  Enc e;
+  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
+                       k.probe_sse, stream, &e);
+  if (rc) return rc;
+  // The first probe's qualities and the limits, in one copy: SearchState's first two arrays.
+  const size_t lim_at = (size_t)((int32_t *)e.ss.limit - e.ss.quality);
+  std::vector<int32_t> w0(lim_at + 2 * (size_t)batch, k.dir == himg_dev::kSearchFromMin ? qmin : qmax);
+  for (int i = 0; i < batch; ++i) {
+    const uint64_t lim = h_limits[i];
+    memcpy(w0.data() + lim_at + 2 * (size_t)i, &lim, 8);
+  }
+  if ((rc = stage_words(ctx, e.ss.quality, w0.data(), w0.size(), nullptr, 0, e.s))) return rc;
+  for (int p = 0; p < probes; ++p) {
+    // (every probe zeroes its own histograms or sums, and its status words)
+    if (k.probe_sse) sse_launch(ctx, e, batch, d_frames, e.ss.value);
+    else enc_q_launch(ctx, e, batch, d_frames, nullptr, 0, d_sizes);
+    himg_dev::launch_search_step(e.ss, ctx->enc_ws, batch, p, probes, k.dir, qmin, qmax, k.probe_sse ? nullptr : d_sizes,
+                                 d_quality, e.s, &ctx->prof);
+  }
+  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
+  himg_dev::launch_search_finish(e.ss, ctx->enc_ws, batch, k.miss_code, d_sizes, k.d_sse, d_status, e.s, &ctx->prof);
+  return enc_end(ctx, e, batch, nullptr);
+}
+
 extern "C" int himg_hip_encode_budget_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
                                              int pixel_stride, int num_channels, int qmin, int qmax, int use_ycbcr,
                                              const uint32_t *h_budgets, void *d_out, size_t out_stride,
                                              uint32_t *d_sizes, int32_t *d_quality, int32_t *d_status, void *stream) {
-  if (!ctx) return HIMG_ERR_ARG;
-  const int probes = himg_hip_budget_probes(qmin, qmax);
-  if (probes < 0) return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  if (!h_budgets || !d_quality) return fail(ctx, HIMG_ERR_ARG, "bad argument");
-  EncQ e;
-  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
-                       d_sizes, stream, &e);
-  if (rc) return rc;
-  // The first probe's qualities (qmin) and the budgets, in one copy: BudgetState's first two arrays.
-  std::vector<int32_t> q0((size_t)batch, qmin);
-  if ((rc = stage_words(ctx, e.bs.quality, q0.data(), (size_t)batch, h_budgets, (size_t)batch, e.s))) return rc;
-  for (int p = 0; p < probes; ++p) {
-    enc_q_launch(ctx, e, batch, d_frames, nullptr, 0, d_sizes);   // (every probe zeroes its own histograms and status words)
-    launch_budget_step(e.bs, ctx->enc_ws, batch, p, probes, qmin, qmax, d_sizes, d_quality, e.s, &ctx->prof);
-  }
-  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
-  launch_budget_finish(e.bs, ctx->enc_ws, batch, d_sizes, d_status, e.s, &ctx->prof);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
-}
-
-// ---- the distortion probe, encode to a distortion target ------------------------------------
-
-// The probe's own buffers: the reconstructed low-res planes beside the workspace's, and where the
-// per-frame words of the search live in e_bud (the quality first, as in EncQ::bs; the 64-bit
-// words behind an even number of them).
-static int sse_begin(himg_hip_ctx *ctx, const EncQ &e, int batch, himg_dev::SseArgs *sa, himg_dev::TargetState *ts) {
-  if (!ctx->e_rec.reserve(ctx->enc_ws.plane_stride * (size_t)batch))
-    return fail(ctx, HIMG_ERR_HIP, "encoder workspace allocation failed");
-  sa->rec = (uint8_t *)ctx->e_rec.p;
-  sa->tab = (const himg_dev::SseTab *)ctx->e_stab.p;
-  sa->sse = nullptr;
-  int32_t *w = (int32_t *)ctx->e_bud.p;
-  const size_t b = (size_t)batch, b2 = (b + 1) & ~(size_t)1;
-  ts->quality = w;
-  ts->target = (const uint64_t *)(w + b2);
-  ts->probe_sse = (uint64_t *)(w + b2 + 2 * b);
-  ts->best_sse = (uint64_t *)(w + b2 + 4 * b);
-  ts->lo = w + b2 + 6 * b; ts->hi = w + b2 + 7 * b; ts->state = w + b2 + 8 * b; ts->err = w + b2 + 9 * b;
-  return HIMG_OK;
-}
-static void sse_launch(himg_hip_ctx *ctx, const EncQ &e, int batch, const void *d_frames, const himg_dev::SseArgs &sa) {
-  himg_dev::launch_encode_sse(e.g, ctx->enc_ws, batch, (const uint8_t *)d_frames, e.sc, e.qs, sa,
-                              (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof,
-                              ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
-}
-
-extern "C" int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
-                                          int pixel_stride, int num_channels, const int32_t *h_quality, int use_ycbcr,
-                                          uint64_t *d_sse, int32_t *d_status, void *stream) {
-  if (!ctx) return HIMG_ERR_ARG;
-  if (batch < 1 || !qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
-  if (!d_sse || ((uintptr_t)d_sse & 7)) return fail(ctx, HIMG_ERR_ARG, "bad argument");
-  EncQ e;
-  // (no sizes: d_sse stands in for the checks' result pointer)
-  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, false, nullptr, 0,
-                       (const uint32_t *)d_sse, stream, &e);
-  if (rc) return rc;
-  himg_dev::SseArgs sa;
-  himg_dev::TargetState ts;
-  if ((rc = sse_begin(ctx, e, batch, &sa, &ts))) return rc;
-  if ((rc = stage_words(ctx, e.bs.quality, h_quality, (size_t)batch, nullptr, 0, e.s))) return rc;
-  sa.sse = d_sse;
-  sse_launch(ctx, e, batch, d_frames, sa);
-  if (d_status)
-    hipLaunchKernelGGL(k_copy_status, dim3((batch + 63) / 64), dim3(64), 0, e.s, ctx->enc_ws.status, d_status, batch);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  const EncSearch k = {himg_dev::kSearchFromMin, false, HIMG_ERR_CAPACITY, nullptr};
+  return encode_search_device(ctx, k, d_frames, batch, width, height, pixel_stride, num_channels, qmin, qmax, use_ycbcr,
+                              h_budgets, d_out, out_stride, d_sizes, d_quality, d_status, stream);
 }
 
 extern "C" int himg_hip_encode_target_device(himg_hip_ctx *ctx, const void *d_frames, int batch, int width, int height,
@@ -994,31 +1011,9 @@ extern "C" int himg_hip_encode_target_device(himg_hip_ctx *ctx, const void *d_fr
                                              const uint64_t *h_max_sse, void *d_out, size_t out_stride,
                                              uint32_t *d_sizes, int32_t *d_quality, uint64_t *d_sse, int32_t *d_status,
                                              void *stream) {
-  if (!ctx) return HIMG_ERR_ARG;
-  const int probes = himg_hip_budget_probes(qmin, qmax);
-  if (probes < 0) return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  if (!h_max_sse || !d_quality || !d_sse || ((uintptr_t)d_sse & 7)) return fail(ctx, HIMG_ERR_ARG, "bad argument");
-  EncQ e;
-  int rc = enc_q_begin(ctx, d_frames, batch, width, height, pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride,
-                       d_sizes, stream, &e);
-  if (rc) return rc;
-  himg_dev::SseArgs sa;
-  himg_dev::TargetState ts;
-  if ((rc = sse_begin(ctx, e, batch, &sa, &ts))) return rc;
-  // The first probe's qualities (qmax) and the targets, in one copy: TargetState's first two arrays.
-  const size_t b2 = ((size_t)batch + 1) & ~(size_t)1;
-  std::vector<int32_t> w0(b2 + 2 * (size_t)batch, qmax);
-  memcpy(w0.data() + b2, h_max_sse, (size_t)batch * 8);
-  if ((rc = stage_words(ctx, ts.quality, w0.data(), w0.size(), nullptr, 0, e.s))) return rc;
-  sa.sse = ts.probe_sse;
-  for (int p = 0; p < probes; ++p) {
-    sse_launch(ctx, e, batch, d_frames, sa);   // (every probe zeroes its own sums and status words)
-    himg_dev::launch_target_step(ts, ctx->enc_ws, batch, p, probes, qmin, qmax, d_quality, e.s, &ctx->prof);
-  }
-  enc_q_launch(ctx, e, batch, d_frames, d_out, out_stride, d_sizes);
-  himg_dev::launch_target_finish(ts, ctx->enc_ws, batch, d_sizes, d_sse, d_status, e.s, &ctx->prof);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  const EncSearch k = {himg_dev::kSearchFromMax, true, HIMG_ERR_TARGET, d_sse};
+  return encode_search_device(ctx, k, d_frames, batch, width, height, pixel_stride, num_channels, qmin, qmax, use_ycbcr,
+                              h_max_sse, d_out, out_stride, d_sizes, d_quality, d_status, stream);
 }
 
 extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int num_channels, uint64_t *max_sse) {
@@ -1427,67 +1422,73 @@ extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, in
 // The stream / the pixels of the last host call stay resident in ctx->h_out; the
 // entry points differ only in where they copy them to.
 
-// The budget forms of the host API: the quality range with each frame's budget, and where the chosen
-// quality goes (-1 for a frame whose budget is below its size at qmin).
-struct HostBudget {
-  int qmin, qmax;
-  const size_t *budgets;
+// What a host encode form asks for, for each of its frames.
+enum HostEncKind { kEncPlain, kEncBudget, kEncTarget };
+struct HostEncReq {
+  HostEncKind kind;
+  int quality;               // kEncPlain
+  int qmin, qmax;            // the searches: the range, each frame's limit, and where the chosen quality goes
+  const size_t *budgets;     // kEncBudget  (-1 for a frame whose budget is below its size at qmin)
+  const uint64_t *max_sse;   // kEncTarget  (-1 for a frame that misses its target at qmax)
   int *qualities;
-  // The distortion-target forms (himg_hip_encode_target_to / _batch) instead: each frame's largest
-  // sse, and where the sse reached goes; a frame that misses its target at qmax has quality -1.
-  const uint64_t *max_sse = nullptr;
-  uint64_t *sses = nullptr;
+  uint64_t *sses;            // kEncTarget: where the sse reached goes
 };
-static const char *const kTargetAboveQmax = "the distortion at qmax is above the target";
-static uint32_t budget_u32(size_t b) { return b > 0xffffffffull ? 0xffffffffu : (uint32_t)b; }
-static const char *const kBudgetBelowQmin = "the budget is below the stream's size at qmin";
+static bool req_range_ok(himg_hip_ctx *ctx, const HostEncReq &rq) {
+  if (himg_hip_budget_probes(rq.qmin, rq.qmax) >= 0) return true;
+  fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
+  return false;
+}
+// The device form of the request for its frame i (at d_in, one frame), the results to *d_res.
+static int encode_request_device(himg_hip_ctx *ctx, const HostEncReq &rq, int i, const void *d_in, int width, int height,
+                                 int pixel_stride, int num_channels, int use_ycbcr, void *d_out, size_t cap,
+                                 HostResult *d_res, hipStream_t s) {
+  switch (rq.kind) {
+    case kEncBudget: {
+      const uint32_t b = rq.budgets[i] > 0xffffffffull ? 0xffffffffu : (uint32_t)rq.budgets[i];
+      return himg_hip_encode_budget_device(ctx, d_in, 1, width, height, pixel_stride, num_channels, rq.qmin, rq.qmax,
+                                           use_ycbcr, &b, d_out, cap, &d_res->size, &d_res->quality, &d_res->status, s);
+    }
+    case kEncTarget:
+      return himg_hip_encode_target_device(ctx, d_in, 1, width, height, pixel_stride, num_channels, rq.qmin, rq.qmax,
+                                           use_ycbcr, rq.max_sse + i, d_out, cap, &d_res->size, &d_res->quality,
+                                           &d_res->sse, &d_res->status, s);
+    default:
+      return himg_hip_encode_device(ctx, d_in, 1, width, height, pixel_stride, num_channels, rq.quality, use_ycbcr, d_out,
+                                    cap, &d_res->size, &d_res->status, s);
+  }
+}
+// Frame i's results to where the request wants them, and its status as the host API reports it.
+static int encode_verdict(himg_hip_ctx *ctx, const HostEncReq &rq, int i, const HostResult &r) {
+  if (rq.kind != kEncPlain) rq.qualities[i] = r.quality;
+  if (rq.kind == kEncTarget) rq.sses[i] = r.sse;
+  if (rq.kind == kEncTarget && r.status == HIMG_ERR_TARGET)
+    return fail(ctx, HIMG_ERR_TARGET, "the distortion at qmax is above the target");
+  if (rq.kind == kEncBudget && r.status == HIMG_ERR_CAPACITY)
+    return fail(ctx, HIMG_ERR_CAPACITY, "the budget is below the stream's size at qmin");
+  if (r.status) return fail(ctx, status_to_code(r.status), "device encode reported an error");
+  return HIMG_OK;
+}
 
-// bud: the budget form (`quality` is then not used).
 static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
-                       int pixel_stride, int num_channels, int quality, int use_ycbcr,
-                       uint32_t *n_out, const HostBudget *bud = nullptr) {
+                       int pixel_stride, int num_channels, int use_ycbcr, const HostEncReq &rq, uint32_t *n_out) {
   Geom g;
   if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t cap = himg_hip_max_packed_size(width, height, num_channels);
   if (!ctx->h_in.reserve(round_up((size_t)g.frame_bytes, 256)) || !ctx->h_out.reserve(cap) ||
-      !ctx->h_sizes.reserve(256) || !ctx->h_status.reserve(256))
+      !ctx->h_result.reserve(256))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   ctx->host_bytes = 0;
   HIP_TRY(ctx, hipMemcpy(ctx->h_in.p, data, (size_t)g.frame_bytes, hipMemcpyHostToDevice));
-  int rc;
-  if (bud && bud->max_sse) {
-    rc = himg_hip_encode_target_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels, bud->qmin,
-                                       bud->qmax, use_ycbcr, bud->max_sse, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
-                                       (int32_t *)ctx->h_status.p + 1, (uint64_t *)ctx->h_status.p + 1,
-                                       (int32_t *)ctx->h_status.p, nullptr);
-  } else if (bud) {
-    const uint32_t b = budget_u32(bud->budgets[0]);
-    rc = himg_hip_encode_budget_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels, bud->qmin,
-                                       bud->qmax, use_ycbcr, &b, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
-                                       (int32_t *)ctx->h_status.p + 1, (int32_t *)ctx->h_status.p, nullptr);
-  } else {
-    rc = himg_hip_encode_device(ctx, ctx->h_in.p, 1, width, height, pixel_stride, num_channels,
-                                quality, use_ycbcr, ctx->h_out.p, cap, (uint32_t *)ctx->h_sizes.p,
-                                (int32_t *)ctx->h_status.p, nullptr);
-  }
+  int rc = encode_request_device(ctx, rq, 0, ctx->h_in.p, width, height, pixel_stride, num_channels, use_ycbcr,
+                                 ctx->h_out.p, cap, (HostResult *)ctx->h_result.p, nullptr);
   if (rc) return rc;
-  uint32_t n = 0;
-  int32_t st2[4] = {0, 0, 0, 0};   // the status, then (budget form) the quality, then (target form) the sse
-  HIP_TRY(ctx, hipMemcpy(&n, ctx->h_sizes.p, 4, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(st2, ctx->h_status.p, bud ? (bud->max_sse ? 16 : 8) : 4, hipMemcpyDeviceToHost));
-  const int32_t st = st2[0];
-  if (bud) {
-    bud->qualities[0] = st2[1];
-    if (bud->max_sse) {
-      memcpy(bud->sses, st2 + 2, 8);
-      if (st == HIMG_ERR_TARGET) return fail(ctx, HIMG_ERR_TARGET, kTargetAboveQmax);
-    } else if (st == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
-  }
-  if (st) return fail(ctx, status_to_code(st), "device encode reported an error");
-  ctx->host_bytes = n;
-  *n_out = n;
+  HostResult r = {};
+  HIP_TRY(ctx, hipMemcpy(&r, ctx->h_result.p, sizeof(r), hipMemcpyDeviceToHost));
+  if ((rc = encode_verdict(ctx, rq, 0, r))) return rc;
+  ctx->host_bytes = r.size;
+  *n_out = r.size;
   return HIMG_OK;
 }
 
@@ -1498,7 +1499,8 @@ extern "C" int himg_hip_encode(himg_hip_ctx *ctx, const uint8_t *data, int width
   *out = nullptr;
   *out_size = 0;
   uint32_t n = 0;
-  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, quality, use_ycbcr, &n);
+  const HostEncReq rq = {kEncPlain, quality};
+  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, &n);
   if (rc) return rc;
   uint8_t *buf = (uint8_t *)std::malloc(n ? n : 1);
   if (!buf) return fail(ctx, HIMG_ERR_ARG, "out of host memory");
@@ -1508,18 +1510,26 @@ extern "C" int himg_hip_encode(himg_hip_ctx *ctx, const uint8_t *data, int width
   return HIMG_OK;
 }
 
-extern "C" int himg_hip_encode_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
-                                  int pixel_stride, int num_channels, int quality, int use_ycbcr,
-                                  uint8_t *dst, size_t dst_cap, size_t *out_size) {
-  if (!ctx || !data || !out_size) return HIMG_ERR_ARG;
-  *out_size = 0;
+// The `_to` forms: the encode, then the size, and the stream where dst has room for it.
+static int encode_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height, int pixel_stride, int num_channels,
+                     int use_ycbcr, const HostEncReq &rq, uint8_t *dst, size_t dst_cap, size_t *out_size) {
+  if (rq.kind != kEncPlain && !req_range_ok(ctx, rq)) return HIMG_ERR_ARG;
   uint32_t n = 0;
-  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, quality, use_ycbcr, &n);
+  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, &n);
   if (rc) return rc;
   *out_size = n;
   if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, n, hipMemcpyDeviceToHost));
   return HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
+                                  int pixel_stride, int num_channels, int quality, int use_ycbcr,
+                                  uint8_t *dst, size_t dst_cap, size_t *out_size) {
+  if (!ctx || !data || !out_size) return HIMG_ERR_ARG;
+  *out_size = 0;
+  const HostEncReq rq = {kEncPlain, quality};
+  return encode_to(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
 }
 
 extern "C" int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
@@ -1528,16 +1538,8 @@ extern "C" int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data,
   if (!ctx || !data || !out_size || !quality) return HIMG_ERR_ARG;
   *out_size = 0;
   *quality = -1;
-  if (himg_hip_budget_probes(qmin, qmax) < 0)
-    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  uint32_t n = 0;
-  const HostBudget bud = {qmin, qmax, &budget, quality};
-  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, 0, use_ycbcr, &n, &bud);
-  if (rc) return rc;
-  *out_size = n;
-  if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, n, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  const HostEncReq rq = {kEncBudget, 0, qmin, qmax, &budget, nullptr, quality, nullptr};
+  return encode_to(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
 }
 
 extern "C" int himg_hip_encode_target_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,
@@ -1548,18 +1550,8 @@ extern "C" int himg_hip_encode_target_to(himg_hip_ctx *ctx, const uint8_t *data,
   *out_size = 0;
   *quality = -1;
   *sse = 0;
-  if (himg_hip_budget_probes(qmin, qmax) < 0)
-    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  uint32_t n = 0;
-  HostBudget bud = {qmin, qmax, nullptr, quality};
-  bud.max_sse = &max_sse;
-  bud.sses = sse;
-  const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, 0, use_ycbcr, &n, &bud);
-  if (rc) return rc;
-  *out_size = n;
-  if (!dst || dst_cap < n) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, n, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  const HostEncReq rq = {kEncTarget, 0, qmin, qmax, nullptr, &max_sse, quality, sse};
+  return encode_to(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
 }
 
 extern "C" int himg_hip_fetch_last(himg_hip_ctx *ctx, uint8_t *dst, size_t dst_cap, size_t *size) {
@@ -1733,18 +1725,26 @@ static int pipe_init(himg_hip_ctx *ctx) {
     HIP_TRY(ctx, hipEventCreateWithFlags(&p.ev_out[k], hipEventDisableTiming));
     if (!p.meta[k].reserve(256)) return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   }
-  HIP_TRY(ctx, hipHostMalloc((void **)&p.h_meta, 64, hipHostMallocDefault));
+  HIP_TRY(ctx, hipHostMalloc((void **)&p.h_meta, sizeof(PipeMeta), hipHostMallocDefault));
   p.ready = true;
   return HIMG_OK;
 }
 
-// himg_hip_encode_batch, and with bud its budget form (frame i: budget bud->budgets[i], the chosen
-// quality to bud->qualities[i]).
+// The slot's HostResult on its way to its pinned mirror, behind the slot's kernels.
+static int pipe_fetch_result(himg_hip_ctx *ctx, int slot) {
+  himg_hip_ctx::Pipe &p = ctx->pipe;
+  HIP_TRY(ctx, hipMemcpyAsync(&p.h_meta->res[slot], p.meta[slot].p, sizeof(HostResult), hipMemcpyDeviceToHost, p.s_comp));
+  HIP_TRY(ctx, hipEventRecord(p.ev_k[slot], p.s_comp));
+  return HIMG_OK;
+}
+
+// The three batch forms of the host encode (rq: frame i's budget / target at [i], its results to [i]).
 static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
-                        int height, int pixel_stride, int num_channels, int quality,
-                        int use_ycbcr, uint8_t *const *dst, const size_t *dst_cap,
-                        size_t *out_sizes, const HostBudget *bud) {
+                        int height, int pixel_stride, int num_channels,
+                        int use_ycbcr, const HostEncReq &rq, uint8_t *const *dst, const size_t *dst_cap,
+                        size_t *out_sizes) {
   if (!ctx || !frames || !dst || !dst_cap || !out_sizes || n < 0) return HIMG_ERR_ARG;
+  if (rq.kind != kEncPlain && !req_range_ok(ctx, rq)) return HIMG_ERR_ARG;
   Geom g;
   if (!make_geom(width, height, pixel_stride, num_channels, use_ycbcr, &g))
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
@@ -1763,18 +1763,12 @@ static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, 
     const int slot = j & 1;
     out_sizes[j] = 0;
     HIP_TRY(ctx, hipEventSynchronize(p.ev_k[slot]));
-    const uint32_t nbytes = p.h_meta[slot * 4 + 0];
-    const int32_t st = (int32_t)p.h_meta[slot * 4 + 1];
-    int err = HIMG_OK;
-    if (bud) bud->qualities[j] = (int32_t)p.h_meta[slot * 4 + 2];
-    if (bud && bud->max_sse) memcpy(&bud->sses[j], p.h_meta + 10 + 2 * slot, 8);
-    if (bud && bud->max_sse && st == HIMG_ERR_TARGET) err = fail(ctx, HIMG_ERR_TARGET, kTargetAboveQmax);
-    else if (bud && !bud->max_sse && st == HIMG_ERR_CAPACITY) err = fail(ctx, HIMG_ERR_CAPACITY, kBudgetBelowQmin);
-    else if (st) err = fail(ctx, status_to_code(st), "device encode reported an error");
-    else if (!dst[j] || dst_cap[j] < nbytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+    const HostResult r = p.h_meta->res[slot];
+    int err = encode_verdict(ctx, rq, j, r);
+    if (!err && (!dst[j] || dst_cap[j] < r.size)) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
     if (!err) {
-      HIP_TRY(ctx, hipMemcpyAsync(dst[j], p.out[slot].p, nbytes, hipMemcpyDeviceToHost, p.s_out));
-      out_sizes[j] = nbytes;
+      HIP_TRY(ctx, hipMemcpyAsync(dst[j], p.out[slot].p, r.size, hipMemcpyDeviceToHost, p.s_out));
+      out_sizes[j] = r.size;
     } else if (!first_err) {
       first_err = err;
     }
@@ -1788,26 +1782,10 @@ static int encode_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, 
     HIP_TRY(ctx, hipMemcpyAsync(p.in[slot].p, frames[i], (size_t)g.frame_bytes, hipMemcpyHostToDevice, p.s_in));
     HIP_TRY(ctx, hipEventRecord(p.ev_in[slot], p.s_in));
     HIP_TRY(ctx, hipStreamWaitEvent(p.s_comp, p.ev_in[slot], 0));
-    if (bud && bud->max_sse) {
-      // (meta: size, status, quality, -, then the sse as one 64-bit word; its pinned mirror: words 10 + 2 slot)
-      rc = himg_hip_encode_target_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, bud->qmin,
-                                         bud->qmax, use_ycbcr, bud->max_sse + i, p.out[slot].p, cap,
-                                         (uint32_t *)p.meta[slot].p, (int32_t *)p.meta[slot].p + 2,
-                                         (uint64_t *)p.meta[slot].p + 2, (int32_t *)p.meta[slot].p + 1, p.s_comp);
-      if (!rc) HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + 10 + 2 * slot, (uint32_t *)p.meta[slot].p + 4, 8, hipMemcpyDeviceToHost, p.s_comp));
-    } else if (bud) {
-      const uint32_t b = budget_u32(bud->budgets[i]);
-      rc = himg_hip_encode_budget_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, bud->qmin,
-                                         bud->qmax, use_ycbcr, &b, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
-                                         (int32_t *)p.meta[slot].p + 2, (int32_t *)p.meta[slot].p + 1, p.s_comp);
-    } else {
-      rc = himg_hip_encode_device(ctx, p.in[slot].p, 1, width, height, pixel_stride, num_channels, quality,
-                                  use_ycbcr, p.out[slot].p, cap, (uint32_t *)p.meta[slot].p,
-                                  (int32_t *)p.meta[slot].p + 1, p.s_comp);
-    }
+    rc = encode_request_device(ctx, rq, i, p.in[slot].p, width, height, pixel_stride, num_channels, use_ycbcr,
+                               p.out[slot].p, cap, (HostResult *)p.meta[slot].p, p.s_comp);
     if (rc) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + slot * 4, p.meta[slot].p, bud ? 12 : 8, hipMemcpyDeviceToHost, p.s_comp));
-    HIP_TRY(ctx, hipEventRecord(p.ev_k[slot], p.s_comp));
+    if ((rc = pipe_fetch_result(ctx, slot))) return rc;
     if (i >= 1 && (rc = finish(i - 1))) return rc;
   }
   if (n >= 1 && (rc = finish(n - 1))) return rc;
@@ -1819,8 +1797,8 @@ extern "C" int himg_hip_encode_batch(himg_hip_ctx *ctx, const uint8_t *const *fr
                                      int height, int pixel_stride, int num_channels, int quality,
                                      int use_ycbcr, uint8_t *const *dst, const size_t *dst_cap,
                                      size_t *out_sizes) {
-  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, quality, use_ycbcr, dst, dst_cap,
-                      out_sizes, nullptr);
+  const HostEncReq rq = {kEncPlain, quality};
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_sizes);
 }
 
 extern "C" int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
@@ -1829,11 +1807,8 @@ extern "C" int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *co
                                             const size_t *dst_cap, size_t *out_sizes, int *qualities) {
   if (!ctx || !budgets || !qualities || n < 0) return HIMG_ERR_ARG;
   for (int i = 0; i < n; ++i) qualities[i] = -1;
-  if (himg_hip_budget_probes(qmin, qmax) < 0)
-    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  const HostBudget bud = {qmin, qmax, budgets, qualities};
-  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, 0, use_ycbcr, dst, dst_cap, out_sizes,
-                      &bud);
+  const HostEncReq rq = {kEncBudget, 0, qmin, qmax, budgets, nullptr, qualities, nullptr};
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_sizes);
 }
 
 extern "C" int himg_hip_encode_target_batch(himg_hip_ctx *ctx, const uint8_t *const *frames, int n, int width,
@@ -1842,13 +1817,8 @@ extern "C" int himg_hip_encode_target_batch(himg_hip_ctx *ctx, const uint8_t *co
                                             const size_t *dst_cap, size_t *out_sizes, int *qualities, uint64_t *sses) {
   if (!ctx || !max_sse || !qualities || !sses || n < 0) return HIMG_ERR_ARG;
   for (int i = 0; i < n; ++i) { qualities[i] = -1; sses[i] = 0; }
-  if (himg_hip_budget_probes(qmin, qmax) < 0)
-    return fail(ctx, HIMG_ERR_ARG, "the quality range must satisfy 0 <= qmin <= qmax <= 100");
-  HostBudget bud = {qmin, qmax, nullptr, qualities};
-  bud.max_sse = max_sse;
-  bud.sses = sses;
-  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, 0, use_ycbcr, dst, dst_cap, out_sizes,
-                      &bud);
+  const HostEncReq rq = {kEncTarget, 0, qmin, qmax, nullptr, max_sse, qualities, sses};
+  return encode_batch(ctx, frames, n, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_sizes);
 }
 
 extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *packed,
@@ -1868,7 +1838,7 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
     const int slot = j & 1;
     if (launched[j]) {
       HIP_TRY(ctx, hipEventSynchronize(p.ev_k[slot]));
-      const int32_t st = (int32_t)p.h_meta[slot * 4 + 1];
+      const int32_t st = p.h_meta->res[slot].status;
       int err = HIMG_OK;
       if (st) {
         err = status_error(ctx, st);
@@ -1898,12 +1868,11 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
       HIP_TRY(ctx, hipMemcpyAsync(p.in[slot].p, packed[i], packed_sizes[i], hipMemcpyHostToDevice, p.s_in));
       HIP_TRY(ctx, hipEventRecord(p.ev_in[slot], p.s_in));
       HIP_TRY(ctx, hipStreamWaitEvent(p.s_comp, p.ev_in[slot], 0));
-      p.h_meta[8 + slot] = (uint32_t)packed_sizes[i];   // pinned: stays valid until the copy has run
-      rc = himg_hip_decode_device(ctx, p.in[slot].p, in_cap, p.h_meta + 8 + slot, 1, W, H, C, p.out[slot].p,
-                                  (int32_t *)p.meta[slot].p + 1, p.s_comp);
+      p.h_meta->dec_size[slot] = (uint32_t)packed_sizes[i];   // pinned: stays valid until the copy has run
+      rc = himg_hip_decode_device(ctx, p.in[slot].p, in_cap, &p.h_meta->dec_size[slot], 1, W, H, C, p.out[slot].p,
+                                  &((HostResult *)p.meta[slot].p)->status, p.s_comp);
       if (rc) return rc;
-      HIP_TRY(ctx, hipMemcpyAsync(p.h_meta + slot * 4, p.meta[slot].p, 8, hipMemcpyDeviceToHost, p.s_comp));
-      HIP_TRY(ctx, hipEventRecord(p.ev_k[slot], p.s_comp));
+      if ((rc = pipe_fetch_result(ctx, slot))) return rc;
       widths[i] = W; heights[i] = H; channels[i] = C;
       launched[i] = 1;
     }

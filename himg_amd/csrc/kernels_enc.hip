@@ -2155,102 +2155,38 @@ __global__ __launch_bounds__(256) void k_sizes_only(Geom g, EncWs ws, StaticChun
 }
 
 // ---------------------------------------------------------------------------
-// k_budget_step: the search of himg_hip_encode_budget_device between two size probes, one lane per
-// frame.  Probe 0 was at qmin, probe 1 at qmax, every later one at the midpoint the step before
-// chose; sizes[f] / ws.status[f] are the probe's.  A settled frame's quality stays where it is (its
-// later probes repeat), so that behind the last step quality[f] is what the final encode takes.
+// k_search_step: the quality searches of himg_hip_encode_budget_device / _target_device between two
+// probes, one lane per frame: search_step (search_step.h) on the frame's state, with the probe's
+// status in probe_status[f] and its value in values[f] (V: 32-bit sizes or 64-bit sums).  A settled
+// frame's quality stays where it is (its later probes repeat), so that behind the last step
+// quality[f] is what the final encode takes.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_budget_step(BudgetState bs, const int32_t *probe_status, const uint32_t *sizes,
-                                                    int batch, int probe, int last, int qmin, int qmax,
+template <typename V>
+__global__ __launch_bounds__(64) void k_search_step(SearchState ss, const int32_t *probe_status, const V *values,
+                                                    int batch, int probe, int last, int dir, int qmin, int qmax,
                                                     int32_t *d_quality) {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= batch) return;
-  int state = probe == 0 ? (int)kBudgetSearch : bs.state[f];
-  int lo = probe == 0 ? qmin : bs.lo[f], hi = probe == 0 ? qmax : bs.hi[f];
-  int err = probe == 0 ? 0 : bs.err[f];
-  if (state == kBudgetSearch) {
-    const int32_t st = probe_status[f];
-    const bool fit = sizes[f] <= bs.budget[f];
-    if (st != 0) { state = kBudgetError; err = st; }
-    else if (probe == 0) {
-      if (!fit) state = kBudgetTooSmall;
-      else if (qmax == qmin) state = kBudgetFound;
-    } else if (probe == 1) {
-      if (fit) { lo = qmax; state = kBudgetFound; }
-    } else {
-      const int mid = (lo + hi) >> 1;   // (what this probe was at)
-      if (fit) lo = mid; else hi = mid;
-    }
-    if (state == kBudgetSearch && probe >= 1 && hi - lo <= 1) state = kBudgetFound;
-  }
-  const bool found = state == kBudgetFound;
-  // The next probe: qmax behind the first, then the midpoint; a settled frame: its result (qmin without one).
-  bs.quality[f] = state == kBudgetSearch ? (probe == 0 ? qmax : (lo + hi) >> 1) : (found ? lo : qmin);
-  bs.lo[f] = lo; bs.hi[f] = hi; bs.state[f] = state; bs.err[f] = err;
-  if (last) d_quality[f] = found ? lo : -1;
+  SearchFrame s;
+  s.limit = ss.limit[f];
+  if (probe != 0) { s.best = ss.best[f]; s.ok = ss.ok[f]; s.bad = ss.bad[f]; s.state = ss.state[f]; s.err = ss.err[f]; }
+  search_step(s, probe, dir, qmin, qmax, probe_status[f], (uint64_t)values[f]);
+  ss.quality[f] = s.quality;
+  ss.best[f] = s.best; ss.ok[f] = s.ok; ss.bad[f] = s.bad; ss.state[f] = s.state; ss.err[f] = s.err;
+  if (last) d_quality[f] = search_result(s);
 }
 
 // Behind the final encode: a frame without a result keeps the search's verdict, whatever its
-// encode at qmin said; the others get the encode's own status.
-__global__ __launch_bounds__(64) void k_budget_finish(BudgetState bs, const int32_t *enc_status, int batch,
-                                                      uint32_t *sizes, int32_t *d_status) {
-  const int f = blockIdx.x * 64 + threadIdx.x;
-  if (f >= batch) return;
-  const int state = bs.state[f];
-  if (state != kBudgetFound) sizes[f] = 0;
-  if (d_status) d_status[f] = state == kBudgetFound ? enc_status[f] : state == kBudgetTooSmall ? -5 /* HIMG_ERR_CAPACITY */ : bs.err[f];
-}
-
-// ---------------------------------------------------------------------------
-// k_target_step: the search of himg_hip_encode_target_device between two distortion probes --
-// k_budget_step with the comparison and the roles of lo and hi turned round.  Probe 0 was at qmax,
-// probe 1 at qmin, every later one at the midpoint the step before chose; ts.probe_sse[f] /
-// probe_status[f] are the probe's.  best_sse[f] follows hi: the distortion at the quality that the
-// search would return now.  (The states are the budget's; kBudgetTooSmall: sse(qmax) misses the target.)
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_target_step(TargetState ts, const int32_t *probe_status, int batch, int probe,
-                                                    int last, int qmin, int qmax, int32_t *d_quality) {
-  const int f = blockIdx.x * 64 + threadIdx.x;
-  if (f >= batch) return;
-  int state = probe == 0 ? (int)kBudgetSearch : ts.state[f];
-  int lo = probe == 0 ? qmin : ts.lo[f], hi = probe == 0 ? qmax : ts.hi[f];
-  int err = probe == 0 ? 0 : ts.err[f];
-  unsigned long long best = probe == 0 ? 0ull : ts.best_sse[f];
-  if (state == kBudgetSearch) {
-    const int32_t st = probe_status[f];
-    const unsigned long long sse = ts.probe_sse[f];
-    const bool meets = sse <= ts.target[f];
-    if (st != 0) { state = kBudgetError; err = st; }
-    else if (probe == 0) {
-      best = sse;
-      if (!meets) state = kBudgetTooSmall;
-      else if (qmax == qmin) state = kBudgetFound;
-    } else if (probe == 1) {
-      if (meets) { hi = qmin; best = sse; state = kBudgetFound; }
-    } else {
-      const int mid = (lo + hi) >> 1;   // (what this probe was at)
-      if (meets) { hi = mid; best = sse; } else lo = mid;
-    }
-    if (state == kBudgetSearch && probe >= 1 && hi - lo <= 1) state = kBudgetFound;
-  }
-  const bool found = state == kBudgetFound;
-  // The next probe: qmin behind the first, then the midpoint; a settled frame: its result (qmin without one).
-  ts.quality[f] = state == kBudgetSearch ? (probe == 0 ? qmin : (lo + hi) >> 1) : (found ? hi : qmin);
-  ts.lo[f] = lo; ts.hi[f] = hi; ts.state[f] = state; ts.err[f] = err; ts.best_sse[f] = best;
-  if (last) d_quality[f] = found ? hi : -1;
-}
-
-// Behind the final encode: a frame without a result keeps the search's verdict, whatever its
-// encode at qmin said; the others get the encode's own status.  d_sse[f]: the distortion at the
-// chosen quality (a frame that misses its target: at qmax).
-__global__ __launch_bounds__(64) void k_target_finish(TargetState ts, const int32_t *enc_status, int batch,
+// encode at qmin said; the others get the encode's own status.  d_sse[f] (when asked for): the value
+// at the chosen quality (a frame that misses its limit: at the first probe's).
+__global__ __launch_bounds__(64) void k_search_finish(SearchState ss, const int32_t *enc_status, int batch, int miss_code,
                                                       uint32_t *sizes, unsigned long long *d_sse, int32_t *d_status) {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= batch) return;
-  const int state = ts.state[f];
-  if (state != kBudgetFound) sizes[f] = 0;
-  d_sse[f] = state == kBudgetError ? 0ull : ts.best_sse[f];
-  if (d_status) d_status[f] = state == kBudgetFound ? enc_status[f] : state == kBudgetTooSmall ? -6 /* HIMG_ERR_TARGET */ : ts.err[f];
+  const int state = ss.state[f];
+  if (state != kSearchFound) sizes[f] = 0;
+  if (d_sse) d_sse[f] = state == kSearchError ? 0ull : ss.best[f];
+  if (d_status) d_status[f] = state == kSearchFound ? enc_status[f] : state == kSearchMissed ? miss_code : ss.err[f];
 }
 
 // ---------------------------------------------------------------------------
@@ -3287,24 +3223,16 @@ void enc_fill_qual_tab(const StaticChunks &sc, const ShiftTables &st, const Lres
   memcpy(qt->qcfg, sc.mid + 8, sizeof(qt->qcfg));   // (built with the chroma table: 64 bytes)
 }
 
-void launch_budget_step(const BudgetState &bs, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
-                        const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof) {
-  HIMG_LAUNCH(k_budget_step, dim3((batch + 63) / 64), dim3(64), bs, ws.status, d_sizes, batch, probe,
-              probe == probes - 1 ? 1 : 0, qmin, qmax, d_quality);
+void launch_search_step(const SearchState &ss, const EncWs &ws, int batch, int probe, int probes, int dir, int qmin,
+                        int qmax, const uint32_t *d_sizes, int32_t *d_quality, hipStream_t stream, Profiler *prof) {
+  const dim3 grid((batch + 63) / 64), block(64);
+  const int last = probe == probes - 1 ? 1 : 0;
+  if (d_sizes) HIMG_LAUNCH(k_search_step<uint32_t>, grid, block, ss, ws.status, d_sizes, batch, probe, last, dir, qmin, qmax, d_quality);
+  else HIMG_LAUNCH(k_search_step<uint64_t>, grid, block, ss, ws.status, (const uint64_t *)ss.value, batch, probe, last, dir, qmin, qmax, d_quality);
 }
-void launch_budget_finish(const BudgetState &bs, const EncWs &ws, int batch, uint32_t *d_sizes, int32_t *d_status,
-                          hipStream_t stream, Profiler *prof) {
-  HIMG_LAUNCH(k_budget_finish, dim3((batch + 63) / 64), dim3(64), bs, ws.status, batch, d_sizes, d_status);
-}
-
-void launch_target_step(const TargetState &ts, const EncWs &ws, int batch, int probe, int probes, int qmin, int qmax,
-                        int32_t *d_quality, hipStream_t stream, Profiler *prof) {
-  HIMG_LAUNCH(k_target_step, dim3((batch + 63) / 64), dim3(64), ts, ws.status, batch, probe,
-              probe == probes - 1 ? 1 : 0, qmin, qmax, d_quality);
-}
-void launch_target_finish(const TargetState &ts, const EncWs &ws, int batch, uint32_t *d_sizes, uint64_t *d_sse,
-                          int32_t *d_status, hipStream_t stream, Profiler *prof) {
-  HIMG_LAUNCH(k_target_finish, dim3((batch + 63) / 64), dim3(64), ts, ws.status, batch, d_sizes,
+void launch_search_finish(const SearchState &ss, const EncWs &ws, int batch, int miss_code, uint32_t *d_sizes,
+                          uint64_t *d_sse, int32_t *d_status, hipStream_t stream, Profiler *prof) {
+  HIMG_LAUNCH(k_search_finish, dim3((batch + 63) / 64), dim3(64), ss, ws.status, batch, miss_code, d_sizes,
               (unsigned long long *)d_sse, d_status);
 }
 
