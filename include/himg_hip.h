@@ -32,6 +32,9 @@ extern "C" {
 #define HIMG_ERR_FORMAT (-4)      /* decode: the reference would return false */
 #define HIMG_ERR_CAPACITY (-5)    /* output buffer too small */
 #define HIMG_ERR_TARGET (-6)      /* encode to a distortion target: not reached at the highest quality */
+/* One deviation from the reference decoder: a Huffman tree (LRES or FRES) with a leaf more than 32
+ * branches below the root is answered with HIMG_ERR_UNSUPPORTED by every decode entry point.  The
+ * reference decodes such a stream; its encoder cannot write one (it keeps codes in 32 bits). */
 
 typedef struct himg_hip_ctx himg_hip_ctx;
 
