@@ -91,6 +91,9 @@ def lib():
     L.himg_hip_encode_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
     L.himg_hip_decode_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_encode_device_q.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp]
+    L.himg_hip_windows_extent.argtypes = [vp, i32, i32, vp, i32, i32, P(sz)]
+    L.himg_hip_encode_windows_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp, vp, vp]
+    L.himg_hip_encode_window_to.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, P(sz)]
     L.himg_hip_encode_sizes_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp]
     L.himg_hip_budget_probes.argtypes = [i32, i32]
     L.himg_hip_encode_budget_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp, vp, vp, vp]
@@ -338,6 +341,21 @@ class Engine:
         array of exactly its size (no intermediate copies)."""
         return self._encode_to(lib().himg_hip_encode_to, "encode", img, channels, pixel_stride,
                                (quality, 1 if use_ycbcr else 0))[0]
+
+    def encode_window(self, data, src, x, y, w, h, quality=50, use_ycbcr=True, channels=None):
+        """himg_hip_encode_window_to + himg_hip_fetch_last: the stream of the window (x, y, w, h) of the
+        host picture `data` (uint8, laid out as `src` says: src_desc; channels: pixel_stride where not
+        given).  Only the rows the window lies in are uploaded."""
+        data = _as_u8(data)
+        ch = src.pixel_stride if channels is None else channels
+        n = C.c_size_t()
+        rc = lib().himg_hip_encode_window_to(self._ctx, data.ctypes.data, C.byref(src), ch, int(x), int(y), int(w),
+                                             int(h), quality, 1 if use_ycbcr else 0, None, 0, C.byref(n))
+        if rc != HIMG_ERR_CAPACITY or n.value == 0:
+            self._check(rc if rc != HIMG_OK else HIMG_ERR_ARG, "encode_window")
+        out = np.empty(n.value, np.uint8)
+        self._check(lib().himg_hip_fetch_last(self._ctx, out.ctypes.data, out.nbytes, C.byref(n)), "encode_window")
+        return out
 
     def decode(self, packed, out=None):
         """himg_hip_peek + himg_hip_decode_to straight into `out` (reused when it has
@@ -641,6 +659,19 @@ class Engine:
                                             q.ctypes.data, 1 if use_ycbcr else 0, _ptr(d_out), out_stride,
                                             _ptr(d_sizes), _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "encode_device_q")
+
+    def encode_windows_device(self, d_src, src, batch, channels, origins, w, h, qualities, use_ycbcr, d_out,
+                              out_stride, d_sizes, d_status, stream=0):
+        """himg_hip_encode_windows_device: encode_device_q of the w x h window at origin (x_f, y_f) =
+        origins[f] of source picture f of `src` (src_desc; frame_pitch 0: every window of one picture).
+        origins: (batch, 2) int32 and qualities: `batch` values, both on the host."""
+        q = np.ascontiguousarray(np.asarray(qualities, np.int32).reshape(batch))
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_encode_windows_device(self._ctx, _ptr(d_src), C.byref(src), batch, channels,
+                                                  org.ctypes.data, int(w), int(h), q.ctypes.data,
+                                                  1 if use_ycbcr else 0, _ptr(d_out), out_stride, _ptr(d_sizes),
+                                                  _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "encode_windows_device")
 
     def encode_sizes_device(self, d_frames, batch, width, height, pixel_stride, channels, qualities,
                             use_ycbcr, d_sizes, d_status, stream=0):
@@ -1004,6 +1035,37 @@ def tensor_bytes(desc, channels, w, h):
     rc = lib().himg_hip_tensor_bytes(C.byref(desc), int(channels), int(w), int(h), C.byref(n))
     if rc != 0:
         raise HimgError(rc, "tensor_bytes")
+    return n.value
+
+
+class SrcDesc(C.Structure):
+    """himg_hip_src."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pixel_stride", C.c_int), ("row_pitch", C.c_size_t),
+                ("frame_pitch", C.c_size_t)]
+
+
+def src_desc(width, height, pixel_stride, row_pitch=None, frame_pitch=None):
+    """A himg_hip_src: pictures of width x height pixels, pixel_stride bytes per pixel, rows row_pitch
+    bytes apart (default: packed) and pictures frame_pitch bytes apart (default: height * row_pitch;
+    0: every window of a call reads ONE picture).  The library validates it (windows_extent, the
+    encode calls)."""
+    d = SrcDesc()
+    d.width, d.height, d.pixel_stride = int(width), int(height), int(pixel_stride)
+    d.row_pitch = int(width) * int(pixel_stride) if row_pitch is None else int(row_pitch)
+    d.frame_pitch = int(height) * d.row_pitch if frame_pitch is None else int(frame_pitch)
+    return d
+
+
+def windows_extent(src, channels, origins, w, h):
+    """himg_hip_windows_extent (no GPU): the bytes of the source buffer that the w x h windows at
+    `origins` ((batch, 2): x_f, y_f) of `src` reach -- nothing at or beyond is read.  Raises HimgError
+    (HIMG_ERR_ARG) for a descriptor or a window that encode_windows_device rejects."""
+    org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+    n = C.c_size_t()
+    rc = lib().himg_hip_windows_extent(C.byref(src), int(channels), len(org), org.ctypes.data, int(w), int(h),
+                                       C.byref(n))
+    if rc != 0:
+        raise HimgError(rc, "windows_extent")
     return n.value
 
 

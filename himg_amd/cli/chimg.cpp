@@ -7,7 +7,11 @@
 // Beyond the reference: "-b <bytes>" encodes to a byte budget through the C ABI
 // (himg_hip_encode_budget_to, qualities 0 .. the -q value, 100 without one) and prints
 // the quality it chose; "-p <dB>" encodes to a quality floor (himg_hip_encode_target_to with
-// himg_hip_psnr_to_sse's target) and prints the chosen quality and the PSNR reached.
+// himg_hip_psnr_to_sse's target) and prints the chosen quality and the PSNR reached;
+// "-r x,y,w,h" (the spelling of dhimg -r) encodes only that rectangle (himg_hip_encode_window_to: only
+// its rows are uploaded).  As there, the rectangle is in the coordinates of the picture as the codec
+// sees it (row 0 = the first coded row, the picture's bottom scanline): dhimg -r of the whole file
+// and dhimg of the -r file show the same pixels.  A malformed rectangle is a bad argument (usage).
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +31,8 @@ struct Request {
   bool have_quality = false;
   long long budget = -1;   // -b: at most this many bytes (-1: not given)
   double psnr = -1.0;      // -p: at least this many dB (-1: not given)
+  bool region = false;     // -r: only this rectangle
+  int rx = 0, ry = 0, rw = 0, rh = 0;
   const char *input = nullptr;
   const char *output = nullptr;
 };
@@ -83,6 +89,14 @@ bool parse(int argc, const char **argv, Request *rq) {
         return false;
       }
       rq->psnr = v;
+    } else if (!strcmp(a, "-r")) {
+      if (++i >= argc) return false;
+      char tail = 0;
+      if (sscanf(argv[i], "%d,%d,%d,%d%c", &rq->rx, &rq->ry, &rq->rw, &rq->rh, &tail) != 4) {
+        printf("Invalid rectangle: %s\n", argv[i]);
+        return false;
+      }
+      rq->region = true;
     } else {
       printf("Invalid option: %s\n", a);
       return false;
@@ -90,6 +104,10 @@ bool parse(int argc, const char **argv, Request *rq) {
   }
   if (rq->budget >= 0 && rq->psnr >= 0.0) {
     printf("-b and -p exclude each other\n");
+    return false;
+  }
+  if (rq->region && (rq->budget >= 0 || rq->psnr >= 0.0)) {
+    printf("-r excludes -b and -p\n");
     return false;
   }
   return nfiles == 2;
@@ -105,7 +123,8 @@ int main(int argc, const char **argv) {
            " -q <quality> Set the quality (0-100)\n"
            " -rgb         Use RGB color space (instead of YCbCr)\n"
            " -b <bytes>   Fit the file into a byte budget (-q: the highest quality to try)\n"
-           " -p <dB>      Reach at least this PSNR in as few bytes as the search finds (-q: as for -b)\n",
+           " -p <dB>      Reach at least this PSNR in as few bytes as the search finds (-q: as for -b)\n"
+           " -r x,y,w,h   Compress only this rectangle (row 0: the first coded row, as dhimg -r)\n",
            argv[0]);
     return 0;
   }
@@ -176,6 +195,31 @@ int main(int argc, const char **argv) {
       return -1;
     }
     printf("Quality: %d\n", quality);
+    printf("Compressed size: %d\n", static_cast<int>(n));
+    FILE *f = fopen(rq.output, "wb");
+    const bool ok = f && fwrite(packed.data(), 1, n, f) == n;
+    if (f) fclose(f);
+    return ok ? 0 : -1;
+  }
+
+  if (rq.region) {
+    himg_hip_ctx *ctx = nullptr;
+    const himg_hip_src src = {picture.width, picture.height, c, (size_t)picture.width * c, 0};
+    std::vector<uint8_t> packed(rq.rw > 0 && rq.rh > 0 ? himg_hip_max_packed_size(rq.rw, rq.rh, c) : 0);
+    size_t n = 0;
+    int rc = himg_hip_create(0, &ctx);
+    if (rc == HIMG_OK)
+      rc = himg_hip_encode_window_to(ctx, pixels.data(), &src, c, rq.rx, rq.ry, rq.rw, rq.rh, rq.quality,
+                                     rq.ycbcr ? 1 : 0, packed.data(), packed.size(), &n);
+    himg_hip_destroy(ctx);
+    if (rc == HIMG_ERR_ARG) {
+      fprintf(stderr, "The rectangle %d,%d,%d,%d does not lie inside %s\n", rq.rx, rq.ry, rq.rw, rq.rh, rq.input);
+      return -1;
+    }
+    if (rc != HIMG_OK) {
+      fprintf(stderr, "Unable to encode %s\n", rq.input);
+      return -1;
+    }
     printf("Compressed size: %d\n", static_cast<int>(n));
     FILE *f = fopen(rq.output, "wb");
     const bool ok = f && fwrite(packed.data(), 1, n, f) == n;

@@ -140,6 +140,15 @@ struct QualSel {
   const int32_t *quality;   // [frame], each in [0, 100]
 };
 
+// A window per frame of pitched source pictures (himg_hip_encode_windows_device): frame f of the
+// launch is the w x h picture (Geom::W, H) whose first pixel is at
+// base + f * frame_pitch + y_f * row_pitch + x_f * Geom::stride, its rows row_pitch bytes apart.
+struct WinSrc {
+  const uint8_t *base;
+  size_t row_pitch, frame_pitch;   // frame_pitch 0: every window of one picture
+  const int32_t *org;              // [frame][x_f, y_f], on the device, checked by the host
+};
+
 // ---- decoder ---------------------------------------------------------------
 
 constexpr int kLutBits = 11;  // width of the Huffman decode group table
@@ -251,6 +260,12 @@ void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d
                      const StaticChunks &sc, const QualSel &qs,
                      const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
                      hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
+// launch_encode_q with frame f read from its window of src (g: the windows' geometry).
+void launch_encode_windows(const Geom &g, const EncWs &ws, int batch, const WinSrc &src,
+                           uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                           const StaticChunks &sc, const QualSel &qs,
+                           const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                           hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join);
 // The quality searches of himg_hip_encode_budget_device and himg_hip_encode_target_device, per frame on
 // the device: a SearchFrame (search_step.h) per frame, one array per field.
 struct SearchState {

@@ -947,6 +947,67 @@ extern "C" int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frame
                          nullptr, 0, nullptr, d_sse, d_status, stream);
 }
 
+// ---- windows of pitched source pictures -------------------------------------------------------
+
+// The host checks of a source descriptor and its windows (include/himg_hip.h); *bytes: the end of the
+// last byte a window owns.  Returns what is wrong, or nullptr.
+static const char *windows_check(const himg_hip_src *src, int num_channels, int batch, const int32_t *h_origins, int w,
+                                 int h, size_t *bytes) {
+  if (!src || !h_origins || batch < 1) return "bad argument";
+  if (src->width < 1 || src->height < 1 || w < 1 || h < 1) return "a source or window size that is not positive";
+  if (num_channels < 1 || num_channels > 4 || src->pixel_stride < num_channels) return "pixel_stride below num_channels";
+  typedef unsigned __int128 u128;
+  const u128 ps = (u128)src->pixel_stride, rp = src->row_pitch, fp = src->frame_pitch;
+  if (rp < (u128)src->width * ps) return "row_pitch below width * pixel_stride";
+  if (fp != 0 && fp < (u128)(src->height - 1) * rp + (u128)src->width * ps) return "frame_pitch neither 0 nor a whole picture";
+  if (src->pixel_stride == 4 && ((src->row_pitch | src->frame_pitch) & 3))
+    return "row_pitch and frame_pitch must be multiples of 4 for 4-byte pixels";
+  u128 end = 0;
+  for (int f = 0; f < batch; ++f) {
+    const int x = h_origins[2 * f], y = h_origins[2 * f + 1];
+    if (x < 0 || y < 0 || w > src->width - x || h > src->height - y) return "a window outside the source picture";
+    const u128 e = (u128)f * fp + (u128)(y + h - 1) * rp + (u128)(x + w) * ps;
+    if (e > end) end = e;
+  }
+  if (end > (u128)SIZE_MAX) return "a source that does not fit the address space";
+  *bytes = (size_t)end;
+  return nullptr;
+}
+
+extern "C" int himg_hip_windows_extent(const himg_hip_src *src, int num_channels, int batch, const int32_t *h_origins,
+                                       int w, int h, size_t *bytes) {
+  if (!bytes) return HIMG_ERR_ARG;
+  *bytes = 0;
+  return windows_check(src, num_channels, batch, h_origins, w, h, bytes) ? HIMG_ERR_ARG : HIMG_OK;
+}
+
+extern "C" int himg_hip_encode_windows_device(himg_hip_ctx *ctx, const void *d_src, const himg_hip_src *src, int batch,
+                                              int num_channels, const int32_t *h_origins, int w, int h,
+                                              const int32_t *h_quality, int use_ycbcr, void *d_out, size_t out_stride,
+                                              uint32_t *d_sizes, int32_t *d_status, void *stream) {
+  if (!ctx || !d_sizes) return HIMG_ERR_ARG;
+  size_t extent = 0;
+  if (const char *bad = windows_check(src, num_channels, batch, h_origins, w, h, &extent)) return fail(ctx, HIMG_ERR_ARG, bad);
+  if (!qualities_ok(h_quality, batch)) return fail(ctx, HIMG_ERR_ARG, "a quality outside [0, 100]");
+  // The workspace and every kernel behind the four that read pixels belong to the WINDOW's geometry.
+  Enc e;
+  int rc = enc_q_begin(ctx, d_src, batch, w, h, src->pixel_stride, num_channels, use_ycbcr, true, d_out, out_stride, false,
+                       stream, &e);
+  if (rc) return rc;
+  // The qualities and the origins in one copy: SearchState's first two arrays (a frame's 64-bit limit
+  // is the room of its two origin words; no search runs here).
+  const size_t org_at = (size_t)((int32_t *)e.ss.limit - e.ss.quality);
+  std::vector<int32_t> w0(org_at + 2 * (size_t)batch, 0);
+  memcpy(w0.data(), h_quality, (size_t)batch * 4);
+  memcpy(w0.data() + org_at, h_origins, (size_t)batch * 8);
+  if ((rc = stage_words(ctx, e.ss.quality, w0.data(), w0.size(), nullptr, 0, e.s))) return rc;
+  const himg_dev::WinSrc ws = {(const uint8_t *)d_src, src->row_pitch, src->frame_pitch, (const int32_t *)e.ss.limit};
+  himg_dev::launch_encode_windows(e.g, ctx->enc_ws, batch, ws, (uint8_t *)d_out, out_stride, d_sizes, e.sc, e.qs,
+                                  (const uint8_t *)ctx->fmap_lut.p, e.s, &ctx->prof,
+                                  ctx->opts.use_side ? ctx->side_enc : nullptr, ctx->ev_fork_e, ctx->ev_join_e);
+  return enc_end(ctx, e, batch, d_status);
+}
+
 extern "C" int himg_hip_budget_probes(int qmin, int qmax) {
   if (qmin < 0 || qmax > 100 || qmin > qmax) return HIMG_ERR_ARG;
   if (qmin == qmax) return 1;
@@ -1423,7 +1484,7 @@ extern "C" int himg_hip_index_host(const uint8_t *packed, size_t packed_size, in
 // entry points differ only in where they copy them to.
 
 // What a host encode form asks for, for each of its frames.
-enum HostEncKind { kEncPlain, kEncBudget, kEncTarget };
+enum HostEncKind { kEncPlain, kEncBudget, kEncTarget, kEncWindow };
 struct HostEncReq {
   HostEncKind kind;
   int quality;               // kEncPlain
@@ -1432,6 +1493,8 @@ struct HostEncReq {
   const uint64_t *max_sse;   // kEncTarget  (-1 for a frame that misses its target at qmax)
   int *qualities;
   uint64_t *sses;            // kEncTarget: where the sse reached goes
+  const himg_hip_src *src;   // kEncWindow (with `quality`): the host picture, and the window's origin in it --
+  int x, y;                  // the width and height of the call are the window's
 };
 static bool req_range_ok(himg_hip_ctx *ctx, const HostEncReq &rq) {
   if (himg_hip_budget_probes(rq.qmin, rq.qmax) >= 0) return true;
@@ -1452,6 +1515,13 @@ static int encode_request_device(himg_hip_ctx *ctx, const HostEncReq &rq, int i,
       return himg_hip_encode_target_device(ctx, d_in, 1, width, height, pixel_stride, num_channels, rq.qmin, rq.qmax,
                                            use_ycbcr, rq.max_sse + i, d_out, cap, &d_res->size, &d_res->quality,
                                            &d_res->sse, &d_res->status, s);
+    case kEncWindow: {
+      // (d_in: the source's rows [y, y + height), so the window begins in its first row)
+      const himg_hip_src rows = {rq.src->width, height, pixel_stride, rq.src->row_pitch, 0};
+      const int32_t org[2] = {rq.x, 0};
+      return himg_hip_encode_windows_device(ctx, d_in, &rows, 1, num_channels, org, width, height, &rq.quality, use_ycbcr,
+                                            d_out, cap, &d_res->size, &d_res->status, s);
+    }
     default:
       return himg_hip_encode_device(ctx, d_in, 1, width, height, pixel_stride, num_channels, rq.quality, use_ycbcr, d_out,
                                     cap, &d_res->size, &d_res->status, s);
@@ -1459,7 +1529,7 @@ static int encode_request_device(himg_hip_ctx *ctx, const HostEncReq &rq, int i,
 }
 // Frame i's results to where the request wants them, and its status as the host API reports it.
 static int encode_verdict(himg_hip_ctx *ctx, const HostEncReq &rq, int i, const HostResult &r) {
-  if (rq.kind != kEncPlain) rq.qualities[i] = r.quality;
+  if (rq.kind == kEncBudget || rq.kind == kEncTarget) rq.qualities[i] = r.quality;
   if (rq.kind == kEncTarget) rq.sses[i] = r.sse;
   if (rq.kind == kEncTarget && r.status == HIMG_ERR_TARGET)
     return fail(ctx, HIMG_ERR_TARGET, "the distortion at qmax is above the target");
@@ -1476,11 +1546,22 @@ static int encode_core(himg_hip_ctx *ctx, const uint8_t *data, int width, int he
     return fail(ctx, HIMG_ERR_ARG, "bad geometry");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t cap = himg_hip_max_packed_size(width, height, num_channels);
-  if (!ctx->h_in.reserve(round_up((size_t)g.frame_bytes, 256)) || !ctx->h_out.reserve(cap) ||
+  // What goes up: the frame; of a window's source the rows it lies in, up to its last pixel.
+  size_t in_bytes = (size_t)g.frame_bytes;
+  if (rq.kind == kEncWindow) {
+    himg_hip_src one = *rq.src;
+    one.frame_pitch = 0;   // (one picture: the descriptor's is ignored)
+    const int32_t org[2] = {rq.x, rq.y};
+    size_t end = 0;
+    if (const char *bad = windows_check(&one, num_channels, 1, org, width, height, &end)) return fail(ctx, HIMG_ERR_ARG, bad);
+    data += (size_t)rq.y * rq.src->row_pitch;
+    in_bytes = end - (size_t)rq.y * rq.src->row_pitch;
+  }
+  if (!ctx->h_in.reserve(round_up(in_bytes, 256)) || !ctx->h_out.reserve(cap) ||
       !ctx->h_result.reserve(256))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   ctx->host_bytes = 0;
-  HIP_TRY(ctx, hipMemcpy(ctx->h_in.p, data, (size_t)g.frame_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(ctx->h_in.p, data, in_bytes, hipMemcpyHostToDevice));
   int rc = encode_request_device(ctx, rq, 0, ctx->h_in.p, width, height, pixel_stride, num_channels, use_ycbcr,
                                  ctx->h_out.p, cap, (HostResult *)ctx->h_result.p, nullptr);
   if (rc) return rc;
@@ -1513,7 +1594,7 @@ extern "C" int himg_hip_encode(himg_hip_ctx *ctx, const uint8_t *data, int width
 // The `_to` forms: the encode, then the size, and the stream where dst has room for it.
 static int encode_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height, int pixel_stride, int num_channels,
                      int use_ycbcr, const HostEncReq &rq, uint8_t *dst, size_t dst_cap, size_t *out_size) {
-  if (rq.kind != kEncPlain && !req_range_ok(ctx, rq)) return HIMG_ERR_ARG;
+  if ((rq.kind == kEncBudget || rq.kind == kEncTarget) && !req_range_ok(ctx, rq)) return HIMG_ERR_ARG;
   uint32_t n = 0;
   const int rc = encode_core(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, &n);
   if (rc) return rc;
@@ -1530,6 +1611,16 @@ extern "C" int himg_hip_encode_to(himg_hip_ctx *ctx, const uint8_t *data, int wi
   *out_size = 0;
   const HostEncReq rq = {kEncPlain, quality};
   return encode_to(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
+}
+
+extern "C" int himg_hip_encode_window_to(himg_hip_ctx *ctx, const uint8_t *data, const himg_hip_src *src, int num_channels,
+                                         int x, int y, int w, int h, int quality, int use_ycbcr, uint8_t *dst,
+                                         size_t dst_cap, size_t *out_size) {
+  if (!ctx || !data || !out_size) return HIMG_ERR_ARG;
+  *out_size = 0;
+  if (!src) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  const HostEncReq rq = {kEncWindow, quality, 0, 0, nullptr, nullptr, nullptr, nullptr, src, x, y};
+  return encode_to(ctx, data, w, h, src->pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
 }
 
 extern "C" int himg_hip_encode_budget_to(himg_hip_ctx *ctx, const uint8_t *data, int width, int height,

@@ -75,54 +75,56 @@ __device__ __forceinline__ void load_pixel(const uint8_t *img, const Geom &g, in
   if (g.ycbcr) lift_fwd(ch[0], ch[1], ch[2]);
 }
 
+// The same with the picture's rows `pitch` bytes apart (the window source form).
+__device__ __forceinline__ void load_pixel(const uint8_t *img, const Geom &g, int x, int y, int ch[4], size_t pitch) {
+  const uint8_t *p = img + (size_t)y * pitch + (size_t)x * g.stride;
+  if (g.stride == 4 && g.C == 4) {
+    const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
+    ch[0] = w & 255; ch[1] = (w >> 8) & 255; ch[2] = (w >> 16) & 255; ch[3] = w >> 24;
+  } else {
+    ch[0] = p[0];
+    ch[1] = g.C > 1 ? p[1] : 0;
+    ch[2] = g.C > 2 ? p[2] : 0;
+    ch[3] = g.C > 3 ? p[3] : 0;
+  }
+  if (g.ycbcr) lift_fwd(ch[0], ch[1], ch[2]);
+}
+
+// The source forms of the four kernels that read pixels (k_lowres_avg, k_tile_fwd, k_pix_fwd, k_front):
+// packed frames behind a pointer, or a window per frame of pitched pictures (WinSrc; the `_w` kernels).
+// Each kernel has ONE body (enc_body_*.inc), compiled into both forms with kWin as a constant -- by
+// include, as k_lres_predict's: the packed forms keep their names and their instructions.
+// The picture of frame f: the window's first pixel in the window form -- the origin is two scalar
+// loads per workgroup (f is uniform), like the quality.
+__device__ __forceinline__ const uint8_t *frame_base(const uint8_t *frames, const Geom &g, int f) {
+  return frames + (long long)f * g.frame_bytes;
+}
+__device__ __forceinline__ const uint8_t *frame_base(const WinSrc &s, const Geom &g, int f) {
+  const uint32_t x = __builtin_amdgcn_readfirstlane(uniform_words(s.org)[2 * f]);
+  const uint32_t y = __builtin_amdgcn_readfirstlane(uniform_words(s.org)[2 * f + 1]);
+  return s.base + (size_t)f * s.frame_pitch + (size_t)y * s.row_pitch + (size_t)x * g.stride;
+}
+__device__ __forceinline__ size_t win_pitch(const WinSrc &s) { return s.row_pitch; }
+__device__ __forceinline__ size_t win_pitch(const uint8_t *) { return 0; }   // (never called: the discarded branch of a packed form)
+// Sixteen bytes of an RGBA8 tile row.  A packed frame's are 16-byte aligned; a window's lie wherever
+// its origin puts them, so the type promises pixel alignment only (still one 16-byte load on gfx950).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
+template <bool WIN> using SrcQuad = std::conditional_t<WIN, u32x4_a4, uint4>;
+
 // ---------------------------------------------------------------------------
 // k_lowres_avg: one thread per tile window.  Window x in [8u-3, 8u+4], y in
 // [8v-3, 8v+4], clipped to the image (downsampled.cpp:76-96).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lowres_avg(Geom g, const uint8_t *frames,
                                                     uint8_t *avg, size_t plane_stride, int v0) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  const int v = blockIdx.y + v0, f = blockIdx.z;
-  if (u >= g.cols) return;
-  const uint8_t *img = frames + (long long)f * g.frame_bytes;
-  const int x0 = max(0, 8 * u - 3), x1 = min(g.W - 1, 8 * u + 4);
-  const int y0 = max(0, 8 * v - 3), y1 = min(g.H - 1, 8 * v + 4);
-  int sum[4] = {0, 0, 0, 0};
-  if (g.stride == 4 && g.C == 4 && (g.W & 7) == 0) {
-    // Packed RGBA8: the window spans pixels 8u-3 .. 8u+4 = the last three of the
-    // 16-byte group before the tile, the tile's first group, and the first pixel
-    // of its second group -> three 16-byte loads per pixel row instead of eight
-    // 4-byte ones.
-    const bool has_left = u > 0;
-    for (int y = y0; y <= y1; ++y) {
-      const uint4 *rp = reinterpret_cast<const uint4 *>(img + ((long long)y * g.W + 8 * u) * 4);
-      const uint4 b = rp[0];
-      const uint32_t c0 = rp[1].x;
-      uint4 a;
-      a.x = a.y = a.z = a.w = 0;
-      if (has_left) a = rp[-1];
-      uint32_t px[8] = {a.y, a.z, a.w, b.x, b.y, b.z, b.w, c0};
-#pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        if (k < 3 && !has_left) continue;
-        int ch[4] = {(int)(px[k] & 255), (int)((px[k] >> 8) & 255), (int)((px[k] >> 16) & 255),
-                     (int)(px[k] >> 24)};
-        if (g.ycbcr) lift_fwd(ch[0], ch[1], ch[2]);
-        sum[0] += ch[0]; sum[1] += ch[1]; sum[2] += ch[2]; sum[3] += ch[3];
-      }
-    }
-  } else {
-    for (int y = y0; y <= y1; ++y)
-      for (int x = x0; x <= x1; ++x) {
-        int ch[4];
-        load_pixel(img, g, x, y, ch);
-        sum[0] += ch[0]; sum[1] += ch[1]; sum[2] += ch[2]; sum[3] += ch[3];
-      }
-  }
-  const int cnt = (x1 - x0 + 1) * (y1 - y0 + 1);
-  uint8_t *a = avg + (size_t)f * plane_stride;
-  for (int c = 0; c < g.C; ++c)
-    a[((size_t)c * g.rows + v) * g.cols + u] = (uint8_t)((sum[c] + (cnt >> 1)) / cnt);
+  constexpr bool kWin = false;
+#include "enc_body_lowres_avg.inc"
+}
+__global__ __launch_bounds__(256) void k_lowres_avg_w(Geom g, WinSrc frames,
+                                                      uint8_t *avg, size_t plane_stride, int v0) {
+  constexpr bool kWin = true;
+#include "enc_body_lowres_avg.inc"
 }
 
 // k_lowres_blend: m = blend of the averages at (v-1,v) x (u-1,u) (downsampled.cpp:98-113).
@@ -313,84 +315,20 @@ __global__ __launch_bounds__(kTileThreads) void k_tile_fwd(Geom g, const uint8_t
                                                   uint8_t *fres_sym, size_t fres_stride,
                                                   const uint8_t *__restrict__ fmap_lut,
                                                   QualArg<QI, ShiftTables> st, int v0) {
-  const int u = blockIdx.x * blockDim.x + threadIdx.x;
-  const int v = blockIdx.y + v0, f = blockIdx.z;
-  if (u >= g.cols) return;
-  const uint8_t *img = frames + (long long)f * g.frame_bytes;
-  const int bw = min(8, g.W - 8 * u), bh = min(8, g.H - 8 * v);
-  const int u2 = min(u + 1, g.cols - 1), v2 = min(v + 1, g.rows - 1);
-  uint8_t *dst_row = fres_sym + (size_t)f * fres_stride + (size_t)v * g.row_block + u;
-  const uint8_t *row0 = img + ((long long)(8 * v) * g.W + 8 * u) * 4;
-  const size_t pitch = (size_t)g.W * 4;
-
-#pragma unroll 1
-  for (int c = 0; c < g.C; ++c) {
-    const uint8_t *m = low + (size_t)f * plane_stride + (size_t)c * g.rows * g.cols;
-    // Bilinear low-res block from the four corners (downsampled.cpp:116-169).
-    int left[9], right[9];
-    left[0] = m[(size_t)v * g.cols + u];   left[8] = m[(size_t)v2 * g.cols + u];
-    right[0] = m[(size_t)v * g.cols + u2]; right[8] = m[(size_t)v2 * g.cols + u2];
-    interp9(left);
-    interp9(right);
-
-    int b[64];
-    if (FAST) {
-      const int mode = (g.ycbcr && c < 3) ? (c + 1) : kChanRaw;  // wave-uniform
-      if (mode == kChanRaw) residual_full_tile<kChanRaw>(row0, pitch, 8 * c, left, right, b);
-      else if (mode == kChanY) residual_full_tile<kChanY>(row0, pitch, 0, left, right, b);
-      else if (mode == kChanCb) residual_full_tile<kChanCb>(row0, pitch, 0, left, right, b);
-      else residual_full_tile<kChanCr>(row0, pitch, 0, left, right, b);
-    } else {
-      // Partial tiles replicate the last valid pixel of the row, rows below the
-      // image repeat the bottom-right valid pixel (encoder.cpp:26-52).
-#pragma unroll
-      for (int y = 0; y < 8; ++y) {
-        int a[9];
-        a[0] = left[y]; a[8] = right[y];
-        interp9(a);
-#pragma unroll
-        for (int x = 0; x < 8; ++x) {
-          const int yy = y < bh ? y : bh - 1;
-          const int xx = y < bh ? min(x, bw - 1) : bw - 1;
-          int ch[4];
-          load_pixel(img, g, 8 * u + xx, 8 * v + yy, ch);
-          b[y * 8 + x] = ch[c] - a[x];
-        }
-      }
-    }
-    // Forward 2-D WHT: rows, then columns (hadamard.cpp:78-88).
-#pragma unroll
-    for (int y = 0; y < 8; ++y)
-      wht8(b[y * 8 + 0], b[y * 8 + 1], b[y * 8 + 2], b[y * 8 + 3], b[y * 8 + 4], b[y * 8 + 5],
-           b[y * 8 + 6], b[y * 8 + 7]);
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-      wht8(b[x], b[8 + x], b[16 + x], b[24 + x], b[32 + x], b[40 + x], b[48 + x], b[56 + x]);
-
-    const bool chroma = g.ycbcr && (c == 1 || c == 2);  // encoder.cpp:284
-    const uint8_t *shift = nullptr;
-    KargWords shift_w = nullptr;
-    if constexpr (QI) shift_w = uniform_words(qual_entry(st, f)->st.s[chroma ? 1 : 0]);
-    else shift = st.s[chroma ? 1 : 0];
-    const int cols = COLS ? COLS : g.cols;  // compile-time stride -> no 64 live store addresses
-    uint8_t *dst = dst_row + (size_t)c * 64 * cols;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) {
-      const int pos = kScan[i];
-      int s;
-      if constexpr (QI) s = (int)((shift_w[pos >> 2] >> (8 * (pos & 3))) & 255u);
-      else s = shift[pos];
-      const int x = (int)(int16_t)b[pos];  // the reference's int16 wrap
-      // Sign-magnitude rounding shift (quantize.cpp:135-148).
-      const int r = s ? (1 << (s - 1)) : 0;
-      const int mag = x < 0 ? ((-x + r) >> s) : ((x + r) >> s);
-      // Companding (mapper.cpp:159-182): the full-res table is the identity up to
-      // 50; larger magnitudes go through the LUT of the restated search.
-      uint32_t code = (uint32_t)mag;
-      if (mag > 50) code = fmap_lut[mag];
-      dst[(size_t)i * cols] = (x < 0) ? (uint8_t)(0u - code) : (uint8_t)code;
-    }
-  }
+  constexpr bool kWin = false;
+#include "enc_body_tile_fwd.inc"
+}
+// The window source form: the generic path, instantiated for a quality per frame alone.  (QI stays a
+// parameter here and in k_pix_fwd_w: the body's table branches are discarded only where they depend on one.)
+template <bool QI>
+__global__ __launch_bounds__(kTileThreads) void k_tile_fwd_w(Geom g, WinSrc frames,
+                                                    const uint8_t *low, size_t plane_stride,
+                                                    uint8_t *fres_sym, size_t fres_stride,
+                                                    const uint8_t *__restrict__ fmap_lut,
+                                                    QualArg<QI, ShiftTables> st, int v0) {
+  constexpr bool FAST = false, kWin = true;
+  constexpr int COLS = 0;
+#include "enc_body_tile_fwd.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -529,150 +467,18 @@ __global__ __launch_bounds__(kPixThreads, 2) void k_pix_fwd(Geom g, const uint8_
                                                             uint8_t *fres_sym, size_t fres_stride,
                                                             const uint8_t *__restrict__ fmap_lut,
                                                             QualArg<QI, PixQuant> pq, int v0) {
-  // Companding LUT for magnitudes below kPixLut (every larger one maps to 127:
-  // the full-res table tops out at 8039, mapper.cpp:54-71,159-182).
-  __shared__ __attribute__((aligned(16))) uint8_t s_lut[kPixLut];
-  for (int k = threadIdx.x; k < kPixLut / 16; k += kPixThreads)
-    reinterpret_cast<uint4 *>(s_lut)[k] = reinterpret_cast<const uint4 *>(fmap_lut)[k];
-  __syncthreads();
-  const int cols = COLS ? COLS : g.cols;
-  const int u = blockIdx.x * kPixThreads + threadIdx.x;
-  const int v = blockIdx.y + v0, f = blockIdx.z;
-  if ((int)(blockIdx.x * kPixThreads + (threadIdx.x & ~63)) >= cols) return;   // the whole wave is beyond the row
-  KargWords qw = nullptr;   // QI: [rr, kk, ss][luma / chroma][coefficient], as k_front indexes PixQuant
-  if constexpr (QI) qw = uniform_words(qual_entry(pq, f)->pq);
-  // FULL: cols is a multiple of 64, every lane of a live wave owns a tile.
-  const bool valid = FULL || u < cols;
-  const int uc = valid ? u : cols - 1;
-  const uint8_t *img = frames + (long long)f * g.frame_bytes;
-  const int u2 = min(uc + 1, cols - 1), v2 = min(v + 1, g.rows - 1);
-  // Wave-uniform base + 32-bit lane offset: the stores take the scalar-base form and
-  // the per-coefficient stride is scalar arithmetic, not 64-bit adds per lane.
-  // The symbol stores go through a buffer descriptor of the frame's symbol plane:
-  // buffer_store_byte takes the lane offset in a VGPR and the (wave-uniform) offset of
-  // the coefficient row in an SGPR -- no address arithmetic on the vector unit.
-  const __amdgpu_buffer_rsrc_t sym_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      fres_sym + (size_t)f * fres_stride, 0, (int)g.fres_size, 0x00020000);
-  const uint32_t row_off = (uint32_t)v * (uint32_t)g.row_block;
-  const uint32_t lane_off = (uint32_t)uc;
-  const uint8_t *row0 = img + ((long long)(8 * v) * g.W + 8 * uc) * 4;
-  const size_t pitch = (size_t)g.W * 4;
-
-  // The tile: 8 rows x 8 pixels, one pass over HBM.
-  uint32_t px[64];
-#pragma unroll
-  for (int y = 0; y < 8; ++y) {
-    const uint4 *rp = reinterpret_cast<const uint4 *>(row0 + (size_t)y * pitch);
-    const uint4 q0 = rp[0], q1 = rp[1];
-    px[y * 8 + 0] = q0.x; px[y * 8 + 1] = q0.y; px[y * 8 + 2] = q0.z; px[y * 8 + 3] = q0.w;
-    px[y * 8 + 4] = q1.x; px[y * 8 + 5] = q1.y; px[y * 8 + 6] = q1.z; px[y * 8 + 7] = q1.w;
-  }
-  // Low-res corners of the four channels: (left, right) of block rows v and v + 1.
-  uint32_t lr0[4], lr8[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const uint8_t *m = low + (size_t)f * plane_stride + (size_t)c * g.rows * cols;
-    lr0[c] = (uint32_t)m[(size_t)v * cols + uc] | ((uint32_t)m[(size_t)v * cols + u2] << 8);
-    lr8[c] = (uint32_t)m[(size_t)v2 * cols + uc] | ((uint32_t)m[(size_t)v2 * cols + u2] << 8);
-  }
-
-#pragma unroll
-  for (int pr = 0; pr < 2; ++pr) {
-    // Channels in the low / high half of this pair, and their shift table.
-    const int cA = YCBCR ? (pr == 0 ? 2 : 0) : (pr == 0 ? 0 : 1);
-    const int cB = YCBCR ? (pr == 0 ? 1 : 3) : (pr == 0 ? 2 : 3);
-    pk16 b[64];
-    {
-      uint32_t LA[2][8], LB[2][8];
-      lowres_quads_e(lr0[cA], lr8[cA], LA);
-      lowres_quads_e(lr0[cB], lr8[cB], LB);
-#pragma unroll
-      for (int y = 0; y < 8; ++y)
-#pragma unroll
-        for (int x = 0; x < 8; ++x) {
-          // (low A, low B) of this pixel, zero-extended to the two halves.
-          const uint32_t sel = 0x0c000c00u | (uint32_t)(y & 3) | ((uint32_t)(4 + (y & 3)) << 16);
-          const pk16 lo = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(LB[y >> 2][x], LA[y >> 2][x], sel));
-          const pk16 pv = pr == 0 ? pix_pair<YCBCR, 0>(px[y * 8 + x]) : pix_pair<YCBCR, 1>(px[y * 8 + x]);
-          b[y * 8 + x] = pv - lo;
-        }
-    }
-    // Forward 2-D WHT: rows, then columns (hadamard.cpp:78-88).
-#pragma unroll
-    for (int y = 0; y < 8; ++y)
-      wht8_pk(b[y * 8 + 0], b[y * 8 + 1], b[y * 8 + 2], b[y * 8 + 3], b[y * 8 + 4], b[y * 8 + 5],
-              b[y * 8 + 6], b[y * 8 + 7]);
-#pragma unroll
-    for (int x = 0; x < 8; ++x)
-      wht8_pk(b[x], b[8 + x], b[16 + x], b[24 + x], b[32 + x], b[40 + x], b[48 + x], b[56 + x]);
-
-    const uint32_t offA = row_off + (uint32_t)(cA * 64 * cols), offB = row_off + (uint32_t)(cB * 64 * cols);
-    // Quantise (quantize.cpp:127-151), compand (mapper.cpp:159-182) and store, in
-    // groups of coefficients in scan order.  sign * ((|x| + r) >> s) is branch free:
-    // (x + r + sign * k) >> s with sign = x >> 15 and k = [s > 0]; r, k and s come
-    // as packed pairs from the kernel arguments (pq, scan order).  Companding is the
-    // identity while |q| <= 50; the group keeps the largest q + 50 (as unsigned: <=
-    // 100 exactly then) and ONE wave-uniform branch per group sends the group
-    // through the LUT -- the first sixteen coefficients (DC and first order, the
-    // ones high-contrast tiles push beyond 50) in groups of four, the rest in
-    // sixteens.  (A test per coefficient was 128 compare + branch pairs per tile,
-    // each behind hazard no-ops, and 128 basic blocks the scheduler could not
-    // interleave across.)
-    const int qt = (YCBCR && pr == 0) ? 1 : 0;
-    auto group = [&](auto i0c, auto nc) {
-      constexpr int I0 = decltype(i0c)::value, N = decltype(nc)::value;
-      pk16 q[N];
-      upk16 top = {0, 0};
-      for_seq<N>([&](auto kc) {
-        constexpr int k = decltype(kc)::value, i = I0 + k, pos = kScan[i];
-        const pk16 x = b[pos];
-        const pk16 fifteen = {15, 15};
-        const pk16 sign = x >> fifteen;                       // 0 or -1 per half
-        pk16 rr, kk, ss;
-        if constexpr (QI) {
-          rr = __builtin_bit_cast(pk16, qw[(0 * 2 + qt) * 64 + i]); kk = __builtin_bit_cast(pk16, qw[(1 * 2 + qt) * 64 + i]);
-          ss = __builtin_bit_cast(pk16, qw[(2 * 2 + qt) * 64 + i]);
-        } else {
-          rr = __builtin_bit_cast(pk16, pq.rr[qt][i]); kk = __builtin_bit_cast(pk16, pq.kk[qt][i]);
-          ss = __builtin_bit_cast(pk16, pq.ss[qt][i]);
-        }
-        q[k] = (sign * kk + x + rr) >> ss;
-        const upk16 fifty = {50, 50};
-        top = __builtin_elementwise_max(top, (upk16)(__builtin_bit_cast(upk16, q[k]) + fifty));
-      });
-      const upk16 hundred = {100, 100};
-      const uint32_t over = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(top, hundred));
-      if (__builtin_expect(__any(over != 0u), 0)) {
-        for_seq<N>([&](auto kc) {
-          constexpr int k = decltype(kc)::value;
-          const pk16 fifteen = {15, 15};
-          const pk16 sign = q[k] >> fifteen;
-          const pk16 mag = (q[k] ^ sign) - sign;
-          const uint32_t ma = min((uint32_t)(uint16_t)mag.x, (uint32_t)(kPixLut - 1));
-          const uint32_t mb = min((uint32_t)(uint16_t)mag.y, (uint32_t)(kPixLut - 1));
-          pk16 code;                                          // the LUT is the identity below 51
-          code.x = (short)s_lut[ma];
-          code.y = (short)s_lut[mb];
-          q[k] = (code ^ sign) - sign;
-        });
-      }
-      if (valid) {
-        for_seq<N>([&](auto kc) {
-          constexpr int k = decltype(kc)::value, i = I0 + k;
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q[k].x, sym_rsrc, lane_off, offA + (uint32_t)(i * cols), 0);
-          __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q[k].y, sym_rsrc, lane_off, offB + (uint32_t)(i * cols), 0);
-        });
-      }
-    };
-    using std::integral_constant;
-    group(integral_constant<int, 0>{}, integral_constant<int, 4>{});
-    group(integral_constant<int, 4>{}, integral_constant<int, 4>{});
-    group(integral_constant<int, 8>{}, integral_constant<int, 4>{});
-    group(integral_constant<int, 12>{}, integral_constant<int, 4>{});
-    group(integral_constant<int, 16>{}, integral_constant<int, 16>{});
-    group(integral_constant<int, 32>{}, integral_constant<int, 16>{});
-    group(integral_constant<int, 48>{}, integral_constant<int, 16>{});
-  }
+  constexpr bool kWin = false;
+#include "enc_body_pix_fwd.inc"
+}
+// The window source form, instantiated for a quality per frame alone.
+template <bool YCBCR, int COLS, bool FULL, bool QI>
+__global__ __launch_bounds__(kPixThreads, 2) void k_pix_fwd_w(Geom g, WinSrc frames,
+                                                              const uint8_t *low, size_t plane_stride,
+                                                              uint8_t *fres_sym, size_t fres_stride,
+                                                              const uint8_t *__restrict__ fmap_lut,
+                                                              QualArg<QI, PixQuant> pq, int v0) {
+  constexpr bool kWin = true;
+#include "enc_body_pix_fwd.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -750,227 +556,25 @@ typedef FrontArgsT<false> FrontArgs;
 // scalar loads at their uses, from a base in HBM.
 template <bool YCBCR, int COLS, bool QI = false>
 __global__ __launch_bounds__(512) void k_front(FrontArgsT<QI> a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const Geom &g = a.g;
-  const uint8_t *frames = a.frames, *fmap_lut = a.fmap_lut;
-  uint8_t *avg = a.avg, *low = a.low, *fres_sym = a.fres_sym;
-  const size_t plane_stride = a.plane_stride, fres_stride = a.fres_stride;
-  const int chunk_rows = a.chunk_rows;
-  const int cols = COLS ? COLS : g.cols;
-  const int nt = (int)blockDim.x;                       // 64 x wavefronts per row
-  uint4 *park = reinterpret_cast<uint4 *>(smem);        // [wave][16][64]: the tile row in waiting
-  uint8_t *s_lut = smem + (size_t)nt * 256;             // (nt / 64 waves x 16 KiB)
-  uint32_t *s_ex = reinterpret_cast<uint32_t *>(s_lut + kPixLut);   // [kFrontExch][nt]
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int f = blockIdx.y;
-  const int v0 = (int)blockIdx.x * chunk_rows, v1 = min(v0 + chunk_rows, g.rows);
-  for (int k = tid; k < kPixLut / 16; k += nt)
-    reinterpret_cast<uint4 *>(s_lut)[k] = reinterpret_cast<const uint4 *>(fmap_lut)[k];
-  const int u = tid;
-  const bool valid = u < cols;
-  const int uc = valid ? u : cols - 1;
-  const uint8_t *img = frames + (long long)f * g.frame_bytes;
-  const size_t pitch = (size_t)g.W * 4;
-  uint4 *slot = park + (size_t)wv * 16 * 64 + lane;     // + k * 64: piece k (pixel row k >> 1, half k & 1)
-  const __amdgpu_buffer_rsrc_t sym_rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      fres_sym + (size_t)f * fres_stride, 0, (int)g.fres_size, 0x00020000);
-  uint8_t *avg_f = avg + (size_t)f * plane_stride, *low_f = low + (size_t)f * plane_stride;
-  const size_t chan = (size_t)g.rows * cols;
-
-  uint32_t px[64];
-  auto load_row = [&](int t) {
-    const uint8_t *row0 = img + ((long long)(8 * t) * g.W + 8 * uc) * 4;
-#pragma unroll
-    for (int y = 0; y < 8; ++y) {
-      const uint4 *rp = reinterpret_cast<const uint4 *>(row0 + (size_t)y * pitch);
-      const uint4 q0 = rp[0], q1 = rp[1];
-      px[y * 8 + 0] = q0.x; px[y * 8 + 1] = q0.y; px[y * 8 + 2] = q0.z; px[y * 8 + 3] = q0.w;
-      px[y * 8 + 4] = q1.x; px[y * 8 + 5] = q1.y; px[y * 8 + 6] = q1.z; px[y * 8 + 7] = q1.w;
-    }
-  };
-  auto park_row = [&]() {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-      uint4 q;
-      q.x = px[k * 4 + 0]; q.y = px[k * 4 + 1]; q.z = px[k * 4 + 2]; q.w = px[k * 4 + 3];
-      slot[k * 64] = q;
-    }
-  };
-
-  const int t_begin = max(v0 - 2, 0), t_end = v1;   // rows whose sums this chunk needs (t_end == rows: nothing to load)
-  load_row(t_begin);
-  KargWords qbase = nullptr;
-  if constexpr (QI) qbase = uniform_words(qual_entry(a.pq, f)->pq);
-  const pk16 zero2 = {0, 0};
-  pk16 bl_prev[2] = {zero2, zero2}, brl_prev[2] = {zero2, zero2};   // BL(u, t-1), BR(u-1, t-1)
-  uint32_t avg_prev[3] = {0, 0, 0};    // averages of row t - 1 at u - 1, u, u + 1 (clipped)
-  uint32_t low_prev[2] = {0, 0};       // low-res row t - 1 at u, u2
-  __syncthreads();                     // (the LUT)
-
-  for (int t = t_begin; t <= t_end; ++t) {
-    // The quantiser's 384 words are scalar loads from the kernel arguments AT THEIR USES, as in
-    // k_pix_fwd: through a pointer the compiler cannot see through, or it hoists all of them out
-    // of this loop (370 scalar registers spilled).
-    KargWords qw;
-    if constexpr (QI) qw = qbase;
-    else qw = (KargWords)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() +
-                          offsetof(FrontArgs, pq));
-    asm volatile("" : "+s"(qw));
-    const bool have = t < g.rows;
-    uint32_t low_cur[2] = {low_prev[0], low_prev[1]};   // (t == rows: the row below the last one is the last one)
-    if (have) {
-      // ---- corner sums of tile row t, windows, box averages ----
-      pk16 tl[2], tr[2], bl[2], br[2];
-      front_sums<YCBCR, 0>(px, tl[0], tr[0], bl[0], br[0]);
-      front_sums<YCBCR, 1>(px, tl[1], tr[1], bl[1], br[1]);
-      s_ex[0 * nt + tid] = __builtin_bit_cast(uint32_t, tr[0]);
-      s_ex[1 * nt + tid] = __builtin_bit_cast(uint32_t, tr[1]);
-      s_ex[2 * nt + tid] = __builtin_bit_cast(uint32_t, br[0]);
-      s_ex[3 * nt + tid] = __builtin_bit_cast(uint32_t, br[1]);
-      __syncthreads();
-      pk16 trl[2] = {zero2, zero2}, brl[2] = {zero2, zero2};   // of the tile to the left (none at u = 0)
-      if (u > 0) {
-        trl[0] = __builtin_bit_cast(pk16, s_ex[0 * nt + tid - 1]); trl[1] = __builtin_bit_cast(pk16, s_ex[1 * nt + tid - 1]);
-        brl[0] = __builtin_bit_cast(pk16, s_ex[2 * nt + tid - 1]); brl[1] = __builtin_bit_cast(pk16, s_ex[3 * nt + tid - 1]);
-      }
-      const upk16 w0 = __builtin_bit_cast(upk16, (pk16)(tl[0] + trl[0] + bl_prev[0] + brl_prev[0]));
-      const upk16 w1 = __builtin_bit_cast(upk16, (pk16)(tl[1] + trl[1] + bl_prev[1] + brl_prev[1]));
-      // (sum + cnt / 2) / cnt with cnt = (u ? 8 : 5) * (t ? 8 : 5): a 24-bit multiply by 2^22 / cnt
-      // rounded up, exact for sums up to 255 * 64.
-      const uint32_t cnt = (u ? 8u : 5u) * (t ? 8u : 5u);
-      const uint32_t half = cnt >> 1, mul = cnt == 64u ? 65536u : cnt == 40u ? 104858u : 167773u;
-      auto mean = [&](uint32_t sum) { return __umul24(sum + half, mul) >> 22; };
-      const uint32_t a_cur = front_pack_channels<YCBCR>(mean(w0.x), mean(w0.y), mean(w1.x), mean(w1.y));
-      s_ex[4 * nt + tid] = a_cur;
-      bl_prev[0] = bl[0]; bl_prev[1] = bl[1];
-      brl_prev[0] = brl[0]; brl_prev[1] = brl[1];
-      __syncthreads();
-      const uint32_t a_l = s_ex[4 * nt + (u > 0 ? tid - 1 : tid)];
-      const uint32_t a_r = s_ex[4 * nt + min(u + 1, cols - 1)];
-      if (t == 0) { avg_prev[0] = a_l; avg_prev[1] = a_cur; avg_prev[2] = a_r; }   // (row -1 reads as row 0)
-      low_cur[0] = front_blend(avg_prev[0], avg_prev[1], a_l, a_cur);
-      low_cur[1] = front_blend(avg_prev[1], avg_prev[2], a_cur, a_r);
-      if (u == cols - 1) low_cur[1] = low_cur[0];
-      avg_prev[0] = a_l; avg_prev[1] = a_cur; avg_prev[2] = a_r;
-      if (valid && t >= v0 && t < v1) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          avg_f[(size_t)c * chan + (size_t)t * cols + u] = (uint8_t)(a_cur >> (8 * c));
-          low_f[(size_t)c * chan + (size_t)t * cols + u] = (uint8_t)(low_cur[0] >> (8 * c));
-        }
-      }
-      // (No third barrier.  The sums' words are next written in front of the next step's first
-      // barrier: by then every wavefront has passed this step's SECOND barrier, which it reached with
-      // its reads of the sums done.  The averages' word is next written behind the next step's first
-      // barrier, which nobody passes before everybody has read this step's averages.)
-    }
-    const int v = t - 1;
-    bool requested = false;   // has tile row t + 1 been requested (and row t parked) inside the transform?
-    if (v >= v0 && v < v1) {
-      // ---- transform of tile row v: pixels from the parking slot, low-res rows v (low_prev) and v + 1 (low_cur) ----
-      uint32_t lr0[4], lr8[4];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        lr0[c] = ((low_prev[0] >> (8 * c)) & 255u) | (((low_prev[1] >> (8 * c)) & 255u) << 8);
-        lr8[c] = ((low_cur[0] >> (8 * c)) & 255u) | (((low_cur[1] >> (8 * c)) & 255u) << 8);
-      }
-      const uint32_t row_off = (uint32_t)v * (uint32_t)g.row_block;
-#pragma unroll
-      for (int pr = 0; pr < 2; ++pr) {
-        const int cA = YCBCR ? (pr == 0 ? 2 : 0) : (pr == 0 ? 0 : 1);
-        const int cB = YCBCR ? (pr == 0 ? 1 : 3) : (pr == 0 ? 2 : 3);
-        pk16 b[64];
-        {
-          uint32_t LA[2][8], LB[2][8];
-          lowres_quads_e(lr0[cA], lr8[cA], LA);
-          lowres_quads_e(lr0[cB], lr8[cB], LB);
-#pragma unroll
-          for (int k = 0; k < 16; ++k) {
-            const uint4 q = slot[k * 64];
-            const uint32_t p4[4] = {q.x, q.y, q.z, q.w};
-            const int y = k >> 1;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              const int x = (k & 1) * 4 + j;
-              const uint32_t sel = 0x0c000c00u | (uint32_t)(y & 3) | ((uint32_t)(4 + (y & 3)) << 16);
-              const pk16 lo = __builtin_bit_cast(pk16, __builtin_amdgcn_perm(LB[y >> 2][x], LA[y >> 2][x], sel));
-              const pk16 pv = pr == 0 ? pix_pair<YCBCR, 0>(p4[j]) : pix_pair<YCBCR, 1>(p4[j]);
-              b[y * 8 + x] = pv - lo;
-            }
-          }
-        }
-        if (pr == 1 && have) {
-          // The slot has been read for the last time: tile row t takes it, and row t + 1 is requested --
-          // the loads fly under this pair's WHT, quantiser and stores.
-          park_row();
-          if (t + 1 <= t_end && t + 1 < g.rows) load_row(t + 1);
-          requested = true;
-        }
-#pragma unroll
-        for (int y = 0; y < 8; ++y)
-          wht8_pk(b[y * 8 + 0], b[y * 8 + 1], b[y * 8 + 2], b[y * 8 + 3], b[y * 8 + 4], b[y * 8 + 5],
-                  b[y * 8 + 6], b[y * 8 + 7]);
-#pragma unroll
-        for (int x = 0; x < 8; ++x)
-          wht8_pk(b[x], b[8 + x], b[16 + x], b[24 + x], b[32 + x], b[40 + x], b[48 + x], b[56 + x]);
-        const uint32_t offA = row_off + (uint32_t)(cA * 64 * cols), offB = row_off + (uint32_t)(cB * 64 * cols);
-        const int qt = (YCBCR && pr == 0) ? 1 : 0;
-        // (quantise / compand / store in groups of coefficients: see k_pix_fwd)
-        auto group = [&](auto i0c, auto nc) {
-          constexpr int I0 = decltype(i0c)::value, N = decltype(nc)::value;
-          pk16 q[N];
-          upk16 top = {0, 0};
-          for_seq<N>([&](auto kc) {
-            constexpr int k = decltype(kc)::value, i = I0 + k, pos = kScan[i];
-            const pk16 x = b[pos];
-            const pk16 fifteen = {15, 15};
-            const pk16 sign = x >> fifteen;
-            const pk16 rr = __builtin_bit_cast(pk16, qw[(0 * 2 + qt) * 64 + i]), kk = __builtin_bit_cast(pk16, qw[(1 * 2 + qt) * 64 + i]);
-            const pk16 ss = __builtin_bit_cast(pk16, qw[(2 * 2 + qt) * 64 + i]);
-            q[k] = (sign * kk + x + rr) >> ss;
-            const upk16 fifty = {50, 50};
-            top = __builtin_elementwise_max(top, (upk16)(__builtin_bit_cast(upk16, q[k]) + fifty));
-          });
-          const upk16 hundred = {100, 100};
-          const uint32_t over = __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(top, hundred));
-          if (__builtin_expect(__any(over != 0u), 0)) {
-            for_seq<N>([&](auto kc) {
-              constexpr int k = decltype(kc)::value;
-              const pk16 fifteen = {15, 15};
-              const pk16 sign = q[k] >> fifteen;
-              const pk16 mag = (q[k] ^ sign) - sign;
-              const uint32_t ma = min((uint32_t)(uint16_t)mag.x, (uint32_t)(kPixLut - 1));
-              const uint32_t mb = min((uint32_t)(uint16_t)mag.y, (uint32_t)(kPixLut - 1));
-              pk16 code;
-              code.x = (short)s_lut[ma];
-              code.y = (short)s_lut[mb];
-              q[k] = (code ^ sign) - sign;
-            });
-          }
-          if (valid) {
-            for_seq<N>([&](auto kc) {
-              constexpr int k = decltype(kc)::value, i = I0 + k;
-              __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q[k].x, sym_rsrc, (uint32_t)uc, offA + (uint32_t)(i * cols), 0);
-              __builtin_amdgcn_raw_buffer_store_b8((uint8_t)q[k].y, sym_rsrc, (uint32_t)uc, offB + (uint32_t)(i * cols), 0);
-            });
-          }
-        };
-        using std::integral_constant;
-        group(integral_constant<int, 0>{}, integral_constant<int, 4>{});
-        group(integral_constant<int, 4>{}, integral_constant<int, 4>{});
-        group(integral_constant<int, 8>{}, integral_constant<int, 4>{});
-        group(integral_constant<int, 12>{}, integral_constant<int, 4>{});
-        group(integral_constant<int, 16>{}, integral_constant<int, 16>{});
-        group(integral_constant<int, 32>{}, integral_constant<int, 16>{});
-        group(integral_constant<int, 48>{}, integral_constant<int, 16>{});
-      }
-    }
-    if (!requested && have) {
-      park_row();
-      if (t + 1 <= t_end && t + 1 < g.rows) load_row(t + 1);
-    }
-    low_prev[0] = low_cur[0]; low_prev[1] = low_cur[1];
-  }
+  constexpr bool kWin = false;
+#include "enc_body_front.inc"
+}
+// The window source form (a quality per frame).
+struct FrontArgsW {
+  Geom g;
+  WinSrc frames;
+  uint8_t *avg, *low;
+  size_t plane_stride;
+  uint8_t *fres_sym;
+  size_t fres_stride;
+  const uint8_t *fmap_lut;
+  int chunk_rows;
+  QualSel pq;
+};
+template <bool YCBCR, int COLS>
+__global__ __launch_bounds__(512) void k_front_w(FrontArgsW a) {
+  constexpr bool QI = true, kWin = true;
+#include "enc_body_front.inc"
 }
 
 // ---------------------------------------------------------------------------
@@ -2833,10 +2437,26 @@ static bool use_pix_path(const Geom &g) {
 }
 
 // The same launch with the quantiser of every frame's own quality (the COLS = 0 forms serve every width).
+// win: the window source form of the same instantiations.
 static void launch_pix_q(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const QualSel &qs,
-                         const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof) {
+                         const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof,
+                         const WinSrc *win = nullptr) {
   const unsigned gxt = (unsigned)((g.cols + kPixThreads - 1) / kPixThreads);
   const dim3 grid(gxt, g.rows, batch), block(kPixThreads);
+  if (win) {
+#define HIMG_PIX_W(Y, COLS, FULL)                                                                          \
+  HIMG_LAUNCH((k_pix_fwd_w<Y, COLS, FULL, true>), grid, block, g, *win, ws.low, ws.plane_stride, ws.fres_sym, \
+              ws.fres_stride, d_fmap_lut, qs, 0)
+    const bool full = g.cols % 64 == 0;
+    if (g.ycbcr) {
+      if (g.cols == 512) HIMG_PIX_W(true, 512, true);
+      else if (full) HIMG_PIX_W(true, 0, true);
+      else HIMG_PIX_W(true, 0, false);
+    }
+    else { if (full) HIMG_PIX_W(false, 0, true); else HIMG_PIX_W(false, 0, false); }
+#undef HIMG_PIX_W
+    return;
+  }
 #define HIMG_PIX_Q(Y, COLS, FULL)                                                                          \
   HIMG_LAUNCH((k_pix_fwd<Y, COLS, FULL, true>), grid, block, g, d_frames, ws.low, ws.plane_stride, ws.fres_sym, \
               ws.fres_stride, d_fmap_lut, qs, 0)
@@ -2884,10 +2504,10 @@ static bool use_front(const Geom &g, int batch) {
   // (256 x 1024^2: 97 against 109 Gpx/s with the three kernels).
   return g.cols > 192 && (long long)g.rows * batch >= 8192;
 }
-// qs (else st): the quality-indexed form.
+// qs (else st): the quality-indexed form; win (with qs): its window source form.
 static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames, const ShiftTables *st,
                          const uint8_t *d_fmap_lut, int batch, hipStream_t stream, Profiler *prof,
-                         const QualSel *qs = nullptr) {
+                         const QualSel *qs = nullptr, const WinSrc *win = nullptr) {
   const int wpr = (g.cols + 63) / 64, nt = 64 * wpr;
   // ~64 block rows per workgroup (a chunk re-reads two tile rows above it), more chunks when the batch
   // alone does not give every CU two rounds of workgroups; never fewer than 16 rows.
@@ -2899,12 +2519,25 @@ static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames
   const size_t lds = (size_t)nt * 256 + kPixLut + (size_t)kFrontExch * nt * 4;
   const dim3 grid((unsigned)((g.rows + chunk - 1) / chunk), (unsigned)batch), block((unsigned)nt);
   auto fill = [&](auto &fa) {
-    fa.g = g; fa.frames = d_frames; fa.avg = ws.avg; fa.low = ws.low; fa.plane_stride = ws.plane_stride;
+    fa.g = g; fa.avg = ws.avg; fa.low = ws.low; fa.plane_stride = ws.plane_stride;
     fa.fres_sym = ws.fres_sym; fa.fres_stride = ws.fres_stride; fa.fmap_lut = d_fmap_lut; fa.chunk_rows = chunk;
   };
+  if (win) {
+    FrontArgsW fw;
+    fill(fw);
+    fw.frames = *win;
+    fw.pq = *qs;
+    prof_begin(prof, "k_front", stream);
+    if (g.ycbcr && g.cols == 512) hipLaunchKernelGGL((k_front_w<true, 512>), grid, block, lds, stream, fw);
+    else if (g.ycbcr) hipLaunchKernelGGL((k_front_w<true, 0>), grid, block, lds, stream, fw);
+    else hipLaunchKernelGGL((k_front_w<false, 0>), grid, block, lds, stream, fw);
+    prof_end(prof, stream);
+    return;
+  }
   if (qs) {
     FrontArgsT<true> fq;
     fill(fq);
+    fq.frames = d_frames;
     fq.pq = *qs;
     prof_begin(prof, "k_front", stream);
     if (g.ycbcr && g.cols == 512) hipLaunchKernelGGL((k_front<true, 512, true>), grid, block, lds, stream, fq);
@@ -2915,6 +2548,7 @@ static void launch_front(const Geom &g, const EncWs &ws, const uint8_t *d_frames
   }
   FrontArgs fa;
   fill(fa);
+  fa.frames = d_frames;
   fa.pq = make_pix_quant(*st);
   static_assert(sizeof(((PixQuant *)0)->rr) == 2 * 64 * 4 && offsetof(PixQuant, kk) == 512 && offsetof(PixQuant, ss) == 1024,
                 "k_front indexes the quantiser's words as [table][luma / chroma][coefficient]");
@@ -2943,7 +2577,10 @@ hipError_t enc_set_kernel_attrs() {
                          reinterpret_cast<const void *>(&k_front<false, 0>),
                          reinterpret_cast<const void *>(&k_front<true, 512, true>),
                          reinterpret_cast<const void *>(&k_front<true, 0, true>),
-                         reinterpret_cast<const void *>(&k_front<false, 0, true>)};
+                         reinterpret_cast<const void *>(&k_front<false, 0, true>),
+                         reinterpret_cast<const void *>(&k_front_w<true, 512>),
+                         reinterpret_cast<const void *>(&k_front_w<true, 0>),
+                         reinterpret_cast<const void *>(&k_front_w<false, 0>)};
   for (const void *k : front) {
     const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (e != hipSuccess) return e;
@@ -3049,12 +2686,14 @@ int loop_counts_read_enc(unsigned long long *out) { return loop_counts_read(out)
 // arguments (launch_encode); qs instead: the quality-indexed forms of the five kernels that read
 // them (launch_encode_q), and with d_out == nullptr its size-only pass.  sse (with qs): the
 // distortion probe (launch_encode_sse) -- the front, the low-res chain in its storing form, then
-// k_sse; no token, tree, size or bit-packing kernel.
+// k_sse; no token, tree, size or bit-packing kernel.  win (with qs, for d_frames): the four kernels
+// that read pixels run in their window source form; nothing behind them knows.
 static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
                             uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
                             const StaticChunks &sc, const ShiftTables *st, const LresTables *lt, const QualSel *qs,
                             const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
-                            hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const SseArgs *sse = nullptr) {
+                            hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const SseArgs *sse = nullptr,
+                            const WinSrc *win = nullptr) {
   const int nsp = g.lres_spans + g.rows;
   const dim3 b256(256);
   const unsigned gx = (unsigned)((g.cols + 255) / 256);
@@ -3093,9 +2732,10 @@ static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uin
   // low-res plane and the symbols; the LRES branch then forks behind it and runs beside the tokeniser.
   const bool front = use_front(g, batch);
   if (front) {
-    launch_front(g, ws, d_frames, st, d_fmap_lut, batch, stream, prof, qs);
+    launch_front(g, ws, d_frames, st, d_fmap_lut, batch, stream, prof, qs, win);
   } else {
-    HIMG_LAUNCH(k_lowres_avg, dim3(gx, g.rows, batch), b256, g, d_frames, ws.avg, ws.plane_stride, 0);
+    if (win) HIMG_LAUNCH(k_lowres_avg_w, dim3(gx, g.rows, batch), b256, g, *win, ws.avg, ws.plane_stride, 0);
+    else HIMG_LAUNCH(k_lowres_avg, dim3(gx, g.rows, batch), b256, g, d_frames, ws.avg, ws.plane_stride, 0);
     if ((g.cols & 3) == 0 && (ws.plane_stride & 3) == 0)
       HIMG_LAUNCH(k_lowres_blend<true>, dim3((g.cols / 4 + 255) / 256, (g.rows + kBlendRows - 1) / kBlendRows, batch * g.C), b256,
                   g, ws.avg, ws.low, ws.plane_stride, 0, g.rows);
@@ -3137,8 +2777,11 @@ static void encode_launches(const Geom &g, const EncWs &ws, int batch, const uin
   if (front) {
     // (the symbols are there already)
   } else if (pix) {
-    if (qs) launch_pix_q(g, ws, d_frames, *qs, d_fmap_lut, batch, stream, prof);
+    if (qs) launch_pix_q(g, ws, d_frames, *qs, d_fmap_lut, batch, stream, prof, win);
     else launch_pix(g, ws, d_frames, *st, d_fmap_lut, 0, g.rows, batch, stream, prof);
+  } else if (win) {
+    HIMG_LAUNCH(k_tile_fwd_w<true>, dim3(gxt, g.rows, batch), dim3(kTileThreads), g, *win,
+                ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, *qs, 0);
   } else if (qs) {
     HIMG_LAUNCH((k_tile_fwd<false, 0, true>), dim3(gxt, g.rows, batch), dim3(kTileThreads), g, d_frames,
                 ws.low, ws.plane_stride, ws.fres_sym, ws.fres_stride, d_fmap_lut, *qs, 0);
@@ -3203,6 +2846,15 @@ void launch_encode_q(const Geom &g, const EncWs &ws, int batch, const uint8_t *d
                      hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
   encode_launches(g, ws, batch, d_frames, d_out, out_stride, d_sizes, sc, nullptr, nullptr, &qs, d_fmap_lut, stream, prof,
                   side, ev_fork, ev_join);
+}
+
+void launch_encode_windows(const Geom &g, const EncWs &ws, int batch, const WinSrc &src,
+                           uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
+                           const StaticChunks &sc, const QualSel &qs,
+                           const uint8_t *d_fmap_lut, hipStream_t stream, Profiler *prof,
+                           hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  encode_launches(g, ws, batch, nullptr, d_out, out_stride, d_sizes, sc, nullptr, nullptr, &qs, d_fmap_lut, stream, prof,
+                  side, ev_fork, ev_join, nullptr, &src);
 }
 
 void launch_encode_sse(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,

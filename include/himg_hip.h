@@ -246,6 +246,66 @@ int himg_hip_encode_budget_batch(himg_hip_ctx *ctx, const uint8_t *const *frames
                                  int use_ycbcr, const size_t *budgets, uint8_t *const *dst,
                                  const size_t *dst_cap, size_t *out_sizes, int *qualities);
 
+/* ---- encode windows of pitched source pictures -------------------------------- */
+/*
+ * The encode entry points above take whole, tightly packed frames.  This one takes a row pitch and a
+ * rectangle per frame, the way the region decodes do on the other side: frames from hipMallocPitch or
+ * a surface with padded rows, the tiles of one large picture (frame_pitch = 0), or a region of
+ * interest per frame are encoded where they lie, without a copy pass that makes them contiguous.
+ */
+typedef struct himg_hip_src {
+  int width, height;      /* the source pictures in pixels: every window lies inside */
+  int pixel_stride;       /* bytes from a pixel to the next, >= num_channels */
+  size_t row_pitch;       /* bytes from a row to the next, >= width * pixel_stride */
+  size_t frame_pitch;     /* bytes from source picture f to f + 1; 0: all windows read ONE picture */
+} himg_hip_src;
+
+/* Window f of the batch is the w x h picture whose pixel (i, j), channel c, is the byte at
+ *   d_src + f * frame_pitch + (y_f + i) * row_pitch + (x_f + j) * pixel_stride + c,
+ * (x_f, y_f) = h_origins[2 f], h_origins[2 f + 1].  Stream f in d_out + f * out_stride, d_sizes[f] and
+ * d_status[f] are byte for byte what himg_hip_encode gives for that picture at quality h_quality[f];
+ * the low-res sampling clips at the window's edges, not the source's.  Otherwise the contract of
+ * himg_hip_encode_device_q: asynchronous, no host synchronisation, the out_stride rule (for the
+ * WINDOW's size), the grid limits.  h_origins is a HOST array of 2 * batch values that rides to the
+ * device with h_quality, as the decode's origins do with its sizes.  Windows may overlap; with
+ * frame_pitch == 0 they all come from one picture.
+ *
+ * Checks, all on the host before anything is launched -- a failure returns HIMG_ERR_ARG and none of
+ * d_out, d_sizes, d_status is written:
+ *   - src NULL, or a source or window size that is not positive;
+ *   - pixel_stride < num_channels;
+ *   - row_pitch < width * pixel_stride;
+ *   - frame_pitch neither 0 nor at least (height - 1) * row_pitch + width * pixel_stride;
+ *   - a window not inside width x height (x_f, y_f >= 0, x_f + w <= width, y_f + h <= height);
+ *   - a quality outside [0, 100];
+ *   - d_src not 16-byte aligned;
+ *   - for pixel_stride == 4: row_pitch or frame_pitch not a multiple of 4.
+ * The origins themselves are unconstrained: an odd x_f is legal (the kernels load a window's tile rows
+ * at pixel alignment).
+ *
+ * Bytes used: only the windows' own pixels decide the result, and nothing at or beyond *bytes of
+ * himg_hip_windows_extent is loaded: the largest
+ *   f * frame_pitch + (y_f + h - 1) * row_pitch + (x_f + w) * pixel_stride
+ * over the batch -- a buffer may end with its last window's last pixel.
+ *
+ * Not in this change: windows for the size probe (himg_hip_encode_sizes_device), for the distortion
+ * probe (its comparison kernel reads the source too), for the two searches, for the row-sharded and
+ * multi-GPU paths; a batch host form; the C++ classes. */
+/* Host only, no GPU: the checks above (those of src, the window size and the origins; num_channels in
+ * 1 .. 4), the same codes, and *bytes. */
+int himg_hip_windows_extent(const himg_hip_src *src, int num_channels, int batch,
+                            const int32_t *h_origins, int w, int h, size_t *bytes);
+int himg_hip_encode_windows_device(himg_hip_ctx *ctx, const void *d_src, const himg_hip_src *src,
+                                   int batch, int num_channels, const int32_t *h_origins, int w, int h,
+                                   const int32_t *h_quality, int use_ycbcr, void *d_out, size_t out_stride,
+                                   uint32_t *d_sizes, int32_t *d_status, void *stream);
+/* One window (x, y, w, h) of a HOST picture described by src (frame_pitch is ignored): only rows
+ * [y, y + h) of the source are uploaded, one contiguous range, and encoded by the device form with
+ * batch 1 and origin (x, 0).  The capacity protocol and himg_hip_fetch_last as himg_hip_encode_to. */
+int himg_hip_encode_window_to(himg_hip_ctx *ctx, const uint8_t *data, const himg_hip_src *src,
+                              int num_channels, int x, int y, int w, int h, int quality, int use_ycbcr,
+                              uint8_t *dst, size_t dst_cap, size_t *out_size);
+
 /* ---- the distortion of an encode, and encode to a distortion target ----------- */
 /*
  * sse(q) of a frame: the sum over all H x W x C samples of (source - decoded)^2, where `decoded` is
