@@ -123,6 +123,10 @@ def lib():
     L.himg_hip_tensor_bytes.argtypes = [vp, i32, i32, i32, P(sz)]
     L.himg_hip_decode_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_regions_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.himg_hip_dst_extent.argtypes = [vp, i32, i32, vp, i32, i32, P(sz)]
+    L.himg_hip_decode_into_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_decode_regions_into_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_decode_into_to.argtypes = [vp, vp, sz, vp, vp, i32, i32, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_regions_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
     L.himg_hip_scaled_size.argtypes = [i32, i32, i32, P(i32), P(i32)]
     L.himg_hip_decode_scaled_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp]
@@ -541,6 +545,49 @@ class Engine:
                                                          C.byref(desc), _ptr(d_out), _ptr(d_status),
                                                          C.c_void_p(stream))
         self._check(rc, "decode_regions_tensor_device")
+
+    def decode_into_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_dst, dst,
+                           origins, d_status, stream=0):
+        """himg_hip_decode_into_device: the contract of decode_device, with frame f's picture written
+        at origin (x_f, y_f) = origins[f] of destination picture f of `dst` (dst_desc; frame_pitch 0:
+        every frame into ONE picture).  origins: (batch, 2) int32, on the host.  Nothing but the
+        pictures' own channel bytes is written."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_decode_into_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch, width,
+                                               height, channels, _ptr(d_dst), C.byref(dst), org.ctypes.data,
+                                               _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_into_device")
+
+    def decode_regions_into_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, src_origins,
+                                   w, h, d_dst, dst, dst_origins, d_status, stream=0):
+        """himg_hip_decode_regions_into_device: the contract of decode_regions_device (window w x h at
+        src_origins[f] of frame f), written at dst_origins[f] of destination picture f of `dst`
+        (dst_desc)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        so = np.ascontiguousarray(np.asarray(src_origins, np.int32).reshape(batch, 2))
+        do = np.ascontiguousarray(np.asarray(dst_origins, np.int32).reshape(batch, 2))
+        rc = lib().himg_hip_decode_regions_into_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch,
+                                                       width, height, channels, so.ctypes.data, int(w), int(h),
+                                                       _ptr(d_dst), C.byref(dst), do.ctypes.data, _ptr(d_status),
+                                                       C.c_void_p(stream))
+        self._check(rc, "decode_regions_into_device")
+
+    def decode_into(self, packed, data, dst, x, y):
+        """himg_hip_decode_into_to: the picture of the host stream `packed` into the host picture `data`
+        (a writable, contiguous uint8 array laid out as `dst` says: dst_desc) at (x, y).  Returns
+        (width, height, channels) of the stream."""
+        packed = _as_u8(packed)
+        if not (isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.flags.c_contiguous and data.flags.writeable):
+            raise HimgError(HIMG_ERR_ARG, "decode_into: data must be a writable contiguous uint8 array")
+        # (the array holds the whole picture `dst` describes: the library writes inside that picture only)
+        if dst.height < 1 or (dst.height - 1) * dst.row_pitch + dst.width * dst.pixel_stride > data.nbytes:
+            raise HimgError(HIMG_ERR_ARG, "decode_into: data is smaller than the picture dst describes")
+        w, h, c = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().himg_hip_decode_into_to(self._ctx, packed.ctypes.data, packed.nbytes, data.ctypes.data,
+                                           C.byref(dst), int(x), int(y), C.byref(w), C.byref(h), C.byref(c))
+        self._check(rc, "decode_into")
+        return w.value, h.value, c.value
 
     def decode_scaled(self, packed, scale_log2, out=None):
         """The picture at 1/2 (scale_log2 = 1) or 1/4 (2) scale (himg_hip_decode_scaled_to) as a
@@ -1066,6 +1113,37 @@ def windows_extent(src, channels, origins, w, h):
                                        C.byref(n))
     if rc != 0:
         raise HimgError(rc, "windows_extent")
+    return n.value
+
+
+class DstDesc(C.Structure):
+    """himg_hip_dst."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("pixel_stride", C.c_int), ("row_pitch", C.c_size_t),
+                ("frame_pitch", C.c_size_t)]
+
+
+def dst_desc(width, height, pixel_stride, row_pitch=None, frame_pitch=None):
+    """A himg_hip_dst: destination pictures of width x height pixels, pixel_stride bytes per pixel, rows
+    row_pitch bytes apart (default: packed) and pictures frame_pitch bytes apart (default:
+    height * row_pitch; 0: every window of a call lies in ONE picture).  The library validates it
+    (dst_extent, the decode_into calls)."""
+    d = DstDesc()
+    d.width, d.height, d.pixel_stride = int(width), int(height), int(pixel_stride)
+    d.row_pitch = int(width) * int(pixel_stride) if row_pitch is None else int(row_pitch)
+    d.frame_pitch = int(height) * d.row_pitch if frame_pitch is None else int(frame_pitch)
+    return d
+
+
+def dst_extent(dst, channels, origins, w, h):
+    """himg_hip_dst_extent (no GPU): the bytes of the destination buffer that the w x h windows at
+    `origins` ((batch, 2): x_f, y_f) of `dst` reach -- nothing at or beyond is written.  Raises
+    HimgError (HIMG_ERR_ARG) for a descriptor or a window that the decode_into calls reject."""
+    org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+    n = C.c_size_t()
+    rc = lib().himg_hip_dst_extent(C.byref(dst), int(channels), len(org), org.ctypes.data, int(w), int(h),
+                                   C.byref(n))
+    if rc != 0:
+        raise HimgError(rc, "dst_extent")
     return n.value
 
 

@@ -1,6 +1,7 @@
-// The body of k_dec_region and of its tensor form k_dec_region_t: one copy, included behind each
-// kernel's own parameters (g, ws, packed, in_stride, sizes, ra) with kRegionTens and td (the
-// descriptor, or nullptr) defined, so that k_dec_region keeps its code instruction for instruction.
+// The body of k_dec_region, of its tensor form k_dec_region_t and of its pitched form k_dec_region_p:
+// one copy, included behind each kernel's own parameters (g, ws, packed, in_stride, sizes, ra) with
+// kRegionTens and td, kRegionPitch and pd (the descriptors, or nullptr) defined, so that k_dec_region
+// keeps its code instruction for instruction.
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const RegionLayout L = region_layout(g.C, ra.sw);
   LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
@@ -93,6 +94,7 @@
   const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
   uint8_t *img;
   if constexpr (kRegionTens) img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * (size_t)(td->co * tens_elem_size(td->dtype)));
+  else if constexpr (kRegionPitch) img = dst_frame(ra.out, pd, f);
   else img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
   const int ycbcr = df->ycbcr;
   const int per_row = ((ww + 31) >> 5) * 64;   // whole wavefronts: both lanes of a pair are active
@@ -101,6 +103,6 @@
     const int ul = pair_tile(it);
     const bool in_strip = ul < ww;
     const int uc = in_strip ? ul : ww - 1;
-    transform_store_region<kRegionTens>(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
-                                 pair_half(it), r, rr, img, in_strip, td);
+    transform_store_region<kRegionTens, kRegionPitch>(g, (int)L.seg, sym + 4 + uc, low, s_unmap, s_shift, s_shiftp, ycbcr, su0 + uc,
+                                 pair_half(it), r, rr, img, in_strip, td, pd);
   }

@@ -360,14 +360,27 @@ struct TensDesc {
 };
 __host__ __device__ inline int tens_elem_size(int dtype) { return dtype == 0 ? 4 : 2; }
 
+// The pitched destination (himg_hip_dst as the kernels take it): pixel (i, j), channel c of frame f's
+// decoded picture -- or of its window, for the region decode -- is the byte at
+//   d_out + f * frame_pitch + (org[2 f + 1] + i) * row_pitch + (org[2 f] + j) * pixel_stride + c.
+// It travels in the kernel-argument segment of the pitched forms of the store kernels
+// (k_dec_row_fused_p, k_tile_inv_p, k_dec_region_p), which read the pitch and the stride there at
+// their stores; org is on the device, behind the packed sizes (and the region decode's own origins).
+struct DstDesc {
+  size_t row_pitch, frame_pitch;
+  const int32_t *org;
+  int pixel_stride;
+};
+
 // tens: the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W] elements);
-// everything in front of them is the same launch.
+// dst: in their pitched form (d_out: the destination pictures); not both.
+// Everything in front of them is the same launch.
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3,
-                   const TensDesc *tens = nullptr);
+                   const TensDesc *tens = nullptr, const DstDesc *dst = nullptr);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 // The 1/8-scale preview: the zeroing of the LRES symbols, the container parse up to the end of
 // the LRES chunk (k_dec_parse_head, which writes where that chunk ends to d_head_sizes[f]), the
@@ -395,7 +408,8 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
 void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds, const TensDesc *tens = nullptr);   // (tens: scale_log2 = 0 only, [batch][co][h][w])
+                   const DecStreams *ds, const TensDesc *tens = nullptr,   // (tens: scale_log2 = 0 only, [batch][co][h][w])
+                   const DstDesc *dst = nullptr);                          // (dst: scale_log2 = 0 only, windows of the pictures)
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
 // The scaled decode (k_dec_scaled): every frame of the batch at 1 / 2^scale_log2 (1 or 2) of its

@@ -517,10 +517,12 @@ static int stage_words(himg_hip_ctx *ctx, void *d_dst, const void *a, size_t na,
   r.busy[k] = true;
   return HIMG_OK;
 }
-// `n` packed sizes on their way to the decoder's d_sizes.  org (the region decode): n origins
-// (x, y) follow the sizes, in the same slot and the same copy.
-static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s, const int32_t *org = nullptr) {
-  return stage_words(ctx, ctx->d_sizes.p, src, (size_t)n, org, org ? (size_t)n * 2 : 0, s);
+// `n` packed sizes on their way to the decoder's d_sizes.  org (the region decode, the decodes into
+// pitched pictures): n origins (x, y) follow the sizes, in the same slot and the same copy -- org_sets
+// of them, one after the other (the region decode into pictures: the windows', then the destinations').
+static int stage_sizes(himg_hip_ctx *ctx, const uint32_t *src, int n, hipStream_t s, const int32_t *org = nullptr,
+                       int org_sets = 1) {
+  return stage_words(ctx, ctx->d_sizes.p, src, (size_t)n, org, org ? (size_t)n * 2 * (size_t)org_sets : 0, s);
 }
 
 static int ensure_enc_ws(himg_hip_ctx *ctx, const Geom &g, int batch, bool allow_row_tokens = true, bool force_row_tokens = false) {
@@ -601,7 +603,8 @@ static int wide_q_hint(const Geom &g, uint32_t max_packed_size) {
 // no row index, lane records or FRES symbol plane (a 16384^2 frame's would be hundreds of MB),
 // the LRES stream's tables only; d_sizes holds the packed sizes, then where each LRES chunk ends.
 // region (the region decode): no FRES symbol plane and no quarter records either; d_sizes holds the
-// packed sizes, then each frame's origin (x, y).
+// packed sizes, then each frame's origin (x, y).  (Either kind has room for two origins per frame
+// behind the sizes: a destination origin, decode_full / region_launch.)
 enum DecWsKind { kWsFull, kWsHead, kWsRegion };
 static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind kind) {
   const bool head_only = kind == kWsHead, region = kind == kWsRegion;
@@ -627,7 +630,7 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind 
       !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (region || himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
       !ctx->d_rows.reserve((size_t)batch * g.rows * 4 * 2) || !ctx->d_lres.reserve(lres * batch) ||
       (!region && !ctx->d_fres.reserve(fres * batch)) || !ctx->d_planes.reserve(plane * batch) ||
-      !ctx->d_sizes.reserve((size_t)batch * (region ? 12 : 4)) ||
+      !ctx->d_sizes.reserve((size_t)batch * 20) ||
       !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4 + (size_t)batch * g.rows * 8) * 4))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
   w.frames = (DecFrame *)ctx->d_frames.p;
@@ -740,13 +743,13 @@ static int decode_args(himg_hip_ctx *ctx, int width, int height, int num_channel
 }
 
 // The reservation: the device, the workspace, the caller's stream as the context's last one, and the
-// packed sizes (org: with each frame's origin, see stage_sizes) on their way to *d_sizes.
+// packed sizes (org: with each frame's origins, see stage_sizes) on their way to *d_sizes.
 static int decode_begin(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind kind, const uint32_t *h_sizes,
-                        void *stream, const uint32_t **d_sizes, const int32_t *org = nullptr) {
+                        void *stream, const uint32_t **d_sizes, const int32_t *org = nullptr, int org_sets = 1) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (int rc = ensure_dec_ws(ctx, g, batch, kind)) return rc;
   ctx->last_stream = (hipStream_t)stream;
-  if (int rc = stage_sizes(ctx, h_sizes, batch, ctx->last_stream, org)) return rc;
+  if (int rc = stage_sizes(ctx, h_sizes, batch, ctx->last_stream, org, org_sets)) return rc;
   *d_sizes = (const uint32_t *)ctx->d_sizes.p;
   return HIMG_OK;
 }
@@ -950,11 +953,12 @@ extern "C" int himg_hip_encode_sse_device(himg_hip_ctx *ctx, const void *d_frame
 // ---- windows of pitched source pictures -------------------------------------------------------
 
 // The host checks of a source descriptor and its windows (include/himg_hip.h); *bytes: the end of the
-// last byte a window owns.  Returns what is wrong, or nullptr.
+// last byte a window owns.  Returns what is wrong, or nullptr.  (dst_check: the same rules for the
+// pictures a decode writes into.)
 static const char *windows_check(const himg_hip_src *src, int num_channels, int batch, const int32_t *h_origins, int w,
                                  int h, size_t *bytes) {
   if (!src || !h_origins || batch < 1) return "bad argument";
-  if (src->width < 1 || src->height < 1 || w < 1 || h < 1) return "a source or window size that is not positive";
+  if (src->width < 1 || src->height < 1 || w < 1 || h < 1) return "a picture or window size that is not positive";
   if (num_channels < 1 || num_channels > 4 || src->pixel_stride < num_channels) return "pixel_stride below num_channels";
   typedef unsigned __int128 u128;
   const u128 ps = (u128)src->pixel_stride, rp = src->row_pitch, fp = src->frame_pitch;
@@ -965,11 +969,11 @@ static const char *windows_check(const himg_hip_src *src, int num_channels, int 
   u128 end = 0;
   for (int f = 0; f < batch; ++f) {
     const int x = h_origins[2 * f], y = h_origins[2 * f + 1];
-    if (x < 0 || y < 0 || w > src->width - x || h > src->height - y) return "a window outside the source picture";
+    if (x < 0 || y < 0 || w > src->width - x || h > src->height - y) return "a window outside its picture";
     const u128 e = (u128)f * fp + (u128)(y + h - 1) * rp + (u128)(x + w) * ps;
     if (e > end) end = e;
   }
-  if (end > (u128)SIZE_MAX) return "a source that does not fit the address space";
+  if (end > (u128)SIZE_MAX) return "pictures that do not fit the address space";
   *bytes = (size_t)end;
   return nullptr;
 }
@@ -1087,23 +1091,36 @@ extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int n
   return HIMG_OK;
 }
 
+// The launch behind the full decodes of a batch in HBM: the interleaved bytes (himg_hip_decode_device),
+// the planar float output (td) or windows of pitched pictures (dd, with each frame's origin in h_org:
+// the origins ride with the sizes, dd->org is filled in here).  bad: what the caller found wrong with
+// its descriptor.
+static int decode_full(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
+                       int width, int height, int num_channels, void *d_out, int32_t *d_status, void *stream,
+                       const char *bad, const himg_dev::TensDesc *td, himg_dev::DstDesc *dd, const int32_t *h_org) {
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, bad, &g))
+    return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes, dd ? h_org : nullptr)) return rc;
+  if (dd) dd->org = (const int32_t *)(d_sizes + batch);
+  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
+                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows,
+                nullptr, false, 3, td, dd);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
 extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
                                       const uint32_t *h_sizes, int batch, int width, int height,
                                       int num_channels, void *d_out, int32_t *d_status,
                                       void *stream) {
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
-  Geom g;
-  const uint32_t *d_sizes = nullptr;
-  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, nullptr, &g))
-    return rc;
-  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
-  { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
-  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
-  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
-                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream,
+                     nullptr, nullptr, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1138,20 +1155,43 @@ extern "C" int himg_hip_decode_tensor_device(himg_hip_ctx *ctx, const void *d_pa
                                              int32_t *d_status, void *stream) {
   if (!ctx || !d_packed || !h_sizes || !t || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
-  Geom g;
-  const uint32_t *d_sizes = nullptr;
   himg_dev::TensDesc td;
   const char *bad = tensor_desc_ok(t, num_channels, &td) ? nullptr : "bad tensor descriptor";
-  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, bad, &g))
-    return rc;
-  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
-  { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
-  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
-  launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
-                (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows,
-                nullptr, false, 3, &td);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream, bad,
+                     &td, nullptr, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// Decode into windows of pitched destination pictures (include/himg_hip.h).  The descriptor and the
+// origins are checked on the host by the rules of the encoder's source windows (windows_check); the
+// descriptor rides in the kernel arguments of the store kernels, the origins with the sizes.
+// ---------------------------------------------------------------------------
+static const char *dst_check(const himg_hip_dst *dst, int num_channels, int batch, const int32_t *h_origins, int w, int h,
+                             size_t *bytes, himg_dev::DstDesc *dd = nullptr) {
+  if (!dst) return "bad argument";
+  const himg_hip_src s = {dst->width, dst->height, dst->pixel_stride, dst->row_pitch, dst->frame_pitch};
+  if (const char *bad = windows_check(&s, num_channels, batch, h_origins, w, h, bytes)) return bad;
+  if (dd) { dd->row_pitch = dst->row_pitch; dd->frame_pitch = dst->frame_pitch; dd->org = nullptr; dd->pixel_stride = dst->pixel_stride; }
+  return nullptr;
+}
+
+extern "C" int himg_hip_dst_extent(const himg_hip_dst *dst, int num_channels, int batch, const int32_t *h_origins,
+                                   int w, int h, size_t *bytes) {
+  if (!bytes) return HIMG_ERR_ARG;
+  *bytes = 0;
+  return dst_check(dst, num_channels, batch, h_origins, w, h, bytes) ? HIMG_ERR_ARG : HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_into_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                           const uint32_t *h_sizes, int batch, int width, int height,
+                                           int num_channels, void *d_dst, const himg_hip_dst *dst,
+                                           const int32_t *h_origins, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_dst || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  himg_dev::DstDesc dd;
+  size_t extent = 0;
+  const char *bad = dst_check(dst, num_channels, batch, h_origins, width, height, &extent, &dd);
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_dst, d_status, stream, bad,
+                     nullptr, &dd, h_origins);
 }
 
 extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_packed, uint32_t packed_size,
@@ -1802,6 +1842,34 @@ extern "C" int himg_hip_decode_to(himg_hip_ctx *ctx, const uint8_t *packed, size
   return HIMG_OK;
 }
 
+// The whole picture of a host stream into a host picture at (x, y): himg_hip_decode_to's decode, then
+// the rows copied at the picture's pitch and stride.  Plumbing, not a hot path.
+extern "C" int himg_hip_decode_into_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst_data,
+                                       const himg_hip_dst *dst, int x, int y, int *width, int *height, int *channels) {
+  if (!ctx || !packed || !width || !height || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  if (int rc = himg_hip_peek(packed, packed_size, &W, &H, &C)) return fail(ctx, rc, "not a HIMG stream");
+  *width = W; *height = H; *channels = C;
+  if (!dst_data || !dst) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  himg_hip_dst one = *dst;
+  one.frame_pitch = 0;
+  const int32_t org[2] = {x, y};
+  size_t extent = 0;
+  if (const char *bad = dst_check(&one, C, 1, org, W, H, &extent)) return fail(ctx, HIMG_ERR_ARG, bad);
+  if (int rc = decode_core(ctx, packed, packed_size, &W, &H, &C)) return rc;
+  std::vector<uint8_t> pix(ctx->host_bytes);
+  HIP_TRY(ctx, hipMemcpy(pix.data(), ctx->h_out.p, pix.size(), hipMemcpyDeviceToHost));
+  const size_t ps = (size_t)one.pixel_stride;
+  for (int i = 0; i < H; ++i) {
+    const uint8_t *srow = pix.data() + (size_t)i * W * C;
+    uint8_t *drow = dst_data + (size_t)(y + i) * one.row_pitch + (size_t)x * ps;
+    if (ps == (size_t)C) memcpy(drow, srow, (size_t)W * C);
+    else
+      for (int j = 0; j < W; ++j) memcpy(drow + (size_t)j * ps, srow + (size_t)j * C, (size_t)C);
+  }
+  return HIMG_OK;
+}
+
 // ---- batched host API: frames in flight ------------------------------------------
 
 static int pipe_init(himg_hip_ctx *ctx) {
@@ -2115,10 +2183,16 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                          int width, int height, int num_channels, const int32_t *h_org, int w, int h,
                          const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0,
-                         const himg_hip_tensor_desc *tens = nullptr) {
+                         const himg_hip_tensor_desc *tens = nullptr, const himg_hip_dst *dst = nullptr,
+                         const int32_t *h_dst_org = nullptr) {
   if (scale_log2 < 0 || scale_log2 > 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
   himg_dev::TensDesc td;
   if (tens && (scale_log2 || !tensor_desc_ok(tens, num_channels, &td))) return fail(ctx, HIMG_ERR_ARG, "bad tensor descriptor");
+  // dst (scale_log2 = 0): d_out holds the destination pictures, frame f's window at h_dst_org[2 f], [2 f + 1].
+  himg_dev::DstDesc dd;
+  size_t extent = 0;
+  if (dst && scale_log2) return fail(ctx, HIMG_ERR_ARG, "a destination descriptor at full scale only");
+  const char *bad_dst = dst || h_dst_org ? dst_check(dst, num_channels, batch, h_dst_org, w, h, &extent, &dd) : nullptr;
   std::vector<int32_t> up_org;
   if (scale_log2) up_org.resize(2 * (size_t)batch);
   const char *bad = nullptr;
@@ -2130,13 +2204,20 @@ static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stri
   if (scale_log2) h_org = up_org.data();
   Geom g;
   const uint32_t *d_sizes = nullptr;
-  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, bad, &g))
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride,
+                           bad ? bad : bad_dst, &g))
     return rc;
-  // (the origins ride with the sizes: no extra copy, no wait)
-  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org)) return rc;
+  // (the origins ride with the sizes: no extra copy, no wait; the destinations' behind the windows')
+  if (dst) {
+    up_org.assign(h_org, h_org + 2 * (size_t)batch);
+    up_org.insert(up_org.end(), h_dst_org, h_dst_org + 2 * (size_t)batch);
+    h_org = up_org.data();
+  }
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org, dst ? 2 : 1)) return rc;
+  if (dst) dd.org = (const int32_t *)(d_sizes + 3 * (size_t)batch);
   launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
                 (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, (hipStream_t)stream,
-                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr, tens ? &td : nullptr);
+                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr, tens ? &td : nullptr, dst ? &dd : nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -2174,6 +2255,19 @@ extern "C" int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const vo
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
                        d_out, d_status, stream, 0, t);
+}
+
+extern "C" int himg_hip_decode_regions_into_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                   const uint32_t *h_sizes, int batch, int width, int height,
+                                                   int num_channels, const int32_t *h_src_origins, int w, int h,
+                                                   void *d_dst, const himg_hip_dst *dst, const int32_t *h_dst_origins,
+                                                   int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_src_origins || !d_dst || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if (!dst || !h_dst_origins) return fail(ctx, HIMG_ERR_ARG, "bad argument");
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_src_origins, w, h, nullptr,
+                       d_dst, d_status, stream, 0, nullptr, dst, h_dst_origins);
 }
 
 // The scaled region decode's device entry: a window of the picture at 1/2 or 1/4 scale.  A rectangle of

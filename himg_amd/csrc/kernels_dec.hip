@@ -22,6 +22,9 @@
 //                     the tensor forms of the three kernels that write full-resolution pixels: a
 //                     planar, normalised float32 / float16 / bfloat16 output converted in the store
 //                     stage (TensDesc; include/himg_hip.h, "tensor decode")
+//   k_dec_row_fused_p, k_tile_inv_p, k_dec_region_p
+//                     their pitched forms: the same interleaved bytes at a row pitch, a pixel
+//                     stride and an origin per frame (DstDesc; include/himg_hip.h, "decode into")
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
 #include "loop_counts.h"
@@ -2707,6 +2710,20 @@ __device__ __forceinline__ void tens_planes(uint32_t q0, uint32_t q1, uint32_t q
   }
   p3 = q3;
 }
+// The pitched destination (DstDesc) in the kernel-argument segment.  dst_at_use: the pointer made
+// opaque where the stores begin, so that the loads of the pitch and the stride cannot be moved up in
+// front of the transform and stay live across it.
+typedef const __attribute__((address_space(4))) DstDesc *DstK;
+__device__ __forceinline__ DstK dst_at_use(DstK pd) {
+  asm volatile("" : "+s"(pd));
+  return pd;
+}
+// Frame f's origin pixel in the destination (f is uniform: scalar loads).
+__device__ __forceinline__ uint8_t *dst_frame(uint8_t *out, DstK pd, int f) {
+  const int32_t *org = pd->org;
+  return out + (size_t)f * pd->frame_pitch + (size_t)org[2 * f + 1] * pd->row_pitch +
+         (size_t)org[2 * f] * (size_t)pd->pixel_stride;
+}
 // FULL4: four channels, whole tiles only (W and H multiples of 8) -- the ragged-edge
 // stores and the channel-count tests are compiled out.
 // SSE (k_sse, the encoder's distortion probe): nothing is stored -- the lane's four pixel rows are
@@ -2722,7 +2739,13 @@ __device__ __forceinline__ void tens_planes(uint32_t q0, uint32_t q1, uint32_t q
 // element alignment for whole tiles and element stores for the ragged right edge (tens_store8), rows
 // masked to H and channels to co.
 // Channels from co on are neither converted nor stored.
-template <int COLS, bool FULL4 = false, bool SSE = false, bool TENS = false>
+// PITCH (the pitched forms): the same pixel words at img + (8 v + y) * row_pitch + 8 u * pixel_stride,
+// img frame f's origin pixel (dst_frame), pd the descriptor in the kernel-argument segment, read at
+// the stores.  Which store, per tile row and from the address itself: 4-byte pixels of four channels --
+// a whole tile row at a 16-byte aligned address the two 16-byte stores, otherwise a dword per real
+// pixel (the host checks make every pixel 4-byte aligned); everything else the C channel bytes of
+// every real pixel.  No store covers a byte that is not a channel byte of a pixel of the picture.
+template <int COLS, bool FULL4 = false, bool SSE = false, bool TENS = false, bool PITCH = false>
 __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols_rt, const uint8_t *sym,
                                                      const uint8_t *low, const int16_t *s_unmap,
                                                      const uint8_t *s_shift, const uint32_t *s_shiftp,
@@ -2730,7 +2753,7 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
                                                      const uint32_t *pre_lr = nullptr, bool store_ok = true,
                                                      bool touched_on = false, uint32_t touched = 0,
                                                      const uint8_t *src = nullptr, int sstride = 0,
-                                                     TensK td = nullptr) {
+                                                     TensK td = nullptr, DstK pd = nullptr) {
   uint32_t sse = 0;
   const int cols = COLS > 0 ? COLS : cols_rt;
   const int C = FULL4 ? 4 : g.C;
@@ -2786,6 +2809,13 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
       // for a store.)
       __builtin_amdgcn_s_waitcnt(0x0f70);   // vmcnt(0)
       asm volatile("" :: "v"(touched));
+    }
+    // (PITCH: the pitch and the stride, read once here -- behind the transform, for the four rows)
+    size_t row_pitch = 0;
+    int ps = 0;
+    if constexpr (PITCH) {
+      const DstK pk = dst_at_use(pd);
+      row_pitch = pk->row_pitch; ps = pk->pixel_stride;
     }
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
@@ -2863,6 +2893,28 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
                   const int d = (int)((px[x] >> (8 * c)) & 255u) - (int)sp[x * sstride + c];
                   sse += (uint32_t)(d * d);
                 }
+          }
+        }
+      } else if constexpr (PITCH) {
+        if (store_ok && (FULL4 || y < bh)) {
+          uint8_t *dst = img + (size_t)(8 * v + y) * row_pitch + (size_t)(8 * u) * (size_t)ps;
+          if (C == 4 && ps == 4) {
+            if ((FULL4 || bw == 8) && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
+              uint4 o0, o1;
+              o0.x = px[0]; o0.y = px[1]; o0.z = px[2]; o0.w = px[3];
+              o1.x = px[4]; o1.y = px[5]; o1.z = px[6]; o1.w = px[7];
+              reinterpret_cast<uint4 *>(dst)[0] = o0;
+              reinterpret_cast<uint4 *>(dst)[1] = o1;
+            } else {
+#pragma unroll
+              for (int x = 0; x < 8; ++x)
+                if (x < bw) reinterpret_cast<uint32_t *>(dst)[x] = px[x];
+            }
+          } else {
+#pragma unroll
+            for (int x = 0; x < 8; ++x)
+              if (x < bw)
+                for (int c = 0; c < C; ++c) dst[(size_t)x * ps + c] = (uint8_t)(px[x] >> (8 * c));
           }
         }
       } else
@@ -2990,6 +3042,49 @@ __global__ __launch_bounds__(256) void k_tile_inv_t(TileArgsT a) {
       pair_half(it), v, a.out_frames + (size_t)f * frame_bytes, nullptr, true, false, 0, nullptr, 0, td);
 }
 
+// k_tile_inv_p: k_tile_inv in its pitched form (DstDesc): frame f's picture at its origin in the
+// destination.  The arguments in one struct, as in k_tile_inv_t.
+struct TileArgsP {
+  Geom g;
+  DecWs ws;
+  uint8_t *out_frames;
+  int v0;
+  DstDesc d;
+};
+template <bool FAST>
+__global__ __launch_bounds__(256) void k_tile_inv_p(TileArgsP a) {
+  __shared__ int16_t s_unmap[256];   // indexed by the code byte
+  __shared__ uint8_t s_shift[2][64];
+  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const DstK pd = &((const __attribute__((address_space(4))) TileArgsP *)__builtin_amdgcn_kernarg_segment_ptr())->d;
+  const int v = blockIdx.y + a.v0, f = blockIdx.z;
+  const DecFrame *df = ws.frames + f;
+  __shared__ int s_status;
+  if (threadIdx.x == 0) s_status = df->status;
+  __syncthreads();
+  if (s_status) return;
+  {
+    const int k = threadIdx.x;
+    const int sc = (int8_t)k;
+    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
+    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
+    if (k < 64) {
+      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
+      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
+    }
+    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
+  }
+  __syncthreads();
+  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
+  if (pair_tile(it) >= g.cols) return;
+  transform_store_pair<(FAST ? -1 : 0), FAST, false, false, true>(
+      g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
+      ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp, df->ycbcr, pair_tile(it),
+      pair_half(it), v, dst_frame(a.out_frames, pd, f), nullptr, true, false, 0, nullptr, 0, nullptr, pd);
+}
+
 // ---------------------------------------------------------------------------
 // k_sse: the encoder's distortion probe (himg_hip_encode_sse_device).  k_tile_inv's transform on
 // the ENCODER's symbol plane (the same [rows][C][64][cols] layout) and its reconstructed low-res
@@ -3043,13 +3138,15 @@ __global__ __launch_bounds__(256) void k_sse(Geom g, const uint8_t *frames, cons
 // after the other (each by all 1024 lanes) and then transformed together.
 // TENS: the planar float output (transform_store_pair's tensor form); out_frames is then the
 // [batch][co][H][W] buffer and td the descriptor in the kernel-argument segment.
-template <int COLS, bool TENS = false>
+// PITCH: the pitched output (transform_store_pair's pitched form); out_frames is then the first
+// destination picture and pd the descriptor in the kernel-argument segment.
+template <int COLS, bool TENS = false, bool PITCH = false>
 __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &ws, const uint8_t *packed,
                                                    size_t in_stride, const uint32_t *sizes,
                                                    uint8_t *out_frames, int r0, int r1, int rpw,
                                                    const int bx, const int f, const int gx, const int gy,
                                                    const uint32_t next_lin, const bool again, const bool same_tables,
-                                                   TensK td = nullptr) {
+                                                   TensK td = nullptr, DstK pd = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   if (COLS == 512) rpw = 1;   // 4096-pixel rows: one row fills the lanes and the LDS (known at compile time)
   const FusedLayout L = fused_layout(g.row_block, rpw);
@@ -3243,6 +3340,7 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   // stay read-only in LDS: no barrier, no second pass over them.
   uint8_t *img;
   if constexpr (TENS) img = out_frames + (size_t)f * ((size_t)g.W * g.H * (size_t)(td->co * tens_elem_size(td->dtype)));
+  else if constexpr (PITCH) img = dst_frame(out_frames, pd, f);
   else img = out_frames + (size_t)f * ((size_t)g.W * g.H * g.C);
   const int per_row = ((cols + 31) >> 5) * 64;   // whole wavefronts: a lane pair never straddles rows
   HIMG_SPAN_BEGIN("dec.transform");
@@ -3253,10 +3351,10 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
     // transforms the last tile once more and stores nothing: no exec-masked region around
     // the transform (with compile-time strides it cost 50 VGPR spills at 1920 pixels).
     const bool in_row = pair_tile(il) < cols;
-    transform_store_pair<COLS, COLS != 0, false, TENS>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
+    transform_store_pair<COLS, COLS != 0, false, TENS, PITCH>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
                                             in_row ? pair_tile(il) : cols - 1, pair_half(il), rb + i, img,
                                             COLS == 512 ? pre_lr : nullptr, in_row, pf_on && it == tid, pf_a,
-                                            nullptr, 0, td);
+                                            nullptr, 0, td, pd);
   }
   HIMG_SPAN_END("dec.transform");
   // A wavefront without a transform iteration (per_row * nr < 1024: narrow rows in a frame's last
@@ -3366,6 +3464,40 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_t(RowArgsT) {
     dec_row_fused_body<COLS, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
                                    ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
                                    nd ? lin + nd : element(i + 1), again, f == f_prev, &ka->t);
+    again = true;
+    f_prev = f;
+  }
+}
+
+// k_dec_row_fused_p: the same kernel in its pitched form.  RowArgs -- unchanged -- followed by the
+// destination descriptor, which stays in the kernel-argument segment: the frame's origin is read
+// where the transform phase begins, the pitch and the stride at the stores.
+struct RowArgsP {
+  RowArgs a;
+  DstDesc d;
+};
+template <int COLS>
+__global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_p(RowArgsP) {
+  typedef const __attribute__((address_space(4))) RowArgsP *KArgs;
+  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
+  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
+  bool again = false;
+  int f_prev = -1;
+#pragma unroll 1
+  for (uint32_t i = 0; i * S < total; ++i) {
+    const uint32_t lin = element(i);
+    if (lin >= total) break;   // (the last round is a partial one)
+    asm volatile("" : "+s"(ka));
+    Geom g;
+    DecWs ws;
+    karg_copy<uint32_t>(&g, &ka->a.g);
+    karg_copy<unsigned long long>(&ws, &ka->a.ws);
+    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
+    const uint32_t nd = (uint32_t)ka->a.next_dist;
+    dec_row_fused_body<COLS, false, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
+                                          ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
+                                          nd ? lin + nd : element(i + 1), again, f == f_prev, nullptr, &ka->d);
     again = true;
     f_prev = f;
   }
@@ -4208,12 +4340,15 @@ __device__ __forceinline__ bool region_walk(GReader &rd, const GrpTables &t, uin
 // planes at the global tile u, and the stores cropped to the rectangle (row pitch w * C).
 // TENS: the planar float output (TensDesc) -- img is frame f's [co][h][w] elements, row pitch w
 // elements per plane, element stores (a window's rows are only element-aligned).
-template <bool TENS = false>
+// PITCH: the pitched output (DstDesc) -- img is the window's origin pixel in frame f's destination
+// picture (dst_frame), rows row_pitch apart, pixels pixel_stride apart: a dword per pixel where four
+// channels meet 4-byte pixels, the C channel bytes otherwise.
+template <bool TENS = false, bool PITCH = false>
 __device__ __forceinline__ void transform_store_region(const Geom &g, int sstride, const uint8_t *sym,
                                                        const uint8_t *low, const int16_t *s_unmap,
                                                        const uint8_t *s_shift, const uint32_t *s_shiftp, int ycbcr,
                                                        int u, int s, int v, const RegionRect &ra, uint8_t *img,
-                                                       bool store_ok, TensK td = nullptr) {
+                                                       bool store_ok, TensK td = nullptr, DstK pd = nullptr) {
   const int cols = g.cols, C = g.C;
   const int v2 = min(v + 1, g.rows - 1), u2 = min(u + 1, cols - 1);
   uint32_t QA[16], QB[16];
@@ -4247,6 +4382,14 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
     ch1[i] = rb_[0]; ch3[i] = rb_[1];
   }
   if (!store_ok) return;
+  // (PITCH: the pitch and the stride, read once here -- behind the transform, for the four rows)
+  size_t row_pitch = (size_t)ra.w * C;
+  int pstr = C;       // bytes from a pixel to the next
+  if constexpr (PITCH) {
+    const DstK pk = dst_at_use(pd);
+    row_pitch = pk->row_pitch; pstr = pk->pixel_stride;
+  }
+  const bool word = C == 4 && pstr == 4;
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int py = 8 * v + 4 * s + rr - ra.y;   // pixel row in the rectangle
@@ -4275,7 +4418,7 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
       }
       continue;
     }
-    uint8_t *drow = img + (size_t)py * ra.w * C;
+    uint8_t *drow = img + (size_t)py * row_pitch;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       uint32_t q0 = ch0[rr * 2 + h], q1 = ch1[rr * 2 + h], q2 = ch2[rr * 2 + h], q3 = ch3[rr * 2 + h];
@@ -4286,8 +4429,8 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
         const uint32_t c3 = (q3 >> (8 * k)) & 255u;
         if (px < 0 || px >= ra.w) continue;
         if (ycbcr) ycc_to_rgb(c0, c1, c2);   // ycbcr.cpp:54-82
-        uint8_t *d = drow + (size_t)px * C;
-        if (C == 4) {
+        uint8_t *d = drow + (size_t)px * pstr;
+        if (word) {
           *reinterpret_cast<uint32_t *>(d) = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);   // (4 w C per row: dword aligned)
         } else {
           d[0] = (uint8_t)c0;
@@ -4301,8 +4444,9 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
 
 __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, RegionArgs ra) {
-  constexpr bool kRegionTens = false;
+  constexpr bool kRegionTens = false, kRegionPitch = false;
   const TensK td = nullptr;
+  const DstK pd = nullptr;
 #include "dec_body_region.inc"
 }
 
@@ -4319,7 +4463,8 @@ struct RegionArgsT {
   TensDesc t;
 };
 __global__ __launch_bounds__(kDecThreads) void k_dec_region_t(RegionArgsT a) {
-  constexpr bool kRegionTens = true;
+  constexpr bool kRegionTens = true, kRegionPitch = false;
+  const DstK pd = nullptr;
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
   const uint8_t *packed = a.packed;
@@ -4327,6 +4472,31 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_region_t(RegionArgsT a) {
   const uint32_t *sizes = a.sizes;
   const RegionArgs &ra = a.ra;
   const TensK td = &((const __attribute__((address_space(4))) RegionArgsT *)__builtin_amdgcn_kernarg_segment_ptr())->t;
+#include "dec_body_region.inc"
+}
+
+// k_dec_region_p: the same kernel in its pitched form -- frame f's window w x h at the origin
+// d.org[2 f], d.org[2 f + 1] of its destination picture (ra.out: the first picture; ra.org stays the
+// window's origin in the decoded picture).
+struct RegionArgsP {
+  Geom g;
+  DecWs ws;
+  const uint8_t *packed;
+  size_t in_stride;
+  const uint32_t *sizes;
+  RegionArgs ra;
+  DstDesc d;
+};
+__global__ __launch_bounds__(kDecThreads) void k_dec_region_p(RegionArgsP a) {
+  constexpr bool kRegionTens = false, kRegionPitch = true;
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const uint8_t *packed = a.packed;
+  const size_t in_stride = a.in_stride;
+  const uint32_t *sizes = a.sizes;
+  const RegionArgs &ra = a.ra;
+  const TensK td = nullptr;
+  const DstK pd = &((const __attribute__((address_space(4))) RegionArgsP *)__builtin_amdgcn_kernarg_segment_ptr())->d;
 #include "dec_body_region.inc"
 }
 
@@ -4919,7 +5089,10 @@ hipError_t dec_set_kernel_attrs() {
                          reinterpret_cast<const void *>(&k_dec_row_fused<0>),
                          reinterpret_cast<const void *>(&k_dec_row_fused_t<512>),
                          reinterpret_cast<const void *>(&k_dec_row_fused_t<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_t<0>)};
+                         reinterpret_cast<const void *>(&k_dec_row_fused_t<0>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_p<512>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_p<-1>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_p<0>)};
   for (const void *k : fused) {
     // (the kernel's static LDS counts against the same 160 KiB)
     hipFuncAttributes fa;
@@ -4939,6 +5112,10 @@ hipError_t dec_set_kernel_attrs() {
   if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region_t));
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_t), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(kLdsMax - fa.sharedSizeBytes));
+  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region_p));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_p), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(kLdsMax - fa.sharedSizeBytes));
   const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
                           reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>),
@@ -5053,7 +5230,7 @@ static WindowExtents window_extents(const Geom &g, int batch, const int32_t *h_o
 void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds, const TensDesc *tens) {
+                   const DecStreams *ds, const TensDesc *tens, const DstDesc *dst) {
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
   const int F = 1 << scale_log2, hf = F * h;
@@ -5096,8 +5273,12 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   if (!scale_log2) {
     RegionArgs ra;
     ra.org = d_org; ra.sw = sw; ra.w = w; ra.h = h; ra.out = d_out;
-    prof_begin(prof, tens ? "k_dec_region_t" : "k_dec_region", stream);
-    if (tens) {
+    prof_begin(prof, tens ? "k_dec_region_t" : dst ? "k_dec_region_p" : "k_dec_region", stream);
+    if (dst) {
+      RegionArgsP rp;
+      rp.g = g; rp.ws = ws; rp.packed = d_packed; rp.in_stride = in_stride; rp.sizes = d_sizes; rp.ra = ra; rp.d = *dst;
+      hipLaunchKernelGGL(k_dec_region_p, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, rp);
+    } else if (tens) {
       RegionArgsT rt;
       rt.g = g; rt.ws = ws; rt.packed = d_packed; rt.in_stride = in_stride; rt.sizes = d_sizes; rt.ra = ra; rt.t = *tens;
       hipLaunchKernelGGL(k_dec_region_t, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, rt);
@@ -5190,7 +5371,8 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
-                   const uint32_t *d_row_index, bool index_only, int phase, const TensDesc *tens) {
+                   const uint32_t *d_row_index, bool index_only, int phase, const TensDesc *tens,
+                   const DstDesc *dst) {
   // d_row_index: the FRES row index is given (k_dec_set_index instead of the serial
   // header walk; one frame).  index_only: container parse and row-header walk only --
   // the caller reads ws.row_off / ws.row_len / DecFrame::rows_first (rank 0 of a
@@ -5353,6 +5535,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       rt_.a = ra_; rt_.t = *tens;                                                               \
       hipLaunchKernelGGL((k_dec_row_fused_t<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
                          dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rt_); \
+    } else if (dst) {                                                                           \
+      RowArgsP rp_;                                                                             \
+      rp_.a = ra_; rp_.d = *dst;                                                                \
+      hipLaunchKernelGGL((k_dec_row_fused_p<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
+                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rp_); \
     } else                                                                                      \
     hipLaunchKernelGGL((k_dec_row_fused<COLS>), dim3((unsigned)(pers_ ? slots_ : all_)),        \
                        dim3(kDecThreads), lds, stream, ra_);                                    \
@@ -5362,11 +5549,13 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       if (ds) (void)hipStreamWaitEvent(stream, ds->ev_cnt[k], 0);
       else row_count(stream, a, b);
       if (b <= a) continue;
-      // (tensor forms: <512>, <-1> -- which also serves 2048 and 1920 -- and <0>)
+      // (tensor and pitched forms: <512>, <-1> -- which also serves 2048 and 1920 -- and <0>)
       const bool whole4 = g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0;   // FULL4
-      // (the tensor forms carry their instantiation in the stage name: the tests assert which one ran)
-      prof_begin(prof, !tens ? "k_dec_row_fused" : g.W == 4096 && whole4 ? "k_dec_row_fused_t<512>"
-                                                 : whole4 ? "k_dec_row_fused_t<-1>" : "k_dec_row_fused_t<0>", stream);
+      // (the tensor and pitched forms carry their instantiation in the stage name: the tests assert which one ran)
+      const int form = g.W == 4096 && whole4 ? 0 : whole4 ? 1 : 2;
+      static const char *const kTensName[3] = {"k_dec_row_fused_t<512>", "k_dec_row_fused_t<-1>", "k_dec_row_fused_t<0>"};
+      static const char *const kPitchName[3] = {"k_dec_row_fused_p<512>", "k_dec_row_fused_p<-1>", "k_dec_row_fused_p<0>"};
+      prof_begin(prof, tens ? kTensName[form] : dst ? kPitchName[form] : "k_dec_row_fused", stream);
       if (g.W == 4096 && whole4) HIMG_FUSED_LAUNCH(512, a, b);
       else if (g.W == 2048 && whole4) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
       else if (g.W == 1920 && whole4) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
@@ -5388,6 +5577,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
         ta.g = g; ta.ws = ws; ta.out_frames = d_out; ta.v0 = a; ta.t = *tens;
         if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_t<true>, dim3(gx, b - a, batch), dim3(256), ta);
         else HIMG_LAUNCH(k_tile_inv_t<false>, dim3(gx, b - a, batch), dim3(256), ta);
+      } else if (dst) {
+        TileArgsP tp;
+        tp.g = g; tp.ws = ws; tp.out_frames = d_out; tp.v0 = a; tp.d = *dst;
+        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_p<true>, dim3(gx, b - a, batch), dim3(256), tp);
+        else HIMG_LAUNCH(k_tile_inv_p<false>, dim3(gx, b - a, batch), dim3(256), tp);
       } else
       if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv<true>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
       else HIMG_LAUNCH(k_tile_inv<false>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);

@@ -497,6 +497,82 @@ int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packe
                                   uint8_t *const *dst, const size_t *dst_cap,
                                   int *widths, int *heights, int *channels);
 
+/* ---- decode into windows of pitched destination pictures ------------------------- */
+/*
+ * The decode entry points above write batch x H x W x C tightly packed bytes.  These take a row pitch,
+ * a pixel stride and an origin per frame, the way himg_hip_encode_windows_device does on the other
+ * side: a surface with padded rows (hipMallocPitch), an RGB stream into an RGBA buffer that keeps its
+ * alpha, a region pasted into a canvas, or the tile streams of one large picture stitched where they
+ * belong (frame_pitch = 0) -- without a second pass that moves every output byte again.
+ */
+typedef struct himg_hip_dst {
+  int width, height;      /* the destination pictures in pixels: every window lies inside */
+  int pixel_stride;       /* bytes from a pixel to the next, >= num_channels */
+  size_t row_pitch;       /* bytes from a row to the next, >= width * pixel_stride */
+  size_t frame_pitch;     /* bytes from destination picture f to f + 1; 0: all windows lie in ONE picture */
+} himg_hip_dst;
+
+/* Where the bytes go.  Frame f's decoded picture is W x H (himg_hip_decode_into_device), or the window
+ * w x h at (sx_f, sy_f) = h_src_origins[2 f], [2 f + 1] of the decoded picture, under the rectangle
+ * rules of himg_hip_decode_regions_device (himg_hip_decode_regions_into_device).  Its pixel (i, j),
+ * channel c < C, is written to
+ *   d_dst + f * frame_pitch + (y_f + i) * row_pitch + (x_f + j) * pixel_stride + c,
+ * (x_f, y_f) = h_origins[2 f], h_origins[2 f + 1] (h_dst_origins), and is byte for byte what
+ * himg_hip_decode_device (himg_hip_decode_regions_device) writes for that stream under the same
+ * HIMG_OPT_FIX_T2 setting.
+ *
+ * Nothing else is written: not bytes C .. pixel_stride - 1 of a pixel (an RGB stream decoded into RGBA
+ * keeps the alpha that was there), not the row padding, not pixels outside the window, not the gap
+ * between pictures, and nothing at or beyond *bytes of himg_hip_dst_extent: the largest
+ *   f * frame_pitch + (y_f + h - 1) * row_pitch + (x_f + w) * pixel_stride
+ * over the batch -- a buffer may end with its last window's last pixel.  The kernels use a 16-byte or a
+ * 4-byte store only where every byte it covers is one of these.
+ *
+ * Status: frame f's d_status is exactly himg_hip_decode_device's (himg_hip_decode_regions_device's,
+ * with that entry's bytes-used rule).  A failed frame's window holds unspecified bytes; nothing outside
+ * that window is touched and its neighbours are unaffected.  The calls are asynchronous: the origins
+ * are HOST arrays of 2 * batch values that ride to the device with the sizes, the descriptor travels
+ * in the kernel arguments.
+ *
+ * Overlapping windows of different frames in one picture (frame_pitch = 0) are not checked: a byte in
+ * an overlap is one of the frames' bytes, which one is unspecified.
+ *
+ * Checks, all on the host before anything is launched -- a failure returns HIMG_ERR_ARG and neither
+ * d_dst nor d_status is written:
+ *   - dst NULL, or a picture or window size that is not positive;
+ *   - pixel_stride < num_channels;
+ *   - row_pitch < width * pixel_stride;
+ *   - frame_pitch neither 0 nor at least (height - 1) * row_pitch + width * pixel_stride;
+ *   - a window not inside width x height (x_f, y_f >= 0, x_f + w <= width, y_f + h <= height);
+ *   - d_dst not 16-byte aligned;
+ *   - for pixel_stride == 4: row_pitch or frame_pitch not a multiple of 4.
+ * The origins are otherwise unconstrained, odd ones included.  The stream-side arguments are checked
+ * as in himg_hip_decode_device / himg_hip_decode_regions_device, whose grid limits apply.
+ *
+ * Not in this change: pitched forms of the preview, scaled, scaled-region and tensor decodes; a batch
+ * host form; the row-sharded and multi-GPU paths; the C++ classes; the command-line tools. */
+/* Host only, no GPU: the checks above (those of dst, the window size w x h and the origins;
+ * num_channels in 1 .. 4), the same codes, and *bytes. */
+int himg_hip_dst_extent(const himg_hip_dst *dst, int num_channels, int batch, const int32_t *h_origins,
+                        int w, int h, size_t *bytes);
+int himg_hip_decode_into_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                const uint32_t *h_sizes, int batch, int width, int height,
+                                int num_channels, void *d_dst, const himg_hip_dst *dst,
+                                const int32_t *h_origins, int32_t *d_status, void *stream);
+int himg_hip_decode_regions_into_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                        const uint32_t *h_sizes, int batch, int width, int height,
+                                        int num_channels, const int32_t *h_src_origins, int w, int h,
+                                        void *d_dst, const himg_hip_dst *dst, const int32_t *h_dst_origins,
+                                        int32_t *d_status, void *stream);
+/* A HOST stream into a HOST picture described by dst (frame_pitch is ignored) at (x, y): decoded on the
+ * device as himg_hip_decode_to does, then its rows are copied into the picture at row_pitch and
+ * pixel_stride (the same bytes, and nothing else, as above).  The geometry is reported through
+ * *width / *height / *channels as soon as the header is read; a picture that does not fit at (x, y), or
+ * a descriptor the checks above refuse, returns HIMG_ERR_ARG with dst_data untouched. */
+int himg_hip_decode_into_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                            uint8_t *dst_data, const himg_hip_dst *dst, int x, int y, int *width,
+                            int *height, int *channels);
+
 /* ---- tensor decode: planar, normalised float output ------------------------------ */
 /*
  * The decode in the form a network takes: the first Co channels of the picture (3 of RGBA drops
