@@ -139,6 +139,9 @@ def lib():
     L.himg_hip_preview_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_preview_batch.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_preview_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_prefix_peek.argtypes = [vp, sz, i32, vp]
+    L.himg_hip_decode_prefix_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32), P(i32)]
+    L.himg_hip_decode_prefix_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_create_multi.argtypes = [vp, i32, P(vp)]
     L.himg_hip_destroy_multi.argtypes = [vp]
     L.himg_hip_destroy_multi.restype = None
@@ -484,6 +487,37 @@ class Engine:
                                            batch, width, height, channels, _ptr(d_out),
                                            _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "preview_device")
+
+    def decode_prefix(self, prefix, out=None):
+        """himg_hip_decode_prefix_to: `prefix` holds the first bytes of a stream, as many as have
+        arrived.  Returns (picture, rows_complete): the (H, W, C) uint8 picture whose first
+        rows_complete block rows are decode()'s and whose other rows come from the low-res plane alone
+        (rows_complete = 0: all of it).  Raises HimgError -- HIMG_ERR_CAPACITY for a prefix that ends
+        before the first row header (prefix_peek tells how many bytes that takes)."""
+        prefix = _as_u8(prefix)
+        w, h, c, k = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        plan = PrefixPlan()
+        lib().himg_hip_prefix_peek(prefix.ctypes.data, prefix.nbytes, 0, C.byref(plan))
+        if plan.num_channels:   # (the geometry is set as soon as FRMT is there and within the engine's limits)
+            cap = plan.width * plan.height * plan.num_channels
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
+        rc = lib().himg_hip_decode_prefix_to(self._ctx, prefix.ctypes.data, prefix.nbytes, dst, cap, C.byref(w),
+                                             C.byref(h), C.byref(c), C.byref(k))
+        self._check(rc, "decode_prefix")
+        return out.ravel()[: h.value * w.value * c.value].reshape(h.value, w.value, c.value), k.value
+
+    def decode_prefix_device(self, d_packed, in_stride, h_avail, batch, width, height, channels, d_out, d_rows,
+                             d_status, stream=0):
+        """himg_hip_decode_prefix_device: the contract of decode_device with h_avail, the bytes present
+        of each frame, where h_sizes stands; d_rows (batch x int32) receives each frame's complete
+        block rows, -1 with a verdict."""
+        ha = np.ascontiguousarray(h_avail, np.uint32)
+        rc = lib().himg_hip_decode_prefix_device(self._ctx, _ptr(d_packed), in_stride, ha.ctypes.data, batch, width,
+                                                 height, channels, _ptr(d_out), _ptr(d_rows), _ptr(d_status),
+                                                 C.c_void_p(stream))
+        self._check(rc, "decode_prefix_device")
 
     def decode_region(self, packed, x, y, w, h, out=None):
         """Rectangle (x, y, w, h) at full resolution (himg_hip_decode_region_to) as an (h, w, C)
@@ -1164,6 +1198,33 @@ def region_peek(packed, x, y, w, h, fix_t2=False):
     if rc != 0:
         raise HimgError(rc, "region_peek")
     return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
+
+
+class PrefixPlan(C.Structure):
+    """himg_hip_prefix_plan."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("num_channels", C.c_int), ("rows", C.c_int),
+                ("rows_complete", C.c_int), ("packed_size", C.c_size_t), ("head_bytes", C.c_size_t),
+                ("used_bytes", C.c_size_t), ("next_bytes", C.c_size_t)]
+
+
+def prefix_peek(packed, avail=None, fix_t2=False):
+    """himg_hip_prefix_peek (no GPU): the plan of a stream of which the first `avail` bytes (default:
+    all of `packed`; more than it holds: ValueError) are present, as a dict -- width, height, num_channels, rows, rows_complete,
+    packed_size, head_bytes, used_bytes, next_bytes.  Raises HimgError (HIMG_ERR_CAPACITY for a
+    prefix that ends before the first row header, else as region_peek); its `plan` holds what the walk
+    had reached."""
+    a = _as_u8(packed)
+    avail = a.nbytes if avail is None else int(avail)
+    if not 0 <= avail <= a.nbytes:
+        raise ValueError("prefix_peek: avail = %d, but `packed` holds %d bytes" % (avail, a.nbytes))
+    plan = PrefixPlan()
+    rc = lib().himg_hip_prefix_peek(a.ctypes.data, avail, 1 if fix_t2 else 0, C.byref(plan))
+    d = {k: getattr(plan, k) for k, _ in PrefixPlan._fields_}
+    if rc != 0:
+        e = HimgError(rc, "prefix_peek")
+        e.plan = d
+        raise e
+    return d
 
 
 def scaled_region_peek(packed, scale_log2, x, y, w, h, fix_t2=False):

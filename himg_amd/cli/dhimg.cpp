@@ -12,6 +12,9 @@
 // (himg_hip_decode_region_to).  The rectangle is in the coordinates of the picture as the decoder
 // returns it (row 0 = the first decoded row); the window then goes through the same row flip
 // and channel swap as a whole picture.  A malformed rectangle is a bad argument (usage, exit 0).
+// A third: "-t image outfile" decodes a TRUNCATED file, its size being the bytes that are present
+// (himg_hip_decode_prefix_to): the block rows that are whole as the full decode writes them, the rest from
+// the low-res plane, and a line "block rows K of N".  Not combined with a scale or a rectangle.
 #include <cstdio>
 #include <cstring>
 #include <vector>
@@ -38,10 +41,11 @@ int main(int argc, const char **argv) {
   int scale_log2 = 0;
   if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
   else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
-  int arg = scale_log2 ? 2 : 1;
+  const bool prefix = !scale_log2 && argc >= 4 && std::strcmp(argv[1], "-t") == 0;
+  int arg = scale_log2 || prefix ? 2 : 1;
   bool region = false;
   int rx = 0, ry = 0, rw = 0, rh = 0;
-  if (argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
+  if (!prefix && argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
     char tail = 0;
     if (std::sscanf(argv[arg + 1], "%d,%d,%d,%d%c", &rx, &ry, &rw, &rh, &tail) != 4) {
       printf("Usage: %s image outfile\n", argv[0]);
@@ -57,18 +61,19 @@ int main(int argc, const char **argv) {
   printf("File size: %zu\n", stream.size());
   fflush(stdout);   // the library reports through std::cout
 
-  if (scale_log2 || region) {
+  if (scale_log2 || region || prefix) {
     himg_hip_ctx *ctx = nullptr;
     if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
     pnm::Image picture;
     int w = 0, h = 0, c = 0;
     std::vector<uint8_t> pixels;
-    int rc;
-    if (!region) rc = himg_hip_decode_scaled_to(ctx, stream.data(), stream.size(), scale_log2, nullptr, 0, &w, &h, &c);
+    int rc, rows_complete = -1;
+    if (prefix) rc = himg_hip_decode_prefix_to(ctx, stream.data(), stream.size(), nullptr, 0, &w, &h, &c, &rows_complete);
+    else if (!region) rc = himg_hip_decode_scaled_to(ctx, stream.data(), stream.size(), scale_log2, nullptr, 0, &w, &h, &c);
     else if (scale_log2)
       rc = himg_hip_decode_scaled_region_to(ctx, stream.data(), stream.size(), scale_log2, rx, ry, rw, rh, nullptr, 0, &w, &h, &c);
     else rc = himg_hip_decode_region_to(ctx, stream.data(), stream.size(), rx, ry, rw, rh, nullptr, 0, &w, &h, &c);
-    if (rc == HIMG_ERR_CAPACITY) {
+    if (rc == HIMG_ERR_CAPACITY && !(prefix && rows_complete < 0)) {   // (a prefix below its first row header: an error)
       size_t n = 0;
       pixels.resize(static_cast<size_t>(w) * h * c);
       rc = himg_hip_fetch_last(ctx, pixels.data(), pixels.size(), &n);
@@ -80,6 +85,7 @@ int main(int argc, const char **argv) {
       return fail("Unable to decode image.", nullptr);
     }
     himg_hip_destroy(ctx);
+    if (prefix) printf("block rows %d of %d\n", rows_complete, (h + 7) / 8);
     picture.width = w;
     picture.height = h;
     picture.channels = c;

@@ -95,6 +95,8 @@
   uint8_t *img;
   if constexpr (kRegionTens) img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * (size_t)(td->co * tens_elem_size(td->dtype)));
   else if constexpr (kRegionPitch) img = dst_frame(ra.out, pd, f);
+  // (k_dec_prefix, whose ra.h differs from frame to frame, relies on this exact form: it adds the rest of the
+  // full picture's stride, f * (H - ra.h) * W * C, to ra.out beforehand)
   else img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
   const int ycbcr = df->ycbcr;
   const int per_row = ((ww + 31) >> 5) * 64;   // whole wavefronts: both lanes of a pair are active

@@ -410,6 +410,16 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
                    const DecStreams *ds, const TensDesc *tens = nullptr,   // (tens: scale_log2 = 0 only, [batch][co][h][w])
                    const DstDesc *dst = nullptr);                          // (dst: scale_log2 = 0 only, windows of the pictures)
+// The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
+// k_prefix_gate (the head of the stream with every load checked against the bytes present), the head
+// phase in its prefix form (k_dec_parse_prefix, the LRES chain bounded by the bytes present),
+// k_prefix_rowwalk beside it (ds given: on ds->side) -- the row index and k_f, the rows that are whole
+// --, k_prefix_fill for rows [k_f, rows), the count kernels and k_dec_region's body (k_dec_prefix) over
+// rows [0, k_f).  d_words: 5 x batch words, the first batch staged by the caller; d_rows: k_f, or -1
+// with a verdict.  The workspace of launch_region.
+void launch_prefix(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                   uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
+                   Profiler *prof, const DecStreams *ds);
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
 // The scaled decode (k_dec_scaled): every frame of the batch at 1 / 2^scale_log2 (1 or 2) of its

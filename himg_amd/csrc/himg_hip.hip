@@ -17,6 +17,7 @@
 
 #include "himg_dev.h"
 #include "himg_tables.h"
+#include "prefix_walk.h"
 
 using namespace himg_dev;
 
@@ -2133,6 +2134,104 @@ extern "C" int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, 
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return preview_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Decode of a stream prefix: whole block rows exact, the rest from the low-res plane
+// (kernels_dec.hip, launch_prefix; the walk's rules: prefix_walk.h, shared with the device).
+// ---------------------------------------------------------------------------
+static uint32_t prefix_avail32(size_t avail) { return avail > 0x80000000u ? 0x80000000u : (uint32_t)avail; }
+
+extern "C" int himg_hip_prefix_peek(const uint8_t *packed, size_t avail, int fix_t2, himg_hip_prefix_plan *plan) {
+  if (!plan || (!packed && avail)) return HIMG_ERR_ARG;
+  *plan = himg_hip_prefix_plan();
+  const uint32_t av = prefix_avail32(avail);
+  himg_dev::PfxHead h;
+  int rc = himg_dev::pfx_chain(packed, av, fix_t2, 0, &h);
+  plan->packed_size = h.T;
+  if (h.frmt) {   // FRMT was reached: its fields are untrusted (himg_hip_peek)
+    Geom g;
+    if (!make_geom((int)h.W, (int)h.H, (int)h.C, (int)h.C, 1, &g)) return HIMG_ERR_UNSUPPORTED;
+    plan->width = (int)h.W; plan->height = (int)h.H; plan->num_channels = (int)h.C;
+    plan->rows = g.rows;
+  }
+  if (rc == himg_dev::kPfxFormat) return h.need > av ? HIMG_ERR_CAPACITY : HIMG_ERR_FORMAT;
+  if (rc == himg_dev::kPfxShort) return HIMG_ERR_CAPACITY;
+  const uint32_t cnt = h.csz < (uint32_t)kTreeStride ? h.csz : (uint32_t)kTreeStride;
+  const uint32_t have = av > h.coff ? (av - h.coff < cnt ? av - h.coff : cnt) : 0u;
+  uint32_t tb = 0;
+  rc = himg_dev::pfx_tree_len(packed + h.coff, have, h.csz, &tb);
+  if (rc == himg_dev::kPfxFormat) return HIMG_ERR_FORMAT;
+  const uint32_t q = h.coff + tb, end = h.coff + h.csz;
+  if (tb) {
+    if (q >= end) return HIMG_ERR_FORMAT;   // nothing behind the tree (huffman_dec.cpp:277-278)
+    plan->head_bytes = q;
+  }
+  if (rc == himg_dev::kPfxShort) return HIMG_ERR_CAPACITY;
+  himg_dev::PfxRows pr;
+  if (himg_dev::pfx_rows(packed, av, h.T, fix_t2, plan->rows, q, end, nullptr, nullptr, &pr) != himg_dev::kPfxOk)
+    return HIMG_ERR_FORMAT;
+  plan->rows_complete = pr.k;
+  plan->used_bytes = pr.used;
+  plan->next_bytes = pr.next;
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_avail, int batch, int width, int height,
+                                             int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
+                                             void *stream) {
+  if (!ctx || !d_packed || !h_avail || !d_out || !d_rows || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  if (int rc = stride_covers(ctx, h_avail, batch, in_stride)) return rc;
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  // (the bytes present ride to the device as the packed sizes do: no wait; four more words per frame
+  // behind them are the walk's, himg_dev::launch_prefix)
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_avail, stream, &d_sizes)) return rc;
+  launch_prefix(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p, (uint8_t *)d_out,
+                d_rows, d_status, (hipStream_t)stream, &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail, uint8_t *dst,
+                                         size_t dst_cap, int *width, int *height, int *channels, int *rows_complete) {
+  if (!ctx || (!packed && avail) || !width || !height || !channels || !rows_complete) return HIMG_ERR_ARG;
+  *rows_complete = -1;
+  // The host needs the geometry alone, to size the launch: the chunk headers as far as FRMT.  Every
+  // check is the device's (k_prefix_gate, k_dec_parse_prefix), which words the verdict.
+  const uint32_t av = prefix_avail32(avail);
+  himg_dev::PfxHead h;
+  const int hc = himg_dev::pfx_chain(packed, av, ctx->fix_t2, 0, &h);
+  if (!h.frmt) {
+    if (hc == himg_dev::kPfxShort) return fail(ctx, HIMG_ERR_CAPACITY, "the prefix ends before the first block row");
+    return fail(ctx, HIMG_ERR_FORMAT, h.stage == 1 ? "Not a RIFF HIMG file.\n" : "Error decoding header.\n");
+  }
+  const int W = (int)h.W, H = (int)h.H, C = (int)h.C;
+  Geom g;
+  if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_cap = round_up((size_t)av + 16, 256);
+  const size_t out_bytes = (size_t)W * H * C;
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  ctx->host_bytes = 0;
+  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, av)) return rc;   // (only the bytes present)
+  int32_t *d_st = (int32_t *)ctx->h_status.p;
+  if (int rc = himg_hip_decode_prefix_device(ctx, ctx->h_in.p, in_cap, &av, 1, W, H, C, ctx->h_out.p, d_st + 1, d_st, nullptr)) {
+    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
+    return rc;
+  }
+  int32_t st[2] = {0, -1};
+  HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
+  if (st[0]) return status_error(ctx, st[0], "the prefix ends before the first block row");
+  ctx->host_bytes = out_bytes;
+  *width = W; *height = H; *channels = C; *rows_complete = st[1];
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -27,6 +27,7 @@
 //                     stride and an origin per frame (DstDesc; include/himg_hip.h, "decode into")
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
+#include "prefix_walk.h"
 #include "loop_counts.h"
 
 #include <cstdlib>
@@ -169,9 +170,13 @@ constexpr int kParseThreads = 1024;
 constexpr int kParseHalf = kParseThreads / 2;   // lanes per stream in step 5
 __device__ __forceinline__ void identity_test_words(const DecFrame *df, int l, uint32_t *dst);
 
-template <bool HEAD>
+// PREFIX (k_dec_parse_prefix, the decode of a stream prefix): sizes[f] is the size the stream's RIFF
+// header declares, the container's bound; avails[f] the bytes present, below which k_prefix_gate has
+// found every header this walk reads -- the staging of the bodies is bounded there.
+template <bool HEAD, bool PREFIX = false>
 __device__ __forceinline__ void dec_parse_body(Geom g, DecWs ws, const uint8_t *packed,
-                                               size_t in_stride, const uint32_t *sizes, uint32_t *head_sizes) {
+                                               size_t in_stride, const uint32_t *sizes, uint32_t *head_sizes,
+                                               const uint32_t *avails = nullptr) {
   __shared__ TreeAux aux[2][kMaxNodes + 1];
   __shared__ uint32_t s_nd[2][kMaxNodes + 1];
   __shared__ __attribute__((aligned(16))) uint32_t s_lut[2][1 << kLutBits];
@@ -243,7 +248,11 @@ __device__ __forceinline__ void dec_parse_body(Geom g, DecWs ws, const uint8_t *
   // (HEAD: LMAP and the LRES tree; the FRES side below finds no tree and recovers nothing.)
   for (int k = lane; k < (HEAD ? 2 : 5) * kBodyBytes; k += kParseThreads) {
     const int b = k / kBodyBytes, j = k - b * kBodyBytes;
-    const uint32_t cnt = s_sz[b] < (uint32_t)kTreeStride ? s_sz[b] : (uint32_t)kTreeStride;
+    uint32_t cnt = s_sz[b] < (uint32_t)kTreeStride ? s_sz[b] : (uint32_t)kTreeStride;
+    if constexpr (PREFIX) {   // (the FRES tree's 384 bytes may reach into rows that have not arrived)
+      const uint32_t av = avails[f], left = av > s_off[b] ? av - s_off[b] : 0u;
+      cnt = cnt < left ? cnt : left;
+    }
     reinterpret_cast<uint8_t *>(s_buf[b])[j] = (uint32_t)j < cnt ? p[s_off[b] + j] : (uint8_t)0;
   }
   __syncthreads();
@@ -672,6 +681,12 @@ __global__ __launch_bounds__(kParseThreads) void k_dec_parse_head(Geom g, DecWs 
                                                                   size_t in_stride, const uint32_t *sizes,
                                                                   uint32_t *head_sizes) {
   dec_parse_body<true>(g, ws, packed, in_stride, sizes, head_sizes);
+}
+
+__global__ __launch_bounds__(kParseThreads) void k_dec_parse_prefix(Geom g, DecWs ws, const uint8_t *packed,
+                                                                    size_t in_stride, const uint32_t *sizes,
+                                                                    const uint32_t *avails) {
+  dec_parse_body<false, true>(g, ws, packed, in_stride, sizes, nullptr, avails);
 }
 
 // ---------------------------------------------------------------------------
@@ -4583,6 +4598,249 @@ __global__ void k_region_walk_end(Geom g, DecWs ws, const uint8_t *packed, size_
 }
 
 // ---------------------------------------------------------------------------
+// The decode of a stream PREFIX (include/himg_hip.h): the first avail_f bytes of frame f's stream.
+// Block rows [0, k_f) -- those whose size header and payload lie wholly below avail_f -- are decoded,
+// rows [k_f, rows) are written from the low-res plane alone.  k_f is found ON THE DEVICE, so the
+// count and row kernels take it from an array (krows) where the region forms compute r1_f from an
+// origin; like those, each includes the body of the kernel it stands beside behind its own values.
+//   k_prefix_gate      (one wavefront per frame) the chunk headers RIFF .. FRES and the length of the
+//                      FRES tree with every load checked against avail_f (prefix_walk.h).  A frame
+//                      whose head has not arrived whole gets the verdict kStShort, and the size 0
+//                      goes to the parse and to every reader for it: nothing of it is loaded again.
+//                      For the others: ptx[f] = T_f, the container's bound for k_dec_parse_prefix;
+//                      pbound[f] = avail_f, the load bound of every later kernel; DecFrame::walk_q /
+//                      walk_end = where the row headers start and the chunk ends.
+//   k_prefix_rowwalk   (one lane per frame) the row headers below avail_f: the row index and k_f.
+//   k_prefix_count(_w) k_row_count<false> / k_row_count_w over rows [0, k_f).
+//   k_dec_prefix       k_dec_region's body over rows [0, k_f), the whole width: the window is the top
+//                      min(8 k_f, H) pixel rows of the picture.
+//   k_prefix_fill      rows [k_f, rows) from the low-res plane.
+//   k_prefix_status    the verdicts and k_f (-1 for a frame with a verdict).
+// ---------------------------------------------------------------------------
+constexpr int kStShort = 5;   // the prefix ends before the first row header: HIMG_ERR_CAPACITY
+
+__global__ __launch_bounds__(64) void k_prefix_gate(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                    const uint32_t *avails, uint32_t *ptx, uint32_t *pbound,
+                                                    int32_t *krows, int32_t *gate) {
+  __shared__ uint8_t s_tree[kTreeStride];
+  __shared__ uint32_t s_hdr[4];
+  const int f = blockIdx.x, lane = threadIdx.x;
+  DecFrame *df = ws.frames + f;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t avail = avails[f];
+  if (lane == 0) {
+    PfxHead h;
+    int rc = pfx_chain(p, avail, g.fix_t2, (uint32_t)g.row_block, &h);
+    // A geometry other than the launch's: k_dec_parse says so (its loads end with FRMT's).
+    const bool geom = h.frmt && ((int)h.W != g.W || (int)h.H != g.H || (int)h.C != g.C);
+    if (geom) rc = kPfxFormat;
+    if (rc == kPfxFormat && !geom && h.need > avail) rc = kPfxShort;   // an earlier check may need those bytes
+    s_hdr[0] = (uint32_t)rc; s_hdr[1] = h.coff; s_hdr[2] = h.csz; s_hdr[3] = h.T;
+    df->walk_status = rc == kPfxFormat ? (geom ? kStGeom : fmt_err(h.stage, h.huff)) : 0;
+    df->rows_first = 0;
+    df->walk_q = 0;
+    krows[f] = 0;
+  }
+  __syncthreads();
+  int rc = (int)s_hdr[0];
+  const uint32_t coff = s_hdr[1], csz = s_hdr[2], T = s_hdr[3];
+  uint32_t have = 0;
+  if (rc == kPfxOk) {   // the serialised tree as far as it has arrived (at most kTreeStride bytes)
+    const uint32_t cnt = csz < (uint32_t)kTreeStride ? csz : (uint32_t)kTreeStride;
+    have = avail > coff ? (avail - coff < cnt ? avail - coff : cnt) : 0u;
+    for (uint32_t k = lane; k < have; k += 64u) s_tree[k] = p[coff + k];
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  if (rc == kPfxOk) {
+    uint32_t tb = 0;
+    rc = pfx_tree_len(s_tree, have, csz, &tb);
+    if (rc == kPfxFormat) {
+      df->walk_status = fmt_err(7, 1);   // (k_dec_parse rejects this tree: its verdict comes first)
+    } else if (rc == kPfxOk) {
+      const uint32_t q = coff + tb, end = coff + csz;
+      if (q < end) { df->rows_first = q; df->walk_q = q; df->walk_end = end; }
+      // (q >= end: nothing behind the tree -- k_dec_parse's verdict, huffman_dec.cpp:277-278)
+    }
+  }
+  const bool is_short = rc == kPfxShort;
+  gate[f] = is_short ? kStShort : 0;
+  ptx[f] = is_short ? 0u : T;
+  pbound[f] = is_short ? 0u : avail;
+}
+
+__global__ __launch_bounds__(64) void k_prefix_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                       const uint32_t *pbound, const uint32_t *ptx, int32_t *krows,
+                                                       int batch) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  DecFrame *df = ws.frames + f;
+  const uint32_t q = df->walk_q;
+  if (q == 0) return;   // no rows to walk: the gate's verdict, or the parse's
+  df->walk_q = 0;
+  PfxRows pr;
+  const int rc = pfx_rows(packed + (size_t)f * in_stride, pbound[f], ptx[f], g.fix_t2, g.rows, q, df->walk_end,
+                          ws.row_off + (size_t)f * g.rows, ws.row_len + (size_t)f * g.rows, &pr);
+  if (rc == kPfxFormat) { df->walk_status = fmt_err(7, 1); return; }
+  krows[f] = pr.k;
+}
+
+// k_row_count<false> over rows [0, k_f) (rows_per_wg of them per workgroup).
+__global__ __launch_bounds__(kDecThreads, 8) void k_prefix_count(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                const int32_t *krows, int rows_per_wg) {
+  constexpr bool LDSPAY = false;
+  const int r0 = 0, r1 = krows[blockIdx.y];
+  if ((int)blockIdx.x * rows_per_wg >= r1) return;
+#include "dec_body_row_count.inc"
+}
+
+// k_row_count_w over rows [0, k_f).
+__global__ __launch_bounds__(kDecThreads, 8) void k_prefix_count_w(Geom g, DecWs ws, const uint8_t *packed,
+                                                                  size_t in_stride, const uint32_t *sizes,
+                                                                  const int32_t *krows) {
+  const int r0 = 0, r1 = krows[blockIdx.y];
+  if ((int)blockIdx.x * kCountRowsW >= r1) return;
+#include "dec_body_row_count_w.inc"
+}
+
+// k_dec_region's body over the window (0, 0, W, min(8 k_f, H)) of frame f, written where the full
+// decode writes it: frame f's picture at out + f * H * W * C.
+struct PrefixArgs {
+  const int32_t *krows;   // [f] k_f
+  int sw;                 // tiles per column strip (blockIdx.x = strip)
+  uint8_t *out;
+};
+struct PrefixOrigin {     // every window starts at (0, 0)
+  __device__ __forceinline__ int operator[](int) const { return 0; }
+};
+struct PrefixWindow {     // what the body reads of a RegionArgs
+  PrefixOrigin org;
+  int sw, w, h;
+  uint8_t *out;           // (the body adds f * h * w * C)
+};
+__global__ __launch_bounds__(kDecThreads) void k_dec_prefix(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                           const uint32_t *sizes, PrefixArgs pa) {
+  constexpr bool kRegionTens = false, kRegionPitch = false;
+  const TensK td = nullptr;
+  const DstK pd = nullptr;
+  const int k_f = pa.krows[blockIdx.z];
+  if ((int)blockIdx.y >= k_f) return;
+  PrefixWindow ra;
+  ra.sw = pa.sw; ra.w = g.W; ra.h = 8 * k_f < g.H ? 8 * k_f : g.H;
+  // The body places frame f at ra.out + f * ra.h * ra.w * C (dec_body_region.inc, "img = ra.out + ...", which names
+  // this kernel): with a height per frame the rest of the full picture's stride is added here, so that frame
+  // f lands at pa.out + f * H * W * C.
+  ra.out = pa.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C);
+#include "dec_body_region.inc"
+}
+
+// k_prefix_fill: the block rows that have not arrived, [k_f, rows) of frame f -- what the full decode
+// writes for a row whose symbols are all zero: the tile's interpolated low-res block (GetLowresBlock,
+// downsampled.cpp:116-169; bytes, so the decoder's clamp changes nothing), the colour inverse
+// (ycbcr.cpp:54-82) where the frame asks for it, clipped at the right and bottom edges.  It reads the
+// low-res plane only (four samples per tile and channel) and is a pure store stream:
+//   * a workgroup per (128 tiles, block row, frame); one whose row is below k_f returns at once;
+//   * a lane per HALF tile, lane 2 t + h: columns 4 h .. 4 h + 3 of tile t, all eight pixel rows.  For
+//     RGBA that is one 16-byte store per pixel row, and a wavefront's 64 stores of a pixel row are
+//     1 KiB of contiguous bytes;
+//   * the vertical interpolation is lowres_quads' (four rows per register), the horizontal one only
+//     the half's four columns: with (lo, hi) = (left, middle) or (middle, right) they are
+//     lo, lerp(lo, m), m = lerp(lo, hi), lerp(m, hi) -- interp9's tree restricted to one half;
+//   * C < 4, a tile the right or bottom edge cuts, and a frame whose pixels are not 16-byte aligned
+//     take the byte path.
+// No LDS, no state of the row kernels.
+__device__ __forceinline__ void fill_half(uint32_t l4, uint32_t r4, int hh, uint32_t x[4]) {
+  const uint32_t rnd = 0x01010101u;
+  const uint32_t m4 = __builtin_amdgcn_lerp(l4, r4, rnd);
+  const uint32_t lo = hh ? m4 : l4, hi = hh ? r4 : m4;
+  const uint32_t m = __builtin_amdgcn_lerp(lo, hi, rnd);
+  x[0] = lo; x[1] = __builtin_amdgcn_lerp(lo, m, rnd); x[2] = m; x[3] = __builtin_amdgcn_lerp(m, hi, rnd);
+}
+
+__global__ __launch_bounds__(256) void k_prefix_fill(Geom g, DecWs ws, const int32_t *krows, uint8_t *out) {
+  const int f = blockIdx.z, v = blockIdx.y;
+  if (v < krows[f]) return;
+  const DecFrame *df = ws.frames + f;
+  if (df->status != 0 || (df->parse_status == 0 && df->walk_status != 0)) return;
+  const int it = (int)blockIdx.x * 256 + (int)threadIdx.x, u = it >> 1, hh = it & 1;
+  const int cols = g.cols, C = g.C, W = g.W, H = g.H;
+  if (u >= cols) return;
+  const int v2 = v + 1 < g.rows ? v + 1 : g.rows - 1, u2 = u + 1 < cols ? u + 1 : cols - 1;
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  uint32_t X[4][2][4];   // [channel][q][k]: the bytes of pixel rows 4 q .. 4 q + 3 at column 4 hh + k
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    if (c < C) {
+      const uint8_t *m = low + (size_t)c * g.rows * cols;
+      uint32_t lr[9];
+      lr[0] = (uint32_t)m[(size_t)v * cols + u] | ((uint32_t)m[(size_t)v * cols + u2] << 8);
+      lr[8] = (uint32_t)m[(size_t)v2 * cols + u] | ((uint32_t)m[(size_t)v2 * cols + u2] << 8);
+      interp9_u8x4(lr);   // bytes 0, 1 = left, right of rows 0 .. 7
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const uint32_t p01 = __builtin_amdgcn_perm(lr[4 * q + 1], lr[4 * q], 0x05010400u);      // L0 L1 R0 R1
+        const uint32_t p23 = __builtin_amdgcn_perm(lr[4 * q + 3], lr[4 * q + 2], 0x05010400u);  // L2 L3 R2 R3
+        fill_half(__builtin_amdgcn_perm(p23, p01, 0x05040100u), __builtin_amdgcn_perm(p23, p01, 0x07060302u), hh,
+                  X[c][q]);
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) X[c][q][k] = 0;
+    }
+  }
+  const int ycc = df->ycbcr;
+  const int x0 = 8 * u + 4 * hh, y0 = 8 * v;
+  if (x0 >= W) return;
+  uint8_t *img = out + (size_t)f * ((size_t)H * W * C);
+  const bool wide = C == 4 && x0 + 4 <= W && ((((uintptr_t)img) | ((size_t)W * 4)) & 15u) == 0;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int y = y0 + 4 * q + i;
+      if (y >= H) continue;
+      uint32_t px[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        uint32_t c0 = (X[0][q][k] >> (8 * i)) & 255u, c1 = (X[1][q][k] >> (8 * i)) & 255u;
+        uint32_t c2 = (X[2][q][k] >> (8 * i)) & 255u;
+        const uint32_t c3 = (X[3][q][k] >> (8 * i)) & 255u;
+        if (ycc) ycc_to_rgb(c0, c1, c2);
+        px[k] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+      }
+      uint8_t *d = img + ((size_t)y * W + x0) * C;
+      if (wide) {
+        *reinterpret_cast<uint4 *>(d) = make_uint4(px[0], px[1], px[2], px[3]);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (x0 + k >= W) continue;
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            if (c < C) d[k * C + c] = (uint8_t)(px[k] >> (8 * c));
+        }
+      }
+    }
+  }
+}
+
+// The verdicts: k_dec_status's rule, kStShort for a frame the gate stopped, and k_f.
+__global__ void k_prefix_status(DecWs ws, const int32_t *gate, const int32_t *krows, int32_t *status, int32_t *rows_out,
+                                int batch) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= batch) return;
+  const DecFrame *df = ws.frames + f;
+  const int w = df->parse_status == 0 ? df->walk_status : 0;
+  int st = df->status > w ? df->status : w;
+  if (gate[f]) st = gate[f];
+  status[f] = st;
+  if (rows_out) rows_out[f] = st ? -1 : krows[f];
+}
+
+// ---------------------------------------------------------------------------
 // k_dec_scaled<S>: the decode at 1/2 scale (S = 4) and 1/4 scale (S = 2): of every tile the
 // S x S lowest-sequency coefficients, the S-point inverse transform, the low-res part as the
 // rounded mean of F x F boxes (F = 8 / S) of the tile's interpolated low-res block -- the
@@ -5117,6 +5375,10 @@ hipError_t dec_set_kernel_attrs() {
   if (e == hipSuccess)
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_p), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)(kLdsMax - fa.sharedSizeBytes));
+  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_prefix));
+  if (e == hipSuccess)
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_prefix), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)(kLdsMax - fa.sharedSizeBytes));
   const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
                           reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>),
                           reinterpret_cast<const void *>(&k_dec_scaled_region<4>), reinterpret_cast<const void *>(&k_dec_scaled_region<2>)};
@@ -5298,6 +5560,56 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   }
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+// The decode of stream prefixes.  d_words: 5 x batch words -- the bytes present (staged by the caller),
+// then what k_prefix_gate and k_prefix_rowwalk leave for the kernels behind them: the declared sizes,
+// the load bounds, k_f, the gate's verdicts.
+void launch_prefix(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
+                   Profiler *prof, const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region)
+  const uint32_t *d_avail = d_words;
+  uint32_t *d_tx = d_words + batch, *d_bound = d_words + 2 * (size_t)batch;
+  int32_t *d_k = (int32_t *)(d_words + 3 * (size_t)batch), *d_gate = (int32_t *)(d_words + 4 * (size_t)batch);
+  launch_zero(g, ws, batch, stream, prof);
+  HIMG_LAUNCH(k_prefix_gate, dim3(batch), dim3(64), g, ws, d_packed, in_stride, d_avail, d_tx, d_bound, d_k, d_gate);
+  // The row headers on the side stream beside k_dec_parse_prefix and the LRES chain (launch_region's fork).
+  hipStream_t ws_ = ds ? ds->side : stream;
+  if (ds) {
+    (void)hipEventRecord(ds->ev_fork, stream);
+    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
+  }
+  prof_begin(prof, "k_prefix_rowwalk", ws_);
+  hipLaunchKernelGGL(k_prefix_rowwalk, dim3((batch + 63) / 64), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_bound, d_tx,
+                     d_k, batch);
+  prof_end(prof, ws_);
+  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
+  HIMG_LAUNCH(k_dec_parse_prefix, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_tx, d_bound);
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_bound, stream, prof);
+  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
+  // The rows that have not arrived: the low-res plane and k_f are all the fill needs.
+  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, d_k, d_out);
+  // Every complete row gets a record (launch_region's rule); the grids cover all rows, a workgroup at or
+  // beyond its frame's k_f returns at once.
+  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
+  if (cr.wave) {
+    HIMG_LAUNCH(k_prefix_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
+                d_packed, in_stride, d_bound, d_k);
+  } else {
+    HIMG_LAUNCH(k_prefix_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
+                in_stride, d_bound, d_k, cr.rpc);
+  }
+  const int smax = region_strip_tiles(g);
+  const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
+  PrefixArgs pa;
+  pa.krows = d_k; pa.sw = sw; pa.out = d_out;
+  prof_begin(prof, "k_dec_prefix", stream);
+  hipLaunchKernelGGL(k_dec_prefix, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
+                     ws, d_packed, in_stride, d_bound, pa);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_prefix_status, dim3((batch + 63) / 64), dim3(64), ws, d_gate, d_k, d_status, d_rows, batch);
 }
 
 void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,

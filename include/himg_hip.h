@@ -728,6 +728,83 @@ int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const
                                          const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
                                          int *widths, int *heights, int *channels);
 
+/* ---- decode a stream prefix: whole block rows exact, the rest from the low-res plane ---- */
+/*
+ * The format is progressive in file order: the whole low-res plane (LRES)
+ * comes first, then QCFG, FMAP and the FRES tree, then the block rows top to bottom, each an
+ * independently coded unit behind its own size header.  A prefix is the first `avail` bytes of a stream
+ * whose RIFF header declares T = file_size + 8 bytes, 0 <= avail <= T (avail > T: HIMG_ERR_FORMAT).
+ * These entry points give the picture as far as it has arrived, at full size.
+ *
+ * Verdict.  The stages are himg_hip_decode's, under the same HIMG_OPT_FIX_T2.
+ *   - RIFF, FRMT, LMAP, LRES, QCFG, FMAP, the FRES chunk header and its tree run exactly as in the full
+ *     decode with T where packed_size stands there: chunk bounds are checked against T.
+ *   - head_bytes is the offset of the first row header, as in himg_hip_region_plan.  A prefix that ends
+ *     before it gives HIMG_ERR_CAPACITY and nothing is decoded.  (A check that fails on bytes below
+ *     avail gives HIMG_ERR_FORMAT even then -- unless a chunk found in front of it is not whole below
+ *     avail: the decoder reports the first failure in its order of checks, and that chunk may hold one.)
+ *   - The row headers are walked by the decoder's rules (huffman_dec.cpp:232-248) for as long as a
+ *     header lies wholly below avail.  A wholly present header the decoder rejects: HIMG_ERR_FORMAT.
+ *     The first row whose header or payload is not wholly below avail ends the walk without a verdict;
+ *     its index is k, the number of complete rows.  A frame of one block row has no header (under
+ *     HIMG_OPT_FIX_T2): k = 1 when the FRES chunk ends at or below avail.
+ *   - What the decoder judges at the end of the chunk is judged where bytes below avail decide it: a
+ *     chunk that ends inside the prefix with fewer blocks than block rows, a header that would cross
+ *     the end of the chunk.
+ *   - Rows 0 .. k-1 go through the entropy decode with the reference's end-of-block checks; a failure
+ *     there is HIMG_ERR_FORMAT.
+ *   - Nothing at or beyond avail decides the verdict or a pixel.
+ *   - avail == T is himg_hip_decode: the same verdict, the same himg_hip_last_error wording, the same
+ *     bytes.
+ * Pixels.  H x W x C interleaved u8, laid out as himg_hip_decode's.  The pixel rows of block rows
+ * 0 .. k-1 are byte for byte the full decode's.  Those of block rows k .. rows-1 are what the full
+ * decode writes for a row whose symbols are all zero: each tile is its interpolated low-res block
+ * (downsampled.cpp:116-169), clamped to 0 .. 255, through the colour inverse (ycbcr.cpp:54-82) where
+ * FRMT says YCbCr and C >= 3, clipped at the right and bottom edges as the full decode clips.  k = 0 is
+ * a useful result: the low-res plane as a smooth full-size picture.
+ * Bytes loaded.  Nothing at or beyond avail rounded up to 4: the bit readers' look-ahead and the
+ * 384-byte staging of the FRES tree are bounded by avail as they are bounded by the stream's size in
+ * the full decode.
+ *
+ * Not in this change: a host batch entry; scaled, tensor and pitched forms; himg::Decoder; the
+ * multi-GPU handle; an incremental "continue from row k" call -- a caller who keeps the picture decodes
+ * the newly complete rows with the region decode.
+ */
+typedef struct himg_hip_prefix_plan {
+  int width, height, num_channels;   /* the frame's geometry (FRMT); 0 where FRMT has not arrived */
+  int rows;                          /* block rows, ceil(height / 8) */
+  int rows_complete;                 /* k */
+  size_t packed_size;                /* T (0 where the RIFF header has not arrived) */
+  size_t head_bytes;                 /* where the first row header starts */
+  size_t used_bytes;                 /* the end of row k-1's payload; head_bytes for k = 0 */
+  size_t next_bytes;                 /* the least avail at which a later call could report more rows */
+} himg_hip_prefix_plan;
+/* Host only, no GPU; reads nothing at or beyond avail.  next_bytes: when the next row's header is wholly
+ * present, the end of that row's payload; when the header is cut, the end of the header as far as that
+ * is known -- its 2 bytes, or 4 when its first two bytes are present and carry the continuation flag;
+ * T when k == rows.  HIMG_ERR_CAPACITY when avail ends before head_bytes (head_bytes set when it is
+ * known, else 0, as in himg_hip_preview_peek; the geometry and T are set as far as they have arrived);
+ * the other codes are himg_hip_region_peek's.  Like that call it looks at the chunk headers, the length
+ * of the FRES tree and the row headers, not into the chunks' bodies. */
+int himg_hip_prefix_peek(const uint8_t *packed, size_t avail, int fix_t2, himg_hip_prefix_plan *plan);
+/* One prefix in host memory into caller-owned host memory.  The capacity protocol of
+ * himg_hip_decode_to: a NULL or too-small dst gives HIMG_ERR_CAPACITY with the geometry and
+ * *rows_complete = k set, and himg_hip_fetch_last copies the resident result.  A prefix that ends
+ * before head_bytes gives HIMG_ERR_CAPACITY with *rows_complete = -1 (also set on every other
+ * failure).  Only avail bytes are read and uploaded. */
+int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail, uint8_t *dst,
+                              size_t dst_cap, int *width, int *height, int *channels, int *rows_complete);
+/* A batch of prefixes in HBM: the contract of himg_hip_decode_device, with h_avail -- a HOST array of
+ * the bytes present in each frame -- where h_sizes stands: in_stride is a multiple of 4 and at least
+ * every avail rounded up to 4, bytes in [avail_f, in_stride) may hold anything, and the values ride to
+ * the device as h_origins do (no host synchronisation: k_f is found on the device).  d_rows[f]
+ * receives k_f, -1 on any failure.  A frame below its head_bytes gets d_status[f] =
+ * HIMG_ERR_CAPACITY's status and its picture is not written; the other frames are unaffected. */
+int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                  const uint32_t *h_avail, int batch, int width, int height,
+                                  int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
+                                  void *stream);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
