@@ -118,17 +118,25 @@ def _head(b, fix_t2, p):
     return q, end
 
 
-def _rows(b, fix_t2, p, q, end):
+def _rows(b, fix_t2, p, q, end, upto=None, ranges=None):
+    """The row headers from q by the decoder's rules (huffman_dec.cpp:232-248), for as long as a header and
+    its payload lie wholly in b.  upto (a region's r1, below the frame's rows): the walk stops behind that
+    many headers; None walks to the end of the chunk, as the full decode does.  ranges (a list): receives
+    (payload offset, length) of every row the walk delimits, at most the frame's rows."""
     avail, T, rows = len(b), p["packed_size"], p["rows"]
+    if upto is None or upto >= rows:
+        upto = None
     p.update(rows_complete=0, used_bytes=q, next_bytes=T)
     if fix_t2 and rows == 1:   # one block row has no size header
         if end <= avail:
             p.update(rows_complete=1, used_bytes=end)
+            if ranges is not None:
+                ranges.append((q, end - q))
         else:
             p["next_bytes"] = end
         return
     r, cut = 0, False
-    while q != end:
+    while q != end and (upto is None or r < upto):
         if q + 2 > end:
             raise _Format
         if q + 2 > avail:
@@ -150,10 +158,12 @@ def _rows(b, fix_t2, p, q, end):
             break
         if r < rows:
             p["used_bytes"] = body + n
+            if ranges is not None:
+                ranges.append((body, n))
         r += 1
         q = body + n
-    if not cut and r < rows:
-        raise _Format   # fewer blocks than block rows
+    if not cut and r < (rows if upto is None else upto):
+        raise _Format   # fewer blocks than block rows (than the rows asked for)
     p["rows_complete"] = min(r, rows)
     if p["rows_complete"] == rows:
         p["next_bytes"] = T

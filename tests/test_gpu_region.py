@@ -163,6 +163,7 @@ FRES_MSG = "Error decoding full-res data.\n"
 
 @pytest.mark.parametrize("fix", [0, 1])
 def test_verdict_fuzz(fix):
+    """A partial rectangle of a stream the oracle rejects in the FRES stage is judged in test_gpu_partial_damage.py."""
     eng = himg_amd.Engine(0)
     eng.set_option("fix_t2", fix)
     rng = np.random.default_rng(7 + fix)
