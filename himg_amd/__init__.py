@@ -132,6 +132,9 @@ def lib():
     L.himg_hip_decode_scaled_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_scaled_to.argtypes = [vp, vp, sz, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_scaled_batch.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_pyramid_size.argtypes = [i32, i32, i32, P(i32), P(i32)]
+    L.himg_hip_decode_pyramid_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_pyramid_to.argtypes = [vp, vp, sz, vp, vp, P(i32), P(i32), P(i32)]
     L.himg_hip_scaled_region_peek.argtypes = [vp, sz, i32, i32, i32, i32, i32, i32, vp]
     L.himg_hip_decode_scaled_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_scaled_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
@@ -664,6 +667,38 @@ class Engine:
                                                  C.c_void_p(stream))
         self._check(rc, "decode_scaled_device")
 
+    def decode_pyramid_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, pyramid,
+                              d_status, stream=0):
+        """himg_hip_decode_pyramid_device: the contract of decode_device with a pyramid_desc() where
+        d_out stands there -- level k holds batch x ceil(H/2^k) x ceil(W/2^k) x C bytes; one verdict per
+        frame, the full decode's.  pyramid: a PyramidDesc, or None (HIMG_ERR_ARG)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_pyramid_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data, batch, width,
+                                                  height, channels, None if pyramid is None else C.addressof(pyramid),
+                                                  _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_pyramid_device")
+
+    def decode_pyramid(self, packed, levels=(0, 1, 2, 3)):
+        """The picture at 1 / 2^k for every k in `levels` (himg_hip_decode_pyramid_to: one upload, one
+        device pass, a download per level) as {level: (ceil(H/2^k), ceil(W/2^k), C) uint8 array}: level 0
+        is decode(), 1 and 2 decode_scaled(), 3 preview() -- with the full decode's verdict."""
+        packed = _as_u8(packed)
+        levels = sorted(set(int(k) for k in levels))
+        if any(k < 0 or k > 3 for k in levels):
+            raise HimgError(HIMG_ERR_ARG, "decode_pyramid: levels are 0..3")
+        geom = _peek(packed)
+        outs, dst, cap = {}, (C.c_void_p * 4)(), (C.c_size_t * 4)()
+        if geom:
+            for k in levels:
+                ow, oh = pyramid_size(geom[0], geom[1], k)
+                outs[k] = np.empty((oh, ow, geom[2]), np.uint8)
+                dst[k], cap[k] = outs[k].ctypes.data, outs[k].nbytes
+        w, h, c = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().himg_hip_decode_pyramid_to(self._ctx, packed.ctypes.data, packed.nbytes, dst, cap,
+                                              C.byref(w), C.byref(h), C.byref(c))
+        self._check(rc, "decode_pyramid")
+        return outs
+
     def decode_scaled_region(self, packed, scale_log2, x, y, w, h, out=None):
         """Rectangle (x, y, w, h) of the picture at 1/2 (scale_log2 = 1) or 1/4 (2) scale, in that
         picture's coordinates (himg_hip_decode_scaled_region_to), as an (h, w, C) uint8 array: sample
@@ -1064,6 +1099,30 @@ def scaled_size(w, h, scale_log2):
     if rc != 0:
         raise HimgError(rc, "scaled_size")
     return ow.value, oh.value
+
+
+def pyramid_size(width, height, level):
+    """himg_hip_pyramid_size (no GPU): (ow, oh) = (ceil(width / 2^level), ceil(height / 2^level)),
+    level 0..3.  Raises HimgError (HIMG_ERR_ARG) for another level or a non-positive size."""
+    ow, oh = C.c_int(), C.c_int()
+    rc = lib().himg_hip_pyramid_size(int(width), int(height), int(level), C.byref(ow), C.byref(oh))
+    if rc != 0:
+        raise HimgError(rc, "pyramid_size")
+    return ow.value, oh.value
+
+
+class PyramidDesc(C.Structure):
+    """himg_hip_pyramid."""
+    _fields_ = [("level", C.c_void_p * 4)]
+
+
+def pyramid_desc(level0=None, level1=None, level2=None, level3=None):
+    """A himg_hip_pyramid: the device buffers (torch tensors or addresses) of levels 0..3; None = the
+    level is not wanted."""
+    d = PyramidDesc()
+    for k, x in enumerate((level0, level1, level2, level3)):
+        d.level[k] = _ptr(x).value
+    return d
 
 
 class TensorDesc(C.Structure):

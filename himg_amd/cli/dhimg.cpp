@@ -15,8 +15,13 @@
 // A third: "-t image outfile" decodes a TRUNCATED file, its size being the bytes that are present
 // (himg_hip_decode_prefix_to): the block rows that are whole as the full decode writes them, the rest from
 // the low-res plane, and a line "block rows K of N".  Not combined with a scale or a rectangle.
+// A fourth: "-m image out.ext" writes the picture pyramid from one decode (himg_hip_decode_pyramid_to):
+// the full picture to out.ext and the 1/2-, 1/4- and 1/8-scale pictures to out.L1.ext, out.L2.ext and
+// out.L3.ext.  On its own only: with a scale, a rectangle or -t it is a bad argument (usage, exit 0),
+// decided before the file is read or the device is opened.
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "decoder.h"
@@ -31,6 +36,15 @@ int fail(const char *what, const char *path) {
   return -1;
 }
 
+// out.ext -> out.L<k>.ext (the extension: behind the last dot of the file's name, if it has one).
+std::string level_path(const char *path, int k) {
+  std::string p(path);
+  const size_t slash = p.find_last_of('/'), dot = p.find_last_of('.');
+  const std::string tag = ".L" + std::to_string(k);
+  if (dot == std::string::npos || (slash != std::string::npos && dot < slash) || dot == 0) return p + tag;
+  return p.substr(0, dot) + tag + p.substr(dot);
+}
+
 }  // namespace
 
 int main(int argc, const char **argv) {
@@ -38,11 +52,19 @@ int main(int argc, const char **argv) {
     printf("Usage: %s image outfile\n", argv[0]);
     return 0;
   }
+  // The pyramid: "-m image outfile" and nothing else.
+  bool mip = false;
+  if (argc >= 4)
+    for (int i = 1; i < argc - 2; ++i) mip = mip || std::strcmp(argv[i], "-m") == 0;
+  if (mip && !(argc == 4 && std::strcmp(argv[1], "-m") == 0)) {
+    printf("Usage: %s image outfile\n", argv[0]);
+    return 0;
+  }
   int scale_log2 = 0;
   if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
   else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
   const bool prefix = !scale_log2 && argc >= 4 && std::strcmp(argv[1], "-t") == 0;
-  int arg = scale_log2 || prefix ? 2 : 1;
+  int arg = scale_log2 || prefix || mip ? 2 : 1;
   bool region = false;
   int rx = 0, ry = 0, rw = 0, rh = 0;
   if (!prefix && argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
@@ -60,6 +82,43 @@ int main(int argc, const char **argv) {
   if (!pnm::slurp(in_path, &stream)) return fail("Unable to read file", in_path);
   printf("File size: %zu\n", stream.size());
   fflush(stdout);   // the library reports through std::cout
+
+  if (mip) {
+    int w = 0, h = 0, c = 0;
+    if (himg_hip_peek(stream.data(), stream.size(), &w, &h, &c) != HIMG_OK) return fail("Unable to decode image.", nullptr);
+    std::vector<uint8_t> pixels[4];
+    uint8_t *dst[4];
+    size_t cap[4];
+    int lw[4], lh[4];
+    for (int k = 0; k < 4; ++k) {
+      (void)himg_hip_pyramid_size(w, h, k, &lw[k], &lh[k]);
+      pixels[k].resize(static_cast<size_t>(lw[k]) * lh[k] * c);
+      dst[k] = pixels[k].data();
+      cap[k] = pixels[k].size();
+    }
+    himg_hip_ctx *ctx = nullptr;
+    if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
+    const int rc = himg_hip_decode_pyramid_to(ctx, stream.data(), stream.size(), dst, cap, &w, &h, &c);
+    if (rc != HIMG_OK) {
+      const char *msg = himg_hip_last_error(ctx);
+      printf("%s%s", msg, (*msg && msg[std::strlen(msg) - 1] == '\n') ? "" : "\n");
+      himg_hip_destroy(ctx);
+      return fail("Unable to decode image.", nullptr);
+    }
+    himg_hip_destroy(ctx);
+    const bool writable = c == 1 || c == 3 || c == 4;
+    for (int k = 0; k < 4; ++k) {
+      pnm::Image picture;
+      picture.width = lw[k];
+      picture.height = lh[k];
+      picture.channels = c;
+      picture.data.resize(pixels[k].size());
+      pnm::flip_and_swap(pixels[k].data(), picture.data.data(), lw[k], lh[k], c);
+      const std::string path = k ? level_path(out_path, k) : std::string(out_path);
+      if (!writable || !pnm::write(path.c_str(), picture)) return fail("Unable to write file", path.c_str());
+    }
+    return 0;
+  }
 
   if (scale_log2 || region || prefix) {
     himg_hip_ctx *ctx = nullptr;

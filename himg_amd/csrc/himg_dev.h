@@ -372,15 +372,25 @@ struct DstDesc {
   int pixel_stride;
 };
 
+// The picture pyramid (himg_hip_pyramid as the kernels take it): level[k] is the picture at 1 / 2^k,
+// batch x ceil(H / 2^k) x ceil(W / 2^k) x C interleaved bytes, frame f at f * oh * ow * C; nullptr: the
+// level is not wanted and nothing of it is computed or stored.  It travels in the kernel-argument
+// segment of the pyramid forms of the store kernels (k_dec_row_fused_m, k_tile_inv_m), which read
+// the pointers there, behind the entropy phase.
+struct PyrDesc {
+  uint8_t *level[4];
+};
+
 // tens: the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W] elements);
-// dst: in their pitched form (d_out: the destination pictures); not both.
+// dst: in their pitched form (d_out: the destination pictures); pyr: in their pyramid form (d_out:
+// pyr->level[0], which may be nullptr; level 3 is k_lres_preview's, behind the LRES chain); one at most.
 // Everything in front of them is the same launch.
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3,
-                   const TensDesc *tens = nullptr, const DstDesc *dst = nullptr);
+                   const TensDesc *tens = nullptr, const DstDesc *dst = nullptr, const PyrDesc *pyr = nullptr);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 // The 1/8-scale preview: the zeroing of the LRES symbols, the container parse up to the end of
 // the LRES chunk (k_dec_parse_head, which writes where that chunk ends to d_head_sizes[f]), the

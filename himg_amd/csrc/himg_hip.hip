@@ -1094,11 +1094,12 @@ extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int n
 
 // The launch behind the full decodes of a batch in HBM: the interleaved bytes (himg_hip_decode_device),
 // the planar float output (td) or windows of pitched pictures (dd, with each frame's origin in h_org:
-// the origins ride with the sizes, dd->org is filled in here).  bad: what the caller found wrong with
-// its descriptor.
+// the origins ride with the sizes, dd->org is filled in here) or the picture pyramid (pm, d_out its
+// level 0).  bad: what the caller found wrong with its descriptor.
 static int decode_full(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                        int width, int height, int num_channels, void *d_out, int32_t *d_status, void *stream,
-                       const char *bad, const himg_dev::TensDesc *td, himg_dev::DstDesc *dd, const int32_t *h_org) {
+                       const char *bad, const himg_dev::TensDesc *td, himg_dev::DstDesc *dd, const int32_t *h_org,
+                       const himg_dev::PyrDesc *pm = nullptr) {
   Geom g;
   const uint32_t *d_sizes = nullptr;
   if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, bad, &g))
@@ -1109,7 +1110,7 @@ static int decode_full(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride
   if (dd) dd->org = (const int32_t *)(d_sizes + batch);
   launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
                 (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows,
-                nullptr, false, 3, td, dd);
+                nullptr, false, 3, td, dd, pm);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -2431,6 +2432,87 @@ extern "C" int himg_hip_decode_scaled_device(himg_hip_ctx *ctx, const void *d_pa
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   return scaled_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, scale_log2, nullptr, d_out,
                        d_status, stream);
+}
+
+// ---------------------------------------------------------------------------
+// Picture pyramid: the full, 1/2-, 1/4- and 1/8-scale pictures from one pass (include/himg_hip.h).
+// The levels' pointers ride in the kernel arguments of the pyramid forms of the store kernels
+// (kernels_dec.hip, launch_decode); level 0 alone is the full decode itself.
+// ---------------------------------------------------------------------------
+extern "C" int himg_hip_pyramid_size(int width, int height, int level, int *ow, int *oh) {
+  if (!ow || !oh || width < 1 || height < 1 || level < 0 || level > 3) return HIMG_ERR_ARG;
+  const int F = 1 << level;
+  *ow = (int)(((long long)width + F - 1) / F);
+  *oh = (int)(((long long)height + F - 1) / F);
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_pyramid_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                              const uint32_t *h_sizes, int batch, int width, int height,
+                                              int num_channels, const himg_hip_pyramid *out, int32_t *d_status,
+                                              void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !out || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  himg_dev::PyrDesc pm;
+  int wanted = 0;
+  const char *bad = nullptr;
+  for (int k = 0; k < 4; ++k) {
+    pm.level[k] = (uint8_t *)out->level[k];
+    if (out->level[k]) ++wanted;
+    if ((uintptr_t)out->level[k] & 15) bad = "buffers must be 16-byte aligned";
+  }
+  if (!wanted) return fail(ctx, HIMG_ERR_ARG, "no pyramid level wanted");
+  // (level 0 alone: the full decode, in its own kernels)
+  const bool only0 = wanted == 1 && pm.level[0];
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, pm.level[0], d_status, stream,
+                     bad, nullptr, nullptr, nullptr, only0 ? nullptr : &pm);
+}
+
+// One host stream: the upload of decode_core (the device walks the row headers), one launch, the
+// verdict, then a copy per wanted level.  The levels lie one behind the other in the output staging,
+// each at a multiple of 256 bytes.
+extern "C" int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                          uint8_t *const dst[4], const size_t dst_cap[4], int *width, int *height,
+                                          int *channels) {
+  if (!ctx || !packed || !dst || !dst_cap || !width || !height || !channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  *width = W; *height = H; *channels = C;
+  size_t bytes[4] = {0, 0, 0, 0}, at[4] = {0, 0, 0, 0}, total = 0;
+  int wanted = 0;
+  bool small = false;
+  for (int k = 0; k < 4; ++k) {
+    if (!dst[k] && !dst_cap[k]) continue;
+    int ow = 0, oh = 0;
+    (void)himg_hip_pyramid_size(W, H, k, &ow, &oh);
+    bytes[k] = (size_t)ow * oh * C;
+    at[k] = total;
+    total += round_up(bytes[k], 256);
+    ++wanted;
+    if (!dst[k] || dst_cap[k] < bytes[k]) small = true;
+  }
+  if (!wanted) return fail(ctx, HIMG_ERR_ARG, "no pyramid level wanted");
+  if (small) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_cap = round_up(packed_size + 16, 256);
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(total) || !ctx->h_status.reserve(256))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  ctx->host_bytes = 0;   // (nothing stays resident: no fetch_last behind this call)
+  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
+  himg_hip_pyramid py;
+  for (int k = 0; k < 4; ++k) py.level[k] = bytes[k] ? (uint8_t *)ctx->h_out.p + at[k] : nullptr;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  if (int rc = himg_hip_decode_pyramid_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, &py, (int32_t *)ctx->h_status.p,
+                                              nullptr)) {
+    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
+    return rc;
+  }
+  int32_t st = 0;
+  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
+  if (st) return status_error(ctx, st);
+  for (int k = 0; k < 4; ++k)
+    if (bytes[k]) HIP_TRY(ctx, hipMemcpy(dst[k], py.level[k], bytes[k], hipMemcpyDeviceToHost));
+  return HIMG_OK;
 }
 
 // ---------------------------------------------------------------------------

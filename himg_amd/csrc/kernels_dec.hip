@@ -25,6 +25,10 @@
 //   k_dec_row_fused_p, k_tile_inv_p, k_dec_region_p
 //                     their pitched forms: the same interleaved bytes at a row pitch, a pixel
 //                     stride and an origin per frame (DstDesc; include/himg_hip.h, "decode into")
+//   k_dec_row_fused_m, k_tile_inv_m
+//                     the pyramid forms of the two row kernels: besides the full picture, the 1/2-
+//                     and 1/4-scale ones from the same symbols (PyrDesc; include/himg_hip.h,
+//                     "picture pyramid"; the 1/8-scale level is k_lres_preview's)
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
 #include "prefix_walk.h"
@@ -3155,13 +3159,22 @@ __global__ __launch_bounds__(256) void k_sse(Geom g, const uint8_t *frames, cons
 // [batch][co][H][W] buffer and td the descriptor in the kernel-argument segment.
 // PITCH: the pitched output (transform_store_pair's pitched form); out_frames is then the first
 // destination picture and pd the descriptor in the kernel-argument segment.
-template <int COLS, bool TENS = false, bool PITCH = false>
+// PYR: the picture pyramid (PyrDesc, pm in the kernel-argument segment); out_frames is level 0, which
+// the loop above stores when it is wanted; a second loop over the rows' tiles then computes the wanted
+// ones of the 1/2- and 1/4-scale levels from the same symbols in LDS (pyr_tile_part: k_dec_scaled's
+// tile arithmetic at stride cols, channel stride 64 cols).
+template <int PART>
+__device__ __forceinline__ void pyr_tile_part(const Geom &g, int sstride, int cstride, const uint8_t *sym,
+                                              const uint8_t *low, const int16_t *s_unmap, const uint8_t *s_shift,
+                                              int ycbcr, int u, int v, int f, uint8_t *level);   // (behind scaled_tile_rows)
+typedef const __attribute__((address_space(4))) PyrDesc *PyrK;
+template <int COLS, bool TENS = false, bool PITCH = false, bool PYR = false>
 __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &ws, const uint8_t *packed,
                                                    size_t in_stride, const uint32_t *sizes,
                                                    uint8_t *out_frames, int r0, int r1, int rpw,
                                                    const int bx, const int f, const int gx, const int gy,
                                                    const uint32_t next_lin, const bool again, const bool same_tables,
-                                                   TensK td = nullptr, DstK pd = nullptr) {
+                                                   TensK td = nullptr, DstK pd = nullptr, PyrK pm = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   if (COLS == 512) rpw = 1;   // 4096-pixel rows: one row fills the lanes and the LDS (known at compile time)
   const FusedLayout L = fused_layout(g.row_block, rpw);
@@ -3358,9 +3371,12 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   else if constexpr (PITCH) img = dst_frame(out_frames, pd, f);
   else img = out_frames + (size_t)f * ((size_t)g.W * g.H * g.C);
   const int per_row = ((cols + 31) >> 5) * 64;   // whole wavefronts: a lane pair never straddles rows
+  // (PYR: level 0 only where it is wanted -- uniform, a scalar load)
+  bool want0 = true;
+  if constexpr (PYR) want0 = pm->level[0] != nullptr;
   HIMG_SPAN_BEGIN("dec.transform");
 #pragma unroll 1
-  for (int it = tid; it < per_row * nr; it += kDecThreads) {
+  for (int it = tid; want0 && it < per_row * nr; it += kDecThreads) {
     const int i = COLS == 512 ? 0 : it / per_row, il = it - i * per_row;
     // A lane pair beyond the row's last tile (widths that are not a multiple of 256 pixels)
     // transforms the last tile once more and stores nothing: no exec-masked region around
@@ -3372,6 +3388,27 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
                                             nullptr, 0, td, pd);
   }
   HIMG_SPAN_END("dec.transform");
+  if constexpr (PYR) {
+    // Without level 0 no wavefront has met the wait for its touch load (transform_store_pair's).
+    if (pf_on && !want0) asm volatile("s_waitcnt vmcnt(0)" ::"v"(pf_a) : "memory");
+    // The 1/2- and 1/4-scale levels, behind the full-resolution loop: its registers are dead, the
+    // symbols still read-only in LDS (the next row's barrier stands in front of their clear).  An
+    // item is (part, row, tile) with the tile fastest: neighbouring lanes take neighbouring tiles,
+    // so that a wavefront's stores of an output row are contiguous.  Part 0 is a tile's 4 x 4 at 1/2
+    // scale -- in one pass: k_dec_scaled's two halves gather and transform the tile's sixteen symbols
+    // twice to stay within 64 registers, which this kernel has no need of --, part 1 its 2 x 2 at 1/4
+    // (4096-pixel rows: 512 + 512 items, one for every lane).
+    uint8_t *const l1 = pm->level[1], *const l2 = pm->level[2];
+    const int nt = cols * nr;
+#pragma unroll 1
+    for (int j = (l1 ? 0 : nt) + tid; j < (l2 ? 2 * nt : nt); j += kDecThreads) {
+      const int part = j >= nt ? 1 : 0, t = j - part * nt;
+      const int i = COLS == 512 ? 0 : t / cols, u = t - i * cols;
+      const uint8_t *sy = sym0 + (size_t)i * rb16 + u;
+      if (part == 0) pyr_tile_part<0>(g, cols, 64 * cols, sy, low, s_unmap, s_shift, ycbcr, u, rb + i, f, l1);
+      else pyr_tile_part<1>(g, cols, 64 * cols, sy, low, s_unmap, s_shift, ycbcr, u, rb + i, f, l2);
+    }
+  }
   // A wavefront without a transform iteration (per_row * nr < 1024: narrow rows in a frame's last
   // workgroup) has not met the wait for its touch load: it waits here, the register its own up to
   // the wait, before the persistent loop hands it the next row.  (4096-pixel rows: every lane
@@ -3513,6 +3550,41 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_p(RowArgsP) {
     dec_row_fused_body<COLS, false, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
                                           ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
                                           nd ? lin + nd : element(i + 1), again, f == f_prev, nullptr, &ka->d);
+    again = true;
+    f_prev = f;
+  }
+}
+
+// k_dec_row_fused_m: the same kernel in its pyramid form.  RowArgs -- unchanged, out_frames level 0 --
+// followed by the levels' descriptor, which stays in the kernel-argument segment: the pointers are
+// read behind the entropy phase, where the stores begin.
+struct RowArgsM {
+  RowArgs a;
+  PyrDesc m;
+};
+template <int COLS>
+__global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_m(RowArgsM) {
+  typedef const __attribute__((address_space(4))) RowArgsM *KArgs;
+  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
+  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
+  bool again = false;
+  int f_prev = -1;
+#pragma unroll 1
+  for (uint32_t i = 0; i * S < total; ++i) {
+    const uint32_t lin = element(i);
+    if (lin >= total) break;   // (the last round is a partial one)
+    asm volatile("" : "+s"(ka));
+    Geom g;
+    DecWs ws;
+    karg_copy<uint32_t>(&g, &ka->a.g);
+    karg_copy<unsigned long long>(&ws, &ka->a.ws);
+    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
+    const uint32_t nd = (uint32_t)ka->a.next_dist;
+    dec_row_fused_body<COLS, false, false, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames,
+                                                 ka->a.r0, ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
+                                                 nd ? lin + nd : element(i + 1), again, f == f_prev, nullptr, nullptr,
+                                                 &ka->m);
     again = true;
     f_prev = f;
   }
@@ -5107,6 +5179,76 @@ __device__ __forceinline__ void scaled_tile_store_crop(const Geom &g, int sstrid
   }
 }
 
+// The pyramid forms' share of one tile (k_dec_row_fused_m, k_tile_inv_m): PART 0 its 4 x 4 at 1/2
+// scale, PART 1 its 2 x 2 at 1/4 scale, to frame f of `level` (batch x ceil(H / F) x ceil(W / F) x C
+// bytes).  scaled_tile_rows, whatever holds the symbols.
+template <int PART>
+__device__ __forceinline__ void pyr_tile_part(const Geom &g, int sstride, int cstride, const uint8_t *sym,
+                                              const uint8_t *low, const int16_t *s_unmap, const uint8_t *s_shift,
+                                              int ycbcr, int u, int v, int f, uint8_t *level) {
+  constexpr int F = PART == 1 ? 4 : 2;
+  ScaledArgs sa;
+  sa.sw = 0; sa.ow = (g.W + F - 1) / F; sa.oh = (g.H + F - 1) / F; sa.out = level;
+  uint8_t *img = level + (size_t)f * ((size_t)sa.oh * sa.ow * g.C);
+  if (PART == 0) scaled_tile_rows<4, 0, 4>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+  else scaled_tile_rows<2, 0, 2>(g, sstride, cstride, sym, low, s_unmap, s_shift, ycbcr, u, v, sa, img);
+}
+
+// k_tile_inv_m: k_tile_inv in its pyramid form (PyrDesc; rows too wide for the LDS).  Level 0 is
+// k_tile_inv's store where it is wanted; then the tile's two lanes share the smaller levels, read from
+// the same symbols in HBM ([C][64][cols] per block row): the first lane of a pair (lanes 0..31 of a
+// wavefront, neighbouring lanes neighbouring tiles) the 1/2-scale samples, the second the 1/4-scale ones.
+// The arguments in one struct, as in k_tile_inv_t.
+struct TileArgsM {
+  Geom g;
+  DecWs ws;
+  int v0;
+  PyrDesc m;
+};
+template <bool FAST>
+__global__ __launch_bounds__(256) void k_tile_inv_m(TileArgsM a) {
+  __shared__ int16_t s_unmap[256];   // indexed by the code byte
+  __shared__ uint8_t s_shift[2][64];
+  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const PyrK pm = &((const __attribute__((address_space(4))) TileArgsM *)__builtin_amdgcn_kernarg_segment_ptr())->m;
+  const int v = blockIdx.y + a.v0, f = blockIdx.z;
+  const DecFrame *df = ws.frames + f;
+  __shared__ int s_status;
+  if (threadIdx.x == 0) s_status = df->status;
+  __syncthreads();
+  if (s_status) return;
+  {
+    const int k = threadIdx.x;
+    const int sc = (int8_t)k;
+    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
+    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
+    if (k < 64) {
+      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
+      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
+    }
+    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
+  }
+  __syncthreads();
+  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
+  const int u = pair_tile(it);
+  if (u >= g.cols) return;
+  const uint8_t *sym = ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block;
+  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  const int ycbcr = df->ycbcr;
+  uint8_t *const l0 = pm->level[0];
+  if (l0)
+    transform_store_pair<(FAST ? -1 : 0), FAST>(g, g.cols, sym, low, s_unmap, &s_shift[0][0], s_shiftp, ycbcr, u,
+                                                pair_half(it), v, l0 + (size_t)f * ((size_t)g.W * g.H * g.C));
+  uint8_t *const l1 = pm->level[1], *const l2 = pm->level[2];
+  if (pair_half(it) == 0) {
+    if (l1) pyr_tile_part<0>(g, g.cols, 64 * g.cols, sym + u, low, s_unmap, &s_shift[0][0], ycbcr, u, v, f, l1);
+  } else if (l2) {
+    pyr_tile_part<1>(g, g.cols, 64 * g.cols, sym + u, low, s_unmap, &s_shift[0][0], ycbcr, u, v, f, l2);
+  }
+}
+
 template <int S, bool ONE>
 __global__ __launch_bounds__(kDecThreads, 8) void k_dec_scaled(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, ScaledArgs sa) {
@@ -5350,7 +5492,10 @@ hipError_t dec_set_kernel_attrs() {
                          reinterpret_cast<const void *>(&k_dec_row_fused_t<0>),
                          reinterpret_cast<const void *>(&k_dec_row_fused_p<512>),
                          reinterpret_cast<const void *>(&k_dec_row_fused_p<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_p<0>)};
+                         reinterpret_cast<const void *>(&k_dec_row_fused_p<0>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_m<512>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_m<-1>),
+                         reinterpret_cast<const void *>(&k_dec_row_fused_m<0>)};
   for (const void *k : fused) {
     // (the kernel's static LDS counts against the same 160 KiB)
     hipFuncAttributes fa;
@@ -5684,7 +5829,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index, bool index_only, int phase, const TensDesc *tens,
-                   const DstDesc *dst) {
+                   const DstDesc *dst, const PyrDesc *pyr) {
   // d_row_index: the FRES row index is given (k_dec_set_index instead of the serial
   // header walk; one frame).  index_only: container parse and row-header walk only --
   // the caller reads ws.row_off / ws.row_len / DecFrame::rows_first (rank 0 of a
@@ -5819,6 +5964,12 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     HIMG_LAUNCH(k_dec_rowwalk, dim3(batch), dim3(64), g, ws, d_packed, in_stride, d_sizes, kWalkAll, 0);
   }
   if (do_head) launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
+  // The pyramid's 1/8-scale level: the low-res plane the chain has just finished, as launch_preview
+  // stores it.  (A frame the rows reject later keeps these bytes: a failed frame's are unspecified.)
+  if (do_head && pyr && pyr->level[3]) {
+    const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
+    HIMG_LAUNCH(k_lres_preview, dim3((npix + 1023u) / 1024u, batch), dim3(256), g, ws, pyr->level[3]);
+  }
   if (!do_rows) return;
   if (wps) {
     // Rows per workgroup: as many as the transform has lanes for and the LDS holds
@@ -5852,6 +6003,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       rp_.a = ra_; rp_.d = *dst;                                                                \
       hipLaunchKernelGGL((k_dec_row_fused_p<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
                          dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rp_); \
+    } else if (pyr) {                                                                           \
+      RowArgsM rm_;                                                                             \
+      rm_.a = ra_; rm_.m = *pyr;                                                                \
+      hipLaunchKernelGGL((k_dec_row_fused_m<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
+                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rm_); \
     } else                                                                                      \
     hipLaunchKernelGGL((k_dec_row_fused<COLS>), dim3((unsigned)(pers_ ? slots_ : all_)),        \
                        dim3(kDecThreads), lds, stream, ra_);                                    \
@@ -5867,7 +6023,8 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       const int form = g.W == 4096 && whole4 ? 0 : whole4 ? 1 : 2;
       static const char *const kTensName[3] = {"k_dec_row_fused_t<512>", "k_dec_row_fused_t<-1>", "k_dec_row_fused_t<0>"};
       static const char *const kPitchName[3] = {"k_dec_row_fused_p<512>", "k_dec_row_fused_p<-1>", "k_dec_row_fused_p<0>"};
-      prof_begin(prof, tens ? kTensName[form] : dst ? kPitchName[form] : "k_dec_row_fused", stream);
+      static const char *const kPyrName[3] = {"k_dec_row_fused_m<512>", "k_dec_row_fused_m<-1>", "k_dec_row_fused_m<0>"};
+      prof_begin(prof, tens ? kTensName[form] : dst ? kPitchName[form] : pyr ? kPyrName[form] : "k_dec_row_fused", stream);
       if (g.W == 4096 && whole4) HIMG_FUSED_LAUNCH(512, a, b);
       else if (g.W == 2048 && whole4) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
       else if (g.W == 1920 && whole4) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
@@ -5894,6 +6051,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
         tp.g = g; tp.ws = ws; tp.out_frames = d_out; tp.v0 = a; tp.d = *dst;
         if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_p<true>, dim3(gx, b - a, batch), dim3(256), tp);
         else HIMG_LAUNCH(k_tile_inv_p<false>, dim3(gx, b - a, batch), dim3(256), tp);
+      } else if (pyr) {
+        TileArgsM tm;
+        tm.g = g; tm.ws = ws; tm.v0 = a; tm.m = *pyr;
+        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_m<true>, dim3(gx, b - a, batch), dim3(256), tm);
+        else HIMG_LAUNCH(k_tile_inv_m<false>, dim3(gx, b - a, batch), dim3(256), tm);
       } else
       if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv<true>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
       else HIMG_LAUNCH(k_tile_inv<false>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);

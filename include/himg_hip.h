@@ -728,6 +728,52 @@ int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uint8_t *const
                                          const int32_t *rects, uint8_t *const *dst, const size_t *dst_cap,
                                          int *widths, int *heights, int *channels);
 
+/* ---- picture pyramid: full, 1/2, 1/4 and 1/8 scale in one pass --------------------- */
+/*
+ * Level k, 0 <= k <= 3, is the picture at 1 / 2^k: oh = ceil(H / 2^k) rows x ow = ceil(W / 2^k)
+ * columns x C channels, interleaved u8, tightly packed.  Nothing new is defined:
+ *   level 0 is byte for byte himg_hip_decode_device's output,
+ *   level 1 and level 2 himg_hip_decode_scaled_device's with scale_log2 = 1 and 2 (the four steps of
+ *   the scaled section above),
+ *   level 3 himg_hip_preview_device's,
+ * for the same stream under either HIMG_OPT_FIX_T2 setting.  What the pyramid saves is the front of
+ * the decode -- container parse, LRES chain, row-header walk, row counts and the entropy walk of
+ * every block row -- which runs once for all the wanted levels instead of once per entry point; the
+ * smaller levels are computed from the row's symbols where the full-resolution store has them.
+ * Verdict: ONE per frame, exactly himg_hip_decode's, for every stream, whichever levels are wanted:
+ * the whole stream is looked at.  (Level 3 alone is therefore not himg_hip_preview_device, which
+ * does not see damage behind LRES and reads only the head of the stream.)  A failed frame's bytes
+ * are unspecified at every level; its neighbours are unaffected.
+ */
+typedef struct himg_hip_pyramid {
+  void *level[4];   /* level[k]: batch x ceil(H/2^k) x ceil(W/2^k) x C bytes, frame f at f*oh*ow*C; NULL = not wanted */
+} himg_hip_pyramid;
+/* Host only, no GPU: level k's size.  Levels 1 and 2: himg_hip_scaled_size; level 3: the preview's
+ * geometry, (ceil(W / 8), ceil(H / 8)); level 0: (W, H).  HIMG_ERR_ARG for a level outside 0..3 or a
+ * non-positive size. */
+int himg_hip_pyramid_size(int width, int height, int level, int *ow, int *oh);
+/* Streams of a batch in HBM: the argument, alignment and grid contract of himg_hip_decode_device,
+ * with out->level[k] where d_out stands there.  Any non-empty subset of the levels is valid; an empty
+ * one, or a NULL `out`, is HIMG_ERR_ARG with nothing launched and nothing written.  Every wanted
+ * level's base is 16-byte aligned, as d_out is for the level's own entry point; no alignment is asked
+ * of a frame's start.  No byte outside a wanted level's batch * oh * ow * C bytes is written, and
+ * nothing at all for a level that is not wanted.  The pointers ride in the kernel arguments, as the
+ * tensor and pitched descriptors do: asynchronous, no host synchronisation, `out` itself is not read
+ * after the call returns.  d_status[f]: the one verdict of frame f. */
+int himg_hip_decode_pyramid_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                   const uint32_t *h_sizes, int batch, int width, int height,
+                                   int num_channels, const himg_hip_pyramid *out, int32_t *d_status,
+                                   void *stream);
+/* One host stream into caller-owned host memory: one upload, one device pass, one download per
+ * wanted level.  Level k is wanted when dst[k] is not NULL or dst_cap[k] is not 0; no level wanted:
+ * HIMG_ERR_ARG.  A wanted level whose dst is NULL or whose dst_cap is below its oh * ow * C bytes:
+ * HIMG_ERR_CAPACITY with *width, *height, *channels (the full picture's) set and nothing decoded;
+ * the caller sizes its buffers from himg_hip_peek and himg_hip_pyramid_size.  Nothing is kept
+ * resident: this entry point has NO himg_hip_fetch_last protocol (a fetch behind it finds no result). */
+int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                               uint8_t *const dst[4], const size_t dst_cap[4], int *width, int *height,
+                               int *channels);
+
 /* ---- decode a stream prefix: whole block rows exact, the rest from the low-res plane ---- */
 /*
  * The format is progressive in file order: the whole low-res plane (LRES)
