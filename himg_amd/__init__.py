@@ -34,6 +34,7 @@ DBG = {
     "avg": 0, "lowres": 1, "lres_sym": 2, "fres_sym": 3, "lres_hist": 4, "fres_hist": 5,
     "lres_len": 6, "fres_len": 7, "lres_code": 8, "fres_code": 9, "fres_row_bytes": 10,
     "dec_stats": 11, "parse_stats": 12, "rowcount_stats": 13, "loop_counts": 14, "fres_tok_sym": 15, "tok_cnt": 16,
+    "lane_start": 17, "lane_off": 18,
 }
 DBG_DECODER = 0x100
 
@@ -90,6 +91,7 @@ def lib():
     L.himg_hip_host_free.restype = None
     L.himg_hip_encode_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp, vp]
     L.himg_hip_decode_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_debug_row_records.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp]
     L.himg_hip_encode_device_q.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, i32, vp, sz, vp, vp, vp]
     L.himg_hip_windows_extent.argtypes = [vp, i32, i32, vp, i32, i32, P(sz)]
     L.himg_hip_encode_windows_device.argtypes = [vp, vp, vp, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp, vp, vp]
@@ -256,7 +258,7 @@ def psnr(a, b):
 # ---- engine ------------------------------------------------------------------
 
 # himg_hip_get_option / himg_hip_set_option: the options by name (HIMG_OPT_*, include/himg_hip.h).
-_OPTIONS = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5}
+_OPTIONS = {"fix_t2": 1, "count_wave": 2, "emit_rows": 3, "row_tokens": 4, "front": 5, "count_stretch": 6}
 
 
 class Engine:
@@ -751,7 +753,8 @@ class Engine:
 
     def set_option(self, option, value):
         """himg_hip_set_option; option names: "fix_t2", and the kernel-variant selectors
-        "count_wave" / "emit_rows" (-1 = by launch size, 0 / 1 = force; see include/himg_hip.h)."""
+        "count_wave" / "emit_rows" (-1 = by launch size, 0 / 1 = force; see include/himg_hip.h),
+        "count_stretch" (sub-sequences per lane of the wavefront-per-row count kernel: -1, 1, 2, 4, 8)."""
         opt = _OPTIONS[option] if isinstance(option, str) else int(option)
         self._check(lib().himg_hip_set_option(self._ctx, opt, int(value)), "set_option")
         if opt == 1:
@@ -841,6 +844,14 @@ class Engine:
                                           batch, width, height, channels, _ptr(d_out),
                                           _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_device")
+
+    def row_records_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_status, stream=0):
+        """himg_hip_debug_row_records: the front of decode_device up to the row records, no row kernel;
+        read them with debug_read("lane_start" / "lane_off", frame, nbytes, np.uint32, decoder=True)."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_debug_row_records(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data,
+                                              batch, width, height, channels, _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "row_records_device")
 
     def decode_tensor_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, desc, d_out,
                              d_status, stream=0):

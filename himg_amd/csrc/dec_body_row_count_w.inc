@@ -1,6 +1,6 @@
   __shared__ __attribute__((aligned(16))) uint32_t gyx[2 * kTabEntries];
   __shared__ uint32_t nd[kMaxNodes + 1];
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[kCountRowsW * kStageAlloc];
+  __shared__ __attribute__((aligned(16))) uint32_t s_stage[kCountRowsW * (NQ > 1 ? kLaneAlloc : kStageAlloc)];
   __shared__ int s_flag;
   uint32_t *gy = gyx, *gx = gyx + kTabEntries;
   const int f = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
@@ -58,7 +58,7 @@
   uint32_t first = rel0;   // where the phase's first lane starts: exact
   uint32_t base = 0;       // symbols in front of the phase
   uint32_t rounds = 0;
-  uint32_t *stage = s_stage + (tid >> 6) * kStageAlloc;
+  uint32_t *stage = s_stage + (tid >> 6) * (NQ > 1 ? kLaneAlloc : kStageAlloc);
   LdsBits bits;
   bits.base = lds_addr(stage);
   auto phases = [&](auto staged_c) {
@@ -158,8 +158,182 @@
     first = (uint32_t)__builtin_amdgcn_readlane((int)(active ? endpos + shift : rel_end), 63);
   }
   };
-  if (sb <= kStageSubBits) phases(std::true_type{});
-  else phases(std::false_type{});
+  // ---- NQ > 1: a lane owns a STRETCH of NQ consecutive sub-sequences -------------------------
+  // Lane l of phase j walks sub-sequences (64 j + l) NQ .. + NQ - 1 as one continuous chain, so a
+  // row takes 16 / NQ phases and only the 64 stretch boundaries of a phase are speculative: one
+  // lead-in and one re-join per stretch where the form above pays them per sub-sequence.  The
+  // records are the same: the chain is the same chain, cut at the same nominal boundaries (every
+  // walk below ends where the walk of a lane of the form above ends: at the first boundary of a
+  // group at or past the sub-sequence's limit, a long code completed).
+  // The wavefront goes through a stretch in NQ sub-steps.  Before each, every walking lane copies
+  // the kLaneWords dwords from the dword of its CURRENT position to its own piece of the staging
+  // buffer (LaneBits) -- the pieces of the lanes of a sub-step lie NQ sub-sequences apart, so
+  // there is no contiguous range to stage.  A lane's boundaries inside its stretch (its marks) and
+  // the symbols of each of its sub-sequences wait in the phase's own 64 NQ records, TRANSPOSED --
+  // sub-step k of lane l at 64 k + l, so that a wave's store is one run of 64 dwords (at l NQ + k,
+  // where the record belongs, it is 64 pieces NQ dwords apart: measured, 3.2 ms for NQ = 8).
+  // Each word is written and read back by the same lane only.  When the phase's chain stands,
+  // marks and offsets go through the (then idle) staging buffer into their places.
+  // Re-join: a lane whose start moves walks to T again (as above); if it arrives where it did
+  // before, everything behind stands and only the first count changes.  If not it walks on,
+  // replacing marks and counts, until it meets one of its earlier marks or reaches the end of
+  // the stretch.  Exact by induction from the phase's first lane, as above.
+  auto stretches = [&]() {
+    uint32_t *piece = stage + (uint32_t)lane * kLaneWords;
+    LaneBits lb;
+    lb.base = 0;
+    // Lanes that are `on` copy their piece: the dwords from the one that holds bit `pos`.
+    auto stage_at = [&](uint32_t pos, bool on) {
+      wave_lds_sync();   // (the walks before are done with the pieces)
+      if (on) {
+        const uint32_t w0 = pos >> 5;
+        if (w0 + kLaneWords - 1u <= rd.jmax) {
+#pragma unroll
+          for (uint32_t i = 0; i + 4u <= kLaneWords; i += 4u) {
+            const PackedU4 u = *reinterpret_cast<const PackedU4 *>(rd.w + w0 + i);
+            piece[i] = u.x; piece[i + 1u] = u.y; piece[i + 2u] = u.z; piece[i + 3u] = u.w;
+          }
+#pragma unroll
+          for (uint32_t i = kLaneWords & ~3u; i < kLaneWords; ++i) piece[i] = rd.w[w0 + i];
+        } else {   // the stream ends inside the piece: clamped, as the reader in place clamps
+#pragma unroll 1
+          for (uint32_t i = 0; i < kLaneWords; ++i) piece[i] = rd.ld(w0 + i);
+        }
+        lb.base = lds_addr(piece) - 4u * w0;
+      }
+      wave_lds_sync();
+    };
+    // sub_grid's boundaries, from the row's S (the grid is moved left so that the last active
+    // sub-sequence is kTailBits long: see sub_grid).
+    const uint32_t la = (rem - 1u) / sb, L = rem - la * sb;
+    const uint32_t S = (L > kTailBits && la + 1u < (uint32_t)kDecThreads) ? sb - (L - kTailBits) : 0u;
+    const uint32_t last_active = (rem - 1u + S) / sb;
+    auto nom_b0 = [&](uint32_t v) { return v ? rel0 + v * sb - S : rel0; };
+    auto nom_lim = [&](uint32_t v) { const uint32_t x = rel0 + (v + 1u) * sb - S; return x > rel_end ? rel_end : x; };
+    const uint32_t lead_in = lead < 256u ? lead : 256u;   // (a piece holds a lead-in of up to 311 bits)
+#pragma unroll 1
+    for (int j = 0; j < kDecThreads / (64 * NQ); ++j) {
+      const uint32_t v0 = (uint32_t)(64 * j + lane) * (uint32_t)NQ;
+      const uint32_t b0 = nom_b0(v0);
+      // sub-step k's word of this lane while the phase is walked: [64 k] of these
+      uint32_t *t_start = l_start + 64 * NQ * j + lane, *t_off = l_off + 64 * NQ * j + lane;
+      const bool active = b0 < rel_end;
+      const uint32_t pb0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0);
+      if (pb0 >= rel_end) {   // a phase beyond the payload: its lanes own nothing
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) { t_start[64 * k] = rem; t_off[64 * k] = base; }
+        continue;
+      }
+      uint32_t start = active ? b0 : rel_end;
+      if (lane == 0) start = first;
+      if (lead_in) {   // lead-in, as above
+        const bool on = lane > 0 && active;
+        const uint32_t from = start - rel0 > lead_in ? start - lead_in : rel0;
+        stage_at(from, on);
+        if (on) {
+          uint32_t guess, none;
+          grp_count_lds(lb, tb, from, start, &guess, &none);
+          start = guess;
+        }
+      }
+      uint32_t endpos = start, cnt0 = 0;
+      bool dirty = active;
+      uint32_t T = b0 + kJoinBits;
+      { const uint32_t lim0 = nom_lim(v0); if (T > lim0 || T < b0) T = lim0; }
+      uint32_t posT = ~0u, cT = 0;
+      bool again = false;   // a round after the first: the lanes that walk have marks from before
+      for (;;) {
+        bool walking = dirty;
+        uint32_t pos = start;
+#pragma unroll 1
+        for (int k = 0; k < NQ; ++k) {
+          if (!__any(walking ? 1 : 0)) break;
+          const uint32_t lim = nom_lim(v0 + (uint32_t)k);
+          stage_at(pos, walking);
+          if (walking) {
+            uint32_t np = pos, c;
+            if (k == 0) {
+              uint32_t p1, c1;
+              grp_count_lds(lb, tb, pos, T, &p1, &c1);
+              if (p1 == posT) {
+                c = c1 + (cnt0 - cT);
+                walking = false;
+              } else {
+                uint32_t c2;
+                grp_count_lds(lb, tb, p1, lim, &np, &c2);
+                c = c1 + c2;
+              }
+              posT = p1;
+              cT = c1;
+              cnt0 = c;
+            } else {
+              grp_count_lds(lb, tb, pos, lim, &np, &c);
+            }
+            t_off[64 * k] = c;
+            if (walking) {
+              if (k + 1 < NQ) {
+                uint32_t *m = t_start + 64 * (k + 1);
+                if (again && *m == np - rel0) walking = false;   // met an earlier mark: the rest stands
+                else *m = np - rel0;
+              } else {
+                endpos = np;
+              }
+              pos = np;
+            }
+          }
+        }
+        // The chain: a lane starts where its left neighbour's stretch ended (one DPP move).
+        const uint32_t ns = wave_shr1_dpp(first, endpos);
+        dirty = active && ns != start;
+        if (active) start = ns;
+        ++rounds;
+        again = true;
+        if (!__any(dirty ? 1 : 0)) break;
+      }
+      // Offsets: one scan over the lanes' stretch totals, then the partial sums inside a lane
+      // (each count clamped like k_row_count's: see row_count_one).
+      uint32_t tot = 0;
+      if (active) {
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) tot += min(t_off[64 * k], 0x3fffffu);
+      }
+      const uint32_t incl = wave_scan_add_dpp(tot);
+      // Into place through the staging buffer, the starts and then the offsets: every lane's
+      // words are in LDS before the first store lands on another lane's.
+      wave_lds_sync();
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) {
+        const uint32_t v = v0 + (uint32_t)k;
+        const bool a = nom_b0(v) < rel_end;
+        if (v == last_active) l_off[kDecThreads + 1] = k + 1 < NQ ? t_start[64 * (k + 1)] : endpos - rel0;
+        // (k = 0 of a lane with no sub-sequence of its own: rel_end, i.e. rem)
+        stage[(uint32_t)lane * NQ + k] = k == 0 ? start - rel0 : (a ? t_start[64 * k] : rem);
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) t_start[64 * k] = stage[64 * k + lane];
+      wave_lds_sync();
+      uint32_t off = base + incl - tot;
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) {
+        const bool a = nom_b0(v0 + (uint32_t)k) < rel_end;
+        stage[(uint32_t)lane * NQ + k] = off;
+        off += a ? min(t_off[64 * k], 0x3fffffu) : 0u;
+      }
+      wave_lds_sync();
+#pragma unroll
+      for (int k = 0; k < NQ; ++k) t_off[64 * k] = stage[64 * k + lane];
+      base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      first = (uint32_t)__builtin_amdgcn_readlane((int)(active ? endpos : rel_end), 63);
+    }
+  };
+  if constexpr (NQ > 1) {
+    if (sb <= kStageSubBits) stretches();
+    else phases(std::false_type{});
+  } else {
+    if (sb <= kStageSubBits) phases(std::true_type{});
+    else phases(std::false_type{});
+  }
   if (lane == 0) {
     l_off[kDecThreads] = base;
     l_off[kDecThreads + 3] = rounds;

@@ -38,6 +38,7 @@ struct Geom {
   // Kernel variants (context options, see himg_hip.h HIMG_OPT_*): -1 = chosen by the launch size.
   int prefetch_rows;         // decoder: the row kernel touches the packed bytes of the row that takes its CU next (HIMG_PREFETCH_ROWS=0 turns it off: an A/B knob)
   int count_wave;            // decoder: k_row_count_w (a wavefront per row) instead of k_row_count
+  int count_stretch;         // decoder, k_row_count_w: sub-sequences per lane (2, 4, 8; 1 = one each, the earlier form; -1 = kCountStretch)
   int wide_q;                // decoder, rows wider than the LDS: the host's estimate says a quarter sub-sequence of a row
                              // (1/4096 of its payload) fits k_row_count_q's staging buffer -- that kernel counts
   int emit_rows;             // encoder: k_emit_t<8> (a wavefront per row) instead of a workgroup per row
@@ -392,6 +393,10 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3,
                    const TensDesc *tens = nullptr, const DstDesc *dst = nullptr, const PyrDesc *pyr = nullptr);
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
+// The front of launch_decode's rows and no more (himg_hip_debug_row_records): container parse, row-header
+// walk, then k_row_count_w over every row in the form g.count_stretch asks for.  No row kernel runs.
+void launch_row_records(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                        const uint32_t *d_sizes, int32_t *d_status, hipStream_t stream, Profiler *prof);
 // The 1/8-scale preview: the zeroing of the LRES symbols, the container parse up to the end of
 // the LRES chunk (k_dec_parse_head, which writes where that chunk ends to d_head_sizes[f]), the
 // LRES chain bounded there, the predictor inverse, then k_lres_preview: batch x ceil(H/8) x

@@ -122,6 +122,7 @@ struct himg_hip_ctx {
   int lres_serial = 0;     // HIMG_FORCE_LRES_SERIAL=1: test knob, see Geom::lres_serial
   int prefetch_rows = 1;   // HIMG_PREFETCH_ROWS: see Geom::prefetch_rows
   int count_wave = -1, emit_rows = -1;   // HIMG_OPT_COUNT_WAVE / _EMIT_ROWS (-1: by launch size)
+  int count_stretch = -1;                // HIMG_OPT_COUNT_STRETCH (-1: the default)
   int row_tokens = -1;                   // HIMG_OPT_ROW_TOKENS (-1: by launch size)
   int front = -1;                        // HIMG_OPT_FRONT (-1: by launch size)
   // Side stream + events: the decoder forks its serial row-header walk onto it.
@@ -247,6 +248,7 @@ static bool make_geom(int width, int height, int pixel_stride, int num_channels,
   g->lead_bits = 128;
   g->lres_serial = 0;
   g->count_wave = g->emit_rows = g->row_tokens = g->front = -1;
+  g->count_stretch = -1;
   g->wide_q = 0;
   g->prefetch_rows = 1;
   g->frame_bytes = (long long)width * height * pixel_stride;
@@ -265,6 +267,7 @@ static void apply_settings(const himg_hip_ctx *ctx, Geom *g) {
   g->lres_serial = ctx->lres_serial;
   g->prefetch_rows = ctx->prefetch_rows;
   g->count_wave = ctx->count_wave;
+  g->count_stretch = ctx->count_stretch;
   g->emit_rows = ctx->emit_rows;
   g->row_tokens = ctx->row_tokens;
   g->front = ctx->front;
@@ -280,6 +283,9 @@ extern "C" size_t himg_hip_max_packed_size(int width, int height, int num_channe
   n += (size_t)g.fres_size + kTreeStride + 4u * (size_t)g.rows;
   return round_up(n + 64, 256);
 }
+
+// HIMG_OPT_COUNT_STRETCH: the forms k_row_count_w is built in.
+static bool stretch_ok(int v) { return v == -1 || v == 1 || v == 2 || v == 4 || v == 8; }
 
 extern "C" int himg_hip_create(int device, himg_hip_ctx **out) {
   if (!out) return HIMG_ERR_ARG;
@@ -303,6 +309,10 @@ extern "C" int himg_hip_create(int device, himg_hip_ctx **out) {
     if (v >= 128 && v <= 4096 && v % 32 == 0) ctx->max_sub = v;
   }
   if (const char *e = std::getenv("HIMG_COUNT_WAVE")) ctx->count_wave = atoi(e) ? 1 : 0;
+  if (const char *e = std::getenv("HIMG_COUNT_STRETCH")) {
+    const int v = std::atoi(e);
+    if (stretch_ok(v)) ctx->count_stretch = v;
+  }
   if (const char *e = std::getenv("HIMG_EMIT_ROWS")) ctx->emit_rows = atoi(e) ? 1 : 0;
   if (const char *e = std::getenv("HIMG_ROW_TOKENS")) ctx->row_tokens = atoi(e) ? 1 : 0;
   if (const char *e = std::getenv("HIMG_FRONT")) ctx->front = atoi(e) ? 1 : 0;
@@ -416,12 +426,18 @@ extern "C" int himg_hip_get_option(himg_hip_ctx *ctx, int option, int *value) {
   if (option == HIMG_OPT_EMIT_ROWS) { *value = ctx->emit_rows; return HIMG_OK; }
   if (option == HIMG_OPT_ROW_TOKENS) { *value = ctx->row_tokens; return HIMG_OK; }
   if (option == HIMG_OPT_FRONT) { *value = ctx->front; return HIMG_OK; }
+  if (option == HIMG_OPT_COUNT_STRETCH) { *value = ctx->count_stretch; return HIMG_OK; }
   return fail(ctx, HIMG_ERR_ARG, "unknown option");
 }
 
 extern "C" int himg_hip_set_option(himg_hip_ctx *ctx, int option, int value) {
   if (!ctx) return HIMG_ERR_ARG;
   if (option == HIMG_OPT_FIX_T2) { ctx->fix_t2 = value ? 1 : 0; return HIMG_OK; }
+  if (option == HIMG_OPT_COUNT_STRETCH) {
+    if (!stretch_ok(value)) return fail(ctx, HIMG_ERR_ARG, "count_stretch: -1, 1, 2, 4 or 8");
+    ctx->count_stretch = value;
+    return HIMG_OK;
+  }
   const int tri = value < 0 ? -1 : (value ? 1 : 0);
   if (option == HIMG_OPT_COUNT_WAVE) { ctx->count_wave = tri; return HIMG_OK; }
   if (option == HIMG_OPT_EMIT_ROWS) { ctx->emit_rows = tri; return HIMG_OK; }
@@ -1123,6 +1139,24 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
     return HIMG_ERR_ARG;
   return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream,
                      nullptr, nullptr, nullptr, nullptr);
+}
+
+// The row records alone (include/himg_hip.h): what himg_hip_decode_device launches in front of its row
+// kernels, with the wavefront-per-row count kernel whatever the batch size.
+extern "C" int himg_hip_debug_row_records(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                          const uint32_t *h_sizes, int batch, int width, int height,
+                                          int num_channels, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, nullptr, &in_stride, nullptr, &g))
+    return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
+  himg_dev::launch_row_records(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_status,
+                               (hipStream_t)stream, &ctx->prof);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
 }
 
 // ---------------------------------------------------------------------------
@@ -3033,6 +3067,10 @@ extern "C" int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void 
       case HIMG_DBG_FRES_SYM: src = w.fres_sym ? w.fres_sym + frame * w.fres_stride : nullptr; n = (size_t)g.fres_size; break;
       case HIMG_DBG_DEC_STATS: src = w.stats + (size_t)frame * (g.rows + 1) * 8; n = (size_t)(g.rows + 1) * 32; break;
       case HIMG_DBG_PARSE_STATS: src = w.parse_stats + (size_t)frame * 4; n = 16; break;
+      case HIMG_DBG_LANE_START: src = w.lane_start ? w.lane_start + (size_t)frame * g.rows * kDecThreads : nullptr; n = (size_t)g.rows * kDecThreads * 4; break;
+      case HIMG_DBG_LANE_OFF:
+        src = w.lane_off ? w.lane_off + (size_t)frame * g.rows * (kDecThreads + himg_dev::kRecHdr) : nullptr;
+        n = (size_t)g.rows * (kDecThreads + himg_dev::kRecHdr) * 4; break;
       case HIMG_DBG_ROWCOUNT_STATS: src = w.rc_stats ? w.rc_stats + (size_t)frame * g.rows * 8 : nullptr; n = (size_t)g.rows * 32; break;
       default: return HIMG_ERR_ARG;
     }

@@ -3773,6 +3773,23 @@ struct LdsBits {
     return __builtin_amdgcn_alignbit(x.y, x.x, pos);   // (the hardware takes pos[4:0])
   }
 };
+// A lane's OWN piece of the payload (k_row_count_w's stretches): kLaneWords dwords from the dword
+// of the lane's current position, at a stride that is co-prime with the 32 banks.  What a walk
+// of one sub-sequence from there can touch: up to 31 bits of alignment, the sub-sequence (at
+// most kStageSubBits), and a last step that starts on its last bit and takes a whole token
+// with it (46 bits: a 32-bit code and 14 extra bits) -- bit 31 + 320 + 45 lies in dword 12.
+// ds_read2 also fetches the dword behind the one it needs: for the last dword of a piece that
+// is the next lane's first one (the buffer ends with a spare dword), whose bits nothing reads.
+constexpr uint32_t kLaneWords = 13;
+constexpr uint32_t kLaneAlloc = (64u * kLaneWords + 1u + 3u) & ~3u;
+struct LaneBits {
+  uint32_t base;   // LDS byte address the piece's first dword WOULD have if the piece began at bit 0
+  __device__ __forceinline__ uint32_t window(uint32_t pos) const {
+    const uint32_t a = base + ((pos >> 5) << 2);
+    const u32x2 x = *(const __attribute__((address_space(3))) u32x2_a4 *)(uintptr_t)a;
+    return __builtin_amdgcn_alignbit(x.y, x.x, pos);
+  }
+};
 constexpr uint32_t kStageSubBits = 320;                                    // longest sub-sequence the staged form takes
 constexpr uint32_t kStageWords = 64u * kStageSubBits / 32u + 32u;          // payload dwords of one phase: 64 sub-sequences + slack
 constexpr uint32_t kStageAlloc = (kStageWords + kStageWords / 32u + 3u) & ~3u;  // the same in blocks of 33
@@ -3787,7 +3804,8 @@ struct BitWin64 {
 
 // The GROUPS that start in [pos, lim), from the staged payload (lean_count<.., GRP = true>
 // over an LdsBits): where the last one ends, how many symbols they produce.
-__device__ __forceinline__ void grp_count_lds(const LdsBits &bits, const GrpTables &t, uint32_t pos, uint32_t lim,
+template <class BITS>
+__device__ __forceinline__ void grp_count_lds(const BITS &bits, const GrpTables &t, uint32_t pos, uint32_t lim,
                                               uint32_t *endpos, uint32_t *count) {
   uint32_t c = 0;
   if (pos < lim) {
@@ -3838,11 +3856,24 @@ __device__ __forceinline__ void grp_count_lds(const LdsBits &bits, const GrpTabl
 // 16-byte loads -- and the walks read it on demand (grp_count_lds); longer rows are read in
 // place through register windows (wave-uniform choice per row).  The body (dec_body_row_count_w.inc)
 // is also the region decode's per-frame form's, k_region_count_w.
+// NQ > 1: a lane owns a STRETCH of NQ consecutive sub-sequences (the body explains); NQ = 1 is
+// the form of a sub-sequence per lane, which the region and prefix decodes keep.  k_row_count_w is
+// the form the decoder launches by default, k_row_count_wn the others (HIMG_OPT_COUNT_STRETCH).
+constexpr int kCountStretch = 4;
 __global__ __launch_bounds__(kDecThreads, 8) void k_row_count_w(Geom g, DecWs ws, const uint8_t *packed,
                                                                size_t in_stride, const uint32_t *sizes,
                                                                int r0, int r1) {
+  constexpr int NQ = kCountStretch;
 #include "dec_body_row_count_w.inc"
 }
+template <int NQ>
+__global__ __launch_bounds__(kDecThreads, 8) void k_row_count_wn(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                int r0, int r1) {
+#include "dec_body_row_count_w.inc"
+}
+static_assert((31u + kStageSubBits + 45u) / 32u < kLaneWords, "a sub-sequence and its overrun fit a lane's piece");
+static_assert(64 * 8 <= kLaneAlloc && 64 * kCountStretch <= kLaneAlloc, "a phase's 64 NQ records pass through a wavefront's staging buffer");
 
 // ---------------------------------------------------------------------------
 // k_row_count_q: the records of a WIDE row (one that goes through k_row_window: wider than the
@@ -4634,6 +4665,7 @@ __global__ __launch_bounds__(kDecThreads, 8) void k_region_count_w(Geom g, DecWs
                                                                   const int32_t *org, int h) {
   const int r0 = region_r0(org, blockIdx.y), r1 = region_r1(org, blockIdx.y, h);
   if (r0 + (int)blockIdx.x * kCountRowsW >= r1) return;
+  constexpr int NQ = 1;   // a sub-sequence per lane
 #include "dec_body_row_count_w.inc"
 }
 
@@ -4773,6 +4805,7 @@ __global__ __launch_bounds__(kDecThreads, 8) void k_prefix_count_w(Geom g, DecWs
                                                                   const int32_t *krows) {
   const int r0 = 0, r1 = krows[blockIdx.y];
   if ((int)blockIdx.x * kCountRowsW >= r1) return;
+  constexpr int NQ = 1;   // a sub-sequence per lane
 #include "dec_body_row_count_w.inc"
 }
 
@@ -5598,6 +5631,19 @@ static CountRule count_rule(const Geom &g, long long all_rows, bool one_record) 
   if (one_record) c.g.max_sub = 0x7fffffff;
   return c;
 }
+// k_row_count_w over rows [a, b) of every frame, in the form the context asks for (HIMG_OPT_COUNT_STRETCH).
+static void launch_row_count_w(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                               const uint32_t *d_sizes, int a, int b, hipStream_t s) {
+  const dim3 grid((b - a + kCountRowsW - 1) / kCountRowsW, batch), block(kDecThreads);
+  const int nq = g.count_stretch < 0 ? kCountStretch : g.count_stretch;
+#define HIMG_COUNT_WN(NQ_) hipLaunchKernelGGL(k_row_count_wn<NQ_>, grid, block, 0, s, g, ws, d_packed, in_stride, d_sizes, a, b)
+  if (nq == kCountStretch) hipLaunchKernelGGL(k_row_count_w, grid, block, 0, s, g, ws, d_packed, in_stride, d_sizes, a, b);
+  else if (nq == 2) HIMG_COUNT_WN(2);
+  else if (nq == 4) HIMG_COUNT_WN(4);
+  else if (nq == 8) HIMG_COUNT_WN(8);
+  else HIMG_COUNT_WN(1);
+#undef HIMG_COUNT_WN
+}
 
 void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                     const uint32_t *d_sizes, uint32_t *d_head_sizes, uint8_t *d_out, int32_t *d_status,
@@ -5781,8 +5827,7 @@ void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   auto row_count = [&](hipStream_t s) {
     prof_begin(prof, "k_row_count", s);
     if (cr.wave)
-      hipLaunchKernelGGL(k_row_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s, cr.g,
-                         ws, d_packed, in_stride, d_sizes, 0, g.rows);
+      launch_row_count_w(cr.g, ws, batch, d_packed, in_stride, d_sizes, 0, g.rows, s);
     else
       hipLaunchKernelGGL(k_row_count<false>, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), 0, s, cr.g, ws,
                          d_packed, in_stride, d_sizes, 0, g.rows, cr.rpc);
@@ -5820,6 +5865,17 @@ void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   else if (one) HIMG_SCALED_LAUNCH(2, true, lds_one);
   else HIMG_SCALED_LAUNCH(2, false, scaled_layout<2>(g.C, sa.sw).total);
 #undef HIMG_SCALED_LAUNCH
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+void launch_row_records(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                        const uint32_t *d_sizes, int32_t *d_status, hipStream_t stream, Profiler *prof) {
+  launch_zero(g, ws, batch, stream, prof);
+  HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
+  HIMG_LAUNCH(k_dec_rowwalk, dim3(batch), dim3(64), g, ws, d_packed, in_stride, d_sizes, 0x7fffffff, 0);
+  prof_begin(prof, "k_row_count", stream);
+  launch_row_count_w(g, ws, batch, d_packed, in_stride, d_sizes, 0, g.rows, stream);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
@@ -5899,8 +5955,7 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     if (b <= a) return;
     prof_begin(prof, "k_row_count", s);
     if (cr.wave)
-      hipLaunchKernelGGL(k_row_count_w, dim3((b - a + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), 0, s,
-                         g, ws, d_packed, in_stride, d_sizes, a, b);
+      launch_row_count_w(g, ws, batch, d_packed, in_stride, d_sizes, a, b, s);
     else if (wps)
       hipLaunchKernelGGL(k_row_count<true>, dim3((b - a + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), 0, s, g, ws,
                          d_packed, in_stride, d_sizes, a, b, cr.rpc);

@@ -77,6 +77,11 @@ const char *himg_hip_last_error(const himg_hip_ctx *ctx);
 #define HIMG_OPT_EMIT_ROWS 3
 #define HIMG_OPT_ROW_TOKENS 4
 #define HIMG_OPT_FRONT 5
+/*   HIMG_OPT_COUNT_STRETCH  the wavefront-per-row form of the FRES row index records: consecutive
+ *                        sub-sequences of a row that one lane walks as a single stretch -- 2, 4 or 8;
+ *                        1 = one each (the earlier form, kept for A/B runs and the tests);
+ *                        -1 = the default.  Other values: HIMG_ERR_ARG.     [env HIMG_COUNT_STRETCH] */
+#define HIMG_OPT_COUNT_STRETCH 6
 int himg_hip_set_option(himg_hip_ctx *ctx, int option, int value);
 /* The option as the context holds it -- including what it took from the environment when it
  * was created (HIMG_FIX_T2=1): a binding that mirrors an option (the row-sharded decoder's host
@@ -1055,9 +1060,24 @@ enum {
   ,
   HIMG_DBG_TOK_CNT = 16 /* encoder, after such an encode: u32 [rows][segments] the slots k_tok wrote per token
                            segment of every block row (before the padding of the tail; himg_hip_tok_layout) */
+  ,
+  HIMG_DBG_LANE_START = 17, /* decoder, after a full decode whose rows went through a count kernel: u32 [rows][1024]
+                             where the chain of every lane of a block row starts (bits from the row's payload) */
+  HIMG_DBG_LANE_OFF = 18   /* decoder, likewise: u32 [rows][1024 + 72] symbols in front of every lane, then the row's
+                             header words (total, end of the chain, valid flag, rounds, records per lane, ...) */
 };
 int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void *host_dst,
                         size_t dst_bytes, size_t *bytes_written);
+
+/* The front of himg_hip_decode_device and no more (its argument contract, without d_out): container
+ * parse, row-header walk, and the row records of every block row by the wavefront-per-row count kernel
+ * in the form HIMG_OPT_COUNT_STRETCH selects, whatever the batch size.  No row kernel runs, no pixel is
+ * written; d_status gets the verdict so far.  The records are then read with HIMG_DBG_LANE_START /
+ * HIMG_DBG_LANE_OFF: the tests compare the forms of the count kernel word for word this way before a
+ * row kernel consumes what a new form writes. */
+int himg_hip_debug_row_records(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                               const uint32_t *h_sizes, int batch, int width, int height,
+                               int num_channels, int32_t *d_status, void *stream);
 
 /* Per-stage device timing with hipEvents recorded on the caller's stream.
  * enable != 0 brackets every kernel of the following calls; stage_ms returns
