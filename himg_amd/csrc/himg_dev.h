@@ -382,16 +382,31 @@ struct PyrDesc {
   uint8_t *level[4];
 };
 
-// tens: the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W] elements);
-// dst: in their pitched form (d_out: the destination pictures); pyr: in their pyramid form (d_out:
-// pyr->level[0], which may be nullptr; level 3 is k_lres_preview's, behind the LRES chain); one at most.
-// Everything in front of them is the same launch.
+// The form in which the pixel-writing kernels store: interleaved uint8 (no descriptor), or one of the
+// three forms above with its descriptor, which the launch copies into the kernel's arguments.
+enum StoreKind { kStoreU8, kStoreTens, kStorePitch, kStorePyr };
+struct StoreForm {
+  StoreKind kind = kStoreU8;
+  const void *desc = nullptr;   // the kind's descriptor
+  StoreForm() = default;
+  StoreForm(const TensDesc *t) : kind(kStoreTens), desc(t) {}
+  StoreForm(const DstDesc *d) : kind(kStorePitch), desc(d) {}
+  StoreForm(const PyrDesc *m) : kind(kStorePyr), desc(m) {}
+  const TensDesc &tens() const { return *static_cast<const TensDesc *>(desc); }
+  const DstDesc &dst() const { return *static_cast<const DstDesc *>(desc); }
+  const PyrDesc &pyr() const { return *static_cast<const PyrDesc *>(desc); }
+};
+
+// form: kStoreTens, the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W]
+// elements); kStorePitch: in their pitched form (d_out: the destination pictures); kStorePyr: in their
+// pyramid form (d_out: level[0], which may be nullptr; level 3 is k_lres_preview's, behind the LRES
+// chain).  Everything in front of them is the same launch.
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
                    const uint32_t *d_row_index = nullptr, bool index_only = false, int phase = 3,
-                   const TensDesc *tens = nullptr, const DstDesc *dst = nullptr, const PyrDesc *pyr = nullptr);
+                   const StoreForm &form = StoreForm());
 constexpr int kDecHead = 1, kDecRows = 2;   // launch_decode's phases
 // The front of launch_decode's rows and no more (himg_hip_debug_row_records): container parse, row-header
 // walk, then k_row_count_w over every row in the form g.count_stretch asks for.  No row kernel runs.
@@ -423,8 +438,8 @@ void launch_preview(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_
 void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds, const TensDesc *tens = nullptr,   // (tens: scale_log2 = 0 only, [batch][co][h][w])
-                   const DstDesc *dst = nullptr);                          // (dst: scale_log2 = 0 only, windows of the pictures)
+                   const DecStreams *ds,
+                   const StoreForm &form = StoreForm());   // (scale_log2 = 0 only: kStoreTens, [batch][co][h][w]; kStorePitch, windows of the pictures)
 // The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
 // k_prefix_gate (the head of the stream with every load checked against the bytes present), the head
 // phase in its prefix form (k_dec_parse_prefix, the LRES chain bounded by the bytes present),

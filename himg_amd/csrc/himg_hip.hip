@@ -1108,25 +1108,31 @@ extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int n
   return HIMG_OK;
 }
 
-// The launch behind the full decodes of a batch in HBM: the interleaved bytes (himg_hip_decode_device),
-// the planar float output (td) or windows of pitched pictures (dd, with each frame's origin in h_org:
-// the origins ride with the sizes, dd->org is filled in here) or the picture pyramid (pm, d_out its
-// level 0).  bad: what the caller found wrong with its descriptor.
+// The launch behind the full decodes of a batch in HBM, in the caller's form: the interleaved bytes
+// (himg_hip_decode_device), the planar float output, windows of pitched pictures (with each frame's
+// origin in h_org: the origins ride with the sizes, the descriptor's org is filled in here) or the
+// picture pyramid (d_out its level 0).  bad: what the caller found wrong with its descriptor.
 static int decode_full(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                        int width, int height, int num_channels, void *d_out, int32_t *d_status, void *stream,
-                       const char *bad, const himg_dev::TensDesc *td, himg_dev::DstDesc *dd, const int32_t *h_org,
-                       const himg_dev::PyrDesc *pm = nullptr) {
+                       const char *bad = nullptr, himg_dev::StoreForm form = himg_dev::StoreForm(),
+                       const int32_t *h_org = nullptr) {
   Geom g;
   const uint32_t *d_sizes = nullptr;
   if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, bad, &g))
     return rc;
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
   { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
-  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes, dd ? h_org : nullptr)) return rc;
-  if (dd) dd->org = (const int32_t *)(d_sizes + batch);
+  const bool pitch = form.kind == himg_dev::kStorePitch;
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes, pitch ? h_org : nullptr)) return rc;
+  himg_dev::DstDesc dd;
+  if (pitch) {
+    dd = form.dst();
+    dd.org = (const int32_t *)(d_sizes + batch);
+    form = &dd;
+  }
   launch_decode(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, (uint8_t *)d_out, d_status,
                 (hipStream_t)stream, &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr, 0, g.rows,
-                nullptr, false, 3, td, dd, pm);
+                nullptr, false, 3, form);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -1137,8 +1143,7 @@ extern "C" int himg_hip_decode_device(himg_hip_ctx *ctx, const void *d_packed, s
                                       void *stream) {
   if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
-  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream,
-                     nullptr, nullptr, nullptr, nullptr);
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream);
 }
 
 // The row records alone (include/himg_hip.h): what himg_hip_decode_device launches in front of its row
@@ -1194,7 +1199,7 @@ extern "C" int himg_hip_decode_tensor_device(himg_hip_ctx *ctx, const void *d_pa
   himg_dev::TensDesc td;
   const char *bad = tensor_desc_ok(t, num_channels, &td) ? nullptr : "bad tensor descriptor";
   return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream, bad,
-                     &td, nullptr, nullptr);
+                     &td);
 }
 
 // ---------------------------------------------------------------------------
@@ -1227,7 +1232,7 @@ extern "C" int himg_hip_decode_into_device(himg_hip_ctx *ctx, const void *d_pack
   size_t extent = 0;
   const char *bad = dst_check(dst, num_channels, batch, h_origins, width, height, &extent, &dd);
   return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_dst, d_status, stream, bad,
-                     nullptr, &dd, h_origins);
+                     &dd, h_origins);
 }
 
 extern "C" int himg_hip_decode_rows_device(himg_hip_ctx *ctx, const void *d_packed, uint32_t packed_size,
@@ -2314,19 +2319,16 @@ extern "C" int himg_hip_region_peek(const uint8_t *packed, size_t packed_size, i
 // d_row_index: the host's index, 2 x rows words per frame (rows r0_f .. r1_f - 1 filled).
 // scale_log2 = 1, 2: the window and the origins are those of the scaled picture (k_dec_scaled_region);
 // what reaches the device are the origins of the full-resolution rectangles the windows cover.
+// form (scale_log2 = 0 only): the caller's checked descriptor.  kStorePitch: d_out holds the destination
+// pictures, frame f's window at h_dst_org[2 f], [2 f + 1], and bad_dst is what dst_check found wrong.
 static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                          int width, int height, int num_channels, const int32_t *h_org, int w, int h,
                          const uint32_t *d_row_index, void *d_out, int32_t *d_status, void *stream, int scale_log2 = 0,
-                         const himg_hip_tensor_desc *tens = nullptr, const himg_hip_dst *dst = nullptr,
-                         const int32_t *h_dst_org = nullptr) {
+                         himg_dev::StoreForm form = himg_dev::StoreForm(), const int32_t *h_dst_org = nullptr,
+                         const char *bad_dst = nullptr) {
   if (scale_log2 < 0 || scale_log2 > 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
-  himg_dev::TensDesc td;
-  if (tens && (scale_log2 || !tensor_desc_ok(tens, num_channels, &td))) return fail(ctx, HIMG_ERR_ARG, "bad tensor descriptor");
-  // dst (scale_log2 = 0): d_out holds the destination pictures, frame f's window at h_dst_org[2 f], [2 f + 1].
-  himg_dev::DstDesc dd;
-  size_t extent = 0;
-  if (dst && scale_log2) return fail(ctx, HIMG_ERR_ARG, "a destination descriptor at full scale only");
-  const char *bad_dst = dst || h_dst_org ? dst_check(dst, num_channels, batch, h_dst_org, w, h, &extent, &dd) : nullptr;
+  if (scale_log2 && form.kind != himg_dev::kStoreU8) return fail(ctx, HIMG_ERR_ARG, "a descriptor at full scale only");
+  const bool pitch = form.kind == himg_dev::kStorePitch;
   std::vector<int32_t> up_org;
   if (scale_log2) up_org.resize(2 * (size_t)batch);
   const char *bad = nullptr;
@@ -2342,16 +2344,21 @@ static int region_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stri
                            bad ? bad : bad_dst, &g))
     return rc;
   // (the origins ride with the sizes: no extra copy, no wait; the destinations' behind the windows')
-  if (dst) {
+  if (pitch) {
     up_org.assign(h_org, h_org + 2 * (size_t)batch);
     up_org.insert(up_org.end(), h_dst_org, h_dst_org + 2 * (size_t)batch);
     h_org = up_org.data();
   }
-  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org, dst ? 2 : 1)) return rc;
-  if (dst) dd.org = (const int32_t *)(d_sizes + 3 * (size_t)batch);
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_sizes, stream, &d_sizes, h_org, pitch ? 2 : 1)) return rc;
+  himg_dev::DstDesc dd;
+  if (pitch) {
+    dd = form.dst();
+    dd.org = (const int32_t *)(d_sizes + 3 * (size_t)batch);
+    form = &dd;
+  }
   launch_region(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, h_org,
                 (const int32_t *)(d_sizes + batch), scale_log2, w, h, (uint8_t *)d_out, d_status, (hipStream_t)stream,
-                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr, tens ? &td : nullptr, dst ? &dd : nullptr);
+                &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr, form);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
@@ -2387,8 +2394,10 @@ extern "C" int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const vo
   if (!ctx || !d_packed || !h_sizes || !h_origins || !t || !d_out || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  himg_dev::TensDesc td;
+  if (!tensor_desc_ok(t, num_channels, &td)) return fail(ctx, HIMG_ERR_ARG, "bad tensor descriptor");
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_origins, w, h, nullptr,
-                       d_out, d_status, stream, 0, t);
+                       d_out, d_status, stream, 0, &td);
 }
 
 extern "C" int himg_hip_decode_regions_into_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
@@ -2400,8 +2409,11 @@ extern "C" int himg_hip_decode_regions_into_device(himg_hip_ctx *ctx, const void
     return HIMG_ERR_ARG;
   if (!dst || !h_dst_origins) return fail(ctx, HIMG_ERR_ARG, "bad argument");
   if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  himg_dev::DstDesc dd;
+  size_t extent = 0;
+  const char *bad_dst = dst_check(dst, num_channels, batch, h_dst_origins, w, h, &extent, &dd);
   return region_launch(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, h_src_origins, w, h, nullptr,
-                       d_dst, d_status, stream, 0, nullptr, dst, h_dst_origins);
+                       d_dst, d_status, stream, 0, &dd, h_dst_origins, bad_dst);
 }
 
 // The scaled region decode's device entry: a window of the picture at 1/2 or 1/4 scale.  A rectangle of
@@ -2498,7 +2510,7 @@ extern "C" int himg_hip_decode_pyramid_device(himg_hip_ctx *ctx, const void *d_p
   // (level 0 alone: the full decode, in its own kernels)
   const bool only0 = wanted == 1 && pm.level[0];
   return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, pm.level[0], d_status, stream,
-                     bad, nullptr, nullptr, nullptr, only0 ? nullptr : &pm);
+                     bad, only0 ? himg_dev::StoreForm() : himg_dev::StoreForm(&pm));
 }
 
 // One host stream: the upload of decode_core (the device walks the row headers), one launch, the

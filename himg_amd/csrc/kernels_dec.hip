@@ -2987,29 +2987,7 @@ __device__ __forceinline__ void identity_test_words(const DecFrame *df, int l, u
 // FAST: four channels, whole tiles (tile_plane's identity-range gather, no ragged edges).
 template <bool FAST>
 __global__ __launch_bounds__(256) void k_tile_inv(Geom g, DecWs ws, uint8_t *out_frames, int v0) {
-  __shared__ int16_t s_unmap[256];   // indexed by the code byte
-  __shared__ uint8_t s_shift[2][64];
-  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
-  const int v = blockIdx.y + v0, f = blockIdx.z;
-  const DecFrame *df = ws.frames + f;
-  __shared__ int s_status;
-  if (threadIdx.x == 0) s_status = df->status;
-  __syncthreads();
-  if (s_status) return;
-  {
-    const int k = threadIdx.x;
-    const int sc = (int8_t)k;
-    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
-    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
-    if (k < 64) {
-      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
-      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
-    }
-    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
-  }
-  __syncthreads();
-  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
-  if (pair_tile(it) >= g.cols) return;
+#include "dec_body_tile_inv.inc"
   transform_store_pair<(FAST ? -1 : 0), FAST>(g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
                           ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp,
                           df->ycbcr, pair_tile(it), pair_half(it), v,
@@ -3028,32 +3006,11 @@ struct TileArgsT {
 };
 template <bool FAST>
 __global__ __launch_bounds__(256) void k_tile_inv_t(TileArgsT a) {
-  __shared__ int16_t s_unmap[256];   // indexed by the code byte
-  __shared__ uint8_t s_shift[2][64];
-  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
+  const int v0 = a.v0;
   const TensK td = &((const __attribute__((address_space(4))) TileArgsT *)__builtin_amdgcn_kernarg_segment_ptr())->t;
-  const int v = blockIdx.y + a.v0, f = blockIdx.z;
-  const DecFrame *df = ws.frames + f;
-  __shared__ int s_status;
-  if (threadIdx.x == 0) s_status = df->status;
-  __syncthreads();
-  if (s_status) return;
-  {
-    const int k = threadIdx.x;
-    const int sc = (int8_t)k;
-    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
-    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
-    if (k < 64) {
-      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
-      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
-    }
-    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
-  }
-  __syncthreads();
-  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
-  if (pair_tile(it) >= g.cols) return;
+#include "dec_body_tile_inv.inc"
   const size_t frame_bytes = (size_t)g.W * g.H * (size_t)(td->co * tens_elem_size(td->dtype));
   transform_store_pair<(FAST ? -1 : 0), FAST, false, true>(
       g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
@@ -3072,32 +3029,11 @@ struct TileArgsP {
 };
 template <bool FAST>
 __global__ __launch_bounds__(256) void k_tile_inv_p(TileArgsP a) {
-  __shared__ int16_t s_unmap[256];   // indexed by the code byte
-  __shared__ uint8_t s_shift[2][64];
-  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
+  const int v0 = a.v0;
   const DstK pd = &((const __attribute__((address_space(4))) TileArgsP *)__builtin_amdgcn_kernarg_segment_ptr())->d;
-  const int v = blockIdx.y + a.v0, f = blockIdx.z;
-  const DecFrame *df = ws.frames + f;
-  __shared__ int s_status;
-  if (threadIdx.x == 0) s_status = df->status;
-  __syncthreads();
-  if (s_status) return;
-  {
-    const int k = threadIdx.x;
-    const int sc = (int8_t)k;
-    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
-    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
-    if (k < 64) {
-      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
-      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
-    }
-    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
-  }
-  __syncthreads();
-  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
-  if (pair_tile(it) >= g.cols) return;
+#include "dec_body_tile_inv.inc"
   transform_store_pair<(FAST ? -1 : 0), FAST, false, false, true>(
       g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
       ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp, df->ycbcr, pair_tile(it),
@@ -3456,139 +3392,69 @@ struct RowArgs {
 // (The arguments are read from the kernel-argument segment anew for every row, through a pointer
 // the compiler cannot see through: read once in front of the loop they all stay live across the
 // body -- 104 scalar registers spilled instead of 36, the row kernel 9 % slower.)
+// The kernel's four forms share the loop, dec_body_row_loop.inc; a form is its argument struct --
+// RowArgs itself, or RowArgs followed by the form's descriptor --, its three flags and HIMG_ROW_A,
+// the RowArgs inside the struct.  row_td / row_pd / row_pm: the descriptor a form's struct carries.
+struct RowArgsT {
+  RowArgs a;
+  TensDesc t;
+};
+struct RowArgsP {
+  RowArgs a;
+  DstDesc d;
+};
+struct RowArgsM {
+  RowArgs a;
+  PyrDesc m;
+};
+template <class K> __device__ __forceinline__ TensK row_td(K) { return nullptr; }
+template <class K> __device__ __forceinline__ DstK row_pd(K) { return nullptr; }
+template <class K> __device__ __forceinline__ PyrK row_pm(K) { return nullptr; }
+__device__ __forceinline__ TensK row_td(const __attribute__((address_space(4))) RowArgsT *ka) { return &ka->t; }
+__device__ __forceinline__ DstK row_pd(const __attribute__((address_space(4))) RowArgsP *ka) { return &ka->d; }
+__device__ __forceinline__ PyrK row_pm(const __attribute__((address_space(4))) RowArgsM *ka) { return &ka->m; }
+
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused(RowArgs) {
-  typedef const __attribute__((address_space(4))) RowArgs *KArgs;
-  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t total = (uint32_t)ka->gx * (uint32_t)ka->gy, S = gridDim.x;
-  // Round i: the grid elements [i S, (i + 1) S), this workgroup the one at (blockIdx.x + 37 i) mod S
-  // -- rotated, or a workgroup would meet the same row positions of every frame (S = 256, 512 rows
-  // per frame: two of them) and the slow rows of similar frames would all be one workgroup's:
-  // 128 identical frames 10.28 ms against 10.01 with a workgroup per row.
-  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };
-  bool again = false;
-  int f_prev = -1;
-#pragma unroll 1
-  for (uint32_t i = 0; i * S < total; ++i) {
-    const uint32_t lin = element(i);
-    if (lin >= total) break;   // (the last round is a partial one)
-    asm volatile("" : "+s"(ka));
-    Geom g;
-    DecWs ws;
-    karg_copy<uint32_t>(&g, &ka->g);
-    karg_copy<unsigned long long>(&ws, &ka->ws);
-    const int gx = ka->gx, f = (int)(lin / (uint32_t)gx);
-    const uint32_t nd = (uint32_t)ka->next_dist;
-    dec_row_fused_body<COLS>(g, ws, ka->packed, ka->in_stride, ka->sizes, ka->out_frames, ka->r0, ka->r1, ka->rpw,
-                             (int)(lin % (uint32_t)gx), f, gx, ka->gy, nd ? lin + nd : element(i + 1), again, f == f_prev);
-    again = true;
-    f_prev = f;
-  }
+  typedef RowArgs KA;
+  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = false;
+#define HIMG_ROW_A(ka) (*(ka))
+#include "dec_body_row_loop.inc"
+#undef HIMG_ROW_A
 }
 
 // k_dec_row_fused_t: the same kernel in its tensor form.  Its arguments are RowArgs -- unchanged, the
 // uint8 kernels keep their code -- followed by the descriptor, which stays in the kernel-argument
 // segment: the transform reads scale and bias there, per row and at the conversion, so that nothing
 // of it is live across the row loop or the entropy phase.
-struct RowArgsT {
-  RowArgs a;
-  TensDesc t;
-};
+#define HIMG_ROW_A(ka) ((ka)->a)
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_t(RowArgsT) {
-  typedef const __attribute__((address_space(4))) RowArgsT *KArgs;
-  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
-  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
-  bool again = false;
-  int f_prev = -1;
-#pragma unroll 1
-  for (uint32_t i = 0; i * S < total; ++i) {
-    const uint32_t lin = element(i);
-    if (lin >= total) break;   // (the last round is a partial one)
-    asm volatile("" : "+s"(ka));
-    Geom g;
-    DecWs ws;
-    karg_copy<uint32_t>(&g, &ka->a.g);
-    karg_copy<unsigned long long>(&ws, &ka->a.ws);
-    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
-    const uint32_t nd = (uint32_t)ka->a.next_dist;
-    dec_row_fused_body<COLS, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
-                                   ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
-                                   nd ? lin + nd : element(i + 1), again, f == f_prev, &ka->t);
-    again = true;
-    f_prev = f;
-  }
+  typedef RowArgsT KA;
+  constexpr bool kRowTens = true, kRowPitch = false, kRowPyr = false;
+#include "dec_body_row_loop.inc"
 }
 
 // k_dec_row_fused_p: the same kernel in its pitched form.  RowArgs -- unchanged -- followed by the
 // destination descriptor, which stays in the kernel-argument segment: the frame's origin is read
 // where the transform phase begins, the pitch and the stride at the stores.
-struct RowArgsP {
-  RowArgs a;
-  DstDesc d;
-};
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_p(RowArgsP) {
-  typedef const __attribute__((address_space(4))) RowArgsP *KArgs;
-  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
-  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
-  bool again = false;
-  int f_prev = -1;
-#pragma unroll 1
-  for (uint32_t i = 0; i * S < total; ++i) {
-    const uint32_t lin = element(i);
-    if (lin >= total) break;   // (the last round is a partial one)
-    asm volatile("" : "+s"(ka));
-    Geom g;
-    DecWs ws;
-    karg_copy<uint32_t>(&g, &ka->a.g);
-    karg_copy<unsigned long long>(&ws, &ka->a.ws);
-    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
-    const uint32_t nd = (uint32_t)ka->a.next_dist;
-    dec_row_fused_body<COLS, false, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames, ka->a.r0,
-                                          ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
-                                          nd ? lin + nd : element(i + 1), again, f == f_prev, nullptr, &ka->d);
-    again = true;
-    f_prev = f;
-  }
+  typedef RowArgsP KA;
+  constexpr bool kRowTens = false, kRowPitch = true, kRowPyr = false;
+#include "dec_body_row_loop.inc"
 }
 
 // k_dec_row_fused_m: the same kernel in its pyramid form.  RowArgs -- unchanged, out_frames level 0 --
 // followed by the levels' descriptor, which stays in the kernel-argument segment: the pointers are
 // read behind the entropy phase, where the stores begin.
-struct RowArgsM {
-  RowArgs a;
-  PyrDesc m;
-};
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_m(RowArgsM) {
-  typedef const __attribute__((address_space(4))) RowArgsM *KArgs;
-  KArgs ka = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
-  const uint32_t total = (uint32_t)ka->a.gx * (uint32_t)ka->a.gy, S = gridDim.x;
-  auto element = [&](uint32_t i) { return i * S + (blockIdx.x + 37u * i) % S; };   // (k_dec_row_fused's rotation)
-  bool again = false;
-  int f_prev = -1;
-#pragma unroll 1
-  for (uint32_t i = 0; i * S < total; ++i) {
-    const uint32_t lin = element(i);
-    if (lin >= total) break;   // (the last round is a partial one)
-    asm volatile("" : "+s"(ka));
-    Geom g;
-    DecWs ws;
-    karg_copy<uint32_t>(&g, &ka->a.g);
-    karg_copy<unsigned long long>(&ws, &ka->a.ws);
-    const int gx = ka->a.gx, f = (int)(lin / (uint32_t)gx);
-    const uint32_t nd = (uint32_t)ka->a.next_dist;
-    dec_row_fused_body<COLS, false, false, true>(g, ws, ka->a.packed, ka->a.in_stride, ka->a.sizes, ka->a.out_frames,
-                                                 ka->a.r0, ka->a.r1, ka->a.rpw, (int)(lin % (uint32_t)gx), f, gx, ka->a.gy,
-                                                 nd ? lin + nd : element(i + 1), again, f == f_prev, nullptr, nullptr,
-                                                 &ka->m);
-    again = true;
-    f_prev = f;
-  }
+  typedef RowArgsM KA;
+  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = true;
+#include "dec_body_row_loop.inc"
 }
+#undef HIMG_ROW_A
 
 // ---------------------------------------------------------------------------
 // k_row_count: the fixpoint rounds of every FRES block row, on their own.  They
@@ -5240,33 +5106,12 @@ struct TileArgsM {
 };
 template <bool FAST>
 __global__ __launch_bounds__(256) void k_tile_inv_m(TileArgsM a) {
-  __shared__ int16_t s_unmap[256];   // indexed by the code byte
-  __shared__ uint8_t s_shift[2][64];
-  __shared__ uint32_t s_shiftp[2 * 32 + 4];   // [chroma][register pair], then the identity-test words
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
+  const int v0 = a.v0;
   const PyrK pm = &((const __attribute__((address_space(4))) TileArgsM *)__builtin_amdgcn_kernarg_segment_ptr())->m;
-  const int v = blockIdx.y + a.v0, f = blockIdx.z;
-  const DecFrame *df = ws.frames + f;
-  __shared__ int s_status;
-  if (threadIdx.x == 0) s_status = df->status;
-  __syncthreads();
-  if (s_status) return;
-  {
-    const int k = threadIdx.x;
-    const int sc = (int8_t)k;
-    s_unmap[k] = (int16_t)(sc >= 0 ? df->fmap[sc] : (sc == -128 ? -df->fmap[127] : -df->fmap[-sc]));
-    if (k < 128) s_shift[k >> 6][k & 63] = df->shift[k >> 6][k & 63];
-    if (k < 64) {
-      const int ch = k >> 5, e = k & 31, x = e >> 2, j = e & 3;
-      s_shiftp[ch * 32 + e] = (uint32_t)df->shift[ch][(2 * j) * 8 + x] | ((uint32_t)df->shift[ch][(2 * j + 1) * 8 + x] << 16);
-    }
-    if (FAST && k >= 192) identity_test_words(df, k - 192, s_shiftp + 64);
-  }
-  __syncthreads();
-  const int it = blockIdx.x * 256 + threadIdx.x;   // (tile, half): both lanes of a pair are in or out
+#include "dec_body_tile_inv.inc"
   const int u = pair_tile(it);
-  if (u >= g.cols) return;
   const uint8_t *sym = ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block;
   const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
   const int ycbcr = df->ycbcr;
@@ -5514,58 +5359,32 @@ constexpr uint32_t kRowWindowLds = (uint32_t)sizeof(LdsTables) + 64u + kRowWindo
 
 bool dec_rows_fit_lds(const Geom &g) { return fused_layout(g.row_block).total <= kLdsMax; }
 
+// The kernels that take dynamic LDS beyond the 64 KiB a kernel gets unasked.  fixed_lds: the size it is
+// allowed; 0: the whole LDS less the kernel's static share, which counts against the same 160 KiB.
 hipError_t dec_set_kernel_attrs() {
-  const void *fused[] = {reinterpret_cast<const void *>(&k_dec_row_fused<512>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused<256>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused<240>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused<0>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_t<512>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_t<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_t<0>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_p<512>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_p<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_p<0>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_m<512>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_m<-1>),
-                         reinterpret_cast<const void *>(&k_dec_row_fused_m<0>)};
-  for (const void *k : fused) {
-    // (the kernel's static LDS counts against the same 160 KiB)
-    hipFuncAttributes fa;
-    hipError_t e = hipFuncGetAttributes(&fa, k);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsMax - fa.sharedSizeBytes));
-    if (e != hipSuccess) return e;
+#define HIMG_K(...) reinterpret_cast<const void *>(&__VA_ARGS__)
+  static const struct { const void *fn; uint32_t fixed_lds; } kDynLds[] = {
+      {HIMG_K(k_dec_row_fused<512>), 0},   {HIMG_K(k_dec_row_fused<256>), 0},   {HIMG_K(k_dec_row_fused<240>), 0},
+      {HIMG_K(k_dec_row_fused<-1>), 0},    {HIMG_K(k_dec_row_fused<0>), 0},
+      {HIMG_K(k_dec_row_fused_t<512>), 0}, {HIMG_K(k_dec_row_fused_t<-1>), 0},  {HIMG_K(k_dec_row_fused_t<0>), 0},
+      {HIMG_K(k_dec_row_fused_p<512>), 0}, {HIMG_K(k_dec_row_fused_p<-1>), 0},  {HIMG_K(k_dec_row_fused_p<0>), 0},
+      {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
+      {HIMG_K(k_row_window), kRowWindowLds},
+      {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
+      {HIMG_K(k_dec_prefix), 0},
+      {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
+      {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
+#undef HIMG_K
+  for (const auto &k : kDynLds) {
+    uint32_t lds = k.fixed_lds;
+    if (!lds) {
+      hipFuncAttributes fa;
+      if (hipError_t e = hipFuncGetAttributes(&fa, k.fn)) return e;
+      lds = kLdsMax - (uint32_t)fa.sharedSizeBytes;
+    }
+    if (hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)) return e;
   }
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_window), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)kRowWindowLds);
-  if (e != hipSuccess) return e;
-  hipFuncAttributes fa;
-  e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(kLdsMax - fa.sharedSizeBytes));
-  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region_t));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_t), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(kLdsMax - fa.sharedSizeBytes));
-  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_region_p));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_region_p), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(kLdsMax - fa.sharedSizeBytes));
-  if (e == hipSuccess) e = hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(&k_dec_prefix));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_dec_prefix), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(kLdsMax - fa.sharedSizeBytes));
-  const void *scaled[] = {reinterpret_cast<const void *>(&k_dec_scaled<4, true>), reinterpret_cast<const void *>(&k_dec_scaled<2, true>),
-                          reinterpret_cast<const void *>(&k_dec_scaled<4, false>), reinterpret_cast<const void *>(&k_dec_scaled<2, false>),
-                          reinterpret_cast<const void *>(&k_dec_scaled_region<4>), reinterpret_cast<const void *>(&k_dec_scaled_region<2>)};
-  for (const void *k : scaled) {
-    if (e == hipSuccess) e = hipFuncGetAttributes(&fa, k);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kLdsMax - fa.sharedSizeBytes));
-  }
-  return e;
+  return hipSuccess;
 }
 
 int region_strip_tiles(const Geom &g) {
@@ -5683,7 +5502,7 @@ static WindowExtents window_extents(const Geom &g, int batch, const int32_t *h_o
 void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
                    const uint32_t *d_sizes, const uint32_t *d_row_index, const int32_t *h_org, const int32_t *d_org,
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
-                   const DecStreams *ds, const TensDesc *tens, const DstDesc *dst) {
+                   const DecStreams *ds, const StoreForm &form) {
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records: no quarter records for k_region_count)
   const int F = 1 << scale_log2, hf = F * h;
@@ -5726,18 +5545,20 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   if (!scale_log2) {
     RegionArgs ra;
     ra.org = d_org; ra.sw = sw; ra.w = w; ra.h = h; ra.out = d_out;
-    prof_begin(prof, tens ? "k_dec_region_t" : dst ? "k_dec_region_p" : "k_dec_region", stream);
-    if (dst) {
-      RegionArgsP rp;
-      rp.g = g; rp.ws = ws; rp.packed = d_packed; rp.in_stride = in_stride; rp.sizes = d_sizes; rp.ra = ra; rp.d = *dst;
-      hipLaunchKernelGGL(k_dec_region_p, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, rp);
-    } else if (tens) {
-      RegionArgsT rt;
-      rt.g = g; rt.ws = ws; rt.packed = d_packed; rt.in_stride = in_stride; rt.sizes = d_sizes; rt.ra = ra; rt.t = *tens;
-      hipLaunchKernelGGL(k_dec_region_t, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, rt);
-    } else
-    hipLaunchKernelGGL(k_dec_region, grid, dim3(kDecThreads), region_layout(g.C, sw).total, stream, g, ws, d_packed,
-                       in_stride, d_sizes, ra);
+    const dim3 block(kDecThreads);
+    const uint32_t lds = region_layout(g.C, sw).total;
+    if (form.kind == kStorePitch) {
+      const RegionArgsP rp = {g, ws, d_packed, in_stride, d_sizes, ra, form.dst()};
+      prof_begin(prof, "k_dec_region_p", stream);
+      hipLaunchKernelGGL(k_dec_region_p, grid, block, lds, stream, rp);
+    } else if (form.kind == kStoreTens) {
+      const RegionArgsT rt = {g, ws, d_packed, in_stride, d_sizes, ra, form.tens()};
+      prof_begin(prof, "k_dec_region_t", stream);
+      hipLaunchKernelGGL(k_dec_region_t, grid, block, lds, stream, rt);
+    } else {
+      prof_begin(prof, "k_dec_region", stream);
+      hipLaunchKernelGGL(k_dec_region, grid, block, lds, stream, g, ws, d_packed, in_stride, d_sizes, ra);
+    }
   } else {
     ScaledRegionArgs sa;
     sa.org = d_org; sa.sw = sw; sa.w = w; sa.h = h; sa.out = d_out;
@@ -5880,12 +5701,67 @@ void launch_row_records(const Geom &g, const DecWs &ws, int batch, const uint8_t
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 
+// The stage name of a store kernel of launch_decode.  The forms with a descriptor carry their
+// instantiation in the name: the tests assert which one ran.
+enum StoreInst { kRow512, kRowWhole4, kRowAny, kTileFast, kTileAny };
+static const char *store_stage_name(StoreKind kind, StoreInst inst) {
+  static const char *const kName[4][5] = {
+      {"k_dec_row_fused", "k_dec_row_fused", "k_dec_row_fused", "k_tile_inv<true>", "k_tile_inv<false>"},
+      {"k_dec_row_fused_t<512>", "k_dec_row_fused_t<-1>", "k_dec_row_fused_t<0>", "k_tile_inv_t<true>", "k_tile_inv_t<false>"},
+      {"k_dec_row_fused_p<512>", "k_dec_row_fused_p<-1>", "k_dec_row_fused_p<0>", "k_tile_inv_p<true>", "k_tile_inv_p<false>"},
+      {"k_dec_row_fused_m<512>", "k_dec_row_fused_m<-1>", "k_dec_row_fused_m<0>", "k_tile_inv_m<true>", "k_tile_inv_m<false>"}};
+  return kName[kind][inst];
+}
+
+// The fused row kernel in the requested form over n_wg workgroups.  The forms with a descriptor have
+// <512>, <-1> -- which also serves 2048 and 1920 -- and <0>.
+template <int COLS>
+static void launch_row_fused(const StoreForm &form, const RowArgs &ra, unsigned n_wg, uint32_t lds, hipStream_t stream,
+                             Profiler *prof) {
+  constexpr int FC = COLS == 256 || COLS == 240 ? -1 : COLS;
+  const dim3 grid(n_wg), block(kDecThreads);
+  prof_begin(prof, store_stage_name(form.kind, FC == 512 ? kRow512 : FC == -1 ? kRowWhole4 : kRowAny), stream);
+  if (form.kind == kStoreTens) {
+    const RowArgsT rt = {ra, form.tens()};
+    hipLaunchKernelGGL((k_dec_row_fused_t<FC>), grid, block, lds, stream, rt);
+  } else if (form.kind == kStorePitch) {
+    const RowArgsP rp = {ra, form.dst()};
+    hipLaunchKernelGGL((k_dec_row_fused_p<FC>), grid, block, lds, stream, rp);
+  } else if (form.kind == kStorePyr) {
+    const RowArgsM rm = {ra, form.pyr()};
+    hipLaunchKernelGGL((k_dec_row_fused_m<FC>), grid, block, lds, stream, rm);
+  } else {
+    hipLaunchKernelGGL((k_dec_row_fused<COLS>), grid, block, lds, stream, ra);
+  }
+  prof_end(prof, stream);
+}
+
+// k_tile_inv in the requested form over block rows v0, v0 + 1, ... (grid.y of them).
+template <bool FAST>
+static void launch_tile_inv(const StoreForm &form, const Geom &g, const DecWs &ws, uint8_t *d_out, int v0, dim3 grid,
+                            hipStream_t stream, Profiler *prof) {
+  const dim3 block(256);
+  prof_begin(prof, store_stage_name(form.kind, FAST ? kTileFast : kTileAny), stream);
+  if (form.kind == kStoreTens) {
+    const TileArgsT ta = {g, ws, d_out, v0, form.tens()};
+    hipLaunchKernelGGL(k_tile_inv_t<FAST>, grid, block, 0, stream, ta);
+  } else if (form.kind == kStorePitch) {
+    const TileArgsP tp = {g, ws, d_out, v0, form.dst()};
+    hipLaunchKernelGGL(k_tile_inv_p<FAST>, grid, block, 0, stream, tp);
+  } else if (form.kind == kStorePyr) {
+    const TileArgsM tm = {g, ws, v0, form.pyr()};
+    hipLaunchKernelGGL(k_tile_inv_m<FAST>, grid, block, 0, stream, tm);
+  } else {
+    hipLaunchKernelGGL(k_tile_inv<FAST>, grid, block, 0, stream, g, ws, d_out, v0);
+  }
+  prof_end(prof, stream);
+}
+
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,
                    const DecStreams *ds, int r0, int r1,
-                   const uint32_t *d_row_index, bool index_only, int phase, const TensDesc *tens,
-                   const DstDesc *dst, const PyrDesc *pyr) {
+                   const uint32_t *d_row_index, bool index_only, int phase, const StoreForm &form) {
   // d_row_index: the FRES row index is given (k_dec_set_index instead of the serial
   // header walk; one frame).  index_only: container parse and row-header walk only --
   // the caller reads ws.row_off / ws.row_len / DecFrame::rows_first (rank 0 of a
@@ -6021,10 +5897,11 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
   if (do_head) launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
   // The pyramid's 1/8-scale level: the low-res plane the chain has just finished, as launch_preview
   // stores it.  (A frame the rows reject later keeps these bytes: a failed frame's are unspecified.)
-  if (do_head && pyr && pyr->level[3]) {
+  if (do_head && form.kind == kStorePyr && form.pyr().level[3]) {
     const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
-    HIMG_LAUNCH(k_lres_preview, dim3((npix + 1023u) / 1024u, batch), dim3(256), g, ws, pyr->level[3]);
+    HIMG_LAUNCH(k_lres_preview, dim3((npix + 1023u) / 1024u, batch), dim3(256), g, ws, form.pyr().level[3]);
   }
+  const bool whole4 = g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0;   // FULL4 / FAST
   if (!do_rows) return;
   if (wps) {
     // Rows per workgroup: as many as the transform has lanes for and the LDS holds
@@ -6038,56 +5915,26 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
     // many as run at once -- one per CU.
     // (Sixteen wavefronts of 120+ registers each: one workgroup per CU whatever the LDS leaves.)
     const int n_cu = ho.n_cu, per_cu = 1;
-#define HIMG_FUSED_LAUNCH(COLS, A, B)                                                           \
-  do {                                                                                          \
-    const int gx_ = ((B) - (A) + rpw - 1) / rpw;                                                \
-    const long long all_ = (long long)gx_ * batch;                                              \
-    const int slots_ = ho.persist_rows > 1 ? ho.persist_rows : n_cu * per_cu;                   \
-    const bool pers_ = ho.persist_rows != 0 && all_ > slots_;                                   \
-    RowArgs ra_;                                                                                \
-    ra_.g = g; ra_.ws = ws; ra_.packed = d_packed; ra_.in_stride = in_stride; ra_.sizes = d_sizes; \
-    ra_.out_frames = d_out; ra_.r0 = (A); ra_.r1 = (B); ra_.rpw = rpw; ra_.gx = gx_; ra_.gy = batch; \
-    ra_.next_dist = pers_ ? 0 : n_cu * per_cu;                                                 \
-    if (tens) {                                                                                 \
-      RowArgsT rt_;                                                                             \
-      rt_.a = ra_; rt_.t = *tens;                                                               \
-      hipLaunchKernelGGL((k_dec_row_fused_t<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
-                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rt_); \
-    } else if (dst) {                                                                           \
-      RowArgsP rp_;                                                                             \
-      rp_.a = ra_; rp_.d = *dst;                                                                \
-      hipLaunchKernelGGL((k_dec_row_fused_p<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
-                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rp_); \
-    } else if (pyr) {                                                                           \
-      RowArgsM rm_;                                                                             \
-      rm_.a = ra_; rm_.m = *pyr;                                                                \
-      hipLaunchKernelGGL((k_dec_row_fused_m<(COLS) == 256 || (COLS) == 240 ? -1 : (COLS)>),     \
-                         dim3((unsigned)(pers_ ? slots_ : all_)), dim3(kDecThreads), lds, stream, rm_); \
-    } else                                                                                      \
-    hipLaunchKernelGGL((k_dec_row_fused<COLS>), dim3((unsigned)(pers_ ? slots_ : all_)),        \
-                       dim3(kDecThreads), lds, stream, ra_);                                    \
-  } while (0)
+    const int slots = ho.persist_rows > 1 ? ho.persist_rows : n_cu * per_cu;
+    RowArgs ra;
+    ra.g = g; ra.ws = ws; ra.packed = d_packed; ra.in_stride = in_stride; ra.sizes = d_sizes;
+    ra.out_frames = d_out; ra.rpw = rpw; ra.gy = batch;
     for (int k = 0; k < nseg; ++k) {
       const int a = seg_lo(k), b = seg_lo(k + 1);
       if (ds) (void)hipStreamWaitEvent(stream, ds->ev_cnt[k], 0);
       else row_count(stream, a, b);
       if (b <= a) continue;
-      // (tensor and pitched forms: <512>, <-1> -- which also serves 2048 and 1920 -- and <0>)
-      const bool whole4 = g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0;   // FULL4
-      // (the tensor and pitched forms carry their instantiation in the stage name: the tests assert which one ran)
-      const int form = g.W == 4096 && whole4 ? 0 : whole4 ? 1 : 2;
-      static const char *const kTensName[3] = {"k_dec_row_fused_t<512>", "k_dec_row_fused_t<-1>", "k_dec_row_fused_t<0>"};
-      static const char *const kPitchName[3] = {"k_dec_row_fused_p<512>", "k_dec_row_fused_p<-1>", "k_dec_row_fused_p<0>"};
-      static const char *const kPyrName[3] = {"k_dec_row_fused_m<512>", "k_dec_row_fused_m<-1>", "k_dec_row_fused_m<0>"};
-      prof_begin(prof, tens ? kTensName[form] : dst ? kPitchName[form] : pyr ? kPyrName[form] : "k_dec_row_fused", stream);
-      if (g.W == 4096 && whole4) HIMG_FUSED_LAUNCH(512, a, b);
-      else if (g.W == 2048 && whole4) HIMG_FUSED_LAUNCH(256, a, b);   // compile-time strides for the other
-      else if (g.W == 1920 && whole4) HIMG_FUSED_LAUNCH(240, a, b);   // BASELINE widths (config 3: 1920)
-      else if (whole4) HIMG_FUSED_LAUNCH(-1, a, b);
-      else HIMG_FUSED_LAUNCH(0, a, b);
-      prof_end(prof, stream);
+      ra.r0 = a; ra.r1 = b; ra.gx = (b - a + rpw - 1) / rpw;
+      const long long all = (long long)ra.gx * batch;
+      const bool pers = ho.persist_rows != 0 && all > slots;
+      ra.next_dist = pers ? 0 : n_cu * per_cu;
+      const unsigned n_wg = (unsigned)(pers ? slots : all);
+      if (g.W == 4096 && whole4) launch_row_fused<512>(form, ra, n_wg, lds, stream, prof);
+      else if (g.W == 2048 && whole4) launch_row_fused<256>(form, ra, n_wg, lds, stream, prof);   // compile-time strides for the other
+      else if (g.W == 1920 && whole4) launch_row_fused<240>(form, ra, n_wg, lds, stream, prof);   // BASELINE widths (config 3: 1920)
+      else if (whole4) launch_row_fused<-1>(form, ra, n_wg, lds, stream, prof);
+      else launch_row_fused<0>(form, ra, n_wg, lds, stream, prof);
     }
-#undef HIMG_FUSED_LAUNCH
   } else {
     // Symbols through HBM: the entropy pass (window_pass above; with side streams it ran on the
     // counts' stream already), then the transform, which needs the low-res plane as well.
@@ -6096,24 +5943,8 @@ void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
       if (ds) (void)hipStreamWaitEvent(stream, ds->ev_win[k], 0);
       else { row_count(stream, a, b); window_pass(stream, a, b); }
       if (b <= a) continue;
-      if (tens) {
-        TileArgsT ta;
-        ta.g = g; ta.ws = ws; ta.out_frames = d_out; ta.v0 = a; ta.t = *tens;
-        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_t<true>, dim3(gx, b - a, batch), dim3(256), ta);
-        else HIMG_LAUNCH(k_tile_inv_t<false>, dim3(gx, b - a, batch), dim3(256), ta);
-      } else if (dst) {
-        TileArgsP tp;
-        tp.g = g; tp.ws = ws; tp.out_frames = d_out; tp.v0 = a; tp.d = *dst;
-        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_p<true>, dim3(gx, b - a, batch), dim3(256), tp);
-        else HIMG_LAUNCH(k_tile_inv_p<false>, dim3(gx, b - a, batch), dim3(256), tp);
-      } else if (pyr) {
-        TileArgsM tm;
-        tm.g = g; tm.ws = ws; tm.v0 = a; tm.m = *pyr;
-        if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv_m<true>, dim3(gx, b - a, batch), dim3(256), tm);
-        else HIMG_LAUNCH(k_tile_inv_m<false>, dim3(gx, b - a, batch), dim3(256), tm);
-      } else
-      if (g.C == 4 && (g.W & 7) == 0 && (g.H & 7) == 0) HIMG_LAUNCH(k_tile_inv<true>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
-      else HIMG_LAUNCH(k_tile_inv<false>, dim3(gx, b - a, batch), dim3(256), g, ws, d_out, a);
+      if (whole4) launch_tile_inv<true>(form, g, ws, d_out, a, dim3(gx, b - a, batch), stream, prof);
+      else launch_tile_inv<false>(form, g, ws, d_out, a, dim3(gx, b - a, batch), stream, prof);
     }
   }
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
