@@ -1026,12 +1026,12 @@ class MultiEngine:
         opt = {"fix_t2": 1}[option] if isinstance(option, str) else int(option)
         self._check(lib().himg_hip_multi_set_option(self._m, opt, int(value)), "set_option")
 
-    def encode(self, img, quality=50, use_ycbcr=True):
+    def encode(self, img, quality=50, use_ycbcr=True, channels=None, pixel_stride=None):
+        """channels / pixel_stride as in Engine.encode: the image's last axis where not given."""
         img = np.ascontiguousarray(img, np.uint8)
-        h, w = img.shape[:2]
-        ch = img.shape[2] if img.ndim == 3 else 1
+        h, w, ch, stride = _image_geom(img, channels, pixel_stride)
         out, n = C.c_void_p(), C.c_size_t()
-        rc = lib().himg_hip_multi_encode(self._m, img.ctypes.data, w, h, ch, ch, quality, 1 if use_ycbcr else 0,
+        rc = lib().himg_hip_multi_encode(self._m, img.ctypes.data, w, h, stride, ch, quality, 1 if use_ycbcr else 0,
                                          C.byref(out), C.byref(n))
         self._check(rc, "multi_encode")
         a = np.ctypeslib.as_array(C.cast(out, C.POINTER(C.c_uint8)), (n.value,)).copy()

@@ -186,7 +186,8 @@ def encode_sharded(backend, rows, cols, channels, use_blocks, group=None, host=T
 class EngineBackend:
     """Device phases on the HIP engine.  `d_frame` is this rank's view of the
     frame: a CUDA uint8 tensor holding pixel rows [y_first, y_first + n) of the
-    W x H image (at least rows 8*r0-11 .. 8*r1+4 clipped to the image).
+    W x H image (at least rows 8*r0-11 .. 8*r1+4 clipped to the image), `pixel_stride`
+    bytes per pixel of which the first `channels` are coded.
 
     Every buffer the phases touch is allocated once, here; the phases only launch
     kernels on the (torch current = null) stream, so the collectives that follow
@@ -195,14 +196,15 @@ class EngineBackend:
     pieces that travel to rank 0)."""
 
     def __init__(self, engine, d_frame, y_first, width, height, quality=50, use_ycbcr=True,
-                 comm_device=None, stream=None):
+                 comm_device=None, stream=None, channels=4, pixel_stride=4):
         import torch
         import himg_amd
         self.eng, self.W, self.H, self.q, self.ycbcr = engine, width, height, quality, use_ycbcr
         self.d_frame, self.y_first, self.stream = d_frame, y_first, stream
         self.dev = d_frame.device
         self.comm = torch.device(comm_device) if comm_device is not None else self.dev
-        self.rows, self.cols, self.C = (height + 7) // 8, (width + 7) // 8, 4
+        self.rows, self.cols, self.C = (height + 7) // 8, (width + 7) // 8, channels
+        self.stride = pixel_stride
         self.r0 = self.r1 = 0
         dev = self.dev
         self._hist32 = torch.zeros(264, dtype=torch.int32, device=dev)
@@ -237,8 +239,8 @@ class EngineBackend:
         self.r0, self.r1 = r0, r1
         # Called for an empty share too: it sets up the per-frame state every later
         # phase (and rank 0's assemble) relies on.
-        base = self.d_frame.data_ptr() - self.y_first * self.W * 4   # virtual frame base
-        self.eng.shard_stats(base, self.W, self.H, 4, 4, self.q, self.ycbcr, r0, r1, self._hist32, self._low,
+        base = self.d_frame.data_ptr() - self.y_first * self.W * self.stride   # virtual frame base
+        self.eng.shard_stats(base, self.W, self.H, self.stride, self.C, self.q, self.ycbcr, r0, r1, self._hist32, self._low,
                              self._s())
         h64 = (self._hist32[:261].to(torch.int64) & 0xFFFFFFFF)    # i64: 8 ranks x 2^31 tokens cannot wrap
         return self._to_comm(h64), self._to_comm(self._low[: self.C * (r1 - r0) * self.cols])
