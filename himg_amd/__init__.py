@@ -147,6 +147,8 @@ def lib():
     L.himg_hip_prefix_peek.argtypes = [vp, sz, i32, vp]
     L.himg_hip_decode_prefix_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32), P(i32)]
     L.himg_hip_decode_prefix_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.himg_hip_decode_conceal_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32), vp, sz, P(i32)]
+    L.himg_hip_decode_conceal_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.himg_hip_create_multi.argtypes = [vp, i32, P(vp)]
     L.himg_hip_destroy_multi.argtypes = [vp]
     L.himg_hip_destroy_multi.restype = None
@@ -523,6 +525,39 @@ class Engine:
                                                  height, channels, _ptr(d_out), _ptr(d_rows), _ptr(d_status),
                                                  C.c_void_p(stream))
         self._check(rc, "decode_prefix_device")
+
+    def decode_conceal(self, packed, out=None):
+        """himg_hip_decode_conceal_to: the decode of a stream that may be damaged.  Returns (picture,
+        rowmap): the (H, W, C) uint8 picture and a bool array with one entry per block row, True where
+        the row was rejected or could not be delimited and was written from the low-res plane; every
+        other row is decode()'s.  Raises HimgError, as decode() does, only for damage in the stream's
+        head.  (No checksums: damage the decoder accepts is decoded as it stands.)"""
+        packed = _as_u8(packed)
+        w, h, c, n = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        dst, cap, rmap, rcap = None, 0, None, 0
+        geom = _peek(packed)
+        if geom:
+            out = _out_buffer(out, geom[0] * geom[1] * geom[2])
+            dst, cap = out.ctypes.data, out.nbytes
+            rmap = np.zeros((geom[1] + 7) // 8, np.uint8)
+            rcap = rmap.nbytes
+        rc = lib().himg_hip_decode_conceal_to(self._ctx, packed.ctypes.data, packed.nbytes, dst, cap, C.byref(w),
+                                              C.byref(h), C.byref(c), rmap.ctypes.data if geom else None, rcap,
+                                              C.byref(n))
+        self._check(rc, "decode_conceal")
+        return out.reshape(h.value, w.value, c.value), rmap.astype(bool)
+
+    def decode_conceal_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, d_out,
+                              d_concealed, d_rowmap, d_status, stream=0):
+        """himg_hip_decode_conceal_device: the contract of decode_device; d_concealed (batch x int32)
+        receives each frame's concealed block rows, -1 with a head verdict; d_rowmap (batch x rows bytes,
+        or None) the rows' map."""
+        hs = None if h_sizes is None else np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_conceal_device(self._ctx, _ptr(d_packed), in_stride,
+                                                  hs.ctypes.data if hs is not None else None, batch, width, height,
+                                                  channels, _ptr(d_out), _ptr(d_concealed), _ptr(d_rowmap),
+                                                  _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_conceal_device")
 
     def decode_region(self, packed, x, y, w, h, out=None):
         """Rectangle (x, y, w, h) at full resolution (himg_hip_decode_region_to) as an (h, w, C)

@@ -19,6 +19,10 @@
 // the full picture to out.ext and the 1/2-, 1/4- and 1/8-scale pictures to out.L1.ext, out.L2.ext and
 // out.L3.ext.  On its own only: with a scale, a rectangle or -t it is a bad argument (usage, exit 0),
 // decided before the file is read or the device is opened.
+// A fifth: "-c image outfile" decodes a file that may be DAMAGED (himg_hip_decode_conceal_to): the block rows
+// the decoder accepts as the full decode writes them, the rows it rejects or cannot delimit from the
+// low-res plane, and on stderr a line "concealed N of R block rows" followed, when N > 0, by a line with
+// the rows' indices.  Exit status 0 whenever the stream's head is sound.  On its own only, like -m.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -60,11 +64,19 @@ int main(int argc, const char **argv) {
     printf("Usage: %s image outfile\n", argv[0]);
     return 0;
   }
+  // The concealing decode: "-c image outfile" and nothing else.
+  bool conceal = false;
+  if (argc >= 4)
+    for (int i = 1; i < argc - 2; ++i) conceal = conceal || std::strcmp(argv[i], "-c") == 0;
+  if (conceal && !(argc == 4 && std::strcmp(argv[1], "-c") == 0)) {
+    printf("Usage: %s image outfile\n", argv[0]);
+    return 0;
+  }
   int scale_log2 = 0;
   if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
   else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
   const bool prefix = !scale_log2 && argc >= 4 && std::strcmp(argv[1], "-t") == 0;
-  int arg = scale_log2 || prefix || mip ? 2 : 1;
+  int arg = scale_log2 || prefix || mip || conceal ? 2 : 1;
   bool region = false;
   int rx = 0, ry = 0, rw = 0, rh = 0;
   if (!prefix && argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
@@ -117,6 +129,40 @@ int main(int argc, const char **argv) {
       const std::string path = k ? level_path(out_path, k) : std::string(out_path);
       if (!writable || !pnm::write(path.c_str(), picture)) return fail("Unable to write file", path.c_str());
     }
+    return 0;
+  }
+
+  if (conceal) {
+    int w = 0, h = 0, c = 0, n = -1;
+    if (himg_hip_peek(stream.data(), stream.size(), &w, &h, &c) != HIMG_OK) return fail("Unable to decode image.", nullptr);
+    const int rows = (h + 7) / 8;
+    std::vector<uint8_t> pixels(static_cast<size_t>(w) * h * c), rowmap(static_cast<size_t>(rows));
+    himg_hip_ctx *ctx = nullptr;
+    if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
+    const int rc = himg_hip_decode_conceal_to(ctx, stream.data(), stream.size(), pixels.data(), pixels.size(), &w, &h, &c,
+                                              rowmap.data(), rowmap.size(), &n);
+    if (rc != HIMG_OK) {
+      const char *msg = himg_hip_last_error(ctx);
+      printf("%s%s", msg, (*msg && msg[std::strlen(msg) - 1] == '\n') ? "" : "\n");
+      himg_hip_destroy(ctx);
+      return fail("Unable to decode image.", nullptr);
+    }
+    himg_hip_destroy(ctx);
+    fprintf(stderr, "concealed %d of %d block rows\n", n, rows);
+    if (n > 0) {
+      bool first = true;
+      for (int r = 0; r < rows; ++r)
+        if (rowmap[r]) { fprintf(stderr, "%s%d", first ? "" : " ", r); first = false; }
+      fprintf(stderr, "\n");
+    }
+    pnm::Image picture;
+    picture.width = w;
+    picture.height = h;
+    picture.channels = c;
+    picture.data.resize(pixels.size());
+    pnm::flip_and_swap(pixels.data(), picture.data.data(), w, h, c);
+    const bool writable = c == 1 || c == 3 || c == 4;
+    if (!writable || !pnm::write(out_path, picture)) return fail("Unable to write file", out_path);
     return 0;
   }
 

@@ -1,7 +1,9 @@
 // The body of k_dec_region, of its tensor form k_dec_region_t and of its pitched form k_dec_region_p:
 // one copy, included behind each kernel's own parameters (g, ws, packed, in_stride, sizes, ra) with
 // kRegionTens and td, kRegionPitch and pd (the descriptors, or nullptr) defined, so that k_dec_region
-// keeps its code instruction for instruction.
+// keeps its code instruction for instruction.  kRegionConceal and cmap (k_dec_conceal; false and nullptr
+// everywhere else): a row the checks reject is not the frame's verdict -- its byte cmap[f * rows + r] is
+// set and its tiles are stored as those of a row of zero symbols.
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const RegionLayout L = region_layout(g.C, ra.sw);
   LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
@@ -31,7 +33,10 @@
   // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
   const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
   const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
-  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+  // (kRegionConceal with several column strips: every strip walks the whole row, so that all of them reach
+  // the same verdict on it)
+  const bool strict = __syncthreads_or((nn <= 1) || (kRegionConceal && gridDim.x > 1) ||
+                                       ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
 
   const size_t ri = (size_t)f * g.rows + (size_t)r;
   const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
@@ -87,8 +92,15 @@
   const unsigned long long E = sh->endbit;
   if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
   if (bad) {
-    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
-    return;
+    if constexpr (kRegionConceal) {
+      // The symbols a partial walk has left are cleared: the strip's tiles come out as the low-res plane's.
+      if (tid == 0) cmap[ri] = 1;
+      for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
+      __syncthreads();
+    } else {
+      if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+      return;
+    }
   }
   // ---- the strip's tiles: transform, colour inverse, cropped stores ----
   const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;

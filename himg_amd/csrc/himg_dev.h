@@ -450,6 +450,14 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
 void launch_prefix(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
                    Profiler *prof, const DecStreams *ds);
+// The concealing decode (include/himg_hip.h): launch_decode as himg_hip_decode_device calls it, into d_out, then
+// the repair pass over the frames it rejected in their FRES rows alone (kernels_dec.hip, k_conceal_gate ..
+// k_conceal_status), on the caller's stream with no host wait.  d_words: 4 x batch words, the first batch --
+// the packed sizes -- staged by the caller; d_cmap: batch x rows bytes of scratch; d_rowmap may be nullptr.
+// The workspace of launch_decode (the repair pass writes plain per-lane records over the full decode's).
+void launch_conceal(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                    uint32_t *d_words, uint8_t *d_cmap, uint8_t *d_out, int32_t *d_concealed, uint8_t *d_rowmap,
+                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho, const DecStreams *ds);
 // Widest column strip of the region kernel, in tiles (its LDS holds C x 64 segments of a strip).
 int region_strip_tiles(const Geom &g);
 // The scaled decode (k_dec_scaled): every frame of the batch at 1 / 2^scale_log2 (1 or 2) of its

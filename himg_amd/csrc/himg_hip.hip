@@ -164,6 +164,7 @@ struct himg_hip_ctx {
 
   // Decoder workspace.
   DevBuf d_frames, d_nodes, d_grp, d_gyc, d_sub, d_lane, d_rows, d_lres, d_fres, d_planes, d_sizes, d_stats, d_spec;
+  DevBuf d_cmap;   // the concealing decode's row map, [frame][rows] bytes
   Geom dec_geom{};
   DecWs dec_ws{};
   int dec_batch = 0;
@@ -397,7 +398,7 @@ extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
   }
   DevBuf *all[] = {&ctx->fmap_lut, &ctx->e_planes, &ctx->e_lres, &ctx->e_fres, &ctx->e_small,
                    &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_search, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
-                   &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->h_in,
+                   &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->d_cmap, &ctx->h_in,
                    &ctx->h_out, &ctx->h_result, &ctx->h_status, &ctx->h_index};
   for (DevBuf *b : all) b->release();
   if (ctx->hp_index) hipHostFree(ctx->hp_index);
@@ -2269,6 +2270,73 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
   if (st[0]) return status_error(ctx, st[0], "the prefix ends before the first block row");
   ctx->host_bytes = out_bytes;
   *width = W; *height = H; *channels = C; *rows_complete = st[1];
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The concealing decode: the full decode, then the block rows it rejected -- or could not delimit -- from
+// the low-res plane (kernels_dec.hip, launch_conceal).
+// ---------------------------------------------------------------------------
+extern "C" int himg_hip_decode_conceal_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                              const uint32_t *h_sizes, int batch, int width, int height,
+                                              int num_channels, void *d_out, int32_t *d_concealed, uint8_t *d_rowmap,
+                                              int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_concealed || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsFull, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  if (int rc = stride_covers(ctx, h_sizes, batch, in_stride)) return rc;
+  { uint32_t mx = 0; for (int i = 0; i < batch; ++i) mx = h_sizes[i] > mx ? h_sizes[i] : mx; g.wide_q = wide_q_hint(g, mx); }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_cmap.reserve(round_up((size_t)batch * g.rows, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
+  // (the sizes ride to the device as in decode_device: no wait; three more words per frame behind them
+  // are the repair pass's, himg_dev::launch_conceal)
+  if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
+  launch_conceal(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p,
+                 (uint8_t *)ctx->d_cmap.p, (uint8_t *)d_out, d_concealed, d_rowmap, d_status, (hipStream_t)stream,
+                 &ctx->prof, ctx->opts, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_conceal_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
+                                          size_t dst_cap, int *width, int *height, int *channels, uint8_t *rowmap,
+                                          size_t rowmap_cap, int *concealed) {
+  if (!ctx || !packed || !width || !height || !channels || !concealed) return HIMG_ERR_ARG;
+  *concealed = -1;
+  int W = 0, H = 0, C = 0;
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  if (rowmap && rowmap_cap < (size_t)g.rows) return fail(ctx, HIMG_ERR_CAPACITY, "row map buffer too small");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // The whole stream goes up and the device walks it: the host index cannot be built over a bad header.
+  const size_t in_cap = round_up(packed_size + 16, 256);
+  const size_t out_bytes = (size_t)W * H * C;
+  const size_t map_at = 256;   // (h_status: the status word, the count, then the row map)
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
+      !ctx->h_status.reserve(map_at + round_up((size_t)g.rows, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  ctx->host_bytes = 0;
+  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  int32_t *d_st = (int32_t *)ctx->h_status.p;
+  uint8_t *d_map = (uint8_t *)ctx->h_status.p + map_at;
+  if (int rc = himg_hip_decode_conceal_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, ctx->h_out.p, d_st + 1, d_map, d_st,
+                                              nullptr)) {
+    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
+    return rc;
+  }
+  int32_t st[2] = {0, -1};
+  HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
+  if (st[0]) return status_error(ctx, st[0]);
+  ctx->host_bytes = out_bytes;
+  *width = W; *height = H; *channels = C; *concealed = st[1];
+  if (rowmap) HIP_TRY(ctx, hipMemcpy(rowmap, d_map, (size_t)g.rows, hipMemcpyDeviceToHost));
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return HIMG_OK;

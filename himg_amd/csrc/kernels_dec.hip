@@ -4429,6 +4429,8 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
 __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, RegionArgs ra) {
   constexpr bool kRegionTens = false, kRegionPitch = false;
+  constexpr bool kRegionConceal = false;
+  uint8_t *const cmap = nullptr;
   const TensK td = nullptr;
   const DstK pd = nullptr;
 #include "dec_body_region.inc"
@@ -4448,6 +4450,8 @@ struct RegionArgsT {
 };
 __global__ __launch_bounds__(kDecThreads) void k_dec_region_t(RegionArgsT a) {
   constexpr bool kRegionTens = true, kRegionPitch = false;
+  constexpr bool kRegionConceal = false;
+  uint8_t *const cmap = nullptr;
   const DstK pd = nullptr;
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
@@ -4473,6 +4477,8 @@ struct RegionArgsP {
 };
 __global__ __launch_bounds__(kDecThreads) void k_dec_region_p(RegionArgsP a) {
   constexpr bool kRegionTens = false, kRegionPitch = true;
+  constexpr bool kRegionConceal = false;
+  uint8_t *const cmap = nullptr;
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
   const uint8_t *packed = a.packed;
@@ -4693,6 +4699,8 @@ struct PrefixWindow {     // what the body reads of a RegionArgs
 __global__ __launch_bounds__(kDecThreads) void k_dec_prefix(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, PrefixArgs pa) {
   constexpr bool kRegionTens = false, kRegionPitch = false;
+  constexpr bool kRegionConceal = false;
+  uint8_t *const cmap = nullptr;
   const TensK td = nullptr;
   const DstK pd = nullptr;
   const int k_f = pa.krows[blockIdx.z];
@@ -4809,6 +4817,140 @@ __global__ void k_prefix_status(DecWs ws, const int32_t *gate, const int32_t *kr
   if (gate[f]) st = gate[f];
   status[f] = st;
   if (rows_out) rows_out[f] = st ? -1 : krows[f];
+}
+
+// ---------------------------------------------------------------------------
+// The CONCEALING decode (include/himg_hip.h): the full decode as it is, then a repair pass over the
+// frames it rejected in their FRES rows alone.  Of such a frame the rows the header walk delimits,
+// [0, k_f), are judged one by one -- an accepted row is the full decode's, a rejected one is stored as a
+// row of zero symbols -- and rows [k_f, rows) are the prefix decode's fill.  Every other frame keeps
+// what the full decode left.
+//   k_conceal_gate     (a lane per frame) act[f]: 1 a frame to repair -- the parse passed and the verdict
+//                      is the rows' (the walk's or a row kernel's); its verdict fields are cleared for the
+//                      kernels below.  0: accepted, 2: a head verdict -- neither is touched again: an
+//                      accepted frame is PARKED (DecFrame::status = kStParked until k_conceal_status), so
+//                      that the kernels shared with the other decodes, which skip a frame with a verdict,
+//                      skip it too.
+//   k_conceal_zero     the LRES symbols of the frames to repair, then the LRES chain over them again: a
+//                      verdict of the rows may have reached a frame while its chain ran, which then
+//                      stopped half way (and a chain that fails now is a head verdict after all: the
+//                      rows' verdict hid it).
+//   k_conceal_rowwalk  (a lane per frame) the row headers again, for the row index and k_f.
+//   k_conceal_map      the row map: 1 for rows [k_f, rows) of a frame to repair, else 0.
+//   k_prefix_fill, k_prefix_count(_w)   as the prefix decode runs them, over k_f.
+//   k_dec_conceal      k_dec_region's body over rows [0, k_f), the whole width (k_dec_prefix's window),
+//                      with kRegionConceal: a rejected row sets its map byte and is stored as zero symbols.
+//   k_conceal_status   (a wavefront per frame) d_status, d_concealed, the caller's row map.
+// ---------------------------------------------------------------------------
+constexpr int kStParked = 1 << 30;
+
+__global__ void k_conceal_gate(DecWs ws, const int32_t *st1, int32_t *krows, int32_t *act, int batch) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= batch) return;
+  DecFrame *df = ws.frames + f;
+  const int m = st1[f];   // k_dec_status's word: the parse's, the walk's and the row kernels' verdicts merged
+  int a = 0;
+  if (m != 0) a = (df->parse_status == 0 && m == fmt_err(7, 1)) ? 1 : 2;
+  act[f] = a;
+  krows[f] = 0;
+  if (a == 1) { df->status = 0; df->walk_status = 0; }
+  else if (a == 0) df->status = kStParked;
+}
+
+__global__ __launch_bounds__(256) void k_conceal_zero(DecWs ws, const int32_t *act) {
+  const int f = blockIdx.y;
+  if (act[f] != 1) return;
+  uint4 *p = reinterpret_cast<uint4 *>(ws.lres_sym + (size_t)f * ws.lres_stride);
+  const uint32_t n16 = (uint32_t)(ws.lres_stride / 16);   // (the stride is a multiple of 256)
+  for (uint32_t k = blockIdx.x * 256u + threadIdx.x; k < n16; k += gridDim.x * 256u) p[k] = make_uint4(0, 0, 0, 0);
+}
+
+__global__ __launch_bounds__(64) void k_conceal_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                        const int32_t *act, int32_t *krows, int batch) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch || act[f] != 1) return;
+  const DecFrame *df = ws.frames + f;
+  const uint8_t *p = packed + (size_t)f * in_stride;
+  const uint32_t end = df->s[1].chunk_end;
+  uint32_t q = df->s[1].payload_off;
+  uint32_t *ro = ws.row_off + (size_t)f * g.rows, *rl = ws.row_len + (size_t)f * g.rows;
+  int r = 0;
+  if (g.fix_t2 && g.rows == 1) {   // one block row without a size header
+    ro[0] = q; rl[0] = end - q;
+    r = 1;
+  } else {
+    while (q != end) {   // (k_dec_rowwalk's header rules; a failure behind the last row conceals nothing)
+      if (q + 2 > end) break;
+      uint32_t len = p[q] | (p[q + 1] << 8);
+      q += 2;
+      if (len & 0x8000u) {
+        if (q + 2 > end) break;
+        len = (len & 0x7fffu) | ((uint32_t)(p[q] | (p[q + 1] << 8)) << 15);
+        q += 2;
+      }
+      if (len > end - q) break;
+      if (r < g.rows) { ro[r] = q; rl[r] = len; }
+      ++r;
+      q += len;
+    }
+  }
+  krows[f] = r < g.rows ? r : g.rows;
+}
+
+__global__ __launch_bounds__(256) void k_conceal_map(const int32_t *act, const int32_t *krows, uint8_t *cmap, int rows,
+                                                     int batch) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)batch * rows) return;
+  const int f = (int)(i / rows), r = (int)(i - (size_t)f * rows);
+  cmap[i] = (act[f] == 1 && r >= krows[f]) ? 1 : 0;
+}
+
+struct ConcealArgs {
+  const int32_t *krows;   // [f] k_f (0: nothing to repair)
+  uint8_t *cmap;          // [f][rows]
+  int sw;                 // tiles per column strip (blockIdx.x = strip)
+  uint8_t *out;
+};
+__global__ __launch_bounds__(kDecThreads) void k_dec_conceal(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                            const uint32_t *sizes, ConcealArgs ca) {
+  constexpr bool kRegionTens = false, kRegionPitch = false, kRegionConceal = true;
+  const TensK td = nullptr;
+  const DstK pd = nullptr;
+  const int k_f = ca.krows[blockIdx.z];
+  if ((int)blockIdx.y >= k_f) return;
+  uint8_t *const cmap = ca.cmap;
+  PrefixWindow ra;
+  ra.sw = ca.sw; ra.w = g.W; ra.h = 8 * k_f < g.H ? 8 * k_f : g.H;
+  ra.out = ca.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C);   // (k_dec_prefix's placement)
+#include "dec_body_region.inc"
+}
+
+__global__ __launch_bounds__(64) void k_conceal_status(DecWs ws, const int32_t *st1, const int32_t *act,
+                                                       const uint8_t *cmap, int rows, uint8_t *rowmap, int32_t *status,
+                                                       int32_t *concealed) {
+  __shared__ int s_n;
+  const int f = blockIdx.x, lane = threadIdx.x;
+  DecFrame *df = ws.frames + f;
+  const int a = act[f];
+  // A frame to repair whose LRES chain failed in the repair pass: a head verdict (the full decode's word).
+  const bool head = a == 2 || (a == 1 && df->status != 0);
+  if (lane == 0) s_n = 0;
+  __syncthreads();
+  if (!head) {
+    int n = 0;
+    for (int r = lane; r < rows; r += 64) {
+      const uint8_t b = a == 1 ? cmap[(size_t)f * rows + r] : (uint8_t)0;
+      if (rowmap) rowmap[(size_t)f * rows + r] = b;
+      n += b;
+    }
+    if (n) atomicAdd(&s_n, n);
+  }
+  __syncthreads();
+  if (lane != 0) return;
+  if (a == 0) df->status = 0;
+  else if (a == 1 && head) df->status = st1[f];
+  status[f] = head ? st1[f] : 0;
+  concealed[f] = head ? -1 : s_n;
 }
 
 // ---------------------------------------------------------------------------
@@ -5371,7 +5513,7 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
       {HIMG_K(k_row_window), kRowWindowLds},
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
-      {HIMG_K(k_dec_prefix), 0},
+      {HIMG_K(k_dec_prefix), 0},           {HIMG_K(k_dec_conceal), 0},
       {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
       {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
 #undef HIMG_K
@@ -5622,6 +5764,46 @@ void launch_prefix(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
                      ws, d_packed, in_stride, d_bound, pa);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_prefix_status, dim3((batch + 63) / 64), dim3(64), ws, d_gate, d_k, d_status, d_rows, batch);
+}
+
+// The concealing decode.  d_words: 4 x batch words -- the packed sizes (staged by the caller), then the full
+// decode's status words, k_f and the gate's classes; d_cmap: batch x rows bytes.  Pass one is launch_decode as
+// himg_hip_decode_device calls it; pass two runs behind it on the caller's stream.
+void launch_conceal(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                    uint32_t *d_words, uint8_t *d_cmap, uint8_t *d_out, int32_t *d_concealed, uint8_t *d_rowmap,
+                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho, const DecStreams *ds) {
+  const uint32_t *d_sizes = d_words;
+  int32_t *d_st1 = (int32_t *)(d_words + batch), *d_k = (int32_t *)(d_words + 2 * (size_t)batch);
+  int32_t *d_act = (int32_t *)(d_words + 3 * (size_t)batch);
+  launch_decode(g, ws_in, batch, d_packed, in_stride, d_sizes, d_out, d_st1, stream, prof, ho, ds, 0, g.rows);
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region: they overwrite the full decode's)
+  const dim3 per_frame((batch + 63) / 64), b64(64);
+  HIMG_LAUNCH(k_conceal_gate, per_frame, b64, ws, d_st1, d_k, d_act, batch);
+  const uint32_t n16 = (uint32_t)(ws.lres_stride / 16);
+  HIMG_LAUNCH(k_conceal_zero, dim3(n16 / 256 < 64 ? (n16 + 255) / 256 : 64, batch), dim3(256), ws, d_act);
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
+  HIMG_LAUNCH(k_conceal_rowwalk, per_frame, b64, g, ws, d_packed, in_stride, d_act, d_k, batch);
+  HIMG_LAUNCH(k_conceal_map, dim3((unsigned)(((size_t)batch * g.rows + 255) / 256)), dim3(256), d_act, d_k, d_cmap, g.rows,
+              batch);
+  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, d_k, d_out);
+  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
+  if (cr.wave) {
+    HIMG_LAUNCH(k_prefix_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
+                d_packed, in_stride, d_sizes, d_k);
+  } else {
+    HIMG_LAUNCH(k_prefix_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
+                in_stride, d_sizes, d_k, cr.rpc);
+  }
+  const int smax = region_strip_tiles(g);
+  const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
+  ConcealArgs ca;
+  ca.krows = d_k; ca.cmap = d_cmap; ca.sw = sw; ca.out = d_out;
+  prof_begin(prof, "k_dec_conceal", stream);
+  hipLaunchKernelGGL(k_dec_conceal, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
+                     ws, d_packed, in_stride, d_sizes, ca);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_conceal_status, dim3(batch), b64, ws, d_st1, d_act, d_cmap, g.rows, d_rowmap, d_status, d_concealed);
 }
 
 void launch_scaled(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,

@@ -856,6 +856,61 @@ int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_
                                   int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
                                   void *stream);
 
+/* ---- decode a damaged stream: rejected block rows concealed from the low-res plane ---- */
+/*
+ * himg_hip_decode rejects a whole picture for one bad block row.  The concealing decode does not: a frame
+ * whose HEAD is sound always yields a picture.  Rows the decoder accepts are byte for byte the full
+ * decode's; rows it rejects or cannot delimit are written from the low-res plane; the caller learns which
+ * rows those were.  Nothing new is defined: a row's verdict is the reference's (huffman_dec.cpp:232-248,
+ * :361-417), the fill is the prefix decode's.
+ *
+ * Head.  RIFF, FRMT, LMAP, LRES (chunk, tree and payload: the whole low-res chain), QCFG, FMAP, the FRES
+ *   chunk header, the T2 check (under the same HIMG_OPT_FIX_T2) and the FRES tree run exactly as in the
+ *   full decode.  A frame that fails there gets the full decode's d_status[f] (and its
+ *   himg_hip_last_error wording in _to) and d_concealed[f] = -1; its row map is not written and its
+ *   picture is unspecified, as in himg_hip_decode_device.  Other frames are unaffected.
+ * Walk.  The row headers are walked by the decoder's rules from the first one.  k_f is the number of rows
+ *   whose header and payload the walk passes before its first failure, at most `rows`.  A failure behind
+ *   the last block row (surplus blocks, a header crossing the chunk's end there) conceals nothing.  A frame
+ *   of one block row under HIMG_OPT_FIX_T2 has no header: k_f = 1.
+ * Rows.  Each row r < k_f is judged on its own with the full decode's checks: the record's total against
+ *   the row block, the end-of-block checks, AtTheEnd, an empty payload.  An accepted row's 8 pixel rows
+ *   are the full decode's, byte for byte.  A rejected row, and every row r >= k_f, is written as a row of
+ *   zero symbols -- exactly the prefix decode's pixels for a row that has not arrived -- and its row-map
+ *   byte is 1, otherwise 0.  A row has ONE verdict across the whole width.
+ * Results.  d_status[f] = 0; d_concealed[f] = the number of 1s in the frame's row map.
+ * A stream himg_hip_decode accepts: the same bytes as himg_hip_decode_device, d_concealed[f] = 0, an
+ *   all-zero row map.  Such frames are decoded by the full decode's own kernels; the repair pass behind
+ *   them costs a clean batch only its (empty) launches.
+ *
+ * Two caveats.
+ *   - The format has no checksums.  A damaged row the decoder ACCEPTS is decoded as it stands, as the full
+ *     decode does today, and a damaged size header that still passes the walk shifts every later row.
+ *   - d_concealed[f] == 0 does not prove that the full decode accepts the stream: the surplus-block case
+ *     above.
+ *
+ * Not in this change: a host batch entry; scaled, region, tensor, pitched and pyramid forms; concealment
+ * combined with a prefix (avail < T); himg::Decoder; the multi-GPU handle and the row-sharded decode; any
+ * smarter concealment than the low-res fill.
+ */
+/* A batch in HBM: the contract of himg_hip_decode_device for the layout and in_stride, the sizes (they
+ * ride to the device without a host wait; the repair pass runs behind the full decode on the same stream),
+ * HIMG_OPT_FIX_T2, and the loads: nothing at or beyond h_sizes[f] rounded up to 4.  d_concealed: batch
+ * int32; d_rowmap: [batch][rows] bytes, rows = ceil(height / 8), may be NULL.  Bad arguments:
+ * HIMG_ERR_ARG, nothing launched. */
+int himg_hip_decode_conceal_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                   const uint32_t *h_sizes, int batch, int width, int height,
+                                   int num_channels, void *d_out, int32_t *d_concealed, uint8_t *d_rowmap,
+                                   int32_t *d_status, void *stream);
+/* One host stream into caller-owned host memory.  The capacity protocol of himg_hip_decode_to, with
+ * himg_hip_fetch_last: a NULL or too-small dst gives HIMG_ERR_CAPACITY with the geometry, *concealed and
+ * the row map set.  The whole stream is uploaded and walked on the device (the host index cannot be built
+ * over a bad header).  rowmap (rows bytes) may be NULL; a non-NULL rowmap with rowmap_cap below rows is
+ * HIMG_ERR_CAPACITY and nothing is decoded.  *concealed = -1 on every failure. */
+int himg_hip_decode_conceal_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, uint8_t *dst,
+                               size_t dst_cap, int *width, int *height, int *channels, uint8_t *rowmap,
+                               size_t rowmap_cap, int *concealed);
+
 /* ---- row-sharded encode of ONE frame over several GPUs -------------------- */
 /*
  * FRES block rows are independently coded units behind size headers
