@@ -157,6 +157,25 @@ void himg_hip_host_free(void *p);
 
 /* ---- device-resident batched API (roofline measurements, pipelines) ----- */
 
+/* Streams.  Every entry point of this section and of the device forms below takes the caller's
+ * `stream` and is asynchronous: it queues its work and returns; nothing is synchronised with the host
+ * (the exceptions: a context's first call at a larger geometry, which reserves workspace; the first call
+ * of the per-quality encode section; and, since four pinned slots carry the host arrays to the device, a
+ * call whose slot is still waiting for its copy four calls back waits for that copy -- not for the
+ * kernels behind it).  All of a call's work is ordered on `stream`: it starts
+ * behind what the stream held at the call and is complete for whatever the caller queues on the stream
+ * afterwards -- the context's own side streams are forked from `stream` and joined back into it before
+ * the call returns.  HOST arrays (h_sizes, h_origins, h_quality, ...) are copied before the call
+ * returns; the caller may reuse them at once.
+ * A context's calls are ordered by the caller's stream ALONE.  The context keeps one workspace and one
+ * set of staging buffers for all its calls, so consecutive calls on one stream need no wait between them,
+ * and a caller who moves a context from one stream to another orders the two: the new stream waits
+ * (hipStreamWaitEvent) for an event recorded on the old one behind the context's last call there, or the
+ * host waits for that call.  Calls of one context on two streams without such an order race on the
+ * workspace.  Distinct contexts share nothing and may run on distinct streams at the same time.
+ * The legacy null stream (stream = NULL) is a stream like any other here; a non-blocking stream is not
+ * synchronised with it, and no call queues anything on it on the caller's behalf. */
+
 /* Encode `batch` frames that already live in HBM.
  *   d_frames : device pointer, batch * height*width*pixel_stride bytes
  *   d_out    : device pointer, batch * out_stride bytes (out_stride a multiple
