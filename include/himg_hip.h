@@ -179,7 +179,15 @@ void himg_hip_host_free(void *p);
 /* Encode `batch` frames that already live in HBM.
  *   d_frames : device pointer, batch * height*width*pixel_stride bytes
  *   d_out    : device pointer, batch * out_stride bytes (out_stride a multiple
- *              of 256 and >= himg_hip_max_packed_size)
+ *              of 256 and >= himg_hip_max_packed_size).  Stream f is the first
+ *              d_sizes[f] bytes of slot f (d_out + f * out_stride); the slot's
+ *              other bytes are unspecified up to offset
+ *              620 + C * (rows * cols + ceil(rows/16) * ceil(cols/16)), rounded
+ *              up to 4, rows = ceil(H/8), cols = ceil(W/8) -- the encoder clears
+ *              the worst-case extent of the low-res chunk in every slot before
+ *              it packs, so a shorter stream is followed by zeros -- and
+ *              are not written from there on when the frame succeeds.  Every
+ *              encode entry point with a d_out obeys this.
  *   d_sizes  : device pointer, batch x uint32 packed sizes (0 on failure)
  *   d_status : device pointer, batch x int32 (HIMG_OK or an error code)
  *   stream   : hipStream_t (NULL = default stream).  Asynchronous: nothing is
