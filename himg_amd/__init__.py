@@ -147,6 +147,9 @@ def lib():
     L.himg_hip_prefix_peek.argtypes = [vp, sz, i32, vp]
     L.himg_hip_decode_prefix_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32), P(i32)]
     L.himg_hip_decode_prefix_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
+    L.himg_hip_prefix_peek_from.argtypes = [vp, sz, i32, vp, vp]
+    L.himg_hip_decode_prefix_more_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.himg_hip_decode_prefix_more_to.argtypes = [vp, vp, sz, vp, vp, sz, P(i32), P(i32), P(i32), P(i32)]
     L.himg_hip_decode_conceal_to.argtypes = [vp, vp, sz, vp, sz, P(i32), P(i32), P(i32), vp, sz, P(i32)]
     L.himg_hip_decode_conceal_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.himg_hip_create_multi.argtypes = [vp, i32, P(vp)]
@@ -525,6 +528,41 @@ class Engine:
                                                  height, channels, _ptr(d_out), _ptr(d_rows), _ptr(d_status),
                                                  C.c_void_p(stream))
         self._check(rc, "decode_prefix_device")
+
+    def decode_prefix_more(self, prefix, state, out=None):
+        """himg_hip_decode_prefix_more_to: decode_prefix continued.  `state`: one element of
+        prefix_states() (or a PrefixState), zeroed for the first call and kept with `out`, the (H, W, C)
+        picture of the calls before; both are updated in place.  Only the block rows that became whole
+        since the state's last call are decoded, uploaded for and copied back.  Returns (picture,
+        rows_complete).  A first call may leave `out` None: the picture it returns is the one to pass on.
+        Raises HimgError, the state unchanged."""
+        prefix = _as_u8(prefix)
+        st = state if isinstance(state, PrefixState) else PrefixState.from_buffer(_state_view(state))
+        w, h, c, k = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        plan = PrefixPlan()
+        lib().himg_hip_prefix_peek(prefix.ctypes.data, prefix.nbytes, 0, C.byref(plan))
+        if plan.num_channels:
+            cap = plan.width * plan.height * plan.num_channels
+            if st.started and (out is None or out.nbytes != cap or out.dtype != np.uint8 or not out.flags["C_CONTIGUOUS"]):
+                raise ValueError("decode_prefix_more: a started state needs its picture, %d contiguous bytes" % cap)
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
+        rc = lib().himg_hip_decode_prefix_more_to(self._ctx, prefix.ctypes.data, prefix.nbytes, C.addressof(st), dst, cap,
+                                                  C.byref(w), C.byref(h), C.byref(c), C.byref(k))
+        self._check(rc, "decode_prefix_more")
+        return out.ravel()[: h.value * w.value * c.value].reshape(h.value, w.value, c.value), k.value
+
+    def decode_prefix_more_device(self, d_packed, in_stride, h_avail, batch, width, height, channels, d_state, d_out,
+                                  d_rows, d_status, stream=0):
+        """himg_hip_decode_prefix_more_device: decode_prefix_device continued from d_state -- batch
+        16-byte states in device memory (prefix_states(batch) uploaded), read and advanced on the
+        device: only the block rows that became whole since a frame's last call are decoded and written."""
+        ha = np.ascontiguousarray(h_avail, np.uint32)
+        rc = lib().himg_hip_decode_prefix_more_device(self._ctx, _ptr(d_packed), in_stride, ha.ctypes.data, batch, width,
+                                                      height, channels, _ptr(d_state), _ptr(d_out), _ptr(d_rows),
+                                                      _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_prefix_more_device")
 
     def decode_conceal(self, packed, out=None):
         """himg_hip_decode_conceal_to: the decode of a stream that may be damaged.  Returns (picture,
@@ -1327,6 +1365,47 @@ def prefix_peek(packed, avail=None, fix_t2=False):
     d = {k: getattr(plan, k) for k, _ in PrefixPlan._fields_}
     if rc != 0:
         e = HimgError(rc, "prefix_peek")
+        e.plan = d
+        raise e
+    return d
+
+
+class PrefixState(C.Structure):
+    """himg_hip_prefix_state."""
+    _fields_ = [("started", C.c_uint32), ("rows_done", C.c_int32), ("walk_pos", C.c_uint32),
+                ("avail_seen", C.c_uint32)]
+
+
+PREFIX_STATE_DTYPE = np.dtype([("started", "<u4"), ("rows_done", "<i4"), ("walk_pos", "<u4"), ("avail_seen", "<u4")])
+
+
+def prefix_states(n):
+    """n fresh himg_hip_prefix_state as a zeroed structured array (16 bytes each): upload its bytes for
+    decode_prefix_more_device, or pass a one-element slice of it to decode_prefix_more / prefix_peek_from."""
+    return np.zeros(int(n), PREFIX_STATE_DTYPE)
+
+
+def _state_view(state):
+    if not (isinstance(state, np.ndarray) and state.dtype == PREFIX_STATE_DTYPE and state.size == 1
+            and state.flags["C_CONTIGUOUS"] and state.flags["WRITEABLE"]):
+        raise TypeError("a prefix state is a PrefixState or a one-element slice of prefix_states()")
+    return state
+
+
+def prefix_peek_from(packed, state, avail=None, fix_t2=False):
+    """himg_hip_prefix_peek_from (no GPU): prefix_peek's dict, reached by resuming the row walk at `state`
+    (a PrefixState or a one-element slice of prefix_states(); not changed).  Raises HimgError as
+    prefix_peek does, and with HIMG_ERR_ARG for a state that cannot belong to these bytes."""
+    a = _as_u8(packed)
+    avail = a.nbytes if avail is None else int(avail)
+    if not 0 <= avail <= a.nbytes:
+        raise ValueError("prefix_peek_from: avail = %d, but `packed` holds %d bytes" % (avail, a.nbytes))
+    st = state if isinstance(state, PrefixState) else PrefixState.from_buffer(_state_view(state))
+    plan = PrefixPlan()
+    rc = lib().himg_hip_prefix_peek_from(a.ctypes.data, avail, 1 if fix_t2 else 0, C.addressof(st), C.byref(plan))
+    d = {k: getattr(plan, k) for k, _ in PrefixPlan._fields_}
+    if rc != 0:
+        e = HimgError(rc, "prefix_peek_from")
         e.plan = d
         raise e
     return d

@@ -450,6 +450,15 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
 void launch_prefix(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
                    uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
                    Profiler *prof, const DecStreams *ds);
+// The prefix decode continued (include/himg_hip.h, himg_hip_decode_prefix_more_device): d_state holds a
+// PfxState (prefix_walk.h) per frame, read and -- for a frame without a verdict -- advanced on the device.
+// A fresh state's frame is launch_prefix's; of a resumed one only block rows [rows_done, k_new) are walked,
+// counted, decoded and stored, and nothing else of its picture is written.  d_words: 8 x batch words, the
+// first batch staged by the caller.  launch_prefix's workspace and streams.
+struct PfxState;
+void launch_prefix_more(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                        uint32_t *d_words, PfxState *d_state, uint8_t *d_out, int32_t *d_rows, int32_t *d_status,
+                        hipStream_t stream, Profiler *prof, const DecStreams *ds);
 // The concealing decode (include/himg_hip.h): launch_decode as himg_hip_decode_device calls it, into d_out, then
 // the repair pass over the frames it rejected in their FRES rows alone (kernels_dec.hip, k_conceal_gate ..
 // k_conceal_status), on the caller's stream with no host wait.  d_words: 4 x batch words, the first batch --

@@ -648,7 +648,7 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind 
       !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (region || himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
       !ctx->d_rows.reserve((size_t)batch * g.rows * 4 * 2) || !ctx->d_lres.reserve(lres * batch) ||
       (!region && !ctx->d_fres.reserve(fres * batch)) || !ctx->d_planes.reserve(plane * batch) ||
-      !ctx->d_sizes.reserve((size_t)batch * 20) ||
+      !ctx->d_sizes.reserve((size_t)batch * 32) ||   // (launch_prefix_more's eight words per frame are the most)
       !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4 + (size_t)batch * g.rows * 8) * 4))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
   w.frames = (DecFrame *)ctx->d_frames.p;
@@ -2183,10 +2183,15 @@ extern "C" int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, 
 // ---------------------------------------------------------------------------
 static uint32_t prefix_avail32(size_t avail) { return avail > 0x80000000u ? 0x80000000u : (uint32_t)avail; }
 
-extern "C" int himg_hip_prefix_peek(const uint8_t *packed, size_t avail, int fix_t2, himg_hip_prefix_plan *plan) {
-  if (!plan || (!packed && avail)) return HIMG_ERR_ARG;
+static_assert(sizeof(himg_hip_prefix_state) == 16 && sizeof(himg_dev::PfxState) == 16, "the state is four words");
+
+// himg_hip_prefix_peek; `state` given and started: the row walk resumes there (himg_hip_prefix_peek_from).
+static int prefix_peek_impl(const uint8_t *packed, size_t avail, int fix_t2, const himg_hip_prefix_state *state,
+                            himg_hip_prefix_plan *plan) {
   *plan = himg_hip_prefix_plan();
   const uint32_t av = prefix_avail32(avail);
+  const bool resume = state && state->started;
+  if (resume && av < state->avail_seen) return HIMG_ERR_ARG;
   himg_dev::PfxHead h;
   int rc = himg_dev::pfx_chain(packed, av, fix_t2, 0, &h);
   plan->packed_size = h.T;
@@ -2210,12 +2215,29 @@ extern "C" int himg_hip_prefix_peek(const uint8_t *packed, size_t avail, int fix
   }
   if (rc == himg_dev::kPfxShort) return HIMG_ERR_CAPACITY;
   himg_dev::PfxRows pr;
-  if (himg_dev::pfx_rows(packed, av, h.T, fix_t2, plan->rows, q, end, nullptr, nullptr, &pr) != himg_dev::kPfxOk)
-    return HIMG_ERR_FORMAT;
+  if (resume) {
+    const himg_dev::PfxState s = {state->started, state->rows_done, state->walk_pos, state->avail_seen};
+    if (!himg_dev::pfx_state_ok(s, av, plan->rows, q, end)) return *plan = himg_hip_prefix_plan(), HIMG_ERR_ARG;
+    rc = himg_dev::pfx_rows_from(packed, av, h.T, fix_t2, plan->rows, s.walk_pos, s.rows_done, end, nullptr, nullptr, &pr);
+  } else {
+    rc = himg_dev::pfx_rows(packed, av, h.T, fix_t2, plan->rows, q, end, nullptr, nullptr, &pr);
+  }
+  if (rc != himg_dev::kPfxOk) return HIMG_ERR_FORMAT;
   plan->rows_complete = pr.k;
   plan->used_bytes = pr.used;
   plan->next_bytes = pr.next;
   return HIMG_OK;
+}
+
+extern "C" int himg_hip_prefix_peek(const uint8_t *packed, size_t avail, int fix_t2, himg_hip_prefix_plan *plan) {
+  if (!plan || (!packed && avail)) return HIMG_ERR_ARG;
+  return prefix_peek_impl(packed, avail, fix_t2, nullptr, plan);
+}
+
+extern "C" int himg_hip_prefix_peek_from(const uint8_t *packed, size_t avail, int fix_t2,
+                                         const himg_hip_prefix_state *state, himg_hip_prefix_plan *plan) {
+  if (!plan || !state || (!packed && avail)) return HIMG_ERR_ARG;
+  return prefix_peek_impl(packed, avail, fix_t2, state, plan);
 }
 
 extern "C" int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
@@ -2272,6 +2294,89 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
   *width = W; *height = H; *channels = C; *rows_complete = st[1];
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+// The prefix decode continued from the rows a caller's picture already holds (kernels_dec.hip,
+// launch_prefix_more): the states are read, judged and advanced on the device.
+extern "C" int himg_hip_decode_prefix_more_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                  const uint32_t *h_avail, int batch, int width, int height,
+                                                  int num_channels, himg_hip_prefix_state *d_state, void *d_out,
+                                                  int32_t *d_rows, int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_avail || !d_state || !d_out || !d_rows || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  if ((uintptr_t)d_state & 15) return fail(ctx, HIMG_ERR_ARG, "the states must be 16-byte aligned");
+  if (int rc = stride_covers(ctx, h_avail, batch, in_stride)) return rc;
+  Geom g;
+  const uint32_t *d_sizes = nullptr;
+  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, nullptr, &g))
+    return rc;
+  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_avail, stream, &d_sizes)) return rc;
+  launch_prefix_more(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p,
+                     (himg_dev::PfxState *)d_state, (uint8_t *)d_out, d_rows, d_status, (hipStream_t)stream, &ctx->prof,
+                     ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_prefix_more_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail,
+                                              himg_hip_prefix_state *state, uint8_t *dst, size_t dst_cap, int *width,
+                                              int *height, int *channels, int *rows_complete) {
+  if (!ctx || (!packed && avail) || !state || !width || !height || !channels || !rows_complete) return HIMG_ERR_ARG;
+  *rows_complete = -1;
+  // The host's own walk says what to upload; every verdict on the stream is the device's (decode_prefix_to).
+  const uint32_t av = prefix_avail32(avail);
+  himg_hip_prefix_plan plan;
+  const int pc = prefix_peek_impl(packed, av, ctx->fix_t2, state, &plan);
+  if (pc == HIMG_ERR_ARG) return fail(ctx, HIMG_ERR_ARG, "the state does not belong to this prefix");
+  if (pc == HIMG_ERR_UNSUPPORTED) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
+  if (!plan.num_channels) {   // FRMT has not arrived, or the walk failed before it
+    if (pc == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, "the prefix ends before the first block row");
+    return fail(ctx, HIMG_ERR_FORMAT, plan.packed_size ? "Error decoding header.\n" : "Not a RIFF HIMG file.\n");
+  }
+  const int W = plan.width, H = plan.height, C = plan.num_channels;
+  const size_t row_bytes = (size_t)W * C, out_bytes = (size_t)H * row_bytes;
+  *width = W; *height = H; *channels = C;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_cap = round_up((size_t)av + 16, 256);
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  ctx->host_bytes = 0;   // (nothing stays resident: no fetch_last behind this call)
+  // A resumed state the host's walk accepts: the head and the bytes from the walk's position on, each at its
+  // offset (the bytes between them are the rows already decoded: nothing reads them).
+  const bool partial = state->started && pc == HIMG_OK;
+  uint8_t *d_in = (uint8_t *)ctx->h_in.p;
+  if (partial) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
+    if (av > state->walk_pos)
+      HIP_TRY(ctx, hipMemcpyAsync(d_in + state->walk_pos, packed + state->walk_pos, av - state->walk_pos,
+                                  hipMemcpyHostToDevice, nullptr));
+  } else if (int rc = upload_zero_tail(ctx, d_in, in_cap, packed, av)) {
+    return rc;
+  }
+  // h_status: the status word, k, then the state at byte 16.
+  int32_t *d_st = (int32_t *)ctx->h_status.p;
+  himg_hip_prefix_state *d_state = (himg_hip_prefix_state *)((uint8_t *)ctx->h_status.p + 16);
+  HIP_TRY(ctx, hipMemcpyAsync(d_state, state, sizeof(*state), hipMemcpyHostToDevice, nullptr));
+  if (int rc = himg_hip_decode_prefix_more_device(ctx, d_in, in_cap, &av, 1, W, H, C, d_state, ctx->h_out.p, d_st + 1, d_st,
+                                                  nullptr)) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still be reading the caller's buffers
+    return rc;
+  }
+  struct { int32_t st, k, pad[2]; himg_hip_prefix_state s; } back;
+  HIP_TRY(ctx, hipMemcpy(&back, d_st, sizeof(back), hipMemcpyDeviceToHost));
+  if (back.st) return status_error(ctx, back.st, status_to_code(back.st) == HIMG_ERR_ARG
+                                                     ? "the state does not belong to this prefix"
+                                                     : "the prefix ends before the first block row");
+  // A fresh state: the whole picture; else the pixel rows of block rows [k_prev, k_new) alone.
+  const size_t y0 = state->started ? 8 * (size_t)state->rows_done : 0;
+  const size_t y1 = state->started ? (8 * (size_t)back.k < (size_t)H ? 8 * (size_t)back.k : (size_t)H) : (size_t)H;
+  if (y1 > y0)
+    HIP_TRY(ctx, hipMemcpy(dst + y0 * row_bytes, (const uint8_t *)ctx->h_out.p + y0 * row_bytes, (y1 - y0) * row_bytes,
+                           hipMemcpyDeviceToHost));
+  *state = back.s;
+  *rows_complete = back.k;
   return HIMG_OK;
 }
 

@@ -4820,6 +4820,147 @@ __global__ void k_prefix_status(DecWs ws, const int32_t *gate, const int32_t *kr
 }
 
 // ---------------------------------------------------------------------------
+// The prefix decode CONTINUED (include/himg_hip.h, himg_hip_decode_prefix_more_device): frame f comes with
+// a PfxState in device memory.  A fresh state (started == 0) makes the frame the prefix decode's, to the
+// byte.  Otherwise block rows [0, k_prev) are in the caller's picture already: the head runs as it always
+// does (the workspace keeps nothing between calls), the header walk resumes where the state says, and only
+// rows [k_prev, k_new) are counted, decoded and stored.  The kernels stand beside the prefix decode's:
+//   k_prefix_gate      as it is.
+//   k_more_gate        (a lane per frame, behind it) the state against the gate's results, every field
+//                      before anything uses it.  A state that cannot be right: the verdict kStGeom -- the
+//                      word the host maps to HIMG_ERR_ARG -- and the frame is closed as the gate closes one
+//                      below its head (size 0 to every reader).  kprev[f] = k_prev (0 for a fresh frame),
+//                      krows[f] = k_prev until the walk says more, DecFrame::walk_q = where the walk resumes,
+//                      kfill[f] = what k_prefix_fill takes for k_f: `rows` for a resumed frame, whose
+//                      missing rows the caller's picture already holds, so that the fill skips it whole.
+//   k_more_rowwalk     pfx_rows_from: the row index of rows [k_prev, k_new), k_new, the walk's position.
+//   k_prefix_fill      as it is, over kfill: fresh frames only.
+//   k_more_count(_w)   k_row_count<false> / k_row_count_w over rows [k_prev, k_new).
+//   k_dec_more         k_dec_region's body over the window (0, 8 k_prev, W, min(8 k_new, H) - 8 k_prev),
+//                      placed at its rows of the full picture.
+//   k_more_status      the verdicts, k_new, and the states of the frames without a verdict.
+// ---------------------------------------------------------------------------
+struct MoreWords {        // per-frame words of one launch (launch_prefix_more carves them)
+  const uint32_t *avail;  // the bytes present, as the caller staged them
+  uint32_t *tx, *bound;   // k_prefix_gate's: the declared size, the load bound
+  int32_t *krows, *gate;  // k_new; the gate's verdict
+  int32_t *kprev, *kfill;
+  uint32_t *pos;          // PfxRows::used of this call's walk
+};
+
+__global__ __launch_bounds__(64) void k_more_gate(Geom g, DecWs ws, const PfxState *state, MoreWords w, int batch) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  DecFrame *df = ws.frames + f;
+  const uint4 raw = *reinterpret_cast<const uint4 *>(state + f);
+  PfxState s;
+  s.started = raw.x; s.rows_done = (int32_t)raw.y; s.walk_pos = raw.z; s.avail_seen = raw.w;
+  w.kprev[f] = 0;
+  w.kfill[f] = 0;
+  w.pos[f] = 0;
+  if (!s.started) return;   // the prefix decode's frame
+  const uint32_t avail = w.avail[f];
+  const uint32_t q = df->walk_q;   // 0: the gate's verdict, or the parse's -- that one stands
+  bool bad = avail < s.avail_seen;
+  if (!bad && w.gate[f] == 0 && q != 0) bad = !pfx_state_ok(s, avail, g.rows, q, df->walk_end);
+  w.kfill[f] = g.rows;
+  if (bad) {
+    w.gate[f] = kStGeom;
+    w.tx[f] = 0; w.bound[f] = 0;
+    df->walk_status = 0; df->rows_first = 0; df->walk_q = 0;
+    return;
+  }
+  if (q == 0) return;
+  w.kprev[f] = s.rows_done;
+  w.krows[f] = s.rows_done;
+  w.pos[f] = s.walk_pos;
+  df->walk_q = s.walk_pos;
+}
+
+__global__ __launch_bounds__(64) void k_more_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                     MoreWords w, int batch) {
+  const int f = blockIdx.x * 64 + threadIdx.x;
+  if (f >= batch) return;
+  DecFrame *df = ws.frames + f;
+  const uint32_t q = df->walk_q;
+  if (q == 0) return;   // no rows to walk: a verdict of the gates, or the parse's
+  df->walk_q = 0;
+  PfxRows pr;
+  const int rc = pfx_rows_from(packed + (size_t)f * in_stride, w.bound[f], w.tx[f], g.fix_t2, g.rows, q, w.kprev[f],
+                               df->walk_end, ws.row_off + (size_t)f * g.rows, ws.row_len + (size_t)f * g.rows, &pr);
+  if (rc == kPfxFormat) { df->walk_status = fmt_err(7, 1); return; }
+  w.krows[f] = pr.k;
+  w.pos[f] = pr.used;
+  if (w.kfill[f] != g.rows) w.kfill[f] = pr.k;   // (a fresh frame: the fill's k_f is the walk's)
+}
+
+// k_row_count<false> over rows [k_prev, k_new) (rows_per_wg of them per workgroup).
+__global__ __launch_bounds__(kDecThreads, 8) void k_more_count(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                              const uint32_t *sizes, const int32_t *kprev,
+                                                              const int32_t *krows, int rows_per_wg) {
+  constexpr bool LDSPAY = false;
+  const int r0 = kprev[blockIdx.y], r1 = krows[blockIdx.y];
+  if (r0 + (int)blockIdx.x * rows_per_wg >= r1) return;
+#include "dec_body_row_count.inc"
+}
+
+// k_row_count_w over rows [k_prev, k_new).
+__global__ __launch_bounds__(kDecThreads, 8) void k_more_count_w(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                const int32_t *kprev, const int32_t *krows) {
+  const int r0 = kprev[blockIdx.y], r1 = krows[blockIdx.y];
+  if (r0 + (int)blockIdx.x * kCountRowsW >= r1) return;
+  constexpr int NQ = 1;   // a sub-sequence per lane
+#include "dec_body_row_count_w.inc"
+}
+
+struct MoreArgs {
+  const int32_t *kprev, *krows;   // [f] k_prev, k_new
+  int sw;                         // tiles per column strip (blockIdx.x = strip)
+  uint8_t *out;
+};
+struct MoreOrigin {       // every window starts at (0, y)
+  int y;
+  __device__ __forceinline__ int operator[](int i) const { return (i & 1) ? y : 0; }
+};
+struct MoreWindow {       // what the body reads of a RegionArgs
+  MoreOrigin org;
+  int sw, w, h;
+  uint8_t *out;           // (the body adds f * h * w * C)
+};
+__global__ __launch_bounds__(kDecThreads) void k_dec_more(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                         const uint32_t *sizes, MoreArgs ma) {
+  constexpr bool kRegionTens = false, kRegionPitch = false;
+  constexpr bool kRegionConceal = false;
+  uint8_t *const cmap = nullptr;
+  const TensK td = nullptr;
+  const DstK pd = nullptr;
+  const int k0 = ma.kprev[blockIdx.z], k1 = ma.krows[blockIdx.z];
+  if ((int)blockIdx.y >= k1 - k0) return;
+  MoreWindow ra;
+  ra.org.y = 8 * k0;
+  ra.sw = ma.sw; ra.w = g.W; ra.h = (8 * k1 < g.H ? 8 * k1 : g.H) - 8 * k0;
+  // k_dec_prefix's placement -- the body adds f * ra.h * ra.w * C, the rest of the full picture's stride is
+  // added here -- then down to the window's first pixel row.
+  ra.out = ma.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C) + (size_t)(8 * k0) * ((size_t)g.W * g.C);
+#include "dec_body_region.inc"
+}
+
+// k_prefix_status's verdicts; a frame without one hands its state on: {1, k_new, the walk's position, avail}.
+__global__ void k_more_status(DecWs ws, MoreWords w, PfxState *state, int32_t *status, int32_t *rows_out, int batch) {
+  const int f = blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= batch) return;
+  const DecFrame *df = ws.frames + f;
+  const int ws_ = df->parse_status == 0 ? df->walk_status : 0;
+  int st = df->status > ws_ ? df->status : ws_;
+  if (w.gate[f]) st = w.gate[f];
+  status[f] = st;
+  rows_out[f] = st ? -1 : w.krows[f];
+  if (!st)
+    *reinterpret_cast<uint4 *>(state + f) = make_uint4(1u, (uint32_t)w.krows[f], w.pos[f], w.avail[f]);
+}
+
+// ---------------------------------------------------------------------------
 // The CONCEALING decode (include/himg_hip.h): the full decode as it is, then a repair pass over the
 // frames it rejected in their FRES rows alone.  Of such a frame the rows the header walk delimits,
 // [0, k_f), are judged one by one -- an accepted row is the full decode's, a rejected one is stored as a
@@ -5513,7 +5654,7 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
       {HIMG_K(k_row_window), kRowWindowLds},
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
-      {HIMG_K(k_dec_prefix), 0},           {HIMG_K(k_dec_conceal), 0},
+      {HIMG_K(k_dec_prefix), 0},           {HIMG_K(k_dec_conceal), 0},          {HIMG_K(k_dec_more), 0},
       {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
       {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
 #undef HIMG_K
@@ -5764,6 +5905,56 @@ void launch_prefix(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
                      ws, d_packed, in_stride, d_bound, pa);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_prefix_status, dim3((batch + 63) / 64), dim3(64), ws, d_gate, d_k, d_status, d_rows, batch);
+}
+
+// The prefix decode continued.  d_words: 8 x batch words -- launch_prefix's five, then k_prev, the fill's
+// k_f and the walk's position.  launch_prefix's order, each kernel's incremental form in its place; k_new
+// is known on the device alone, so the grids cover all rows here too.
+void launch_prefix_more(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                        uint32_t *d_words, PfxState *d_state, uint8_t *d_out, int32_t *d_rows, int32_t *d_status,
+                        hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region)
+  const size_t n = (size_t)batch;
+  MoreWords w;
+  w.avail = d_words; w.tx = d_words + n; w.bound = d_words + 2 * n;
+  w.krows = (int32_t *)(d_words + 3 * n); w.gate = (int32_t *)(d_words + 4 * n);
+  w.kprev = (int32_t *)(d_words + 5 * n); w.kfill = (int32_t *)(d_words + 6 * n);
+  w.pos = d_words + 7 * n;
+  const dim3 per_frame((batch + 63) / 64), b64(64);
+  launch_zero(g, ws, batch, stream, prof);
+  HIMG_LAUNCH(k_prefix_gate, dim3(batch), b64, g, ws, d_packed, in_stride, w.avail, w.tx, w.bound, w.krows, w.gate);
+  HIMG_LAUNCH(k_more_gate, per_frame, b64, g, ws, d_state, w, batch);
+  hipStream_t ws_ = ds ? ds->side : stream;
+  if (ds) {
+    (void)hipEventRecord(ds->ev_fork, stream);
+    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
+  }
+  prof_begin(prof, "k_more_rowwalk", ws_);
+  hipLaunchKernelGGL(k_more_rowwalk, per_frame, b64, 0, ws_, g, ws, d_packed, in_stride, w, batch);
+  prof_end(prof, ws_);
+  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
+  HIMG_LAUNCH(k_dec_parse_prefix, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, w.tx, w.bound);
+  launch_lres_chain(g, ws, batch, d_packed, in_stride, w.bound, stream, prof);
+  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
+  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, w.kfill, d_out);
+  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
+  if (cr.wave) {
+    HIMG_LAUNCH(k_more_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
+                d_packed, in_stride, w.bound, w.kprev, w.krows);
+  } else {
+    HIMG_LAUNCH(k_more_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
+                in_stride, w.bound, w.kprev, w.krows, cr.rpc);
+  }
+  const int smax = region_strip_tiles(g);
+  const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
+  MoreArgs ma;
+  ma.kprev = w.kprev; ma.krows = w.krows; ma.sw = sw; ma.out = d_out;
+  prof_begin(prof, "k_dec_more", stream);
+  hipLaunchKernelGGL(k_dec_more, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
+                     ws, d_packed, in_stride, w.bound, ma);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_more_status, per_frame, b64, ws, w, d_state, d_status, d_rows, batch);
 }
 
 // The concealing decode.  d_words: 4 x batch words -- the packed sizes (staged by the caller), then the full

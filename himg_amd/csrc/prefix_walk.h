@@ -158,5 +158,68 @@ __host__ __device__ inline int pfx_rows(const uint8_t *p, uint32_t avail, uint32
   return kPfxOk;
 }
 
+// The state a caller keeps between the calls of the incremental prefix decode (himg_hip_prefix_state of
+// include/himg_hip.h, field for field).
+struct PfxState {
+  uint32_t started;      // 0: a fresh state
+  int32_t rows_done;     // k: block rows [0, k) are in the caller's picture
+  uint32_t walk_pos;     // PfxRows::used of the walk that found k
+  uint32_t avail_seen;   // the bytes present then
+};
+
+// Can `s` (started != 0) be the state a call at fewer or as many bytes left on this stream?  q: the first
+// row header, end: the chunk's end (pfx_chain, pfx_tree_len).  Every field is judged before a load uses it.
+__host__ __device__ inline bool pfx_state_ok(const PfxState &s, uint32_t avail, int rows, uint32_t q, uint32_t end) {
+  return avail >= s.avail_seen && s.rows_done >= 0 && s.rows_done <= rows && s.walk_pos >= q && s.walk_pos <= end &&
+         s.walk_pos <= avail;
+}
+
+// pfx_rows resumed: the walk stands at `q` = PfxRows::used of an earlier walk over fewer (or as many) bytes
+// of the same stream, which found r0 complete rows.  Same rules, same result as pfx_rows from the first
+// header; row_off / row_len are written for rows [r0, k) only.  (A copy of the loop, not a call from
+// pfx_rows: that one keeps its code.)  Where the chunk holds blocks behind the last block row, `used`
+// stays at the last row's end and their headers are walked again by every call.
+__host__ __device__ inline int pfx_rows_from(const uint8_t *p, uint32_t avail, uint32_t T, int fix_t2, int rows,
+                                             uint32_t q, int r0, uint32_t end, uint32_t *row_off, uint32_t *row_len,
+                                             PfxRows *out) {
+  out->k = r0; out->used = q; out->next = T;
+  if (fix_t2 && rows == 1) {   // one block row without a size header
+    if (r0 == 0) {
+      if (end <= avail) {
+        out->k = 1; out->used = end;
+        if (row_off) { row_off[0] = q; row_len[0] = end - q; }
+      } else {
+        out->next = end;
+      }
+    }
+    return kPfxOk;
+  }
+  int r = r0;
+  bool cut = false;
+  while (q != end) {
+    if (q + 2 > end) return kPfxFormat;
+    if (q + 2 > avail) { cut = true; out->next = q + 2; break; }
+    uint32_t len = (uint32_t)p[q] | ((uint32_t)p[q + 1] << 8), b = q + 2;
+    if (len & 0x8000u) {
+      if (b + 2 > end) return kPfxFormat;
+      if (b + 2 > avail) { cut = true; out->next = b + 2; break; }
+      len = (len & 0x7fffu) | (((uint32_t)p[b] | ((uint32_t)p[b + 1] << 8)) << 15);
+      b += 2;
+    }
+    if (len > end - b) return kPfxFormat;
+    if (b + len > avail) { cut = true; out->next = b + len; break; }
+    if (r < rows) {
+      if (row_off) { row_off[r] = b; row_len[r] = len; }
+      out->used = b + len;
+    }
+    ++r;
+    q = b + len;
+  }
+  if (!cut && r < rows) return kPfxFormat;   // fewer blocks than block rows
+  out->k = r < rows ? r : rows;
+  if (out->k == rows) out->next = T;
+  return kPfxOk;
+}
+
 }  // namespace himg_dev
 #endif  // HIMG_PREFIX_WALK_H_

@@ -845,8 +845,7 @@ int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t 
  * the full decode.
  *
  * Not in this change: a host batch entry; scaled, tensor and pitched forms; himg::Decoder; the
- * multi-GPU handle; an incremental "continue from row k" call -- a caller who keeps the picture decodes
- * the newly complete rows with the region decode.
+ * multi-GPU handle.
  */
 typedef struct himg_hip_prefix_plan {
   int width, height, num_channels;   /* the frame's geometry (FRMT); 0 where FRMT has not arrived */
@@ -882,6 +881,82 @@ int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_
                                   const uint32_t *h_avail, int batch, int width, int height,
                                   int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
                                   void *stream);
+
+/* ---- continue a prefix decode: only the block rows that have become whole since the last call ---- */
+/*
+ * The prefix decode is stateless: every call decodes every complete row again.  A caller who keeps the
+ * picture while a stream arrives keeps one himg_hip_prefix_state per picture beside it and calls these
+ * entry points instead.
+ *
+ * The defining property.  For any chain of calls at a_0 <= a_1 <= ... <= a_n on one picture and one state,
+ * over a stream whose bytes below each a_i do not change, the picture, d_rows and d_status after the last
+ * call are byte for byte those of ONE himg_hip_decode_prefix_device call at a_n (a_n == T: those of
+ * himg_hip_decode_device).
+ *
+ * Per frame, with state s and a bytes present:
+ *   - s.started == 0 (a zeroed state is a fresh one): the call IS himg_hip_decode_prefix_device for that
+ *     frame -- the same verdict, d_rows and bytes, the whole picture written.  Without a verdict the state
+ *     becomes {1, k, the walk's position, a}.  Below head_bytes: HIMG_ERR_CAPACITY's status, the picture
+ *     is not written, the state stays zero.
+ *   - s.started != 0: the head -- RIFF .. the FRES tree and the whole LRES chain -- runs again with the
+ *     prefix decode's verdicts (the context keeps nothing between calls).  The header walk resumes at
+ *     s.walk_pos with row s.rows_done and finds k_new >= s.rows_done by the prefix decode's rules.  Only
+ *     block rows [s.rows_done, k_new) are entropy-decoded, with the same checks.  WRITTEN: pixel rows
+ *     8 s.rows_done .. min(8 k_new, H) - 1 of the frame's picture and NO OTHER BYTE of d_out: no fill, no
+ *     row below s.rows_done.  Rows from k_new on keep what the picture held -- the first call's fill.
+ *     d_rows[f] = k_new, d_status[f] = 0, the state advances.  No new bytes, or new bytes that complete no
+ *     row: nothing of the picture is written.
+ *   - A verdict in the new bytes (a header the walk rejects, fewer blocks than rows at the chunk's end, a
+ *     new row that fails its checks): the status word himg_hip_decode_prefix_device gives at a,
+ *     d_rows[f] = -1, the state is LEFT AS IT WAS (the call repeats with the same verdict).  Pixel rows
+ *     from 8 s.rows_done on are unspecified; those above are untouched.
+ *   - A state that cannot be right: HIMG_ERR_ARG's status word (1), nothing written, the state left as it
+ *     was.  The rules: a < s.avail_seen (judged first, before the head); then, where the head has passed,
+ *     rows_done outside [0, rows], walk_pos outside [head_bytes, the end of the FRES chunk], walk_pos > a.
+ *     The state is untrusted memory: every field is judged before anything is loaded through it, and the
+ *     prefix decode's bound on the bytes loaded holds.  (A state that passes these rules but belongs to
+ *     another stream gives that stream's verdicts or pixels, never a load or store out of bounds.)
+ *   - walk_pos is himg_hip_prefix_plan::used_bytes of the call that wrote the state.  Where a chunk holds
+ *     blocks behind its last block row, their headers are walked again by every call.
+ * One launch takes fresh, resumed, idle and below-head frames together.
+ *
+ * Where it loses: a single call from a fresh state is the prefix decode plus two small kernels, and the
+ * head (the parse and the LRES chain) is paid at every step.
+ *
+ * Not in this change: the command-line tools and himg::Decoder; a host batch form; scaled, tensor, pitched
+ * and concealing forms; the multi-GPU handle; keeping the head's products between calls; a cap on the rows
+ * decoded per call.
+ */
+typedef struct himg_hip_prefix_state {   /* 16 bytes; an array of them is 16-byte aligned */
+  uint32_t started;      /* 0: nothing decoded yet -- a zeroed state is a fresh one */
+  int32_t  rows_done;    /* k: block rows [0, k) of the caller's picture are the full decode's */
+  uint32_t walk_pos;     /* where the header walk stands: the first row header not yet passed (the end of
+                            the FRES chunk once it has been reached); equals used_bytes while k < rows */
+  uint32_t avail_seen;   /* the avail of the last call that advanced this state */
+} himg_hip_prefix_state;
+/* himg_hip_prefix_peek's result, reached by resuming the walk at *state (host only, no GPU; the chunk
+ * headers are checked as there; nothing at or beyond avail is read).  Its codes, plus HIMG_ERR_ARG for a
+ * state that cannot be right (the plan is zeroed then).  A fresh state: himg_hip_prefix_peek. */
+int himg_hip_prefix_peek_from(const uint8_t *packed, size_t avail, int fix_t2,
+                              const himg_hip_prefix_state *state, himg_hip_prefix_plan *plan);
+/* A batch in HBM: the layout, in_stride, h_avail, asynchrony and HIMG_OPT_FIX_T2 of
+ * himg_hip_decode_prefix_device.  d_state: `batch` states in DEVICE memory, 16-byte aligned, read and
+ * updated on the device -- no host round trip learns k, and two calls queued on one stream are ordered by
+ * the stream alone: the second consumes what the first wrote.  Bad arguments (a NULL or misaligned d_state,
+ * or what himg_hip_decode_prefix_device refuses): HIMG_ERR_ARG, nothing launched. */
+int himg_hip_decode_prefix_more_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                       const uint32_t *h_avail, int batch, int width, int height,
+                                       int num_channels, himg_hip_prefix_state *d_state, void *d_out,
+                                       int32_t *d_rows, int32_t *d_status, void *stream);
+/* One prefix in host memory; dst is the caller's full H x W x C picture, *state its state in host memory.
+ * A fresh state behaves as himg_hip_decode_prefix_to.  Otherwise only [0, head_bytes) and
+ * [state->walk_pos, avail) are uploaded, each at its offset, and only the pixel rows of block rows
+ * [k_prev, k_new) are copied back, into their place in dst.  A NULL or too-small dst: HIMG_ERR_CAPACITY
+ * with the geometry set, nothing decoded, the state unchanged.  *rows_complete = -1 and the state unchanged
+ * on every failure.  Nothing is kept resident: this entry point has NO himg_hip_fetch_last protocol. */
+int himg_hip_decode_prefix_more_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail,
+                                   himg_hip_prefix_state *state, uint8_t *dst, size_t dst_cap,
+                                   int *width, int *height, int *channels, int *rows_complete);
 
 /* ---- decode a damaged stream: rejected block rows concealed from the low-res plane ---- */
 /*
