@@ -1,7 +1,7 @@
 // The body of k_dec_region, of its tensor form k_dec_region_t and of its pitched form k_dec_region_p:
 // one copy, included behind each kernel's own parameters (g, ws, packed, in_stride, sizes, ra) with
 // kRegionTens and td, kRegionPitch and pd (the descriptors, or nullptr) defined, so that k_dec_region
-// keeps its code instruction for instruction.  kRegionConceal and cmap (k_dec_conceal; false and nullptr
+// keeps its code instruction for instruction.  kRegionConceal and cmap (k_dec_span<true>; false and unused
 // everywhere else): a row the checks reject is not the frame's verdict -- its byte cmap[f * rows + r] is
 // set and its tiles are stored as those of a row of zero symbols.
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -107,7 +107,7 @@
   uint8_t *img;
   if constexpr (kRegionTens) img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * (size_t)(td->co * tens_elem_size(td->dtype)));
   else if constexpr (kRegionPitch) img = dst_frame(ra.out, pd, f);
-  // (k_dec_prefix, whose ra.h differs from frame to frame, relies on this exact form: it adds the rest of the
+  // (k_dec_span, whose ra.h differs from frame to frame, relies on this exact form: it adds the rest of the
   // full picture's stride, f * (H - ra.h) * W * C, to ra.out beforehand)
   else img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * g.C);
   const int ycbcr = df->ycbcr;

@@ -441,27 +441,23 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    const DecStreams *ds,
                    const StoreForm &form = StoreForm());   // (scale_log2 = 0 only: kStoreTens, [batch][co][h][w]; kStorePitch, windows of the pictures)
 // The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
-// k_prefix_gate (the head of the stream with every load checked against the bytes present), the head
-// phase in its prefix form (k_dec_parse_prefix, the LRES chain bounded by the bytes present),
-// k_prefix_rowwalk beside it (ds given: on ds->side) -- the row index and k_f, the rows that are whole
-// --, k_prefix_fill for rows [k_f, rows), the count kernels and k_dec_region's body (k_dec_prefix) over
-// rows [0, k_f).  d_words: 5 x batch words, the first batch staged by the caller; d_rows: k_f, or -1
-// with a verdict.  The workspace of launch_region.
-void launch_prefix(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
-                   uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
-                   Profiler *prof, const DecStreams *ds);
-// The prefix decode continued (include/himg_hip.h, himg_hip_decode_prefix_more_device): d_state holds a
-// PfxState (prefix_walk.h) per frame, read and -- for a frame without a verdict -- advanced on the device.
-// A fresh state's frame is launch_prefix's; of a resumed one only block rows [rows_done, k_new) are walked,
-// counted, decoded and stored, and nothing else of its picture is written.  d_words: 8 x batch words, the
-// first batch staged by the caller.  launch_prefix's workspace and streams.
+// k_span_gate (the head of the stream with every load checked against the bytes present, then the frame's
+// state against what it found), the head phase in its prefix form (k_dec_parse_prefix, the LRES chain
+// bounded by the bytes present), k_span_rowwalk beside it (ds given: on ds->side) -- the row index and k_f,
+// the rows that are whole --, k_prefix_fill for rows [k_f, rows), the count kernels and k_dec_region's body
+// (k_dec_span) over the rows to decode.  d_state == nullptr: those are rows [0, k_f) of every frame.  Else
+// the prefix decode continued (himg_hip_decode_prefix_more_device): d_state holds a PfxState (prefix_walk.h)
+// per frame, read and -- for a frame without a verdict -- advanced on the device.  A fresh state's frame is
+// decoded as without states; of a resumed one only block rows [rows_done, k_new) are walked, counted, decoded
+// and stored, and nothing else of its picture is written.  d_words: 8 x batch words, the first batch staged
+// by the caller; d_rows: k_f, or -1 with a verdict.  The workspace of launch_region.
 struct PfxState;
-void launch_prefix_more(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
-                        uint32_t *d_words, PfxState *d_state, uint8_t *d_out, int32_t *d_rows, int32_t *d_status,
-                        hipStream_t stream, Profiler *prof, const DecStreams *ds);
+void launch_prefix(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                   uint32_t *d_words, PfxState *d_state /* may be null */, uint8_t *d_out, int32_t *d_rows,
+                   int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
 // The concealing decode (include/himg_hip.h): launch_decode as himg_hip_decode_device calls it, into d_out, then
 // the repair pass over the frames it rejected in their FRES rows alone (kernels_dec.hip, k_conceal_gate ..
-// k_conceal_status), on the caller's stream with no host wait.  d_words: 4 x batch words, the first batch --
+// k_conceal_status), on the caller's stream with no host wait.  d_words: 5 x batch words, the first batch --
 // the packed sizes -- staged by the caller; d_cmap: batch x rows bytes of scratch; d_rowmap may be nullptr.
 // The workspace of launch_decode (the repair pass writes plain per-lane records over the full decode's).
 void launch_conceal(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,

@@ -648,7 +648,7 @@ static int ensure_dec_ws(himg_hip_ctx *ctx, const Geom &g, int batch, DecWsKind 
       !ctx->d_lane.reserve((size_t)batch * g.rows * (2 * kDecThreads + himg_dev::kRecHdr + (region || himg_dev::dec_rows_fit_lds(g) ? 0 : 6 * kDecThreads)) * 4) ||
       !ctx->d_rows.reserve((size_t)batch * g.rows * 4 * 2) || !ctx->d_lres.reserve(lres * batch) ||
       (!region && !ctx->d_fres.reserve(fres * batch)) || !ctx->d_planes.reserve(plane * batch) ||
-      !ctx->d_sizes.reserve((size_t)batch * 32) ||   // (launch_prefix_more's eight words per frame are the most)
+      !ctx->d_sizes.reserve((size_t)batch * 32) ||   // (launch_prefix's eight words per frame are the most)
       !ctx->d_stats.reserve(((size_t)batch * (g.rows + 1) * 8 + (size_t)batch * 4 + (size_t)batch * g.rows * 8) * 4))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
   w.frames = (DecFrame *)ctx->d_frames.p;
@@ -2240,23 +2240,49 @@ extern "C" int himg_hip_prefix_peek_from(const uint8_t *packed, size_t avail, in
   return prefix_peek_impl(packed, avail, fix_t2, state, plan);
 }
 
-extern "C" int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
-                                             const uint32_t *h_avail, int batch, int width, int height,
-                                             int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
-                                             void *stream) {
-  if (!ctx || !d_packed || !h_avail || !d_out || !d_rows || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+// What the two device entry points of the prefix decode run behind their argument checks.  d_state: the
+// continued decode's states, or nullptr (kernels_dec.hip, launch_prefix).
+static int prefix_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_avail, int batch,
+                         int width, int height, int num_channels, himg_hip_prefix_state *d_state, void *d_out,
+                         int32_t *d_rows, int32_t *d_status, void *stream) {
   if (int rc = stride_covers(ctx, h_avail, batch, in_stride)) return rc;
   Geom g;
   const uint32_t *d_sizes = nullptr;
   if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, nullptr, &g))
     return rc;
-  // (the bytes present ride to the device as the packed sizes do: no wait; four more words per frame
+  // (the bytes present ride to the device as the packed sizes do: no wait; seven more words per frame
   // behind them are the walk's, himg_dev::launch_prefix)
   if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_avail, stream, &d_sizes)) return rc;
-  launch_prefix(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p, (uint8_t *)d_out,
-                d_rows, d_status, (hipStream_t)stream, &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  launch_prefix(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p,
+                (himg_dev::PfxState *)d_state, (uint8_t *)d_out, d_rows, d_status, (hipStream_t)stream, &ctx->prof,
+                ctx->opts.use_side ? &ctx->dstr : nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_avail, int batch, int width, int height,
+                                             int num_channels, void *d_out, int32_t *d_rows, int32_t *d_status,
+                                             void *stream) {
+  if (!ctx || !d_packed || !h_avail || !d_out || !d_rows || !d_status || batch < 1 || batch > 65535) return HIMG_ERR_ARG;
+  return prefix_launch(ctx, d_packed, in_stride, h_avail, batch, width, height, num_channels, nullptr, d_out, d_rows,
+                       d_status, stream);
+}
+
+// The one-stream host forms stage alike: h_in (in_cap bytes), h_out and h_status reserved, nothing resident,
+// and -- `packed` given -- its first n bytes up with a zeroed tail.
+static int stage_stream(himg_hip_ctx *ctx, size_t in_cap, size_t out_bytes, size_t status_bytes, const uint8_t *packed,
+                        size_t n) {
+  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(status_bytes))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  ctx->host_bytes = 0;   // (nothing stays resident until the call says so)
+  return packed ? upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, n) : HIMG_OK;
+}
+
+// A launch refused behind the uploads, which may still be reading the caller's buffers.
+static int launch_refused(int rc) {
+  (void)hipStreamSynchronize(nullptr);
+  return rc;
 }
 
 extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail, uint8_t *dst,
@@ -2264,7 +2290,7 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
   if (!ctx || (!packed && avail) || !width || !height || !channels || !rows_complete) return HIMG_ERR_ARG;
   *rows_complete = -1;
   // The host needs the geometry alone, to size the launch: the chunk headers as far as FRMT.  Every
-  // check is the device's (k_prefix_gate, k_dec_parse_prefix), which words the verdict.
+  // check is the device's (k_span_gate, k_dec_parse_prefix), which words the verdict.
   const uint32_t av = prefix_avail32(avail);
   himg_dev::PfxHead h;
   const int hc = himg_dev::pfx_chain(packed, av, ctx->fix_t2, 0, &h);
@@ -2278,15 +2304,10 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t in_cap = round_up((size_t)av + 16, 256);
   const size_t out_bytes = (size_t)W * H * C;
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;
-  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, av)) return rc;   // (only the bytes present)
+  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, packed, av)) return rc;   // (only the bytes present)
   int32_t *d_st = (int32_t *)ctx->h_status.p;
-  if (int rc = himg_hip_decode_prefix_device(ctx, ctx->h_in.p, in_cap, &av, 1, W, H, C, ctx->h_out.p, d_st + 1, d_st, nullptr)) {
-    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
-    return rc;
-  }
+  if (int rc = himg_hip_decode_prefix_device(ctx, ctx->h_in.p, in_cap, &av, 1, W, H, C, ctx->h_out.p, d_st + 1, d_st, nullptr))
+    return launch_refused(rc);
   int32_t st[2] = {0, -1};
   HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
   if (st[0]) return status_error(ctx, st[0], "the prefix ends before the first block row");
@@ -2298,7 +2319,7 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
 }
 
 // The prefix decode continued from the rows a caller's picture already holds (kernels_dec.hip,
-// launch_prefix_more): the states are read, judged and advanced on the device.
+// launch_prefix with states): the states are read, judged and advanced on the device.
 extern "C" int himg_hip_decode_prefix_more_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
                                                   const uint32_t *h_avail, int batch, int width, int height,
                                                   int num_channels, himg_hip_prefix_state *d_state, void *d_out,
@@ -2306,17 +2327,8 @@ extern "C" int himg_hip_decode_prefix_more_device(himg_hip_ctx *ctx, const void 
   if (!ctx || !d_packed || !h_avail || !d_state || !d_out || !d_rows || !d_status || batch < 1 || batch > 65535)
     return HIMG_ERR_ARG;
   if ((uintptr_t)d_state & 15) return fail(ctx, HIMG_ERR_ARG, "the states must be 16-byte aligned");
-  if (int rc = stride_covers(ctx, h_avail, batch, in_stride)) return rc;
-  Geom g;
-  const uint32_t *d_sizes = nullptr;
-  if (int rc = decode_args(ctx, width, height, num_channels, batch, kWsRegion, d_packed, d_out, &in_stride, nullptr, &g))
-    return rc;
-  if (int rc = decode_begin(ctx, g, batch, kWsRegion, h_avail, stream, &d_sizes)) return rc;
-  launch_prefix_more(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p,
-                     (himg_dev::PfxState *)d_state, (uint8_t *)d_out, d_rows, d_status, (hipStream_t)stream, &ctx->prof,
-                     ctx->opts.use_side ? &ctx->dstr : nullptr);
-  HIP_TRY(ctx, hipGetLastError());
-  return HIMG_OK;
+  return prefix_launch(ctx, d_packed, in_stride, h_avail, batch, width, height, num_channels, d_state, d_out, d_rows,
+                       d_status, stream);
 }
 
 extern "C" int himg_hip_decode_prefix_more_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail,
@@ -2340,30 +2352,25 @@ extern "C" int himg_hip_decode_prefix_more_to(himg_hip_ctx *ctx, const uint8_t *
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t in_cap = round_up((size_t)av + 16, 256);
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(256))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;   // (nothing stays resident: no fetch_last behind this call)
   // A resumed state the host's walk accepts: the head and the bytes from the walk's position on, each at its
-  // offset (the bytes between them are the rows already decoded: nothing reads them).
+  // offset (the bytes between them are the rows already decoded: nothing reads them).  Else the whole prefix.
+  // (Nothing stays resident: no fetch_last behind this call.)
   const bool partial = state->started && pc == HIMG_OK;
+  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, partial ? nullptr : packed, av)) return rc;
   uint8_t *d_in = (uint8_t *)ctx->h_in.p;
   if (partial) {
     HIP_TRY(ctx, hipMemcpyAsync(d_in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
     if (av > state->walk_pos)
       HIP_TRY(ctx, hipMemcpyAsync(d_in + state->walk_pos, packed + state->walk_pos, av - state->walk_pos,
                                   hipMemcpyHostToDevice, nullptr));
-  } else if (int rc = upload_zero_tail(ctx, d_in, in_cap, packed, av)) {
-    return rc;
   }
   // h_status: the status word, k, then the state at byte 16.
   int32_t *d_st = (int32_t *)ctx->h_status.p;
   himg_hip_prefix_state *d_state = (himg_hip_prefix_state *)((uint8_t *)ctx->h_status.p + 16);
   HIP_TRY(ctx, hipMemcpyAsync(d_state, state, sizeof(*state), hipMemcpyHostToDevice, nullptr));
   if (int rc = himg_hip_decode_prefix_more_device(ctx, d_in, in_cap, &av, 1, W, H, C, d_state, ctx->h_out.p, d_st + 1, d_st,
-                                                  nullptr)) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still be reading the caller's buffers
-    return rc;
-  }
+                                                  nullptr))
+    return launch_refused(rc);
   struct { int32_t st, k, pad[2]; himg_hip_prefix_state s; } back;
   HIP_TRY(ctx, hipMemcpy(&back, d_st, sizeof(back), hipMemcpyDeviceToHost));
   if (back.st) return status_error(ctx, back.st, status_to_code(back.st) == HIMG_ERR_ARG
@@ -2399,7 +2406,7 @@ extern "C" int himg_hip_decode_conceal_device(himg_hip_ctx *ctx, const void *d_p
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!ctx->d_cmap.reserve(round_up((size_t)batch * g.rows, 256)))
     return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
-  // (the sizes ride to the device as in decode_device: no wait; three more words per frame behind them
+  // (the sizes ride to the device as in decode_device: no wait; four more words per frame behind them
   // are the repair pass's, himg_dev::launch_conceal)
   if (int rc = decode_begin(ctx, g, batch, kWsFull, h_sizes, stream, &d_sizes)) return rc;
   launch_conceal(g, ctx->dec_ws, batch, (const uint8_t *)d_packed, in_stride, (uint32_t *)ctx->d_sizes.p,
@@ -2423,19 +2430,13 @@ extern "C" int himg_hip_decode_conceal_to(himg_hip_ctx *ctx, const uint8_t *pack
   const size_t in_cap = round_up(packed_size + 16, 256);
   const size_t out_bytes = (size_t)W * H * C;
   const size_t map_at = 256;   // (h_status: the status word, the count, then the row map)
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
-      !ctx->h_status.reserve(map_at + round_up((size_t)g.rows, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;
-  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
+  if (int rc = stage_stream(ctx, in_cap, out_bytes, map_at + round_up((size_t)g.rows, 256), packed, packed_size)) return rc;
   const uint32_t sz32 = (uint32_t)packed_size;
   int32_t *d_st = (int32_t *)ctx->h_status.p;
   uint8_t *d_map = (uint8_t *)ctx->h_status.p + map_at;
   if (int rc = himg_hip_decode_conceal_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, ctx->h_out.p, d_st + 1, d_map, d_st,
-                                              nullptr)) {
-    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
-    return rc;
-  }
+                                              nullptr))
+    return launch_refused(rc);
   int32_t st[2] = {0, -1};
   HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
   if (st[0]) return status_error(ctx, st[0]);

@@ -175,7 +175,7 @@ constexpr int kParseHalf = kParseThreads / 2;   // lanes per stream in step 5
 __device__ __forceinline__ void identity_test_words(const DecFrame *df, int l, uint32_t *dst);
 
 // PREFIX (k_dec_parse_prefix, the decode of a stream prefix): sizes[f] is the size the stream's RIFF
-// header declares, the container's bound; avails[f] the bytes present, below which k_prefix_gate has
+// header declares, the container's bound; avails[f] the bytes present, below which k_span_gate has
 // found every header this walk reads -- the staging of the bodies is bounded there.
 template <bool HEAD, bool PREFIX = false>
 __device__ __forceinline__ void dec_parse_body(Geom g, DecWs ws, const uint8_t *packed,
@@ -4558,52 +4558,70 @@ __global__ void k_region_walk_end(Geom g, DecWs ws, const uint8_t *packed, size_
   const uint8_t *p = packed + (size_t)f * in_stride;
   const uint32_t end = df->s[1].chunk_end;
   uint32_t q = df->s[1].payload_off;
-  for (int r = 0; r < r1; ++r) {   // (k_dec_rowwalk's header rules)
-    if (q + 2 > end) return;
-    uint32_t len = p[q] | (p[q + 1] << 8);
-    q += 2;
-    if (len & 0x8000u) {
-      if (q + 2 > end) return;
-      len = (len & 0x7fffu) | ((uint32_t)(p[q] | (p[q + 1] << 8)) << 15);
-      q += 2;
-    }
-    if (len > end - q) return;
-    q += len;
+  for (int r = 0; r < r1; ++r) {   // (k_dec_rowwalk's header rules; the whole chunk is present)
+    uint32_t b, len, need;
+    if (pfx_row_header(p, q, end, end, &b, &len, &need) != kPfxOk) return;
+    q = b + len;
   }
   if (q == end) df->walk_status = 0;
 }
 
 // ---------------------------------------------------------------------------
-// The decode of a stream PREFIX (include/himg_hip.h): the first avail_f bytes of frame f's stream.
-// Block rows [0, k_f) -- those whose size header and payload lie wholly below avail_f -- are decoded,
-// rows [k_f, rows) are written from the low-res plane alone.  k_f is found ON THE DEVICE, so the
-// count and row kernels take it from an array (krows) where the region forms compute r1_f from an
-// origin; like those, each includes the body of the kernel it stands beside behind its own values.
-//   k_prefix_gate      (one wavefront per frame) the chunk headers RIFF .. FRES and the length of the
+// The ROW-SPAN family: block rows [k0_f, k1_f) of frame f at the full width, k0_f and k1_f known ON THE
+// DEVICE alone, so the count and row kernels take them from arrays where the region forms compute r1_f
+// from an origin; like those, each includes the body of the kernel it stands beside behind its own
+// values.  Rows [kfill_f, rows) are written from the low-res plane alone.  Three decodes run it
+// (include/himg_hip.h):
+//   * the decode of a stream PREFIX, the first avail_f bytes of frame f's stream: k0 = 0, k1 = kfill = k_f,
+//     the block rows whose size header and payload lie wholly below avail_f;
+//   * the prefix decode CONTINUED (himg_hip_decode_prefix_more_device): frame f comes with a PfxState in
+//     device memory.  A fresh state (started == 0) makes the frame the prefix decode's, to the byte.
+//     Otherwise block rows [0, k_prev) are in the caller's picture already: the head runs as it always does
+//     (the workspace keeps nothing between calls), the header walk resumes where the state says, and only
+//     rows [k0, k1) = [k_prev, k_new) are counted, decoded and stored; kfill = rows, so that the fill skips
+//     the frame whole -- its missing rows are in the caller's picture too;
+//   * the CONCEALING decode (below), whose own gate and walk set k0 = 0 and k1 = kfill = k_f.
+// The kernels:
+//   k_span_gate        (one wavefront per frame) the chunk headers RIFF .. FRES and the length of the
 //                      FRES tree with every load checked against avail_f (prefix_walk.h).  A frame
 //                      whose head has not arrived whole gets the verdict kStShort, and the size 0
 //                      goes to the parse and to every reader for it: nothing of it is loaded again.
-//                      For the others: ptx[f] = T_f, the container's bound for k_dec_parse_prefix;
-//                      pbound[f] = avail_f, the load bound of every later kernel; DecFrame::walk_q /
-//                      walk_end = where the row headers start and the chunk ends.
-//   k_prefix_rowwalk   (one lane per frame) the row headers below avail_f: the row index and k_f.
-//   k_prefix_count(_w) k_row_count<false> / k_row_count_w over rows [0, k_f).
-//   k_dec_prefix       k_dec_region's body over rows [0, k_f), the whole width: the window is the top
-//                      min(8 k_f, H) pixel rows of the picture.
-//   k_prefix_fill      rows [k_f, rows) from the low-res plane.
-//   k_prefix_status    the verdicts and k_f (-1 for a frame with a verdict).
+//                      For the others: tx[f] = T_f, the container's bound for k_dec_parse_prefix;
+//                      bound[f] = avail_f, the load bound of every later kernel; DecFrame::walk_q /
+//                      walk_end = where the row headers start and the chunk ends.  Then the frame's state,
+//                      if there is one and it is started, against those results, every field before
+//                      anything uses it.  A state that cannot be right: the verdict kStGeom -- the word the
+//                      host maps to HIMG_ERR_ARG -- and the frame is closed like one below its head.
+//                      Otherwise k0[f] = k1[f] = k_prev until the walk says more, and the walk resumes at
+//                      the state's position.
+//   k_span_rowwalk     (one lane per frame) the row headers below avail_f from the walk's position: the
+//                      row index of rows [k0, k1), k1, where the walk stands now.
+//   k_prefix_fill      rows [kfill_f, rows) from the low-res plane.
+//   k_span_count(_w)   k_row_count<false> / k_row_count_w over rows [k0, k1).
+//   k_dec_span         k_dec_region's body over the window (0, 8 k0, W, min(8 k1, H) - 8 k0), placed at
+//                      its rows of the full picture.
+//   k_span_status      the verdicts, k1 (-1 for a frame with a verdict), and the states of the frames
+//                      without one.
 // ---------------------------------------------------------------------------
 constexpr int kStShort = 5;   // the prefix ends before the first row header: HIMG_ERR_CAPACITY
 
-__global__ __launch_bounds__(64) void k_prefix_gate(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                    const uint32_t *avails, uint32_t *ptx, uint32_t *pbound,
-                                                    int32_t *krows, int32_t *gate) {
+struct SpanWords {        // per-frame words of one launch (the launch function carves them)
+  const uint32_t *avail;  // the bytes present, as the caller staged them
+  uint32_t *tx, *bound;   // the gate's: the declared size, the load bound
+  int32_t *k0, *k1;       // the rows to decode, [k0, k1)
+  int32_t *gate;          // the gate's verdict
+  int32_t *kfill;         // k_prefix_fill's k_f
+  uint32_t *pos;          // PfxRows::used of this call's walk
+};
+
+__global__ __launch_bounds__(64) void k_span_gate(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                  const PfxState *state, SpanWords w) {
   __shared__ uint8_t s_tree[kTreeStride];
   __shared__ uint32_t s_hdr[4];
   const int f = blockIdx.x, lane = threadIdx.x;
   DecFrame *df = ws.frames + f;
   const uint8_t *p = packed + (size_t)f * in_stride;
-  const uint32_t avail = avails[f];
+  const uint32_t avail = w.avail[f];
   if (lane == 0) {
     PfxHead h;
     int rc = pfx_chain(p, avail, g.fix_t2, (uint32_t)g.row_block, &h);
@@ -4614,8 +4632,6 @@ __global__ __launch_bounds__(64) void k_prefix_gate(Geom g, DecWs ws, const uint
     s_hdr[0] = (uint32_t)rc; s_hdr[1] = h.coff; s_hdr[2] = h.csz; s_hdr[3] = h.T;
     df->walk_status = rc == kPfxFormat ? (geom ? kStGeom : fmt_err(h.stage, h.huff)) : 0;
     df->rows_first = 0;
-    df->walk_q = 0;
-    krows[f] = 0;
   }
   __syncthreads();
   int rc = (int)s_hdr[0];
@@ -4628,6 +4644,7 @@ __global__ __launch_bounds__(64) void k_prefix_gate(Geom g, DecWs ws, const uint
   }
   __syncthreads();
   if (lane != 0) return;
+  uint32_t wq = 0, wend = 0;   // the first row header and the chunk's end (0: no rows to walk)
   if (rc == kPfxOk) {
     uint32_t tb = 0;
     rc = pfx_tree_len(s_tree, have, csz, &tb);
@@ -4635,19 +4652,41 @@ __global__ __launch_bounds__(64) void k_prefix_gate(Geom g, DecWs ws, const uint
       df->walk_status = fmt_err(7, 1);   // (k_dec_parse rejects this tree: its verdict comes first)
     } else if (rc == kPfxOk) {
       const uint32_t q = coff + tb, end = coff + csz;
-      if (q < end) { df->rows_first = q; df->walk_q = q; df->walk_end = end; }
+      if (q < end) { df->rows_first = q; df->walk_end = end; wq = q; wend = end; }
       // (q >= end: nothing behind the tree -- k_dec_parse's verdict, huffman_dec.cpp:277-278)
     }
   }
   const bool is_short = rc == kPfxShort;
-  gate[f] = is_short ? kStShort : 0;
-  ptx[f] = is_short ? 0u : T;
-  pbound[f] = is_short ? 0u : avail;
+  int gt = is_short ? kStShort : 0, k0 = 0, kfill = 0;
+  uint32_t tx = is_short ? 0u : T, bound = is_short ? 0u : avail, pos = 0;
+  PfxState s;
+  s.started = 0;
+  if (state) {
+    const uint4 raw = *reinterpret_cast<const uint4 *>(state + f);
+    s.started = raw.x; s.rows_done = (int32_t)raw.y; s.walk_pos = raw.z; s.avail_seen = raw.w;
+  }
+  if (s.started) {   // (else a fresh frame: the prefix decode's)
+    bool bad = avail < s.avail_seen;
+    // (wq == 0: the verdict above, or the parse's -- that one stands)
+    if (!bad && gt == 0 && wq != 0) bad = !pfx_state_ok(s, avail, g.rows, wq, wend);
+    kfill = g.rows;
+    if (bad) {
+      gt = kStGeom;
+      tx = 0; bound = 0;
+      df->walk_status = 0; df->rows_first = 0;
+      wq = 0;
+    } else if (wq != 0) {
+      k0 = s.rows_done;
+      wq = pos = s.walk_pos;
+    }
+  }
+  df->walk_q = wq;
+  w.gate[f] = gt; w.tx[f] = tx; w.bound[f] = bound;
+  w.k0[f] = k0; w.k1[f] = k0; w.kfill[f] = kfill; w.pos[f] = pos;
 }
 
-__global__ __launch_bounds__(64) void k_prefix_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                       const uint32_t *pbound, const uint32_t *ptx, int32_t *krows,
-                                                       int batch) {
+__global__ __launch_bounds__(64) void k_span_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                     SpanWords w, int batch) {
   const int f = blockIdx.x * 64 + threadIdx.x;
   if (f >= batch) return;
   DecFrame *df = ws.frames + f;
@@ -4655,62 +4694,68 @@ __global__ __launch_bounds__(64) void k_prefix_rowwalk(Geom g, DecWs ws, const u
   if (q == 0) return;   // no rows to walk: the gate's verdict, or the parse's
   df->walk_q = 0;
   PfxRows pr;
-  const int rc = pfx_rows(packed + (size_t)f * in_stride, pbound[f], ptx[f], g.fix_t2, g.rows, q, df->walk_end,
-                          ws.row_off + (size_t)f * g.rows, ws.row_len + (size_t)f * g.rows, &pr);
+  const int rc = pfx_rows_from(packed + (size_t)f * in_stride, w.bound[f], w.tx[f], g.fix_t2, g.rows, q, w.k0[f],
+                               df->walk_end, ws.row_off + (size_t)f * g.rows, ws.row_len + (size_t)f * g.rows, &pr);
   if (rc == kPfxFormat) { df->walk_status = fmt_err(7, 1); return; }
-  krows[f] = pr.k;
+  w.k1[f] = pr.k;
+  w.pos[f] = pr.used;
+  if (w.kfill[f] != g.rows) w.kfill[f] = pr.k;   // (a fresh frame: the fill's k_f is the walk's)
 }
 
-// k_row_count<false> over rows [0, k_f) (rows_per_wg of them per workgroup).
-__global__ __launch_bounds__(kDecThreads, 8) void k_prefix_count(Geom g, DecWs ws, const uint8_t *packed,
-                                                                size_t in_stride, const uint32_t *sizes,
-                                                                const int32_t *krows, int rows_per_wg) {
+// k_row_count<false> over rows [k0, k1) (rows_per_wg of them per workgroup).
+__global__ __launch_bounds__(kDecThreads, 8) void k_span_count(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                              const uint32_t *sizes, const int32_t *k0,
+                                                              const int32_t *k1, int rows_per_wg) {
   constexpr bool LDSPAY = false;
-  const int r0 = 0, r1 = krows[blockIdx.y];
-  if ((int)blockIdx.x * rows_per_wg >= r1) return;
+  const int r0 = k0[blockIdx.y], r1 = k1[blockIdx.y];
+  if (r0 + (int)blockIdx.x * rows_per_wg >= r1) return;
 #include "dec_body_row_count.inc"
 }
 
-// k_row_count_w over rows [0, k_f).
-__global__ __launch_bounds__(kDecThreads, 8) void k_prefix_count_w(Geom g, DecWs ws, const uint8_t *packed,
-                                                                  size_t in_stride, const uint32_t *sizes,
-                                                                  const int32_t *krows) {
-  const int r0 = 0, r1 = krows[blockIdx.y];
-  if ((int)blockIdx.x * kCountRowsW >= r1) return;
+// k_row_count_w over rows [k0, k1).
+__global__ __launch_bounds__(kDecThreads, 8) void k_span_count_w(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                const int32_t *k0, const int32_t *k1) {
+  const int r0 = k0[blockIdx.y], r1 = k1[blockIdx.y];
+  if (r0 + (int)blockIdx.x * kCountRowsW >= r1) return;
   constexpr int NQ = 1;   // a sub-sequence per lane
 #include "dec_body_row_count_w.inc"
 }
 
-// k_dec_region's body over the window (0, 0, W, min(8 k_f, H)) of frame f, written where the full
-// decode writes it: frame f's picture at out + f * H * W * C.
-struct PrefixArgs {
-  const int32_t *krows;   // [f] k_f
-  int sw;                 // tiles per column strip (blockIdx.x = strip)
+// k_dec_region's body over the window (0, 8 k0, W, min(8 k1, H) - 8 k0) of frame f, written where the full
+// decode writes it: frame f's picture at out + f * H * W * C.  kConceal: kRegionConceal of the body -- a
+// rejected row sets its byte of cmap and is stored as zero symbols.
+struct SpanArgs {
+  const int32_t *k0, *k1;   // [f] the rows to decode
+  uint8_t *cmap;            // [f][rows] (kConceal)
+  int sw;                   // tiles per column strip (blockIdx.x = strip)
   uint8_t *out;
 };
-struct PrefixOrigin {     // every window starts at (0, 0)
-  __device__ __forceinline__ int operator[](int) const { return 0; }
+struct SpanOrigin {       // every window starts at (0, y)
+  int y;
+  __device__ __forceinline__ int operator[](int i) const { return (i & 1) ? y : 0; }
 };
-struct PrefixWindow {     // what the body reads of a RegionArgs
-  PrefixOrigin org;
+struct SpanWindow {       // what the body reads of a RegionArgs
+  SpanOrigin org;
   int sw, w, h;
   uint8_t *out;           // (the body adds f * h * w * C)
 };
-__global__ __launch_bounds__(kDecThreads) void k_dec_prefix(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                           const uint32_t *sizes, PrefixArgs pa) {
-  constexpr bool kRegionTens = false, kRegionPitch = false;
-  constexpr bool kRegionConceal = false;
-  uint8_t *const cmap = nullptr;
+template <bool kConceal>
+__global__ __launch_bounds__(kDecThreads) void k_dec_span(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                         const uint32_t *sizes, SpanArgs sa) {
+  constexpr bool kRegionTens = false, kRegionPitch = false, kRegionConceal = kConceal;
+  uint8_t *const cmap = sa.cmap;
   const TensK td = nullptr;
   const DstK pd = nullptr;
-  const int k_f = pa.krows[blockIdx.z];
-  if ((int)blockIdx.y >= k_f) return;
-  PrefixWindow ra;
-  ra.sw = pa.sw; ra.w = g.W; ra.h = 8 * k_f < g.H ? 8 * k_f : g.H;
+  const int k0 = sa.k0[blockIdx.z], k1 = sa.k1[blockIdx.z];
+  if ((int)blockIdx.y >= k1 - k0) return;
+  SpanWindow ra;
+  ra.org.y = 8 * k0;
+  ra.sw = sa.sw; ra.w = g.W; ra.h = (8 * k1 < g.H ? 8 * k1 : g.H) - 8 * k0;
   // The body places frame f at ra.out + f * ra.h * ra.w * C (dec_body_region.inc, "img = ra.out + ...", which names
   // this kernel): with a height per frame the rest of the full picture's stride is added here, so that frame
-  // f lands at pa.out + f * H * W * C.
-  ra.out = pa.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C);
+  // f lands at sa.out + f * H * W * C -- then down to the window's first pixel row.
+  ra.out = sa.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C) + (size_t)(8 * k0) * ((size_t)g.W * g.C);
 #include "dec_body_region.inc"
 }
 
@@ -4806,148 +4851,9 @@ __global__ __launch_bounds__(256) void k_prefix_fill(Geom g, DecWs ws, const int
   }
 }
 
-// The verdicts: k_dec_status's rule, kStShort for a frame the gate stopped, and k_f.
-__global__ void k_prefix_status(DecWs ws, const int32_t *gate, const int32_t *krows, int32_t *status, int32_t *rows_out,
-                                int batch) {
-  const int f = blockIdx.x * blockDim.x + threadIdx.x;
-  if (f >= batch) return;
-  const DecFrame *df = ws.frames + f;
-  const int w = df->parse_status == 0 ? df->walk_status : 0;
-  int st = df->status > w ? df->status : w;
-  if (gate[f]) st = gate[f];
-  status[f] = st;
-  if (rows_out) rows_out[f] = st ? -1 : krows[f];
-}
-
-// ---------------------------------------------------------------------------
-// The prefix decode CONTINUED (include/himg_hip.h, himg_hip_decode_prefix_more_device): frame f comes with
-// a PfxState in device memory.  A fresh state (started == 0) makes the frame the prefix decode's, to the
-// byte.  Otherwise block rows [0, k_prev) are in the caller's picture already: the head runs as it always
-// does (the workspace keeps nothing between calls), the header walk resumes where the state says, and only
-// rows [k_prev, k_new) are counted, decoded and stored.  The kernels stand beside the prefix decode's:
-//   k_prefix_gate      as it is.
-//   k_more_gate        (a lane per frame, behind it) the state against the gate's results, every field
-//                      before anything uses it.  A state that cannot be right: the verdict kStGeom -- the
-//                      word the host maps to HIMG_ERR_ARG -- and the frame is closed as the gate closes one
-//                      below its head (size 0 to every reader).  kprev[f] = k_prev (0 for a fresh frame),
-//                      krows[f] = k_prev until the walk says more, DecFrame::walk_q = where the walk resumes,
-//                      kfill[f] = what k_prefix_fill takes for k_f: `rows` for a resumed frame, whose
-//                      missing rows the caller's picture already holds, so that the fill skips it whole.
-//   k_more_rowwalk     pfx_rows_from: the row index of rows [k_prev, k_new), k_new, the walk's position.
-//   k_prefix_fill      as it is, over kfill: fresh frames only.
-//   k_more_count(_w)   k_row_count<false> / k_row_count_w over rows [k_prev, k_new).
-//   k_dec_more         k_dec_region's body over the window (0, 8 k_prev, W, min(8 k_new, H) - 8 k_prev),
-//                      placed at its rows of the full picture.
-//   k_more_status      the verdicts, k_new, and the states of the frames without a verdict.
-// ---------------------------------------------------------------------------
-struct MoreWords {        // per-frame words of one launch (launch_prefix_more carves them)
-  const uint32_t *avail;  // the bytes present, as the caller staged them
-  uint32_t *tx, *bound;   // k_prefix_gate's: the declared size, the load bound
-  int32_t *krows, *gate;  // k_new; the gate's verdict
-  int32_t *kprev, *kfill;
-  uint32_t *pos;          // PfxRows::used of this call's walk
-};
-
-__global__ __launch_bounds__(64) void k_more_gate(Geom g, DecWs ws, const PfxState *state, MoreWords w, int batch) {
-  const int f = blockIdx.x * 64 + threadIdx.x;
-  if (f >= batch) return;
-  DecFrame *df = ws.frames + f;
-  const uint4 raw = *reinterpret_cast<const uint4 *>(state + f);
-  PfxState s;
-  s.started = raw.x; s.rows_done = (int32_t)raw.y; s.walk_pos = raw.z; s.avail_seen = raw.w;
-  w.kprev[f] = 0;
-  w.kfill[f] = 0;
-  w.pos[f] = 0;
-  if (!s.started) return;   // the prefix decode's frame
-  const uint32_t avail = w.avail[f];
-  const uint32_t q = df->walk_q;   // 0: the gate's verdict, or the parse's -- that one stands
-  bool bad = avail < s.avail_seen;
-  if (!bad && w.gate[f] == 0 && q != 0) bad = !pfx_state_ok(s, avail, g.rows, q, df->walk_end);
-  w.kfill[f] = g.rows;
-  if (bad) {
-    w.gate[f] = kStGeom;
-    w.tx[f] = 0; w.bound[f] = 0;
-    df->walk_status = 0; df->rows_first = 0; df->walk_q = 0;
-    return;
-  }
-  if (q == 0) return;
-  w.kprev[f] = s.rows_done;
-  w.krows[f] = s.rows_done;
-  w.pos[f] = s.walk_pos;
-  df->walk_q = s.walk_pos;
-}
-
-__global__ __launch_bounds__(64) void k_more_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                     MoreWords w, int batch) {
-  const int f = blockIdx.x * 64 + threadIdx.x;
-  if (f >= batch) return;
-  DecFrame *df = ws.frames + f;
-  const uint32_t q = df->walk_q;
-  if (q == 0) return;   // no rows to walk: a verdict of the gates, or the parse's
-  df->walk_q = 0;
-  PfxRows pr;
-  const int rc = pfx_rows_from(packed + (size_t)f * in_stride, w.bound[f], w.tx[f], g.fix_t2, g.rows, q, w.kprev[f],
-                               df->walk_end, ws.row_off + (size_t)f * g.rows, ws.row_len + (size_t)f * g.rows, &pr);
-  if (rc == kPfxFormat) { df->walk_status = fmt_err(7, 1); return; }
-  w.krows[f] = pr.k;
-  w.pos[f] = pr.used;
-  if (w.kfill[f] != g.rows) w.kfill[f] = pr.k;   // (a fresh frame: the fill's k_f is the walk's)
-}
-
-// k_row_count<false> over rows [k_prev, k_new) (rows_per_wg of them per workgroup).
-__global__ __launch_bounds__(kDecThreads, 8) void k_more_count(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                              const uint32_t *sizes, const int32_t *kprev,
-                                                              const int32_t *krows, int rows_per_wg) {
-  constexpr bool LDSPAY = false;
-  const int r0 = kprev[blockIdx.y], r1 = krows[blockIdx.y];
-  if (r0 + (int)blockIdx.x * rows_per_wg >= r1) return;
-#include "dec_body_row_count.inc"
-}
-
-// k_row_count_w over rows [k_prev, k_new).
-__global__ __launch_bounds__(kDecThreads, 8) void k_more_count_w(Geom g, DecWs ws, const uint8_t *packed,
-                                                                size_t in_stride, const uint32_t *sizes,
-                                                                const int32_t *kprev, const int32_t *krows) {
-  const int r0 = kprev[blockIdx.y], r1 = krows[blockIdx.y];
-  if (r0 + (int)blockIdx.x * kCountRowsW >= r1) return;
-  constexpr int NQ = 1;   // a sub-sequence per lane
-#include "dec_body_row_count_w.inc"
-}
-
-struct MoreArgs {
-  const int32_t *kprev, *krows;   // [f] k_prev, k_new
-  int sw;                         // tiles per column strip (blockIdx.x = strip)
-  uint8_t *out;
-};
-struct MoreOrigin {       // every window starts at (0, y)
-  int y;
-  __device__ __forceinline__ int operator[](int i) const { return (i & 1) ? y : 0; }
-};
-struct MoreWindow {       // what the body reads of a RegionArgs
-  MoreOrigin org;
-  int sw, w, h;
-  uint8_t *out;           // (the body adds f * h * w * C)
-};
-__global__ __launch_bounds__(kDecThreads) void k_dec_more(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                         const uint32_t *sizes, MoreArgs ma) {
-  constexpr bool kRegionTens = false, kRegionPitch = false;
-  constexpr bool kRegionConceal = false;
-  uint8_t *const cmap = nullptr;
-  const TensK td = nullptr;
-  const DstK pd = nullptr;
-  const int k0 = ma.kprev[blockIdx.z], k1 = ma.krows[blockIdx.z];
-  if ((int)blockIdx.y >= k1 - k0) return;
-  MoreWindow ra;
-  ra.org.y = 8 * k0;
-  ra.sw = ma.sw; ra.w = g.W; ra.h = (8 * k1 < g.H ? 8 * k1 : g.H) - 8 * k0;
-  // k_dec_prefix's placement -- the body adds f * ra.h * ra.w * C, the rest of the full picture's stride is
-  // added here -- then down to the window's first pixel row.
-  ra.out = ma.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C) + (size_t)(8 * k0) * ((size_t)g.W * g.C);
-#include "dec_body_region.inc"
-}
-
-// k_prefix_status's verdicts; a frame without one hands its state on: {1, k_new, the walk's position, avail}.
-__global__ void k_more_status(DecWs ws, MoreWords w, PfxState *state, int32_t *status, int32_t *rows_out, int batch) {
+// The verdicts: k_dec_status's rule, then the gate's word for a frame it stopped, and k1.  With states, a
+// frame without a verdict hands its state on: {1, k1, the walk's position, avail}.
+__global__ void k_span_status(DecWs ws, SpanWords w, PfxState *state, int32_t *status, int32_t *rows_out, int batch) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= batch) return;
   const DecFrame *df = ws.frames + f;
@@ -4955,9 +4861,9 @@ __global__ void k_more_status(DecWs ws, MoreWords w, PfxState *state, int32_t *s
   int st = df->status > ws_ ? df->status : ws_;
   if (w.gate[f]) st = w.gate[f];
   status[f] = st;
-  rows_out[f] = st ? -1 : w.krows[f];
-  if (!st)
-    *reinterpret_cast<uint4 *>(state + f) = make_uint4(1u, (uint32_t)w.krows[f], w.pos[f], w.avail[f]);
+  if (rows_out) rows_out[f] = st ? -1 : w.k1[f];
+  if (state && !st)
+    *reinterpret_cast<uint4 *>(state + f) = make_uint4(1u, (uint32_t)w.k1[f], w.pos[f], w.avail[f]);
 }
 
 // ---------------------------------------------------------------------------
@@ -4968,7 +4874,7 @@ __global__ void k_more_status(DecWs ws, MoreWords w, PfxState *state, int32_t *s
 // what the full decode left.
 //   k_conceal_gate     (a lane per frame) act[f]: 1 a frame to repair -- the parse passed and the verdict
 //                      is the rows' (the walk's or a row kernel's); its verdict fields are cleared for the
-//                      kernels below.  0: accepted, 2: a head verdict -- neither is touched again: an
+//                      kernels below.  The span of every frame starts empty (k0 = k_f = 0).  0: accepted, 2: a head verdict -- neither is touched again: an
 //                      accepted frame is PARKED (DecFrame::status = kStParked until k_conceal_status), so
 //                      that the kernels shared with the other decodes, which skip a frame with a verdict,
 //                      skip it too.
@@ -4978,14 +4884,13 @@ __global__ void k_more_status(DecWs ws, MoreWords w, PfxState *state, int32_t *s
 //                      rows' verdict hid it).
 //   k_conceal_rowwalk  (a lane per frame) the row headers again, for the row index and k_f.
 //   k_conceal_map      the row map: 1 for rows [k_f, rows) of a frame to repair, else 0.
-//   k_prefix_fill, k_prefix_count(_w)   as the prefix decode runs them, over k_f.
-//   k_dec_conceal      k_dec_region's body over rows [0, k_f), the whole width (k_dec_prefix's window),
-//                      with kRegionConceal: a rejected row sets its map byte and is stored as zero symbols.
+//   k_prefix_fill, k_span_count(_w), k_dec_span<true>   the row-span family over [0, k_f), with
+//                      kRegionConceal: a rejected row sets its map byte and is stored as zero symbols.
 //   k_conceal_status   (a wavefront per frame) d_status, d_concealed, the caller's row map.
 // ---------------------------------------------------------------------------
 constexpr int kStParked = 1 << 30;
 
-__global__ void k_conceal_gate(DecWs ws, const int32_t *st1, int32_t *krows, int32_t *act, int batch) {
+__global__ void k_conceal_gate(DecWs ws, const int32_t *st1, int32_t *k0, int32_t *krows, int32_t *act, int batch) {
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= batch) return;
   DecFrame *df = ws.frames + f;
@@ -4993,6 +4898,7 @@ __global__ void k_conceal_gate(DecWs ws, const int32_t *st1, int32_t *krows, int
   int a = 0;
   if (m != 0) a = (df->parse_status == 0 && m == fmt_err(7, 1)) ? 1 : 2;
   act[f] = a;
+  k0[f] = 0;
   krows[f] = 0;
   if (a == 1) { df->status = 0; df->walk_status = 0; }
   else if (a == 0) df->status = kStParked;
@@ -5021,18 +4927,11 @@ __global__ __launch_bounds__(64) void k_conceal_rowwalk(Geom g, DecWs ws, const 
     r = 1;
   } else {
     while (q != end) {   // (k_dec_rowwalk's header rules; a failure behind the last row conceals nothing)
-      if (q + 2 > end) break;
-      uint32_t len = p[q] | (p[q + 1] << 8);
-      q += 2;
-      if (len & 0x8000u) {
-        if (q + 2 > end) break;
-        len = (len & 0x7fffu) | ((uint32_t)(p[q] | (p[q + 1] << 8)) << 15);
-        q += 2;
-      }
-      if (len > end - q) break;
-      if (r < g.rows) { ro[r] = q; rl[r] = len; }
+      uint32_t b, len, need;
+      if (pfx_row_header(p, q, end, end, &b, &len, &need) != kPfxOk) break;
+      if (r < g.rows) { ro[r] = b; rl[r] = len; }
       ++r;
-      q += len;
+      q = b + len;
     }
   }
   krows[f] = r < g.rows ? r : g.rows;
@@ -5044,26 +4943,6 @@ __global__ __launch_bounds__(256) void k_conceal_map(const int32_t *act, const i
   if (i >= (size_t)batch * rows) return;
   const int f = (int)(i / rows), r = (int)(i - (size_t)f * rows);
   cmap[i] = (act[f] == 1 && r >= krows[f]) ? 1 : 0;
-}
-
-struct ConcealArgs {
-  const int32_t *krows;   // [f] k_f (0: nothing to repair)
-  uint8_t *cmap;          // [f][rows]
-  int sw;                 // tiles per column strip (blockIdx.x = strip)
-  uint8_t *out;
-};
-__global__ __launch_bounds__(kDecThreads) void k_dec_conceal(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
-                                                            const uint32_t *sizes, ConcealArgs ca) {
-  constexpr bool kRegionTens = false, kRegionPitch = false, kRegionConceal = true;
-  const TensK td = nullptr;
-  const DstK pd = nullptr;
-  const int k_f = ca.krows[blockIdx.z];
-  if ((int)blockIdx.y >= k_f) return;
-  uint8_t *const cmap = ca.cmap;
-  PrefixWindow ra;
-  ra.sw = ca.sw; ra.w = g.W; ra.h = 8 * k_f < g.H ? 8 * k_f : g.H;
-  ra.out = ca.out + (size_t)blockIdx.z * ((size_t)(g.H - ra.h) * g.W * g.C);   // (k_dec_prefix's placement)
-#include "dec_body_region.inc"
 }
 
 __global__ __launch_bounds__(64) void k_conceal_status(DecWs ws, const int32_t *st1, const int32_t *act,
@@ -5654,7 +5533,7 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
       {HIMG_K(k_row_window), kRowWindowLds},
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
-      {HIMG_K(k_dec_prefix), 0},           {HIMG_K(k_dec_conceal), 0},          {HIMG_K(k_dec_more), 0},
+      {HIMG_K(k_dec_span<false>), 0},      {HIMG_K(k_dec_span<true>), 0},
       {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
       {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
 #undef HIMG_K
@@ -5777,6 +5656,22 @@ static WindowExtents window_extents(const Geom &g, int batch, const int32_t *h_o
   return e;
 }
 
+// The fork to the side stream for a header walk that runs beside the head phase on `stream` (no side streams:
+// the walk runs on `stream` itself), and the join: side_walked behind the walk's launch, side_join where the
+// work on `stream` first needs what it wrote.
+static hipStream_t side_fork(const DecStreams *ds, hipStream_t stream) {
+  if (!ds) return stream;
+  (void)hipEventRecord(ds->ev_fork, stream);
+  (void)hipStreamWaitEvent(ds->side, ds->ev_fork, 0);
+  return ds->side;
+}
+static void side_walked(const DecStreams *ds) {
+  if (ds) (void)hipEventRecord(ds->ev_walk[0], ds->side);
+}
+static void side_join(const DecStreams *ds, hipStream_t stream) {
+  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
+}
+
 // scale_log2 = 0: the region decode.  1, 2: the window w x h of the picture at scale 2^-scale_log2, frame
 // f's origin (x_f, y_f) in that picture; h_org / d_org hold the origins of the full-resolution rectangles
 // the windows cover, (F x_f, F y_f): with the height F h the walk and count kernels, which derive a
@@ -5794,21 +5689,17 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   // Each frame's row headers up to its r1_f (all of them for the whole frame's last row: the full decode's
   // verdict), on the side stream beside k_dec_parse and the LRES chain where there is one (launch_decode's
   // fork: the serial walk to a row deep in a 16384^2 frame is as long as the LRES chain).
-  hipStream_t ws_ = ds ? ds->side : stream;
-  if (ds) {
-    (void)hipEventRecord(ds->ev_fork, stream);
-    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
-  }
+  hipStream_t ws_ = side_fork(ds, stream);
   prof_begin(prof, d_row_index ? "k_region_set_index" : "k_region_rowwalk", ws_);
   if (d_row_index)
     hipLaunchKernelGGL(k_region_set_index, dim3(batch), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, d_org, hf);
   else
     hipLaunchKernelGGL(k_region_rowwalk, dim3(batch), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, d_org, hf);
   prof_end(prof, ws_);
-  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
+  side_walked(ds);
   HIMG_LAUNCH(k_dec_parse, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
-  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
+  side_join(ds, stream);
   if (!d_row_index && e.stop_early)
     HIMG_LAUNCH(k_region_walk_end, dim3((batch + 63) / 64), dim3(64), g, ws, d_packed, in_stride, d_org, hf, batch);
   // Every touched row gets a record: the count kernels that read the payload in place (k_row_count<true>
@@ -5857,143 +5748,92 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
 }
 
-// The decode of stream prefixes.  d_words: 5 x batch words -- the bytes present (staged by the caller),
-// then what k_prefix_gate and k_prefix_rowwalk leave for the kernels behind them: the declared sizes,
-// the load bounds, k_f, the gate's verdicts.
-void launch_prefix(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                   uint32_t *d_words, uint8_t *d_out, int32_t *d_rows, int32_t *d_status, hipStream_t stream,
-                   Profiler *prof, const DecStreams *ds) {
-  DecWs ws = ws_in;
-  ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region)
-  const uint32_t *d_avail = d_words;
-  uint32_t *d_tx = d_words + batch, *d_bound = d_words + 2 * (size_t)batch;
-  int32_t *d_k = (int32_t *)(d_words + 3 * (size_t)batch), *d_gate = (int32_t *)(d_words + 4 * (size_t)batch);
-  launch_zero(g, ws, batch, stream, prof);
-  HIMG_LAUNCH(k_prefix_gate, dim3(batch), dim3(64), g, ws, d_packed, in_stride, d_avail, d_tx, d_bound, d_k, d_gate);
-  // The row headers on the side stream beside k_dec_parse_prefix and the LRES chain (launch_region's fork).
-  hipStream_t ws_ = ds ? ds->side : stream;
-  if (ds) {
-    (void)hipEventRecord(ds->ev_fork, stream);
-    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
-  }
-  prof_begin(prof, "k_prefix_rowwalk", ws_);
-  hipLaunchKernelGGL(k_prefix_rowwalk, dim3((batch + 63) / 64), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_bound, d_tx,
-                     d_k, batch);
-  prof_end(prof, ws_);
-  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
-  HIMG_LAUNCH(k_dec_parse_prefix, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, d_tx, d_bound);
-  launch_lres_chain(g, ws, batch, d_packed, in_stride, d_bound, stream, prof);
-  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
-  // The rows that have not arrived: the low-res plane and k_f are all the fill needs.
-  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, d_k, d_out);
-  // Every complete row gets a record (launch_region's rule); the grids cover all rows, a workgroup at or
-  // beyond its frame's k_f returns at once.
+// What the row-span decodes share behind their gates and walks: the fill over w.kfill, the counts and the row
+// kernel over rows [w.k0, w.k1), every load bounded by w.bound.  cmap: the concealing decode's row map, or
+// nullptr.  k1 is known on the device alone, so the grids cover all rows and a workgroup outside its frame's
+// span returns at once.
+static void launch_span_rows(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed, size_t in_stride,
+                             const SpanWords &w, uint8_t *d_cmap, uint8_t *d_out, hipStream_t stream, Profiler *prof) {
+  // The rows that have not arrived: the low-res plane and kfill are all the fill needs.
+  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, w.kfill, d_out);
+  // Every complete row gets a record (launch_region's rule).
   const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
   if (cr.wave) {
-    HIMG_LAUNCH(k_prefix_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
-                d_packed, in_stride, d_bound, d_k);
+    HIMG_LAUNCH(k_span_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
+                d_packed, in_stride, w.bound, w.k0, w.k1);
   } else {
-    HIMG_LAUNCH(k_prefix_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
-                in_stride, d_bound, d_k, cr.rpc);
+    HIMG_LAUNCH(k_span_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
+                in_stride, w.bound, w.k0, w.k1, cr.rpc);
   }
   const int smax = region_strip_tiles(g);
   const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
-  PrefixArgs pa;
-  pa.krows = d_k; pa.sw = sw; pa.out = d_out;
-  prof_begin(prof, "k_dec_prefix", stream);
-  hipLaunchKernelGGL(k_dec_prefix, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
-                     ws, d_packed, in_stride, d_bound, pa);
+  SpanArgs sa;
+  sa.k0 = w.k0; sa.k1 = w.k1; sa.cmap = d_cmap; sa.sw = sw; sa.out = d_out;
+  const dim3 grid(nstrip, g.rows, batch);
+  const uint32_t lds = region_layout(g.C, sw).total;
+  prof_begin(prof, d_cmap ? "k_dec_span<true>" : "k_dec_span<false>", stream);
+  if (d_cmap)
+    hipLaunchKernelGGL(k_dec_span<true>, grid, dim3(kDecThreads), lds, stream, g, ws, d_packed, in_stride, w.bound, sa);
+  else
+    hipLaunchKernelGGL(k_dec_span<false>, grid, dim3(kDecThreads), lds, stream, g, ws, d_packed, in_stride, w.bound, sa);
   prof_end(prof, stream);
-  HIMG_LAUNCH(k_prefix_status, dim3((batch + 63) / 64), dim3(64), ws, d_gate, d_k, d_status, d_rows, batch);
 }
 
-// The prefix decode continued.  d_words: 8 x batch words -- launch_prefix's five, then k_prev, the fill's
-// k_f and the walk's position.  launch_prefix's order, each kernel's incremental form in its place; k_new
-// is known on the device alone, so the grids cover all rows here too.
-void launch_prefix_more(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
-                        uint32_t *d_words, PfxState *d_state, uint8_t *d_out, int32_t *d_rows, int32_t *d_status,
-                        hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+// The decode of stream prefixes, fresh (d_state == nullptr) or continued from the states.  d_words: 8 x batch
+// words -- the bytes present (staged by the caller), then what k_span_gate and k_span_rowwalk leave for the
+// kernels behind them (SpanWords).
+void launch_prefix(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
+                   uint32_t *d_words, PfxState *d_state, uint8_t *d_out, int32_t *d_rows, int32_t *d_status,
+                   hipStream_t stream, Profiler *prof, const DecStreams *ds) {
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region)
   const size_t n = (size_t)batch;
-  MoreWords w;
+  SpanWords w;
   w.avail = d_words; w.tx = d_words + n; w.bound = d_words + 2 * n;
-  w.krows = (int32_t *)(d_words + 3 * n); w.gate = (int32_t *)(d_words + 4 * n);
-  w.kprev = (int32_t *)(d_words + 5 * n); w.kfill = (int32_t *)(d_words + 6 * n);
+  w.k0 = (int32_t *)(d_words + 3 * n); w.k1 = (int32_t *)(d_words + 4 * n);
+  w.gate = (int32_t *)(d_words + 5 * n); w.kfill = (int32_t *)(d_words + 6 * n);
   w.pos = d_words + 7 * n;
   const dim3 per_frame((batch + 63) / 64), b64(64);
   launch_zero(g, ws, batch, stream, prof);
-  HIMG_LAUNCH(k_prefix_gate, dim3(batch), b64, g, ws, d_packed, in_stride, w.avail, w.tx, w.bound, w.krows, w.gate);
-  HIMG_LAUNCH(k_more_gate, per_frame, b64, g, ws, d_state, w, batch);
-  hipStream_t ws_ = ds ? ds->side : stream;
-  if (ds) {
-    (void)hipEventRecord(ds->ev_fork, stream);
-    (void)hipStreamWaitEvent(ws_, ds->ev_fork, 0);
-  }
-  prof_begin(prof, "k_more_rowwalk", ws_);
-  hipLaunchKernelGGL(k_more_rowwalk, per_frame, b64, 0, ws_, g, ws, d_packed, in_stride, w, batch);
+  HIMG_LAUNCH(k_span_gate, dim3(batch), b64, g, ws, d_packed, in_stride, d_state, w);
+  // The row headers on the side stream beside k_dec_parse_prefix and the LRES chain (launch_region's fork).
+  hipStream_t ws_ = side_fork(ds, stream);
+  prof_begin(prof, "k_span_rowwalk", ws_);
+  hipLaunchKernelGGL(k_span_rowwalk, per_frame, b64, 0, ws_, g, ws, d_packed, in_stride, w, batch);
   prof_end(prof, ws_);
-  if (ds) (void)hipEventRecord(ds->ev_walk[0], ws_);
+  side_walked(ds);
   HIMG_LAUNCH(k_dec_parse_prefix, dim3(batch), dim3(kParseThreads), g, ws, d_packed, in_stride, w.tx, w.bound);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, w.bound, stream, prof);
-  if (ds) (void)hipStreamWaitEvent(stream, ds->ev_walk[0], 0);
-  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, w.kfill, d_out);
-  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
-  if (cr.wave) {
-    HIMG_LAUNCH(k_more_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
-                d_packed, in_stride, w.bound, w.kprev, w.krows);
-  } else {
-    HIMG_LAUNCH(k_more_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
-                in_stride, w.bound, w.kprev, w.krows, cr.rpc);
-  }
-  const int smax = region_strip_tiles(g);
-  const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
-  MoreArgs ma;
-  ma.kprev = w.kprev; ma.krows = w.krows; ma.sw = sw; ma.out = d_out;
-  prof_begin(prof, "k_dec_more", stream);
-  hipLaunchKernelGGL(k_dec_more, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
-                     ws, d_packed, in_stride, w.bound, ma);
-  prof_end(prof, stream);
-  HIMG_LAUNCH(k_more_status, per_frame, b64, ws, w, d_state, d_status, d_rows, batch);
+  side_join(ds, stream);
+  launch_span_rows(g, ws, batch, d_packed, in_stride, w, nullptr, d_out, stream, prof);
+  HIMG_LAUNCH(k_span_status, per_frame, b64, ws, w, d_state, d_status, d_rows, batch);
 }
 
-// The concealing decode.  d_words: 4 x batch words -- the packed sizes (staged by the caller), then the full
-// decode's status words, k_f and the gate's classes; d_cmap: batch x rows bytes.  Pass one is launch_decode as
-// himg_hip_decode_device calls it; pass two runs behind it on the caller's stream.
+// The concealing decode.  d_words: 5 x batch words -- the packed sizes (staged by the caller), then the full
+// decode's status words, k_f, the gate's classes and the zeros that are the span's k0; d_cmap: batch x rows
+// bytes.  Pass one is launch_decode as himg_hip_decode_device calls it; pass two runs behind it on the
+// caller's stream.
 void launch_conceal(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *d_packed, size_t in_stride,
                     uint32_t *d_words, uint8_t *d_cmap, uint8_t *d_out, int32_t *d_concealed, uint8_t *d_rowmap,
                     int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho, const DecStreams *ds) {
+  const size_t n = (size_t)batch;
   const uint32_t *d_sizes = d_words;
-  int32_t *d_st1 = (int32_t *)(d_words + batch), *d_k = (int32_t *)(d_words + 2 * (size_t)batch);
-  int32_t *d_act = (int32_t *)(d_words + 3 * (size_t)batch);
+  int32_t *d_st1 = (int32_t *)(d_words + n), *d_k = (int32_t *)(d_words + 2 * n);
+  int32_t *d_act = (int32_t *)(d_words + 3 * n);
+  SpanWords w = {};   // (no gate of the prefix decode's: the loads are bounded by the packed sizes)
+  w.bound = d_words; w.k0 = (int32_t *)(d_words + 4 * n); w.k1 = d_k; w.kfill = d_k;
   launch_decode(g, ws_in, batch, d_packed, in_stride, d_sizes, d_out, d_st1, stream, prof, ho, ds, 0, g.rows);
   DecWs ws = ws_in;
   ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region: they overwrite the full decode's)
   const dim3 per_frame((batch + 63) / 64), b64(64);
-  HIMG_LAUNCH(k_conceal_gate, per_frame, b64, ws, d_st1, d_k, d_act, batch);
+  HIMG_LAUNCH(k_conceal_gate, per_frame, b64, ws, d_st1, w.k0, d_k, d_act, batch);
   const uint32_t n16 = (uint32_t)(ws.lres_stride / 16);
   HIMG_LAUNCH(k_conceal_zero, dim3(n16 / 256 < 64 ? (n16 + 255) / 256 : 64, batch), dim3(256), ws, d_act);
   launch_lres_chain(g, ws, batch, d_packed, in_stride, d_sizes, stream, prof);
   HIMG_LAUNCH(k_conceal_rowwalk, per_frame, b64, g, ws, d_packed, in_stride, d_act, d_k, batch);
   HIMG_LAUNCH(k_conceal_map, dim3((unsigned)(((size_t)batch * g.rows + 255) / 256)), dim3(256), d_act, d_k, d_cmap, g.rows,
               batch);
-  HIMG_LAUNCH(k_prefix_fill, dim3((2 * g.cols + 255) / 256, g.rows, batch), dim3(256), g, ws, d_k, d_out);
-  const CountRule cr = count_rule(g, (long long)batch * g.rows, true);
-  if (cr.wave) {
-    HIMG_LAUNCH(k_prefix_count_w, dim3((g.rows + kCountRowsW - 1) / kCountRowsW, batch), dim3(kDecThreads), cr.g, ws,
-                d_packed, in_stride, d_sizes, d_k);
-  } else {
-    HIMG_LAUNCH(k_prefix_count, dim3((g.rows + cr.rpc - 1) / cr.rpc, batch), dim3(kDecThreads), cr.g, ws, d_packed,
-                in_stride, d_sizes, d_k, cr.rpc);
-  }
-  const int smax = region_strip_tiles(g);
-  const int nstrip = (g.cols + smax - 1) / smax, sw = (g.cols + nstrip - 1) / nstrip;
-  ConcealArgs ca;
-  ca.krows = d_k; ca.cmap = d_cmap; ca.sw = sw; ca.out = d_out;
-  prof_begin(prof, "k_dec_conceal", stream);
-  hipLaunchKernelGGL(k_dec_conceal, dim3(nstrip, g.rows, batch), dim3(kDecThreads), region_layout(g.C, sw).total, stream, g,
-                     ws, d_packed, in_stride, d_sizes, ca);
-  prof_end(prof, stream);
+  launch_span_rows(g, ws, batch, d_packed, in_stride, w, d_cmap, d_out, stream, prof);
   HIMG_LAUNCH(k_conceal_status, dim3(batch), b64, ws, d_st1, d_act, d_cmap, g.rows, d_rowmap, d_status, d_concealed);
 }
 

@@ -1,6 +1,6 @@
 // prefix_walk.h -- the walk over a stream PREFIX: the first `avail` bytes of a stream whose RIFF
 // header declares T bytes (include/himg_hip.h, "decode a stream prefix").  One copy of the rules for
-// the host (himg_hip_prefix_peek) and the device (k_prefix_gate, k_prefix_rowwalk): every load is
+// the host (himg_hip_prefix_peek) and the device (k_span_gate, k_span_rowwalk): every load is
 // checked against `avail` first, every container bound against T.
 #ifndef HIMG_PREFIX_WALK_H_
 #define HIMG_PREFIX_WALK_H_
@@ -112,51 +112,33 @@ __host__ __device__ inline int pfx_tree_len(const uint8_t *tree, uint32_t have, 
   return *bytes > have ? kPfxShort : kPfxOk;
 }
 
-// The row headers from `q` (the first one) to the chunk's end by k_dec_rowwalk's rules, for as long as
-// a header and its payload lie wholly below avail (huffman_dec.cpp:232-248).
+// One row header at `q` by k_dec_rowwalk's rules (huffman_dec.cpp:232-248): two bytes of length, or four
+// with the top bit of the first pair set, header and payload inside the chunk (`end`) and below `avail`.
+// kPfxOk: the payload is bytes [*body, *body + *len).  kPfxShort: *need is the least avail at which the
+// step passes.  (A caller that holds the whole chunk passes avail = end and sees no kPfxShort.)
+__host__ __device__ inline int pfx_row_header(const uint8_t *p, uint32_t q, uint32_t end, uint32_t avail, uint32_t *body,
+                                              uint32_t *len, uint32_t *need) {
+  if (q + 2 > end) return kPfxFormat;
+  if (q + 2 > avail) return *need = q + 2, kPfxShort;
+  uint32_t n = (uint32_t)p[q] | ((uint32_t)p[q + 1] << 8), b = q + 2;
+  if (n & 0x8000u) {
+    if (b + 2 > end) return kPfxFormat;
+    if (b + 2 > avail) return *need = b + 2, kPfxShort;
+    n = (n & 0x7fffu) | (((uint32_t)p[b] | ((uint32_t)p[b + 1] << 8)) << 15);
+    b += 2;
+  }
+  if (n > end - b) return kPfxFormat;
+  if (b + n > avail) return *need = b + n, kPfxShort;
+  *body = b; *len = n;
+  return kPfxOk;
+}
+
+// What a walk over the row headers finds: the rows whose header and payload lie wholly below avail.
 struct PfxRows {
   int k;             // complete rows, at most `rows`
   uint32_t used;     // where row k - 1's payload ends (q for k = 0)
   uint32_t next;     // the least avail at which more rows could be complete (T for k == rows)
 };
-__host__ __device__ inline int pfx_rows(const uint8_t *p, uint32_t avail, uint32_t T, int fix_t2, int rows, uint32_t q,
-                                        uint32_t end, uint32_t *row_off, uint32_t *row_len, PfxRows *out) {
-  out->k = 0; out->used = q; out->next = T;
-  if (fix_t2 && rows == 1) {   // the encoder writes one block row without a size header
-    if (end <= avail) {
-      out->k = 1; out->used = end;
-      if (row_off) { row_off[0] = q; row_len[0] = end - q; }
-    } else {
-      out->next = end;
-    }
-    return kPfxOk;
-  }
-  int r = 0;
-  bool cut = false;
-  while (q != end) {
-    if (q + 2 > end) return kPfxFormat;
-    if (q + 2 > avail) { cut = true; out->next = q + 2; break; }
-    uint32_t len = (uint32_t)p[q] | ((uint32_t)p[q + 1] << 8), b = q + 2;
-    if (len & 0x8000u) {
-      if (b + 2 > end) return kPfxFormat;
-      if (b + 2 > avail) { cut = true; out->next = b + 2; break; }
-      len = (len & 0x7fffu) | (((uint32_t)p[b] | ((uint32_t)p[b + 1] << 8)) << 15);
-      b += 2;
-    }
-    if (len > end - b) return kPfxFormat;
-    if (b + len > avail) { cut = true; out->next = b + len; break; }
-    if (r < rows) {
-      if (row_off) { row_off[r] = b; row_len[r] = len; }
-      out->used = b + len;
-    }
-    ++r;
-    q = b + len;
-  }
-  if (!cut && r < rows) return kPfxFormat;   // fewer blocks than block rows
-  out->k = r < rows ? r : rows;
-  if (out->k == rows) out->next = T;
-  return kPfxOk;
-}
 
 // The state a caller keeps between the calls of the incremental prefix decode (himg_hip_prefix_state of
 // include/himg_hip.h, field for field).
@@ -174,16 +156,16 @@ __host__ __device__ inline bool pfx_state_ok(const PfxState &s, uint32_t avail, 
          s.walk_pos <= avail;
 }
 
-// pfx_rows resumed: the walk stands at `q` = PfxRows::used of an earlier walk over fewer (or as many) bytes
-// of the same stream, which found r0 complete rows.  Same rules, same result as pfx_rows from the first
-// header; row_off / row_len are written for rows [r0, k) only.  (A copy of the loop, not a call from
-// pfx_rows: that one keeps its code.)  Where the chunk holds blocks behind the last block row, `used`
-// stays at the last row's end and their headers are walked again by every call.
+// The row headers from `q` to the chunk's end, for as long as a header and its payload lie wholly below
+// avail.  The walk stands at `q` = PfxRows::used of an earlier walk over fewer (or as many) bytes of the same
+// stream, which found r0 complete rows (r0 = 0: q is the first header); row_off / row_len are written for
+// rows [r0, k) only.  Where the chunk holds blocks behind the last block row, `used` stays at the last row's
+// end and their headers are walked again by every call.
 __host__ __device__ inline int pfx_rows_from(const uint8_t *p, uint32_t avail, uint32_t T, int fix_t2, int rows,
                                              uint32_t q, int r0, uint32_t end, uint32_t *row_off, uint32_t *row_len,
                                              PfxRows *out) {
   out->k = r0; out->used = q; out->next = T;
-  if (fix_t2 && rows == 1) {   // one block row without a size header
+  if (fix_t2 && rows == 1) {   // the encoder writes one block row without a size header
     if (r0 == 0) {
       if (end <= avail) {
         out->k = 1; out->used = end;
@@ -197,17 +179,10 @@ __host__ __device__ inline int pfx_rows_from(const uint8_t *p, uint32_t avail, u
   int r = r0;
   bool cut = false;
   while (q != end) {
-    if (q + 2 > end) return kPfxFormat;
-    if (q + 2 > avail) { cut = true; out->next = q + 2; break; }
-    uint32_t len = (uint32_t)p[q] | ((uint32_t)p[q + 1] << 8), b = q + 2;
-    if (len & 0x8000u) {
-      if (b + 2 > end) return kPfxFormat;
-      if (b + 2 > avail) { cut = true; out->next = b + 2; break; }
-      len = (len & 0x7fffu) | (((uint32_t)p[b] | ((uint32_t)p[b + 1] << 8)) << 15);
-      b += 2;
-    }
-    if (len > end - b) return kPfxFormat;
-    if (b + len > avail) { cut = true; out->next = b + len; break; }
+    uint32_t b = 0, len = 0;
+    const int rc = pfx_row_header(p, q, end, avail, &b, &len, &out->next);
+    if (rc == kPfxFormat) return kPfxFormat;
+    if (rc == kPfxShort) { cut = true; break; }
     if (r < rows) {
       if (row_off) { row_off[r] = b; row_len[r] = len; }
       out->used = b + len;
@@ -219,6 +194,12 @@ __host__ __device__ inline int pfx_rows_from(const uint8_t *p, uint32_t avail, u
   out->k = r < rows ? r : rows;
   if (out->k == rows) out->next = T;
   return kPfxOk;
+}
+
+// The walk from the first row header.
+__host__ __device__ inline int pfx_rows(const uint8_t *p, uint32_t avail, uint32_t T, int fix_t2, int rows, uint32_t q,
+                                        uint32_t end, uint32_t *row_off, uint32_t *row_len, PfxRows *out) {
+  return pfx_rows_from(p, avail, T, fix_t2, rows, q, 0, end, row_off, row_len, out);
 }
 
 }  // namespace himg_dev

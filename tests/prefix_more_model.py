@@ -100,3 +100,19 @@ def step(model, st, avail):
     if not st["started"]:
         return pm.OK, k, (0, model.rows), new
     return pm.OK, k, ((st["rows_done"], k) if k > st["rows_done"] else None), new
+
+
+def mixed_batch(model):
+    """Six (state, avail, code) for ONE launch over model's stream (five block rows): the kinds of frame the
+    gate must keep apart when they share its per-frame words.  code: what step() must say of each.  The
+    resumed states are the model's own, each reached by one step from a fresh one."""
+    e = model.row_ends()
+    assert len(e) == 6 and model.T // 2 > e[1]
+    rows_st = step(model, state(), e[1] + 1)[3]      # one row done, the walk behind it
+    idle_st = step(model, state(), e[2] + 3)[3]      # two rows done, three bytes of the next header seen
+    return [(state(), model.T // 2, pm.OK),                # fresh, about half the stream
+            (rows_st, e[3], pm.OK),                        # resumed: rows 1 and 2 are new
+            (idle_st, e[2] + 3, pm.OK),                    # resumed: no new bytes
+            (state(), e[0] - 1, pm.CAPACITY),              # the bytes end inside the head
+            (state(1, 3, e[3], e[1]), e[2], ARG),          # resumed, walk_pos beyond avail
+            (state(), model.T, pm.OK)]                     # fresh, the whole stream

@@ -236,6 +236,30 @@ def test_more_frames_than_cus(eng, wave):
     assert seen[0][1] == -1 and seen[1][3] == -1 and (seen[2] >= 0).all()
 
 
+@pytest.mark.parametrize("wave", [0, 1])
+def test_six_kinds_of_frame_in_one_launch(eng, wave):
+    """Six frames of 72 x 40 x 3 (five block rows, q50) in ONE call, under both count kernels: fresh at half the
+    stream, resumed with new rows, resumed with no new bytes, below the head (capacity), a state that cannot
+    be right (argument), fresh at the whole stream (prefix_more_model.mixed_batch; its verdicts are checked on
+    the host in test_prefix_more_host).  The frames share the launch's per-frame words and one gate: each must
+    come out as the model says -- status, rows, state, picture, and the sentinel outside a resumed frame's new
+    rows -- whatever its neighbours are."""
+    eng.set_option("count_wave", wave)
+    m = _model("randtile", 72, 40, 3)
+    cases = mm.mixed_batch(m)
+    want = [mm.step(m, st, a) for st, a, _ in cases]
+    assert [x[0] for x in want] == [c[2] for c in cases] == [0, 0, 0, pm.CAPACITY, mm.ARG, 0]
+    assert [x[2] for x in want] == [(0, 5), (1, 3), None, None, None, (0, 5)]
+    ch = Chain(eng, [m] * 6)
+    ch.set_states([c[0] for c in cases])
+    rows = ch.step([c[1] for c in cases], what=("mixed", wave))
+    assert list(rows) == [1, 3, 2, -1, -1, 5]
+    st, _, out, _ = ch.read()
+    assert list(st) == [0, 0, 0, ST_SHORT, ST_ARG, 0]
+    assert (out[3] == SENTINEL).all() and (out[4] == SENTINEL).all()   # a verdict: nothing of the picture written
+    assert ch.states[3] == cases[3][0] and ch.states[4] == cases[4][0]
+
+
 @pytest.mark.parametrize("W,H,Cn,ycc,fix", [(100, 45, 3, True, False), (37, 19, 1, True, False), (72, 40, 3, False, False),
                                             (40, 8, 4, True, True)])
 def test_ragged_shapes_and_few_channels(eng, W, H, Cn, ycc, fix):

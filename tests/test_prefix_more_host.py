@@ -115,6 +115,22 @@ def test_peek_from_against_the_model(name):
             _same(piece, st, a, m.fix_t2)
 
 
+def test_mixed_batch_verdicts():
+    """prefix_more_model.mixed_batch -- the six frames test_gpu_prefix_more sends through one launch -- gives its
+    six intended verdicts, by the model and by himg_hip_prefix_peek_from."""
+    img = np.ascontiguousarray(himg_amd.synth("randtile", 0, 72, 40)[:, :, :3])
+    m = pm.Model(np.frombuffer(ol.oracle_encode(img, 50, True), np.uint8).copy())
+    cases = mm.mixed_batch(m)
+    assert [c[2] for c in cases] == [0, 0, 0, himg_amd.HIMG_ERR_CAPACITY, himg_amd.HIMG_ERR_ARG, 0]
+    got = [mm.step(m, st, a) for st, a, _ in cases]
+    assert [g[0] for g in got] == [c[2] for c in cases]
+    assert [g[1] for g in got] == [1, 3, 2, -1, -1, 5]
+    assert [g[2] for g in got] == [(0, 5), (1, 3), None, None, None, (0, 5)]
+    for (st, a, code), g in zip(cases, got):
+        assert _same(m.packed[:a].copy(), st, a, False)[0] == code, (st, a)
+        assert g[3] == (dict(st) if code else mm.state(1, g[1], m.row_ends()[g[1]], a))
+
+
 def test_impossible_states():
     m, _ = _case("randtile64")
     b, e = m.packed, m.row_ends()

@@ -175,9 +175,9 @@ for name, av in (("no_new_bytes", half), ("one_new_row", nxt)):
         more(av)
     torch.cuda.synchronize()
     st = {k: v[0] / v[1] for k, v in eng.profile_read().items() if v[1]}
-    walk = sum(v for k, v in st.items() if k == "k_more_rowwalk")
-    grids = sum(v for k, v in st.items() if k in ("k_prefix_fill", "k_more_count", "k_more_count_w", "k_dec_more"))
-    ends = sum(v for k, v in st.items() if k in ("k_prefix_gate", "k_more_gate", "k_more_status"))
+    walk = sum(v for k, v in st.items() if k == "k_span_rowwalk")
+    grids = sum(v for k, v in st.items() if k in ("k_prefix_fill", "k_span_count", "k_span_count_w", "k_dec_span<false>"))
+    ends = sum(v for k, v in st.items() if k in ("k_span_gate", "k_span_status"))
     floor["stages_%s_ms_per_launch" % name] = {
         "head_parse_and_lres_chain": sum(st.values()) - walk - grids - ends, "resumed_walk": walk,
         "full_height_grids_fill_count_rows": grids, "gates_and_status": ends, "all": st}
