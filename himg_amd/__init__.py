@@ -122,6 +122,9 @@ def lib():
     L.himg_hip_decode_region_to.argtypes = [vp, vp, sz, i32, i32, i32, i32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_decode_region_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]
     L.himg_hip_decode_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp]
+    L.himg_hip_decode_stream_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_stream_regions_peek.argtypes = [vp, sz, i32, i32, vp, i32, i32, vp, vp, P(i32)]
+    L.himg_hip_decode_stream_regions_to.argtypes = [vp, vp, sz, i32, vp, i32, i32, vp, sz, vp, P(i32), P(i32), P(i32)]
     L.himg_hip_tensor_bytes.argtypes = [vp, i32, i32, i32, P(sz)]
     L.himg_hip_decode_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_regions_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
@@ -645,6 +648,48 @@ class Engine:
                                                   height, channels, org.ctypes.data, int(w), int(h), _ptr(d_out),
                                                   _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_regions_device")
+
+    def decode_stream_regions_device(self, d_packed, in_stride, h_sizes, n_streams, width, height, channels,
+                                     stream_of, origins, w, h, d_out, d_status, stream=0):
+        """himg_hip_decode_stream_regions_device: window k is the w x h rectangle at origins[k] of stream
+        stream_of[k] (both on the host; any order, repeats and overlaps allowed); d_out holds
+        n_windows x h x w x C bytes (window k at k * h * w * C), d_status n_windows words.  A stream's head
+        runs once however many windows name it; every window's bytes and status are decode_regions_device's
+        for that stream with that rectangle alone."""
+        hs = None if h_sizes is None else np.ascontiguousarray(h_sizes, np.uint32)
+        so = None if stream_of is None else np.ascontiguousarray(np.asarray(stream_of, np.int32).ravel())
+        org = None if origins is None else np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = 0 if so is None else int(so.size)
+        if org is not None and so is not None and org.shape[0] != n:
+            raise ValueError("stream_of and origins differ in length")
+        rc = lib().himg_hip_decode_stream_regions_device(
+            self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data if hs is not None else None, int(n_streams), width,
+            height, channels, so.ctypes.data if n else None, org.ctypes.data if org is not None and org.size else None,
+            n, int(w), int(h), _ptr(d_out), _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_stream_regions_device")
+
+    def decode_stream_regions(self, packed, origins, w, h, out=None):
+        """himg_hip_decode_stream_regions_to: n windows of w x h at origins[k] = (x, y) of ONE host stream, as
+        ((n, h, w, C) uint8 array, statuses): statuses[k] is 0 or window k's error code, and a failed window's
+        pixels are unspecified.  Only the stream's head and the union of the windows' block rows are uploaded
+        (stream_regions_peek).  Raises HimgError only where no window could run (a bad stream or rectangle)."""
+        packed = _as_u8(packed)
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = org.shape[0]
+        st = np.zeros(max(n, 1), np.int32)
+        wo, ho, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        geom = _peek(packed)
+        if geom:
+            cap = n * max(int(w), 0) * max(int(h), 0) * geom[2]
+            out = _out_buffer(out, cap)
+            dst = out.ctypes.data
+        rc = lib().himg_hip_decode_stream_regions_to(self._ctx, packed.ctypes.data, packed.nbytes, n, org.ctypes.data,
+                                                     int(w), int(h), dst, cap, st.ctypes.data, C.byref(wo),
+                                                     C.byref(ho), C.byref(c))
+        if rc != 0 and (wo.value == 0 or rc == HIMG_ERR_CAPACITY):
+            self._check(rc, "decode_stream_regions")
+        return out.ravel()[: n * ho.value * wo.value * c.value].reshape(n, ho.value, wo.value, c.value), st[:n].copy()
 
     def decode_regions_tensor_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, origins,
                                      w, h, desc, d_out, d_status, stream=0):
@@ -1341,6 +1386,26 @@ def region_peek(packed, x, y, w, h, fix_t2=False):
     if rc != 0:
         raise HimgError(rc, "region_peek")
     return {k: getattr(plan, k) for k, _ in RegionPlan._fields_}
+
+
+def stream_regions_peek(packed, origins, w, h, fix_t2=False):
+    """himg_hip_stream_regions_peek (no GPU): (plans, ranges) for n windows of w x h at origins[k] = (x, y)
+    of one stream.  plans[k] is region_peek's dict for window k, or its int error code where it has no plan
+    (HIMG_ERR_ARG for a bad rectangle, HIMG_ERR_FORMAT where the header chain breaks before its last row);
+    ranges is the sorted, disjoint list of (begin, end) byte ranges a caller must have present:
+    [0, head_bytes) and the union of the planned windows' [rows_begin, rows_end)."""
+    a = _as_u8(packed)
+    org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+    n = org.shape[0]
+    plans = (RegionPlan * max(n, 1))()
+    rng = np.zeros(2 * (n + 1), np.uintp)
+    nr = C.c_int(0)
+    rc = lib().himg_hip_stream_regions_peek(a.ctypes.data, a.nbytes, 1 if fix_t2 else 0, n, org.ctypes.data, int(w),
+                                            int(h), plans, rng.ctypes.data, C.byref(nr))
+    if n < 1:
+        raise HimgError(rc, "stream_regions_peek")
+    out = [{k: getattr(p, k) for k, _ in RegionPlan._fields_} if p.row1 > 0 else int(p.row0) for p in plans[:n]]
+    return out, [(int(rng[2 * i]), int(rng[2 * i + 1])) for i in range(nr.value)]
 
 
 class PrefixPlan(C.Structure):

@@ -3,7 +3,9 @@
 // kRegionTens and td, kRegionPitch and pd (the descriptors, or nullptr) defined, so that k_dec_region
 // keeps its code instruction for instruction.  kRegionConceal and cmap (k_dec_span<true>; false and unused
 // everywhere else): a row the checks reject is not the frame's verdict -- its byte cmap[f * rows + r] is
-// set and its tiles are stored as those of a row of zero symbols.
+// set and its tiles are stored as those of a row of zero symbols.  kRegionMap, smap and wstat
+// (k_dec_stream_region; false and unused everywhere else): blockIdx.z is a WINDOW -- its origin, its output
+// slot and its verdict word wstat[f] -- of stream fs = smap[f], whose records, tables and planes it reads.
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const RegionLayout L = region_layout(g.C, ra.sw);
   LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
@@ -13,6 +15,8 @@
   const uint32_t *s_shiftp = reinterpret_cast<const uint32_t *>(smem + L.rowtab + 640);
   uint8_t *sym = smem + L.sym;
   const int tid = threadIdx.x, f = blockIdx.z;
+  int fs = f;
+  if constexpr (kRegionMap) fs = __builtin_amdgcn_readfirstlane(smap[f]);
   // The frame's own rectangle: its rows and tile columns; a workgroup past either has nothing to do.
   RegionRect rr;
   rr.x = ra.org[2 * f]; rr.y = ra.org[2 * f + 1]; rr.w = ra.w; rr.h = ra.h;
@@ -20,11 +24,14 @@
   const int su0 = rr.x / 8 + (int)blockIdx.x * ra.sw;
   if (r >= (rr.y + rr.h + 7) / 8 || su0 >= u1) return;
   const int ww = min(ra.sw, u1 - su0);
-  DecFrame *df = ws.frames + f;
-  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
+  DecFrame *df = ws.frames + fs;
+  if (tid == 0) {
+    sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull;
+    if constexpr (kRegionMap) sh->flag |= wstat[f];   // (the stream's head verdict, or this window's own)
+  }
   __syncthreads();
   if (sh->flag) return;
-  load_dec_tables(ws, df, f, 1, &T);
+  load_dec_tables(ws, df, fs, 1, &T);
   if (tid < kRowTabWords / 4)
     reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
   const uint32_t nsym16 = (L.seg * 64u * (uint32_t)g.C + 15u) / 16u;
@@ -38,10 +45,10 @@
   const bool strict = __syncthreads_or((nn <= 1) || (kRegionConceal && gridDim.x > 1) ||
                                        ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
 
-  const size_t ri = (size_t)f * g.rows + (size_t)r;
+  const size_t ri = (size_t)fs * g.rows + (size_t)r;
   const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
+  const uint8_t *p = packed + (size_t)fs * in_stride;
+  const uint32_t end = (uint32_t)min((unsigned long long)sizes[fs], (unsigned long long)pay_off + pay_len);
   const GrpTables tb = tables_of(&T);
   RegionWin win;
   win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
@@ -98,12 +105,13 @@
       for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
       __syncthreads();
     } else {
-      if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+      if constexpr (kRegionMap) { if (tid == 0) atomicMax(&wstat[f], fmt_err(7, 1)); }
+      else if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
       return;
     }
   }
   // ---- the strip's tiles: transform, colour inverse, cropped stores ----
-  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
+  const uint8_t *low = ws.low + (size_t)fs * ws.plane_stride;
   uint8_t *img;
   if constexpr (kRegionTens) img = ra.out + (size_t)f * ((size_t)ra.h * ra.w * (size_t)(td->co * tens_elem_size(td->dtype)));
   else if constexpr (kRegionPitch) img = dst_frame(ra.out, pd, f);

@@ -1,3 +1,5 @@
+  // (Also included under a SHADOWED blockIdx -- k_stream_count / k_stream_count_w give a list entry's stream as
+  // .y and 0 as .x: this body may read blockIdx.x and blockIdx.y only, never blockIdx.z or gridDim.)
   // Both tables as two arrays: the step words (gy), then their .x words (gx).
   __shared__ __attribute__((aligned(16))) uint32_t gyx[2 * kTabEntries];
   __shared__ __attribute__((aligned(16))) uint32_t s_pay[LDSPAY ? kPayWords : 4];   // the row's payload

@@ -1,3 +1,5 @@
+  // (Also included under a SHADOWED blockIdx -- k_stream_count / k_stream_count_w give a list entry's stream as
+  // .y and 0 as .x: this body may read blockIdx.x and blockIdx.y only, never blockIdx.z or gridDim.)
   __shared__ __attribute__((aligned(16))) uint32_t gyx[2 * kTabEntries];
   __shared__ uint32_t nd[kMaxNodes + 1];
   __shared__ __attribute__((aligned(16))) uint32_t s_stage[kCountRowsW * (NQ > 1 ? kLaneAlloc : kStageAlloc)];

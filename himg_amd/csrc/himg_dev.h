@@ -440,6 +440,24 @@ void launch_region(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_p
                    int scale_log2, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof,
                    const DecStreams *ds,
                    const StoreForm &form = StoreForm());   // (scale_log2 = 0 only: kStoreTens, [batch][co][h][w]; kStorePitch, windows of the pictures)
+// Many windows of one stream (include/himg_hip.h, himg_hip_decode_stream_regions_device): window k, the
+// w x h rectangle at (org[2 k], org[2 k + 1]) of stream stream_of[k], to d_out + k h w C and d_status[k].
+// The head phase runs once per stream; the walk once per stream, to row_end[s] (the largest r1_k of its
+// windows, 0x7fffffff to the end of the chunk where one reaches the last block row, 0 for a stream no window
+// names) -- or, with d_row_index, the host's index of rows [index_rows[2 s], index_rows[2 s + 1]) --; the
+// counts run over list, n_list entries (stream, first row, end row) of at most stream_count_chunk() rows,
+// every touched (stream, row) once; the row kernel over (strip, row, window).  The words are device
+// pointers, staged by the caller behind the packed sizes; scratch: 2 n_streams + n_windows words.  h_org:
+// the origins on the host.  The workspace of launch_region.
+struct StreamRegionWords {
+  const int32_t *stream_of, *org, *row_end, *list, *index_rows;
+  int32_t *scratch;
+};
+int stream_count_chunk(const Geom &g, long long list_rows);
+void launch_stream_regions(const Geom &g, const DecWs &ws, int n_streams, const uint8_t *d_packed, size_t in_stride,
+                           const uint32_t *d_sizes, const uint32_t *d_row_index, const StreamRegionWords &d_words,
+                           int n_windows, const int32_t *h_org, int n_list, long long list_rows, int w, int h,
+                           uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
 // The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
 // k_span_gate (the head of the stream with every load checked against the bytes present, then the frame's
 // state against what it found), the head phase in its prefix form (k_dec_parse_prefix, the LRES chain

@@ -2560,6 +2560,96 @@ extern "C" int himg_hip_decode_regions_device(himg_hip_ctx *ctx, const void *d_p
                        d_out, d_status, stream);
 }
 
+// Many windows of one stream (kernels_dec.hip, launch_stream_regions): window k is the w x h rectangle at
+// (h_org[2 k], h_org[2 k + 1]) of stream h_stream_of[k].  Every map entry and rectangle is checked before
+// anything is launched.  The host holds every window, so it plans what the device shares between them: where
+// each stream's walk stops, and the runs of block rows to count, each touched (stream, row) once.  All of it
+// rides with the sizes in one pinned slot; the walk's and the windows' words follow it in d_sizes.
+// d_row_index (one host stream, himg_hip_decode_stream_regions_to): the host's index of rows
+// [index_rows[0], index_rows[1]).
+static int stream_regions_launch(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes,
+                                 int n_streams, int width, int height, int num_channels, const int32_t *h_stream_of,
+                                 const int32_t *h_org, int n_windows, int w, int h, const uint32_t *d_row_index,
+                                 const int32_t *index_rows, void *d_out, int32_t *d_status, void *stream) {
+  const char *bad = nullptr;
+  for (int k = 0; k < n_windows && !bad; ++k) {
+    if (h_stream_of[k] < 0 || h_stream_of[k] >= n_streams) bad = "stream_of outside the streams";
+    else if (!region_ok(width, height, h_org[2 * k], h_org[2 * k + 1], w, h)) bad = "bad rectangle";
+  }
+  Geom g;
+  if (!bad && height > 0 && num_channels > 0 && ((height + 7) / 8 + 1 > 65535 || (long long)n_streams * num_channels > 65535))
+    bad = "grid too large";   // (HIMG_ERR_ARG here, like every other check of this entry)
+  if (int rc = decode_args(ctx, width, height, num_channels, n_streams, kWsRegion, d_packed, d_out, &in_stride, bad, &g))
+    return rc;
+  // Each stream's touched rows: its windows' [r0_k, r1_k) sorted and merged.
+  std::vector<std::vector<std::pair<int, int>>> runs(n_streams);
+  for (int k = 0; k < n_windows; ++k)
+    runs[h_stream_of[k]].push_back({h_org[2 * k + 1] / 8, (h_org[2 * k + 1] + h + 7) / 8});
+  long long list_rows = 0;
+  std::vector<int32_t> row_end(n_streams, 0);
+  for (int s = 0; s < n_streams; ++s) {
+    auto &v = runs[s];
+    if (v.empty()) continue;
+    std::sort(v.begin(), v.end());
+    size_t m = 0;
+    for (size_t i = 1; i < v.size(); ++i) {
+      if (v[i].first <= v[m].second) v[m].second = v[i].second > v[m].second ? v[i].second : v[m].second;
+      else v[++m] = v[i];
+    }
+    v.resize(m + 1);
+    for (const auto &r : v) list_rows += r.second - r.first;
+    row_end[s] = v.back().second == g.rows ? 0x7fffffff : v.back().second;
+  }
+  const int chunk = himg_dev::stream_count_chunk(g, list_rows);
+  // The words: sizes, stream_of, origins, row_end, index_rows, then the count list.
+  const size_t o_map = (size_t)n_streams, o_org = o_map + n_windows, o_end = o_org + 2 * (size_t)n_windows,
+               o_idx = o_end + n_streams, o_list = o_idx + 2 * (size_t)n_streams;
+  std::vector<uint32_t> words(o_list);
+  memcpy(words.data(), h_sizes, (size_t)n_streams * 4);
+  memcpy(words.data() + o_map, h_stream_of, (size_t)n_windows * 4);
+  memcpy(words.data() + o_org, h_org, (size_t)n_windows * 8);
+  memcpy(words.data() + o_end, row_end.data(), (size_t)n_streams * 4);
+  for (int s = 0; s < n_streams; ++s) {
+    words[o_idx + 2 * s] = index_rows ? (uint32_t)index_rows[2 * s] : 0u;
+    words[o_idx + 2 * s + 1] = index_rows ? (uint32_t)index_rows[2 * s + 1] : 0u;
+  }
+  for (int s = 0; s < n_streams; ++s)
+    for (const auto &r : runs[s])
+      for (int a = r.first; a < r.second; a += chunk) {
+        words.push_back((uint32_t)s); words.push_back((uint32_t)a);
+        words.push_back((uint32_t)(a + chunk < r.second ? a + chunk : r.second));
+      }
+  const size_t n_list = (words.size() - o_list) / 3, n_scratch = 2 * (size_t)n_streams + n_windows;
+  if (n_list > 0x7fffffffu) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_sizes.reserve((words.size() + n_scratch) * 4)) return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
+  if (int rc = ensure_dec_ws(ctx, g, n_streams, kWsRegion)) return rc;
+  ctx->last_stream = (hipStream_t)stream;
+  if (int rc = stage_words(ctx, ctx->d_sizes.p, words.data(), words.size(), nullptr, 0, ctx->last_stream)) return rc;
+  const uint32_t *d_sizes = (const uint32_t *)ctx->d_sizes.p;
+  const int32_t *dw = (const int32_t *)d_sizes;
+  const himg_dev::StreamRegionWords sw = {dw + o_map, dw + o_org, dw + o_end, dw + o_list, dw + o_idx,
+                                          (int32_t *)ctx->d_sizes.p + words.size()};
+  himg_dev::launch_stream_regions(g, ctx->dec_ws, n_streams, (const uint8_t *)d_packed, in_stride, d_sizes, d_row_index, sw,
+                                  n_windows, h_org, (int)n_list, list_rows, w, h, (uint8_t *)d_out, d_status,
+                                  (hipStream_t)stream, &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_stream_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                                     const uint32_t *h_sizes, int n_streams, int width, int height,
+                                                     int num_channels, const int32_t *h_stream_of,
+                                                     const int32_t *h_origins, int n_windows, int w, int h, void *d_out,
+                                                     int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !h_stream_of || !h_origins || !d_out || !d_status || n_streams < 1 ||
+      n_streams > 65535 || n_windows < 1 || n_windows > 65535)
+    return HIMG_ERR_ARG;
+  if (int rc = stride_covers(ctx, h_sizes, n_streams, in_stride)) return rc;
+  return stream_regions_launch(ctx, d_packed, in_stride, h_sizes, n_streams, width, height, num_channels, h_stream_of,
+                               h_origins, n_windows, w, h, nullptr, nullptr, d_out, d_status, stream);
+}
+
 extern "C" int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
                                                      const uint32_t *h_sizes, int batch, int width, int height,
                                                      int num_channels, const int32_t *h_origins, int w, int h,
@@ -3023,6 +3113,139 @@ extern "C" int himg_hip_decode_scaled_regions_batch(himg_hip_ctx *ctx, const uin
   if (!ctx) return HIMG_ERR_ARG;
   if (scale_log2 != 1 && scale_log2 != 2) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1 or 2");
   return regions_batch(ctx, packed, packed_sizes, n, scale_log2, rects, dst, dst_cap, widths, heights, channels);
+}
+
+// The windows' plans and the merged, sorted byte ranges of those that have one: [0, head_bytes), then the
+// union of their [rows_begin, rows_end).  codes[k]: region_index's for window k; returns the first error.
+// One walk serves every window of a sound stream: host_walk to the largest r1_k (to the end of the chunk where
+// a window reaches the last block row) with its index of rows [0, r1) -- row r's header starts where row r - 1
+// ends, row 0's at head_bytes.  row_index (2 x rows words, or nullptr for scratch of its own) keeps that index.
+// Only where that walk fails -- a damaged header chain, which leaves the windows above the break their plans --
+// each window is walked on its own.
+static int stream_regions_plan(const uint8_t *packed, size_t packed_size, int fix_t2, int n, const int32_t *origins,
+                               int w, int h, himg_hip_region_plan *plans, int *codes, std::vector<size_t> *ranges,
+                               uint32_t *row_index = nullptr) {
+  int first = HIMG_OK, W = 0, H = 0, C = 0;
+  size_t head = 0;
+  std::vector<std::pair<size_t, size_t>> v;
+  const int peek = himg_hip_peek(packed, packed_size, &W, &H, &C);
+  const int rows = (H + 7) / 8;
+  int rmax = 0;
+  for (int k = 0; k < n; ++k) {
+    plans[k] = himg_hip_region_plan();
+    codes[k] = peek;
+    if (peek) continue;
+    plans[k].width = W; plans[k].height = H; plans[k].num_channels = C;
+    if (!region_ok(W, H, origins[2 * k], origins[2 * k + 1], w, h)) { codes[k] = HIMG_ERR_ARG; continue; }
+    plans[k].row0 = origins[2 * k + 1] / 8; plans[k].row1 = (origins[2 * k + 1] + h + 7) / 8;
+    rmax = plans[k].row1 > rmax ? plans[k].row1 : rmax;
+  }
+  std::vector<uint32_t> own;
+  if (!row_index && rmax) { own.resize(2 * (size_t)rows); row_index = own.data(); }
+  himg_hip_region_plan all = himg_hip_region_plan();
+  const bool sound = rmax && host_walk(packed, packed_size, fix_t2, rows, 0, rmax, &all, row_index) == HIMG_OK;
+  for (int k = 0; k < n; ++k) {
+    if (codes[k] == HIMG_OK && sound) {
+      const int r0 = plans[k].row0, r1 = plans[k].row1;
+      plans[k].head_bytes = all.head_bytes;
+      plans[k].rows_begin = r0 ? (size_t)row_index[r0 - 1] + row_index[rows + r0 - 1] : all.head_bytes;
+      plans[k].rows_end = (size_t)row_index[r1 - 1] + row_index[rows + r1 - 1];
+    } else if (codes[k] == HIMG_OK) {
+      codes[k] = host_walk(packed, packed_size, fix_t2, rows, plans[k].row0, plans[k].row1, &plans[k], nullptr);
+    }
+    if (plans[k].head_bytes) head = plans[k].head_bytes;
+    if (codes[k] == HIMG_OK) v.push_back({plans[k].rows_begin, plans[k].rows_end});
+    else if (!first) first = codes[k];
+  }
+  ranges->clear();
+  if (head) v.push_back({0, head});
+  std::sort(v.begin(), v.end());
+  for (const auto &r : v) {
+    if (!ranges->empty() && r.first <= ranges->back()) ranges->back() = r.second > ranges->back() ? r.second : ranges->back();
+    else { ranges->push_back(r.first); ranges->push_back(r.second); }
+  }
+  return first;
+}
+
+extern "C" int himg_hip_stream_regions_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int n,
+                                            const int32_t *origins, int w, int h, himg_hip_region_plan *plans,
+                                            size_t *ranges, int *n_ranges) {
+  if (!packed || !origins || !plans || !ranges || !n_ranges || n < 1) return HIMG_ERR_ARG;
+  std::vector<int> codes(n);
+  std::vector<size_t> r;
+  const int rc = stream_regions_plan(packed, packed_size, fix_t2, n, origins, w, h, plans, codes.data(), &r);
+  for (int k = 0; k < n; ++k)
+    if (codes[k]) {   // (no plan: the geometry if the header gave one, and the window's code)
+      plans[k].row0 = codes[k]; plans[k].row1 = 0;
+      plans[k].head_bytes = plans[k].rows_begin = plans[k].rows_end = 0;
+    }
+  memcpy(ranges, r.data(), r.size() * sizeof(size_t));
+  *n_ranges = (int)(r.size() / 2);
+  return rc;
+}
+
+// One host stream, n windows: planned on the host like himg_hip_decode_region_to -- the head and the merged
+// ranges of the windows' rows go up, each at its offset, with the host's index of rows [min r0_k, max r1_k) --
+// then one launch of stream_regions_launch.  A stream the host does not index for every window (damaged
+// headers, one block row) goes up whole and takes the device walk, which gives each window its own verdict.
+extern "C" int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int n,
+                                                 const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
+                                                 int *statuses, int *width, int *height, int *channels) {
+  if (!ctx || !packed || !origins || !statuses || !width || !height || !channels || n < 1 || n > 65535)
+    return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  for (int k = 0; k < n; ++k)
+    if (!region_ok(W, H, origins[2 * k], origins[2 * k + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  const size_t stride = round_up(packed_size + 16, 256), out_bytes = (size_t)n * h * w * C, n_idx = 2 * (size_t)g.rows;
+  if (!ctx->h_in.reserve(stride) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
+      !ctx->h_status.reserve(round_up((size_t)n * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  std::vector<himg_hip_region_plan> plans(n);
+  std::vector<int> codes(n);
+  std::vector<size_t> ranges;
+  std::vector<int32_t> map(n, 0);
+  int32_t index_rows[2] = {g.rows, 0};
+  for (int k = 0; k < n; ++k) {
+    const int r0 = origins[2 * k + 1] / 8, r1 = (origins[2 * k + 1] + h + 7) / 8;
+    index_rows[0] = r0 < index_rows[0] ? r0 : index_rows[0];
+    index_rows[1] = r1 > index_rows[1] ? r1 : index_rows[1];
+  }
+  // (every window planned means the one walk passed: hp_index holds rows [0, max r1_k))
+  const bool indexed = g.rows >= 2 && stream_regions_plan(packed, packed_size, ctx->fix_t2, n, origins, w, h, plans.data(),
+                                                          codes.data(), &ranges, ctx->hp_index) == HIMG_OK;
+  uint8_t *in = (uint8_t *)ctx->h_in.p;
+  if (indexed) {
+    for (size_t i = 0; i + 1 < ranges.size(); i += 2)
+      HIP_TRY(ctx, hipMemcpyAsync(in + ranges[i], packed + ranges[i], ranges[i + 1] - ranges[i], hipMemcpyHostToDevice, nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  } else if (int rc = upload_zero_tail(ctx, in, stride, packed, packed_size)) {
+    return rc;
+  }
+  const uint32_t sz = (uint32_t)packed_size;
+  int32_t *d_status = (int32_t *)ctx->h_status.p;
+  if (int rc = stream_regions_launch(ctx, in, stride, &sz, 1, W, H, C, map.data(), origins, n, w, h,
+                                     indexed ? (const uint32_t *)ctx->h_index.p : nullptr, indexed ? index_rows : nullptr,
+                                     ctx->h_out.p, d_status, nullptr)) {
+    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
+    return rc;
+  }
+  std::vector<int32_t> st(n);
+  HIP_TRY(ctx, hipMemcpy(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
+  int first = HIMG_OK;
+  for (int k = n - 1; k >= 0; --k) {   // (backwards: the message left is the first failing window's)
+    statuses[k] = status_to_code(st[k]);
+    if (st[k]) first = status_error(ctx, st[k]);
+  }
+  *width = w; *height = h; *channels = C;
+  ctx->host_bytes = out_bytes;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return first;
 }
 
 // The host walks every row header (the whole frame as a rectangle) and the index goes up with the

@@ -4429,8 +4429,10 @@ __device__ __forceinline__ void transform_store_region(const Geom &g, int sstrid
 __global__ __launch_bounds__(kDecThreads) void k_dec_region(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                            const uint32_t *sizes, RegionArgs ra) {
   constexpr bool kRegionTens = false, kRegionPitch = false;
-  constexpr bool kRegionConceal = false;
+  constexpr bool kRegionConceal = false, kRegionMap = false;
   uint8_t *const cmap = nullptr;
+  const int32_t *const smap = nullptr;
+  int32_t *const wstat = nullptr;
   const TensK td = nullptr;
   const DstK pd = nullptr;
 #include "dec_body_region.inc"
@@ -4450,8 +4452,10 @@ struct RegionArgsT {
 };
 __global__ __launch_bounds__(kDecThreads) void k_dec_region_t(RegionArgsT a) {
   constexpr bool kRegionTens = true, kRegionPitch = false;
-  constexpr bool kRegionConceal = false;
+  constexpr bool kRegionConceal = false, kRegionMap = false;
   uint8_t *const cmap = nullptr;
+  const int32_t *const smap = nullptr;
+  int32_t *const wstat = nullptr;
   const DstK pd = nullptr;
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
@@ -4477,8 +4481,10 @@ struct RegionArgsP {
 };
 __global__ __launch_bounds__(kDecThreads) void k_dec_region_p(RegionArgsP a) {
   constexpr bool kRegionTens = false, kRegionPitch = true;
-  constexpr bool kRegionConceal = false;
+  constexpr bool kRegionConceal = false, kRegionMap = false;
   uint8_t *const cmap = nullptr;
+  const int32_t *const smap = nullptr;
+  int32_t *const wstat = nullptr;
   const Geom &g = a.g;
   const DecWs &ws = a.ws;
   const uint8_t *packed = a.packed;
@@ -4564,6 +4570,124 @@ __global__ void k_region_walk_end(Geom g, DecWs ws, const uint8_t *packed, size_
     q = b + len;
   }
   if (q == end) df->walk_status = 0;
+}
+
+// ---------------------------------------------------------------------------
+// MANY WINDOWS OF ONE STREAM (himg_hip_decode_stream_regions_device): window k is the w x h rectangle at
+// its own origin of stream s_k = stream_of[k].  The head phase and the row index are per STREAM and run once
+// however many windows name a stream; the verdict is per WINDOW, exactly that of the region decode of the
+// stream with that rectangle alone.  So nothing a row says reaches DecFrame::status, which keeps the head's
+// verdict (RIFF .. FMAP, the FRES tree, the LRES chain) alone:
+//   k_stream_rowwalk / k_stream_set_index   one walk per stream to the largest r1_k of its windows (to the
+//                      end of the chunk when a window reaches the last block row).  What it found goes to
+//                      words of its own, walk_rows[s] -- the rows whose headers it delimited -- and walk_st[s]
+//                      -- k_dec_rowwalk's verdict of a walk to the end of the chunk --, and
+//                      DecFrame::walk_status is cleared, so that the count kernels fold nothing into the frame.
+//   k_stream_gate      (a lane per window) wstat[k], window k's own word, starts as the walk's verdict FOR
+//                      r1_k: a window below the last block row needs rows 0 .. r1_k - 1 delimited and nothing
+//                      more (k_region_walk_end's rule: a chunk that ends right behind row r1_k - 1 is
+//                      accepted); one that reaches the last block row takes the verdict of the whole walk.
+//   k_stream_count(_w) k_row_count<false> / k_row_count_w over a LIST of (stream, first row, last row) runs the
+//                      host has deduplicated: a block row that several windows touch is counted once.
+//   k_dec_stream_region   k_dec_region's body on a grid of (strip, row - r0_k, window): the records,
+//                      tables and low-res plane of stream s_k, read only; a rejected row is raised into
+//                      wstat[k].
+//   k_stream_status    d_status[k] = max(head verdict of s_k, wstat[k]).
+// ---------------------------------------------------------------------------
+struct StreamWinWords {       // per launch (himg_hip.hip stages the first five, the rest is scratch)
+  const int32_t *stream_of;   // [n_windows] s_k
+  const int32_t *org;         // [2 n_windows] (x_k, y_k)
+  const int32_t *row_end;     // [n_streams] where stream s's walk stops: 0 for a stream no window names
+  const int32_t *list;        // [3 n_list] (stream, first row, end row) of a count workgroup
+  const int32_t *index_rows;  // [2 n_streams] k_stream_set_index: the rows the host's index holds
+  int32_t *walk_rows, *walk_st;   // [n_streams]
+  int32_t *wstat;             // [n_windows]
+};
+constexpr int kWalkNoVerdict = 0x7fffffff;   // walk_rows: the walk has nothing to say (the parse's verdict, or one row)
+
+__global__ __launch_bounds__(64) void k_stream_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                       const uint32_t *sizes, StreamWinWords sw) {
+  const int row_end = sw.row_end[blockIdx.x], resume = 0;
+  if (threadIdx.x == 0) {
+    sw.walk_rows[blockIdx.x] = kWalkNoVerdict; sw.walk_st[blockIdx.x] = 0;
+    if (row_end == 0) ws.frames[blockIdx.x].walk_status = 0;
+  }
+  if (row_end == 0) return;
+#include "dec_body_rowwalk.inc"
+  // (lane 0, behind the row headers: r rows delimited; st, the verdict where the walk reached the chunk's end)
+  sw.walk_rows[f] = r; sw.walk_st[f] = st;
+  df->walk_status = 0;
+}
+
+// k_region_set_index with a row range per stream; an index that points outside the stream fails every window.
+__global__ __launch_bounds__(256) void k_stream_set_index(Geom g, DecWs ws_all, const uint32_t *index_all,
+                                                          const uint32_t *sizes_all, StreamWinWords sw) {
+  const int f_ = blockIdx.x;
+  DecWs ws = ws_all;
+  ws.frames += f_;
+  ws.row_off += (size_t)f_ * g.rows;
+  ws.row_len += (size_t)f_ * g.rows;
+  const uint32_t *index = index_all + (size_t)f_ * 2 * g.rows, *sizes = sizes_all + f_;
+  const int r0 = sw.index_rows[2 * f_], r1 = sw.index_rows[2 * f_ + 1];
+#include "dec_body_set_index.inc"
+  if (threadIdx.x == 0) {
+    sw.walk_rows[f_] = bad ? 0 : kWalkNoVerdict; sw.walk_st[f_] = bad ? fmt_err(7, 1) : 0;
+    df->walk_status = 0;
+  }
+}
+
+__global__ void k_stream_gate(Geom g, DecWs ws, StreamWinWords sw, int h, int n_windows) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_windows) return;
+  const int s = sw.stream_of[k], r1 = region_r1(sw.org, k, h);
+  int v = 0;
+  if (ws.frames[s].parse_status == 0)   // (k_row_count's rule: the walk's verdict counts if the parse passed)
+    v = r1 >= g.rows ? sw.walk_st[s] : (sw.walk_rows[s] < r1 ? fmt_err(7, 1) : 0);
+  sw.wstat[k] = v;
+}
+
+// The count kernels over the list: entry e = (stream, r0, r1) is one workgroup's rows.  The bodies take the
+// frame from blockIdx.y and their first row from blockIdx.x: here both are the entry's, under those names.
+__global__ __launch_bounds__(kDecThreads, 8) void k_stream_count(Geom g, DecWs ws, const uint8_t *packed,
+                                                                size_t in_stride, const uint32_t *sizes,
+                                                                StreamWinWords sw, int rows_per_wg) {
+  constexpr bool LDSPAY = false;
+  const int32_t *e = sw.list + 3 * (size_t)blockIdx.x;
+  const int es = __builtin_amdgcn_readfirstlane(e[0]);
+  const int r0 = e[1], r1 = min(e[2], sw.walk_rows[es]);   // (rows the walk did not delimit have no index)
+  if (r0 >= r1) return;
+  const struct { unsigned x, y; } blockIdx = {0u, (unsigned)es};
+#include "dec_body_row_count.inc"
+}
+
+__global__ __launch_bounds__(kDecThreads, 8) void k_stream_count_w(Geom g, DecWs ws, const uint8_t *packed,
+                                                                  size_t in_stride, const uint32_t *sizes,
+                                                                  StreamWinWords sw) {
+  const int32_t *e = sw.list + 3 * (size_t)blockIdx.x;
+  const int es = __builtin_amdgcn_readfirstlane(e[0]);
+  const int r0 = e[1], r1 = min(e[2], sw.walk_rows[es]);
+  if (r0 >= r1) return;
+  const struct { unsigned x, y; } blockIdx = {0u, (unsigned)es};
+  constexpr int NQ = 1;   // a sub-sequence per lane
+#include "dec_body_row_count_w.inc"
+}
+
+__global__ __launch_bounds__(kDecThreads) void k_dec_stream_region(Geom g, DecWs ws, const uint8_t *packed,
+                                                                  size_t in_stride, const uint32_t *sizes,
+                                                                  RegionArgs ra, const int32_t *smap, int32_t *wstat) {
+  constexpr bool kRegionTens = false, kRegionPitch = false;
+  constexpr bool kRegionConceal = false, kRegionMap = true;
+  uint8_t *const cmap = nullptr;
+  const TensK td = nullptr;
+  const DstK pd = nullptr;
+#include "dec_body_region.inc"
+}
+
+__global__ void k_stream_status(DecWs ws, StreamWinWords sw, int32_t *status, int n_windows) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_windows) return;
+  const int hd = ws.frames[sw.stream_of[k]].status, own = sw.wstat[k];
+  status[k] = hd > own ? hd : own;
 }
 
 // ---------------------------------------------------------------------------
@@ -4743,8 +4867,10 @@ struct SpanWindow {       // what the body reads of a RegionArgs
 template <bool kConceal>
 __global__ __launch_bounds__(kDecThreads) void k_dec_span(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
                                                          const uint32_t *sizes, SpanArgs sa) {
-  constexpr bool kRegionTens = false, kRegionPitch = false, kRegionConceal = kConceal;
+  constexpr bool kRegionTens = false, kRegionPitch = false, kRegionConceal = kConceal, kRegionMap = false;
   uint8_t *const cmap = sa.cmap;
+  const int32_t *const smap = nullptr;
+  int32_t *const wstat = nullptr;
   const TensK td = nullptr;
   const DstK pd = nullptr;
   const int k0 = sa.k0[blockIdx.z], k1 = sa.k1[blockIdx.z];
@@ -5533,7 +5659,7 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
       {HIMG_K(k_row_window), kRowWindowLds},
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
-      {HIMG_K(k_dec_span<false>), 0},      {HIMG_K(k_dec_span<true>), 0},
+      {HIMG_K(k_dec_span<false>), 0},      {HIMG_K(k_dec_span<true>), 0},       {HIMG_K(k_dec_stream_region), 0},
       {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
       {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
 #undef HIMG_K
@@ -5746,6 +5872,57 @@ void launch_region(const Geom &g, const DecWs &ws_in, int batch, const uint8_t *
   }
   prof_end(prof, stream);
   HIMG_LAUNCH(k_dec_status, dim3((batch + 63) / 64), dim3(64), ws, d_status, batch);
+}
+
+// Many windows of one stream (the kernels' comment above): the head phase over the n_streams streams as
+// launch_region runs it, one walk per stream beside it, then the gate, the counts over the host's list and
+// the row kernel over the windows.  d_words: the staged words and the scratch behind them, carved by the
+// caller (himg_hip.hip, stream_regions_launch); list_rows: the rows the list holds, list_chunk: the most
+// rows of an entry (stream_count_chunk's); d_row_index: the host's index, 2 x rows words per stream.
+int stream_count_chunk(const Geom &g, long long list_rows) {
+  const CountRule cr = count_rule(g, list_rows, true);
+  return cr.wave ? kCountRowsW : cr.rpc;
+}
+
+void launch_stream_regions(const Geom &g, const DecWs &ws_in, int n_streams, const uint8_t *d_packed, size_t in_stride,
+                           const uint32_t *d_sizes, const uint32_t *d_row_index, const StreamRegionWords &d_words,
+                           int n_windows, const int32_t *h_org, int n_list, long long list_rows, int w, int h,
+                           uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;   // (plain per-lane records, as in launch_region)
+  StreamWinWords sw;
+  sw.stream_of = d_words.stream_of; sw.org = d_words.org; sw.row_end = d_words.row_end; sw.list = d_words.list;
+  sw.index_rows = d_words.index_rows;
+  sw.walk_rows = d_words.scratch; sw.walk_st = sw.walk_rows + n_streams; sw.wstat = sw.walk_st + n_streams;
+  const WindowExtents e = window_extents(g, n_windows, h_org, 8, w, h);
+  launch_zero(g, ws, n_streams, stream, prof);
+  hipStream_t ws_ = side_fork(ds, stream);
+  prof_begin(prof, d_row_index ? "k_stream_set_index" : "k_stream_rowwalk", ws_);
+  if (d_row_index)
+    hipLaunchKernelGGL(k_stream_set_index, dim3(n_streams), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, sw);
+  else
+    hipLaunchKernelGGL(k_stream_rowwalk, dim3(n_streams), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, sw);
+  prof_end(prof, ws_);
+  side_walked(ds);
+  HIMG_LAUNCH(k_dec_parse, dim3(n_streams), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
+  launch_lres_chain(g, ws, n_streams, d_packed, in_stride, d_sizes, stream, prof);
+  side_join(ds, stream);
+  HIMG_LAUNCH(k_stream_gate, dim3((n_windows + 63) / 64), dim3(64), g, ws, sw, h, n_windows);
+  const CountRule cr = count_rule(g, list_rows, true);
+  if (cr.wave) {
+    HIMG_LAUNCH(k_stream_count_w, dim3(n_list), dim3(kDecThreads), cr.g, ws, d_packed, in_stride, d_sizes, sw);
+  } else {
+    HIMG_LAUNCH(k_stream_count, dim3(n_list), dim3(kDecThreads), cr.g, ws, d_packed, in_stride, d_sizes, sw, cr.rpc);
+  }
+  const int smax = region_strip_tiles(g);
+  const int nstrip = (e.ntiles + smax - 1) / smax, swt = (e.ntiles + nstrip - 1) / nstrip;
+  RegionArgs ra;
+  ra.org = sw.org; ra.sw = swt; ra.w = w; ra.h = h; ra.out = d_out;
+  prof_begin(prof, "k_dec_stream_region", stream);
+  hipLaunchKernelGGL(k_dec_stream_region, dim3(nstrip, e.nrows, n_windows), dim3(kDecThreads), region_layout(g.C, swt).total,
+                     stream, g, ws, d_packed, in_stride, d_sizes, ra, sw.stream_of, sw.wstat);
+  prof_end(prof, stream);
+  HIMG_LAUNCH(k_stream_status, dim3((n_windows + 63) / 64), dim3(64), ws, sw, d_status, n_windows);
 }
 
 // What the row-span decodes share behind their gates and walks: the fill over w.kfill, the counts and the row

@@ -529,6 +529,69 @@ int himg_hip_decode_regions_batch(himg_hip_ctx *ctx, const uint8_t *const *packe
                                   uint8_t *const *dst, const size_t *dst_cap,
                                   int *widths, int *heights, int *channels);
 
+/* ---- region decode: many windows of one stream ----------------------------------- */
+/*
+ * The region entry points above take one window per stream.  These take a window -> stream map, the
+ * stream-side counterpart of frame_pitch = 0 in himg_hip_src / himg_hip_dst ("all windows in ONE
+ * picture"): a tile or viewport server over one very large picture, detection crops, several random
+ * crops per image.  The head of a stream -- the container parse, the LRES chain for the low-res plane,
+ * the walk over the row headers -- runs ONCE per stream however many windows name it, and a block row
+ * that several windows touch is counted once.
+ *
+ * Window k is the w x h rectangle at (x_k, y_k) = h_origins[2k], h_origins[2k+1] of stream
+ * s_k = h_stream_of[k]; its pixels go to d_out + k * h * w * C, tightly packed, and its verdict to
+ * d_status[k].  For every window, bytes and status are EXACTLY what himg_hip_decode_regions_device
+ * gives for that stream as a frame of its own with that rectangle alone, under the same
+ * HIMG_OPT_FIX_T2: the same status word and the same bytes used (the head, the size headers of rows
+ * 0 .. r1_k-1, the payloads of rows r0_k .. r1_k-1).
+ * Independence: damage that window k's rectangle does not look at changes neither its status nor its
+ * pixels -- also when another window of the SAME stream looks at it and fails.  A payload row that is
+ * rejected fails only the windows that touch that row.  A size header rejected at row j fails exactly
+ * the windows with r1_k > j.  A window with r1_k below the last block row accepts a FRES chunk that
+ * ends right behind row r1_k - 1; only windows that reach the last block row take the verdict of the
+ * walk to the end of the chunk.  A head verdict (RIFF .. FMAP, the FRES tree, the LRES chain) is every
+ * window's of that stream and no other stream's.
+ * A failed window's pixels are unspecified but stay inside its own h x w x C bytes; nothing outside
+ * n_windows x h x w x C bytes of d_out and n_windows words of d_status is written.  Windows may
+ * overlap, repeat and come in any order of stream.  A stream that no window names is allowed: it decides
+ * nothing, has no status of its own, and its bytes may be anything (its h_sizes entry still has to fit
+ * in_stride).
+ * Asynchronous on `stream` like the other device entries; h_stream_of (n_windows values) and h_origins
+ * (2 x n_windows) are HOST arrays that reach the device with the sizes, with no host synchronisation.
+ * Checked on the host before anything is launched -- NULLs, n_streams or n_windows outside 1 .. 65535, the
+ * grid limits of himg_hip_decode_regions_device over the streams (n_streams x C <= 65535,
+ * block rows + 1 <= 65535), an s_k outside [0, n_streams), a rectangle outside width x height: any of them
+ * returns HIMG_ERR_ARG and neither d_out nor d_status is written.
+ *
+ * Not in this change: scaled, tensor and pitched store forms; a host batch over many streams; the
+ * row-sharded and multi-GPU paths; the C++ classes and the command-line tools; keeping a parsed head
+ * across calls.
+ */
+int himg_hip_decode_stream_regions_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                          const uint32_t *h_sizes, int n_streams, int width, int height,
+                                          int num_channels, const int32_t *h_stream_of,
+                                          const int32_t *h_origins, int n_windows, int w, int h, void *d_out,
+                                          int32_t *d_status, void *stream);
+/* Host only, no GPU: per window its himg_hip_region_plan, and the merged, sorted byte ranges a caller
+ * must have present: [0, head_bytes) and the union of the windows' [rows_begin, rows_end), as
+ * ranges[2i] .. ranges[2i+1], *n_ranges of them; ranges holds up to 2 * (n + 1) values.  Codes as
+ * himg_hip_region_peek (a bad rectangle: HIMG_ERR_ARG); the call returns the first window's that is not
+ * HIMG_OK.  A window without a plan contributes no range; its plan has row1 = 0, row0 = its code and no
+ * bytes -- a header chain that breaks at row j leaves the windows with r1 <= j their plans. */
+int himg_hip_stream_regions_peek(const uint8_t *packed, size_t packed_size, int fix_t2, int n,
+                                 const int32_t *origins, int w, int h, himg_hip_region_plan *plans,
+                                 size_t *ranges, int *n_ranges);
+/* One HOST stream, n windows of w x h into dst (n x h x w x C bytes, window k at k * h * w * C);
+ * statuses[k]: HIMG_OK or window k's error; returns the first error (himg_hip_last_error words it).  A bad
+ * rectangle fails the call (HIMG_ERR_ARG) before anything runs.  The capacity protocol of
+ * himg_hip_decode_region_to: HIMG_ERR_CAPACITY with *width = w, *height = h, *channels = C and the
+ * statuses set, and himg_hip_fetch_last copies the resident n x h x w x C bytes.  The host plans the
+ * windows and uploads only the merged ranges of himg_hip_stream_regions_peek with its row index; a
+ * stream it cannot index for every window goes up whole and takes the device walk. */
+int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int n,
+                                      const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
+                                      int *statuses, int *width, int *height, int *channels);
+
 /* ---- decode into windows of pitched destination pictures ------------------------- */
 /*
  * The decode entry points above write batch x H x W x C tightly packed bytes.  These take a row pitch,
