@@ -125,6 +125,14 @@ def lib():
     L.himg_hip_decode_stream_regions_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp]
     L.himg_hip_stream_regions_peek.argtypes = [vp, sz, i32, i32, vp, i32, i32, vp, vp, P(i32)]
     L.himg_hip_decode_stream_regions_to.argtypes = [vp, vp, sz, i32, vp, i32, i32, vp, sz, vp, P(i32), P(i32), P(i32)]
+    L.himg_hip_opened_bytes.argtypes = [i32, i32, i32, i32, P(sz)]
+    L.himg_hip_open_streams_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, P(vp), vp]
+    L.himg_hip_open_stream_host.argtypes = [vp, vp, sz, P(vp)]
+    L.himg_hip_opened_regions_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_opened_regions_to.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, sz, vp, P(i32), P(i32), P(i32)]
+    L.himg_hip_opened_info.argtypes = [vp, P(i32), P(i32), P(i32), P(i32), P(sz), P(C.c_longlong)]
+    L.himg_hip_close_streams.argtypes = [vp, vp]
+    L.himg_hip_close_streams.restype = None
     L.himg_hip_tensor_bytes.argtypes = [vp, i32, i32, i32, P(sz)]
     L.himg_hip_decode_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_regions_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
@@ -691,6 +699,28 @@ class Engine:
             self._check(rc, "decode_stream_regions")
         return out.ravel()[: n * ho.value * wo.value * c.value].reshape(n, ho.value, wo.value, c.value), st[:n].copy()
 
+    def open_streams_device(self, d_packed, in_stride, h_sizes, n_streams, width, height, channels,
+                            d_head_status=None, stream=0):
+        """himg_hip_open_streams_device: the head of every stream once, all its row headers walked once; returns
+        an OpenedStreams whose calls decode windows with no parse, LRES chain or walk.  d_packed stays the
+        caller's and must stay valid, its payloads unchanged, while the handle lives.  d_head_status (optional):
+        n_streams int32 words on the device, each stream's head verdict."""
+        hs = None if h_sizes is None else np.ascontiguousarray(h_sizes, np.uint32)
+        o = C.c_void_p()
+        rc = lib().himg_hip_open_streams_device(self._ctx, _ptr(d_packed), in_stride,
+                                                hs.ctypes.data if hs is not None else None, int(n_streams), width, height,
+                                                channels, _ptr(d_head_status), C.byref(o), C.c_void_p(stream))
+        self._check(rc, "open_streams_device")
+        return OpenedStreams(self, o, keep=d_packed)
+
+    def open_stream(self, packed):
+        """himg_hip_open_stream_host: one host stream, uploaded whole into memory the handle owns."""
+        packed = _as_u8(packed)
+        o = C.c_void_p()
+        rc = lib().himg_hip_open_stream_host(self._ctx, packed.ctypes.data, packed.nbytes, C.byref(o))
+        self._check(rc, "open_stream")
+        return OpenedStreams(self, o)
+
     def decode_regions_tensor_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, origins,
                                      w, h, desc, d_out, d_status, stream=0):
         """himg_hip_decode_regions_tensor_device: the contract of decode_regions_device with the
@@ -1110,6 +1140,87 @@ class Engine:
         rc = lib().himg_hip_profile_read(self._ctx, C.byref(n), names, ms, cnt)
         self._check(rc, "profile_read")
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(n.value)}
+
+
+class OpenedStreams:
+    """An opened-streams handle (Engine.open_streams_device, Engine.open_stream): the heads' products and the
+    rows' records stay on the device between calls.  A context manager; close() waits for the last call."""
+
+    def __init__(self, engine, handle, keep=None):
+        self._eng, self._h, self._keep = engine, handle, keep   # (keep: the caller's device buffer stays alive)
+
+    def _ctx(self):
+        return self._eng._ctx if self._h else None
+
+    def regions_device(self, stream_of, origins, w, h, d_out, d_status, stream=0, engine=None):
+        """himg_hip_opened_regions_device: window k is the w x h rectangle at origins[k] of stream stream_of[k];
+        bytes and status words as Engine.decode_stream_regions_device.  engine: the context to call with (the
+        one that opened the handle; any other is refused)."""
+        so = None if stream_of is None else np.ascontiguousarray(np.asarray(stream_of, np.int32).ravel())
+        org = None if origins is None else np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = 0 if so is None else int(so.size)
+        if org is not None and so is not None and org.shape[0] != n:
+            raise ValueError("stream_of and origins differ in length")
+        eng = engine or self._eng
+        rc = lib().himg_hip_opened_regions_device(
+            eng._ctx if self._h else None, self._h, so.ctypes.data if n else None,
+            org.ctypes.data if org is not None and org.size else None, n, int(w), int(h), _ptr(d_out), _ptr(d_status),
+            C.c_void_p(stream))
+        eng._check(rc, "opened regions_device")
+
+    def regions(self, origins, w, h, stream_of=None, out=None):
+        """himg_hip_opened_regions_to: ((n, h, w, C) uint8 array, statuses) as Engine.decode_stream_regions;
+        stream_of None: every window of stream 0."""
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = org.shape[0]
+        so = None if stream_of is None else np.ascontiguousarray(np.asarray(stream_of, np.int32).ravel())
+        c = self.info()["channels"]
+        cap = n * max(int(w), 0) * max(int(h), 0) * c
+        out = _out_buffer(out, cap)
+        st = np.zeros(max(n, 1), np.int32)
+        wo, ho, co = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().himg_hip_opened_regions_to(self._ctx(), self._h, n, so.ctypes.data if so is not None else None,
+                                              org.ctypes.data, int(w), int(h), out.ctypes.data, cap, st.ctypes.data,
+                                              C.byref(wo), C.byref(ho), C.byref(co))
+        if rc != 0 and (wo.value == 0 or rc == HIMG_ERR_CAPACITY):
+            self._eng._check(rc, "opened regions")
+        return out.ravel()[:cap].reshape(n, ho.value, wo.value, co.value), st[:n].copy()
+
+    def info(self):
+        """himg_hip_opened_info as a dict: n_streams, width, height, channels, device_bytes, rows_counted."""
+        if not self._h:
+            raise HimgError(HIMG_ERR_ARG, "the handle is closed")
+        n, w, h, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        b, r = C.c_size_t(), C.c_longlong()
+        lib().himg_hip_opened_info(self._h, C.byref(n), C.byref(w), C.byref(h), C.byref(c), C.byref(b), C.byref(r))
+        return dict(n_streams=n.value, width=w.value, height=h.value, channels=c.value, device_bytes=b.value,
+                    rows_counted=r.value)
+
+    def close(self):
+        if self._h and self._eng._ctx:
+            lib().himg_hip_close_streams(self._eng._ctx, self._h)
+        self._h, self._keep = C.c_void_p(), None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def opened_bytes(width, height, channels, n_streams=1):
+    """himg_hip_opened_bytes (no GPU): the device bytes an opened-streams handle of this geometry holds."""
+    b = C.c_size_t()
+    rc = lib().himg_hip_opened_bytes(width, height, channels, n_streams, C.byref(b))
+    if rc:
+        raise HimgError(rc, "opened_bytes")
+    return b.value
 
 
 class MultiEngine:

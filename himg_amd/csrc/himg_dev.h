@@ -458,6 +458,25 @@ void launch_stream_regions(const Geom &g, const DecWs &ws, int n_streams, const 
                            const uint32_t *d_sizes, const uint32_t *d_row_index, const StreamRegionWords &d_words,
                            int n_windows, const int32_t *h_org, int n_list, long long list_rows, int w, int h,
                            uint8_t *d_out, int32_t *d_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
+// Opened streams (include/himg_hip.h, himg_hip_open_streams_device): the head of launch_stream_regions once per
+// stream with the walk over ALL its row headers (d_row_index: the host's index of all rows instead), its
+// products written through ws -- the HANDLE's frames, tables, row index, low-res planes, records and counters,
+// with the context's LRES scratch (lres_sym, spec_*) beside them --, every record's valid word cleared, the
+// head verdicts to d_head_status (may be null).  walk: n_streams words each, the handle's.
+struct OpenedWalk {
+  int32_t *rows, *st;   // k_stream_rowwalk's walk_rows / walk_st of a walk to the end of the chunk
+};
+void launch_open_streams(const Geom &g, const DecWs &ws, int n_streams, const uint8_t *d_packed, size_t in_stride,
+                         const uint32_t *d_sizes, const uint32_t *d_row_index, const OpenedWalk &walk,
+                         int32_t *d_head_status, hipStream_t stream, Profiler *prof, const DecStreams *ds);
+// A call on the handle (himg_hip_opened_regions_device): launch_stream_regions' gate, counts and row kernel
+// and nothing in front of them.  d_list: n_list entries over the list_rows rows that no earlier call has
+// counted (opened_plan.h), n_list = 0: no count kernel runs.  d_status doubles as the windows' own words.
+void launch_opened_regions(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
+                           const uint32_t *d_sizes, const OpenedWalk &walk, const int32_t *d_stream_of,
+                           const int32_t *d_org, const int32_t *d_list, int n_windows, const int32_t *h_org, int n_list,
+                           long long list_rows, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream,
+                           Profiler *prof);
 // The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
 // k_span_gate (the head of the stream with every load checked against the bytes present, then the frame's
 // state against what it found), the head phase in its prefix form (k_dec_parse_prefix, the LRES chain

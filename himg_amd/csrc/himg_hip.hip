@@ -17,6 +17,7 @@
 
 #include "himg_dev.h"
 #include "himg_tables.h"
+#include "opened_plan.h"
 #include "prefix_walk.h"
 
 using namespace himg_dev;
@@ -210,6 +211,10 @@ struct himg_hip_ctx {
     LresTables lt{};
     int r0 = 0, r1 = 0;
   } shard;
+
+  // The opened-streams handles that belong to this context (himg_hip_open_streams_device); himg_hip_destroy
+  // closes the ones that are left.
+  std::vector<himg_hip_opened *> opened;
 };
 
 static int fail(himg_hip_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess) {
@@ -366,10 +371,14 @@ extern "C" int himg_hip_create(int device, himg_hip_ctx **out) {
   return HIMG_OK;
 }
 
+static void opened_free(himg_hip_opened *o);
+
 extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
   if (!ctx) return;
   hipSetDevice(ctx->device);
   hipDeviceSynchronize();
+  for (himg_hip_opened *o : ctx->opened) opened_free(o);
+  ctx->opened.clear();
   if (ctx->dstr.ev_fork) hipEventDestroy(ctx->dstr.ev_fork);
   for (int k = 0; k < kWalkSegs; ++k) {
     if (ctx->dstr.ev_walk[k]) hipEventDestroy(ctx->dstr.ev_walk[k]);
@@ -3246,6 +3255,247 @@ extern "C" int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_
   if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return first;
+}
+
+// ---------------------------------------------------------------------------
+// Opened streams: the head's products and the rows' records of n streams in memory of their own, and the
+// window part of stream_regions_launch alone against them (kernels_dec.hip, launch_open_streams /
+// launch_opened_regions; the planning of a call: opened_plan.h).
+// ---------------------------------------------------------------------------
+struct himg_hip_opened {
+  himg_hip_ctx *ctx = nullptr;
+  int n_streams = 0, W = 0, H = 0, C = 0, fix_t2 = 0;
+  const uint8_t *d_packed = nullptr;   // the caller's (device form) or own_in's (host form)
+  size_t in_stride = 0;
+  DevBuf mem, own_in;
+  DecWs ws{};                          // the handle's buffers; the LRES scratch fields are filled per open
+  uint32_t *d_sizes = nullptr;
+  himg_dev::OpenedWalk walk{};
+  himg_dev::OpenedRows rows;
+  hipEvent_t ev = nullptr;             // behind the handle's last call
+};
+static_assert(sizeof(DecFrame) == 1616, "include/himg_hip.h states a handle's bytes");
+
+// The handle's memory: every array of its own at a 256-byte boundary.  base == nullptr: the size alone.
+static size_t opened_carve(const Geom &g, int n_streams, uint8_t *base, himg_hip_opened *o) {
+  const size_t n = (size_t)n_streams, rows = (size_t)g.rows;
+  const size_t plane = round_up((size_t)g.C * g.rows * g.cols, 256);
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t at = off; off += round_up(bytes, 256); return base ? base + at : nullptr; };
+  uint8_t *frames = carve(n * sizeof(DecFrame)), *nodes = carve(n * 2 * (2 * kNumSym) * 4);
+  uint8_t *grp = carve(n * 2 * (1u << kLutBits) * 8), *gyc = carve(n * 2 * (1u << kLutBits) * 4);
+  uint8_t *sub = carve(n * 2 * kSubEntries * 8), *index = carve(n * rows * 8), *low = carve(n * plane);
+  uint8_t *rec = carve(n * rows * (2 * kDecThreads + himg_dev::kRecHdr) * 4);
+  uint8_t *stats = carve((n * (rows + 1) * 8 + n * 4 + n * rows * 8) * 4), *words = carve(n * 12);
+  if (o) {
+    DecWs &w = o->ws;
+    w = DecWs{};
+    w.frames = (DecFrame *)frames; w.nodes = (uint32_t *)nodes; w.grp = (uint2 *)grp; w.gyc = (uint32_t *)gyc;
+    w.sub = (uint2 *)sub;
+    w.row_off = (uint32_t *)index; w.row_len = w.row_off + n * rows;
+    w.low = low; w.plane_stride = plane;
+    w.lane_start = (uint32_t *)rec; w.lane_off = w.lane_start + n * rows * kDecThreads;
+    w.stats = (uint32_t *)stats; w.parse_stats = w.stats + n * (rows + 1) * 8; w.rc_stats = w.parse_stats + n * 4;
+    o->d_sizes = (uint32_t *)words;
+    o->walk.rows = (int32_t *)words + n; o->walk.st = (int32_t *)words + 2 * n;
+  }
+  return off;
+}
+
+extern "C" int himg_hip_opened_bytes(int width, int height, int num_channels, int n_streams, size_t *bytes) {
+  Geom g;
+  if (!bytes || n_streams < 1 || n_streams > 65535 || !make_geom(width, height, num_channels, num_channels, 1, &g))
+    return HIMG_ERR_ARG;
+  *bytes = opened_carve(g, n_streams, nullptr, nullptr);
+  return HIMG_OK;
+}
+
+static void opened_free(himg_hip_opened *o) {
+  if (o->ev) { (void)hipEventSynchronize(o->ev); (void)hipEventDestroy(o->ev); }
+  o->mem.release();
+  o->own_in.release();
+  delete o;
+}
+
+static bool opened_owned(const himg_hip_ctx *ctx, const himg_hip_opened *o) {
+  if (!ctx || !o) return false;
+  for (const himg_hip_opened *p : ctx->opened)   // (no look into o: a closed handle's memory is gone)
+    if (p == o) return true;
+  return false;
+}
+
+// d_row_index: the host's index of all rows (one stream), or nullptr for the device walk.
+static int open_streams(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int n_streams,
+                        int width, int height, int num_channels, const uint32_t *d_row_index, int32_t *d_head_status,
+                        DevBuf *own_in, himg_hip_opened **out, void *stream) {
+  Geom g;
+  const char *bad = nullptr;
+  if (height > 0 && num_channels > 0 && ((height + 7) / 8 + 1 > 65535 || (long long)n_streams * num_channels > 65535))
+    bad = "grid too large";   // (HIMG_ERR_ARG, as in himg_hip_decode_stream_regions_device)
+  if (int rc = decode_args(ctx, width, height, num_channels, n_streams, kWsRegion, d_packed, nullptr, &in_stride, bad, &g))
+    return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  himg_hip_opened *o = new himg_hip_opened();
+  if (own_in) { o->own_in = *own_in; *own_in = DevBuf(); }
+  o->ctx = ctx; o->n_streams = n_streams; o->W = width; o->H = height; o->C = num_channels; o->fix_t2 = g.fix_t2;
+  o->d_packed = (const uint8_t *)d_packed; o->in_stride = in_stride;
+  o->rows.reset(n_streams, g.rows);
+  int rc = HIMG_OK;
+  if (!o->mem.reserve(opened_carve(g, n_streams, nullptr, nullptr)) ||
+      hipEventCreateWithFlags(&o->ev, hipEventDisableTiming) != hipSuccess)
+    rc = fail(ctx, HIMG_ERR_HIP, "opened-streams allocation failed");
+  // (the context's workspace in its head-only form: the LRES scratch; everything else is the handle's)
+  if (!rc) rc = ensure_dec_ws(ctx, g, n_streams, kWsHead);
+  if (!rc) {
+    opened_carve(g, n_streams, (uint8_t *)o->mem.p, o);
+    ctx->last_stream = (hipStream_t)stream;
+    rc = stage_words(ctx, o->d_sizes, h_sizes, (size_t)n_streams, nullptr, 0, ctx->last_stream);
+  }
+  if (rc) { opened_free(o); return rc; }
+  DecWs ws = ctx->dec_ws;
+  const DecWs &h = o->ws;
+  ws.frames = h.frames; ws.nodes = h.nodes; ws.grp = h.grp; ws.gyc = h.gyc; ws.sub = h.sub;
+  ws.row_off = h.row_off; ws.row_len = h.row_len; ws.low = h.low; ws.plane_stride = h.plane_stride;
+  ws.lane_start = h.lane_start; ws.lane_off = h.lane_off; ws.lane_q = nullptr;
+  ws.stats = h.stats; ws.parse_stats = h.parse_stats; ws.rc_stats = h.rc_stats;
+  himg_dev::launch_open_streams(g, ws, n_streams, o->d_packed, in_stride, o->d_sizes, d_row_index, o->walk, d_head_status,
+                                (hipStream_t)stream, &ctx->prof, ctx->opts.use_side ? &ctx->dstr : nullptr);
+  (void)hipEventRecord(o->ev, (hipStream_t)stream);
+  ctx->opened.push_back(o);
+  *out = o;
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_open_streams_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                            const uint32_t *h_sizes, int n_streams, int width, int height,
+                                            int num_channels, int32_t *d_head_status, himg_hip_opened **out,
+                                            void *stream) {
+  if (out) *out = nullptr;
+  if (!ctx || !d_packed || !h_sizes || !out || n_streams < 1 || n_streams > 65535) return HIMG_ERR_ARG;
+  if (int rc = stride_covers(ctx, h_sizes, n_streams, in_stride)) return rc;
+  return open_streams(ctx, d_packed, in_stride, h_sizes, n_streams, width, height, num_channels, nullptr, d_head_status,
+                      nullptr, out, stream);
+}
+
+extern "C" int himg_hip_open_stream_host(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                         himg_hip_opened **out) {
+  if (out) *out = nullptr;
+  if (!ctx || !packed || !out) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t stride = round_up(packed_size + 16, 256), n_idx = 2 * (size_t)g.rows;
+  DevBuf in;
+  if (!in.reserve(stride) || !ctx->h_index.reserve(round_up(n_idx * 4, 256))) {
+    in.release();
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  }
+  int rc = reserve_hp_index(ctx, n_idx);
+  if (!rc) rc = upload_zero_tail(ctx, (uint8_t *)in.p, stride, packed, packed_size);
+  uint32_t first = 0;
+  int w2 = 0, h2 = 0, c2 = 0;
+  const bool indexed = !rc && g.rows >= 2 &&
+                       himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows,
+                                           &first) == HIMG_OK;
+  if (indexed && hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess)
+    rc = fail(ctx, HIMG_ERR_HIP, "index upload failed");
+  const uint32_t sz = (uint32_t)packed_size;
+  if (!rc)
+    rc = open_streams(ctx, in.p, stride, &sz, 1, W, H, C, indexed ? (const uint32_t *)ctx->h_index.p : nullptr, nullptr, &in,
+                      out, nullptr);
+  (void)hipStreamSynchronize(nullptr);   // the uploads read the caller's and the pinned buffers
+  in.release();                          // (open_streams took it over unless it refused)
+  return rc;
+}
+
+extern "C" int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, const int32_t *h_stream_of,
+                                              const int32_t *h_org, int n_windows, int w, int h, void *d_out,
+                                              int32_t *d_status, void *stream) {
+  if (!opened_owned(ctx, o) || !h_stream_of || !h_org || !d_out || !d_status || n_windows < 1 || n_windows > 65535)
+    return HIMG_ERR_ARG;
+  for (int k = 0; k < n_windows; ++k) {
+    if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams) return fail(ctx, HIMG_ERR_ARG, "stream_of outside the streams");
+    if (!region_ok(o->W, o->H, h_org[2 * k], h_org[2 * k + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+  }
+  Geom g;
+  if (int rc = decode_args(ctx, o->W, o->H, o->C, o->n_streams, kWsRegion, o->d_packed, d_out, nullptr, nullptr, &g)) return rc;
+  g.fix_t2 = o->fix_t2;
+  ctx->head.valid = false;   // (the words below overwrite the sizes a head phase staged)
+  // The rows of these windows that no call has counted yet, cut into the count kernels' entries.
+  std::vector<himg_dev::OpenedRun> runs;
+  const long long list_rows = o->rows.pending(h_stream_of, h_org, n_windows, h, &runs);
+  const size_t o_org = (size_t)n_windows, o_list = o_org + 2 * (size_t)n_windows;
+  std::vector<uint32_t> words(o_list);
+  memcpy(words.data(), h_stream_of, (size_t)n_windows * 4);
+  memcpy(words.data() + o_org, h_org, (size_t)n_windows * 8);
+  if (list_rows) himg_dev::opened_cut(runs, himg_dev::stream_count_chunk(g, list_rows), &words);
+  const size_t n_list = (words.size() - o_list) / 3;
+  if (n_list > 0x7fffffffu) return fail(ctx, HIMG_ERR_UNSUPPORTED, "grid too large");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (!ctx->d_sizes.reserve(words.size() * 4)) return fail(ctx, HIMG_ERR_HIP, "decoder workspace allocation failed");
+  ctx->last_stream = (hipStream_t)stream;
+  if (int rc = stage_words(ctx, ctx->d_sizes.p, words.data(), words.size(), nullptr, 0, ctx->last_stream)) return rc;
+  o->rows.mark(runs);   // (queued: the stream orders the counts in front of whatever call reads them)
+  const int32_t *dw = (const int32_t *)ctx->d_sizes.p;
+  himg_dev::launch_opened_regions(g, o->ws, o->d_packed, o->in_stride, o->d_sizes, o->walk, dw, dw + o_org, dw + o_list,
+                                  n_windows, h_org, (int)n_list, list_rows, w, h, (uint8_t *)d_out, d_status,
+                                  (hipStream_t)stream, &ctx->prof);
+  (void)hipEventRecord(o->ev, (hipStream_t)stream);
+  HIP_TRY(ctx, hipGetLastError());
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
+                                          const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
+                                          int *statuses, int *width, int *height, int *channels) {
+  if (!opened_owned(ctx, o) || !origins || !statuses || !width || !height || !channels || n < 1 || n > 65535)
+    return HIMG_ERR_ARG;
+  std::vector<int32_t> map;
+  if (!h_stream_of) { map.assign((size_t)n, 0); h_stream_of = map.data(); }
+  for (int k = 0; k < n; ++k)
+    if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams || !region_ok(o->W, o->H, origins[2 * k], origins[2 * k + 1], w, h))
+      return fail(ctx, HIMG_ERR_ARG, "bad window");
+  const size_t out_bytes = (size_t)n * h * w * o->C;
+  *width = w; *height = h; *channels = o->C;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->host_bytes = 0;
+  if (!ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(round_up((size_t)n * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
+  int32_t *d_status = (int32_t *)ctx->h_status.p;
+  if (int rc = himg_hip_opened_regions_device(ctx, o, h_stream_of, origins, n, w, h, ctx->h_out.p, d_status, nullptr))
+    return launch_refused(rc);
+  std::vector<int32_t> st(n);
+  HIP_TRY(ctx, hipMemcpy(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
+  int first = HIMG_OK;
+  for (int k = n - 1; k >= 0; --k) {   // (backwards: the message left is the first failing window's)
+    statuses[k] = status_to_code(st[k]);
+    if (st[k]) first = status_error(ctx, st[k]);
+  }
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
+  return first;
+}
+
+extern "C" int himg_hip_opened_info(const himg_hip_opened *o, int *n_streams, int *width, int *height, int *channels,
+                                    size_t *device_bytes, long long *rows_counted) {
+  if (!o) return HIMG_ERR_ARG;
+  if (n_streams) *n_streams = o->n_streams;
+  if (width) *width = o->W;
+  if (height) *height = o->H;
+  if (channels) *channels = o->C;
+  if (device_bytes) *device_bytes = o->mem.cap + o->own_in.cap;
+  if (rows_counted) *rows_counted = o->rows.counted();
+  return HIMG_OK;
+}
+
+extern "C" void himg_hip_close_streams(himg_hip_ctx *ctx, himg_hip_opened *o) {
+  if (!opened_owned(ctx, o)) return;
+  for (size_t i = 0; i < ctx->opened.size(); ++i)
+    if (ctx->opened[i] == o) { ctx->opened.erase(ctx->opened.begin() + i); break; }
+  (void)hipSetDevice(ctx->device);
+  opened_free(o);
 }
 
 // The host walks every row header (the whole frame as a rectangle) and the index goes up with the

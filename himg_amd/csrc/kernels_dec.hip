@@ -4691,6 +4691,72 @@ __global__ void k_stream_status(DecWs ws, StreamWinWords sw, int32_t *status, in
 }
 
 // ---------------------------------------------------------------------------
+// OPENED STREAMS (himg_hip_open_streams_device, himg_hip_opened_regions_device): the products of the head --
+// DecFrame, the FRES tables, the row index, the low-res plane -- and the rows' records live in a HANDLE's
+// buffers, behind a DecWs of their own, and outlast the call.  Open runs the head of the many-windows decode
+// with these forms:
+//   k_open_rowwalk / k_open_set_index   k_stream_rowwalk / k_stream_set_index over ALL rows of every stream: one
+//                      walk serves whatever r1 a later window has.  walk_rows[s] and walk_st[s] are the handle's.
+//   k_open_finish      clears the valid word of every row record -- an uncounted row can never be read as
+//                      counted (the row kernel walks such a row serially: slow, never wrong) -- and copies the
+//                      head verdicts out.
+// A call on the handle runs no head:
+//   k_opened_gate      k_stream_gate from the kept walk words, and the kept head verdict with it:
+//                      status[k] = max(head of s_k, walk verdict for r1_k), written straight to the caller's
+//                      d_status, which then serves k_dec_stream_region as its window words.  That kernel reads
+//                      head | word and raises a rejected row with atomicMax: the word ends as
+//                      max(head, walk, row), which is k_stream_status's max(head, max(walk, row)).
+//   k_stream_count(_w) over the rows of this call's windows that no earlier call has counted (the host keeps
+//                      the bitmap), into the handle's records; no launch where nothing is new.  A record's
+//                      valid word is 1 (k_stream_count) or 3 (k_stream_count_w) whichever call wrote it;
+//                      dec_body_region.inc asks only valid != 0 and walks a lane's range token by token to
+//                      the next lane's start either way, so records of both forms serve one handle.
+//   k_dec_stream_region   as it is, against the handle's DecWs.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_open_rowwalk(Geom g, DecWs ws, const uint8_t *packed, size_t in_stride,
+                                                     const uint32_t *sizes, int32_t *walk_rows, int32_t *walk_st) {
+  constexpr int row_end = 0x7fffffff, resume = 0;
+  if (threadIdx.x == 0) { walk_rows[blockIdx.x] = kWalkNoVerdict; walk_st[blockIdx.x] = 0; }
+#include "dec_body_rowwalk.inc"
+  walk_rows[f] = r; walk_st[f] = st;
+  df->walk_status = 0;
+}
+
+__global__ __launch_bounds__(256) void k_open_set_index(Geom g, DecWs ws_all, const uint32_t *index_all,
+                                                        const uint32_t *sizes_all, int32_t *walk_rows, int32_t *walk_st) {
+  const int f_ = blockIdx.x;
+  DecWs ws = ws_all;
+  ws.frames += f_;
+  ws.row_off += (size_t)f_ * g.rows;
+  ws.row_len += (size_t)f_ * g.rows;
+  const uint32_t *index = index_all + (size_t)f_ * 2 * g.rows, *sizes = sizes_all + f_;
+  const int r0 = 0, r1 = g.rows;
+#include "dec_body_set_index.inc"
+  if (threadIdx.x == 0) {
+    walk_rows[f_] = bad ? 0 : kWalkNoVerdict; walk_st[f_] = bad ? fmt_err(7, 1) : 0;
+    df->walk_status = 0;
+  }
+}
+
+__global__ void k_open_finish(Geom g, DecWs ws, int32_t *head_status, int n_streams) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < (size_t)n_streams * g.rows) ws.lane_off[i * (kDecThreads + kRecHdr) + kDecThreads + 2] = 0;
+  if (head_status && i < (size_t)n_streams) head_status[i] = ws.frames[i].status;
+}
+
+__global__ void k_opened_gate(Geom g, DecWs ws, const int32_t *stream_of, const int32_t *org, const int32_t *walk_rows,
+                              const int32_t *walk_st, int32_t *status, int h, int n_windows) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_windows) return;
+  const int s = stream_of[k], r1 = region_r1(org, k, h);
+  int v = 0;
+  if (ws.frames[s].parse_status == 0)   // (k_stream_gate's rule)
+    v = r1 >= g.rows ? walk_st[s] : (walk_rows[s] < r1 ? fmt_err(7, 1) : 0);
+  const int hd = ws.frames[s].status;
+  status[k] = hd > v ? hd : v;
+}
+
+// ---------------------------------------------------------------------------
 // The ROW-SPAN family: block rows [k0_f, k1_f) of frame f at the full width, k0_f and k1_f known ON THE
 // DEVICE alone, so the count and row kernels take them from arrays where the region forms compute r1_f
 // from an origin; like those, each includes the body of the kernel it stands beside behind its own
@@ -5923,6 +5989,63 @@ void launch_stream_regions(const Geom &g, const DecWs &ws_in, int n_streams, con
                      stream, g, ws, d_packed, in_stride, d_sizes, ra, sw.stream_of, sw.wstat);
   prof_end(prof, stream);
   HIMG_LAUNCH(k_stream_status, dim3((n_windows + 63) / 64), dim3(64), ws, sw, d_status, n_windows);
+}
+
+// Opened streams (the kernels' comment above).  ws: the handle's products and records, with the context's LRES
+// scratch (lres_sym, spec_*) beside them.  The head as launch_stream_regions runs it, the walk to the end of
+// every stream's chunk beside it.
+void launch_open_streams(const Geom &g, const DecWs &ws_in, int n_streams, const uint8_t *d_packed, size_t in_stride,
+                         const uint32_t *d_sizes, const uint32_t *d_row_index, const OpenedWalk &walk,
+                         int32_t *d_head_status, hipStream_t stream, Profiler *prof, const DecStreams *ds) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;
+  launch_zero(g, ws, n_streams, stream, prof);
+  hipStream_t ws_ = side_fork(ds, stream);
+  prof_begin(prof, d_row_index ? "k_open_set_index" : "k_open_rowwalk", ws_);
+  if (d_row_index)
+    hipLaunchKernelGGL(k_open_set_index, dim3(n_streams), dim3(256), 0, ws_, g, ws, d_row_index, d_sizes, walk.rows, walk.st);
+  else
+    hipLaunchKernelGGL(k_open_rowwalk, dim3(n_streams), dim3(64), 0, ws_, g, ws, d_packed, in_stride, d_sizes, walk.rows,
+                       walk.st);
+  prof_end(prof, ws_);
+  side_walked(ds);
+  HIMG_LAUNCH(k_dec_parse, dim3(n_streams), dim3(kParseThreads), g, ws, d_packed, in_stride, d_sizes);
+  launch_lres_chain(g, ws, n_streams, d_packed, in_stride, d_sizes, stream, prof);
+  side_join(ds, stream);
+  const size_t n_rec = (size_t)n_streams * g.rows;
+  HIMG_LAUNCH(k_open_finish, dim3((unsigned)((n_rec + 255) / 256)), dim3(256), g, ws, d_head_status, n_streams);
+}
+
+// A call on the handle: the gate, the counts over the list (n_list = 0: none), the row kernel.  ws: the handle's.
+void launch_opened_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_packed, size_t in_stride,
+                           const uint32_t *d_sizes, const OpenedWalk &walk, const int32_t *d_stream_of,
+                           const int32_t *d_org, const int32_t *d_list, int n_windows, const int32_t *h_org, int n_list,
+                           long long list_rows, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream,
+                           Profiler *prof) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;
+  const WindowExtents e = window_extents(g, n_windows, h_org, 8, w, h);
+  HIMG_LAUNCH(k_opened_gate, dim3((n_windows + 63) / 64), dim3(64), g, ws, d_stream_of, d_org, walk.rows, walk.st, d_status,
+              h, n_windows);
+  if (n_list > 0) {
+    StreamWinWords sw = {};
+    sw.stream_of = d_stream_of; sw.org = d_org; sw.list = d_list;
+    sw.walk_rows = walk.rows; sw.walk_st = walk.st;
+    const CountRule cr = count_rule(g, list_rows, true);
+    if (cr.wave) {
+      HIMG_LAUNCH(k_stream_count_w, dim3(n_list), dim3(kDecThreads), cr.g, ws, d_packed, in_stride, d_sizes, sw);
+    } else {
+      HIMG_LAUNCH(k_stream_count, dim3(n_list), dim3(kDecThreads), cr.g, ws, d_packed, in_stride, d_sizes, sw, cr.rpc);
+    }
+  }
+  const int smax = region_strip_tiles(g);
+  const int nstrip = (e.ntiles + smax - 1) / smax, swt = (e.ntiles + nstrip - 1) / nstrip;
+  RegionArgs ra;
+  ra.org = d_org; ra.sw = swt; ra.w = w; ra.h = h; ra.out = d_out;
+  prof_begin(prof, "k_dec_stream_region", stream);
+  hipLaunchKernelGGL(k_dec_stream_region, dim3(nstrip, e.nrows, n_windows), dim3(kDecThreads), region_layout(g.C, swt).total,
+                     stream, g, ws, d_packed, in_stride, d_sizes, ra, d_stream_of, d_status);
+  prof_end(prof, stream);
 }
 
 // What the row-span decodes share behind their gates and walks: the fill over w.kfill, the counts and the row

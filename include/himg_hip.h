@@ -592,6 +592,89 @@ int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_t *packed, 
                                       const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
                                       int *statuses, int *width, int *height, int *channels);
 
+/* ---- region decode: streams opened once, windows in many calls -------------------- */
+/*
+ * himg_hip_decode_stream_regions_device makes ONE call with many windows cheap; a tile server, a viewer
+ * that pans or a loader that draws crops over an epoch makes MANY calls on the same streams, and each of
+ * them ran the whole head again.  An opened-streams handle keeps what the head produces -- the parsed
+ * frame, the FRES tables, the row index, the low-res plane -- and the per-row records of the count
+ * kernels in device memory of its own:
+ *   open     runs the head once per stream and walks ALL row headers once;
+ *   a call   decodes windows against the handle.  No parse, no LRES chain, no walk; a block row is counted
+ *            the first time any call touches it and never again.
+ *
+ * Nothing new is defined about pixels or verdicts.  For any sequence of himg_hip_opened_regions_device
+ * calls on a handle -- w x h may differ from call to call; windows may overlap, repeat and come in any
+ * order of stream -- each call's d_status words, and the pixels of every window with status 0, are EXACTLY
+ * what himg_hip_decode_stream_regions_device gives for the same streams, map, origins and w x h under the
+ * HIMG_OPT_FIX_T2 the context had at open (the handle records it; a later change of the option does not
+ * reach the handle).  Its independence rules hold in whichever call a window comes, and so do its argument
+ * checks (HIMG_ERR_ARG, nothing written, no row marked as counted), its grid limits and the rule that
+ * nothing outside n_windows x h x w x C bytes of d_out and n_windows words of d_status is written.
+ *
+ * Bytes used.  Open loads [0, head_bytes) and the size headers to the end of the FRES chunk.  After open
+ * the device form loads only payload bytes of touched rows from d_packed (with the bit readers' look-ahead):
+ * the head and the size headers are never read again.  The caller keeps d_packed valid and its payloads
+ * unchanged while the handle lives; the host form uploads the stream into memory the handle owns.
+ *
+ * Ownership and order.  A handle belongs to the context that opened it; with another context, or after
+ * himg_hip_close_streams, every entry returns HIMG_ERR_ARG.  It is ordered by the caller's stream alone,
+ * under the rule of "Streams" above: open and the calls queued behind it on one stream need no host wait.
+ * Open may wait for the device once, when it allocates the handle's memory (the rule of a context's first
+ * call at a larger geometry); nothing else synchronises.  himg_hip_close_streams waits for the handle's
+ * last call and frees; himg_hip_destroy closes the handles that are left.  A stream whose head fails still
+ * opens: its windows get that status.
+ *
+ * Device memory of a handle over n streams, each term rounded up to 256 bytes (himg_hip_opened_bytes;
+ * rows = ceil(H / 8), cols = ceil(W / 8)):
+ *   n x 1616                                        the parsed frames
+ *   n x 4176 + n x 32768 + n x 16384 + n x 16384    the tables (nodes, groups, count groups, second level)
+ *   n x rows x 8                                    the row index
+ *   n x roundup256(C x rows x cols)                 the low-res planes
+ *   n x rows x (2 x 1024 + 72) x 4                  the records
+ *   (n x (rows + 1) x 8 + n x 4 + n x rows x 8) x 4 the kernels' diagnostics
+ *   n x 12                                          the packed sizes and the walk's words
+ * The records (8480 bytes per block row) and the low-res planes dominate: 17.4 + 16.8 MB for one 16384^2
+ * RGBA stream, 704 MB for 128 x 4096^2.
+ *
+ * Not in this change: scaled, tensor and pitched store forms; eviction or a cap on a handle's memory;
+ * re-opening on a changed stream; a prefix that grows under a handle; the C++ classes and the
+ * command-line tools; the multi-GPU handle and the row-sharded paths.
+ */
+typedef struct himg_hip_opened himg_hip_opened;
+
+/* Host only, no GPU: the device bytes a handle over n_streams streams of this geometry holds, without the
+ * streams.  HIMG_ERR_ARG: a bad geometry, n_streams outside 1 .. 65535, bytes NULL. */
+int himg_hip_opened_bytes(int width, int height, int num_channels, int n_streams, size_t *bytes);
+
+/* Streams in HBM: the argument contract of himg_hip_decode_stream_regions_device up to num_channels.
+ * d_head_status (may be NULL): n_streams words, each stream's head verdict. */
+int himg_hip_open_streams_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes,
+                                 int n_streams, int width, int height, int num_channels,
+                                 int32_t *d_head_status, himg_hip_opened **out, void *stream);
+/* One HOST stream, uploaded whole into memory the handle owns; the geometry from FRMT.  The rows are
+ * indexed on the host where it can (himg_hip_index_host); a stream it cannot index takes the device walk.
+ * On the null stream; returns when the upload has read `packed`. */
+int himg_hip_open_stream_host(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, himg_hip_opened **out);
+
+/* Windows against a handle: h_stream_of, h_origins, n_windows, w, h, d_out, d_status and stream as in
+ * himg_hip_decode_stream_regions_device. */
+int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, const int32_t *h_stream_of,
+                                   const int32_t *h_origins, int n_windows, int w, int h,
+                                   void *d_out, int32_t *d_status, void *stream);
+/* The host form: n windows into dst (n x h x w x C bytes), statuses[k] as himg_hip_decode_stream_regions_to;
+ * h_stream_of may be NULL (every window of stream 0).  The capacity rule of himg_hip_decode_pyramid_to: a
+ * NULL or short dst gives HIMG_ERR_CAPACITY with *width = w, *height = h, *channels = C and nothing
+ * decoded.  Waits for its result (on the null stream). */
+int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
+                               const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
+                               int *statuses, int *width, int *height, int *channels);
+/* What a handle holds (any pointer may be NULL); rows_counted: the (stream, block row) pairs a call has
+ * queued a count for. */
+int himg_hip_opened_info(const himg_hip_opened *o, int *n_streams, int *width, int *height, int *channels,
+                         size_t *device_bytes, long long *rows_counted);
+void himg_hip_close_streams(himg_hip_ctx *ctx, himg_hip_opened *o);
+
 /* ---- decode into windows of pitched destination pictures ------------------------- */
 /*
  * The decode entry points above write batch x H x W x C tightly packed bytes.  These take a row pitch,
