@@ -181,6 +181,7 @@ def lib():
     L.himg_hip_shard_head.argtypes = [vp, vp, vp, vp, sz, vp, vp, vp, vp]
     L.himg_hip_shard_finish.argtypes = [vp, vp, sz, vp, vp]
     L.himg_hip_debug_read.argtypes = [vp, i32, i32, vp, sz, P(sz)]
+    L.himg_hip_debug_trees.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp]
     L.himg_hip_profile_enable.argtypes = [vp, i32]
     L.himg_hip_profile_reset.argtypes = [vp]
     L.himg_hip_profile_read.argtypes = [vp, P(i32), P(C.c_char_p), P(C.c_double), P(i32)]
@@ -1125,6 +1126,20 @@ class Engine:
         rc = lib().himg_hip_debug_read(self._ctx, sel, frame, buf.ctypes.data, nbytes, C.byref(n))
         self._check(rc, "debug_read(%s)" % what)
         return buf[: n.value].view(dtype)
+
+    def debug_trees(self, hists):
+        """himg_hip_debug_trees: k_tree alone on n histograms of 261 counts, each in both stream slots of
+        its own frame.  Returns codes [n][2][261] u64, lens [n][2][261] u32, trees [n][2][384] u8,
+        tree_bytes [n][2] u32 and status [n] i32 (3: a code longer than 32 bits)."""
+        h = np.ascontiguousarray(hists, np.uint32).reshape(-1, 261)
+        n = h.shape[0]
+        codes, lens = np.zeros((n, 2, 261), np.uint64), np.zeros((n, 2, 261), np.uint32)
+        trees, nb = np.zeros((n, 2, 384), np.uint8), np.zeros((n, 2), np.uint32)
+        status = np.zeros(n, np.int32)
+        rc = lib().himg_hip_debug_trees(self._ctx, h.ctypes.data, n, codes.ctypes.data, lens.ctypes.data,
+                                        trees.ctypes.data, nb.ctypes.data, status.ctypes.data)
+        self._check(rc, "debug_trees")
+        return codes, lens, trees, nb, status
 
     def profile(self, enable):
         lib().himg_hip_profile_enable(self._ctx, 1 if enable else 0)

@@ -244,6 +244,10 @@ inline bool enc_tok_stage_fits(const Geom &g) { return tok_stage_need(g.row_bloc
 // Debug: expand frame `frame`'s token stream into symbols again (dst: fres_size bytes).
 void launch_tok_expand(const Geom &g, const EncWs &ws, int frame, uint8_t *dst, hipStream_t stream);
 
+// Debug: k_tree alone over both stream slots of n frames (only hist, codes, lens, tree, tree_nbytes and
+// status of ws are touched: himg_hip_debug_trees).
+void launch_debug_trees(const EncWs &ws, int n, hipStream_t stream);
+
 void launch_encode(const Geom &g, const EncWs &ws, int batch, const uint8_t *d_frames,
                    uint8_t *d_out, size_t out_stride, uint32_t *d_sizes,
                    const StaticChunks &sc, const ShiftTables &st, const LresTables &lt,

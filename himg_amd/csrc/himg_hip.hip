@@ -151,6 +151,7 @@ struct himg_hip_ctx {
 
   // Encoder workspace.
   DevBuf e_planes, e_lres, e_fres, e_small, e_spanhist, e_tok, e_tokx;
+  DevBuf e_dbgtree;          // himg_hip_debug_trees' scratch workspace
   // Quality per frame and the searches: the tables of all 101 qualities (built on first use) and
   // the per-frame words of a launch (a SearchState's arrays, the quality first).
   DevBuf e_qtab, e_search;
@@ -406,7 +407,7 @@ extern "C" void himg_hip_destroy(himg_hip_ctx *ctx) {
     hipHostFree(ctx->pipe.h_meta);
   }
   DevBuf *all[] = {&ctx->fmap_lut, &ctx->e_planes, &ctx->e_lres, &ctx->e_fres, &ctx->e_small,
-                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_qtab, &ctx->e_search, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
+                   &ctx->e_spanhist, &ctx->e_tok, &ctx->e_tokx, &ctx->e_dbgtree, &ctx->e_qtab, &ctx->e_search, &ctx->e_stab, &ctx->e_rec, &ctx->d_frames, &ctx->d_nodes, &ctx->d_grp, &ctx->d_gyc, &ctx->d_sub, &ctx->d_lane, &ctx->d_rows,
                    &ctx->d_lres, &ctx->d_fres, &ctx->d_planes, &ctx->d_sizes, &ctx->d_stats, &ctx->d_spec, &ctx->d_cmap, &ctx->h_in,
                    &ctx->h_out, &ctx->h_result, &ctx->h_status, &ctx->h_index};
   for (DevBuf *b : all) b->release();
@@ -3738,6 +3739,49 @@ extern "C" int himg_hip_debug_read(himg_hip_ctx *ctx, int what, int frame, void 
   if (dst_bytes < n) return HIMG_ERR_CAPACITY;
   HIP_TRY(ctx, hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
   if (written) *written = n;
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_debug_trees(himg_hip_ctx *ctx, const uint32_t *hist, int n, uint64_t *codes,
+                                    uint32_t *lens, uint8_t *trees, uint32_t *tree_bytes, int32_t *status) {
+  if (!ctx || !hist || !codes || !lens || !trees || !tree_bytes || !status || n < 1 || n > 16384) return HIMG_ERR_ARG;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  // The workspace as k_tree expects it: [frame][2 slots][padded row]; nothing else of an EncWs is read.
+  const size_t slots = (size_t)n * 2;
+  size_t total = 0;
+  auto carve = [&](size_t bytes) { const size_t o = total; total += round_up(bytes, 256); return o; };
+  const size_t o_hist = carve(slots * kHistStride * 4), o_codes = carve(slots * kHistStride * 8);
+  const size_t o_lens = carve(slots * kHistStride * 4), o_tree = carve(slots * kTreeStride);
+  const size_t o_nb = carve(slots * 4), o_status = carve((size_t)n * 4);
+  if (!ctx->e_dbgtree.reserve(total)) return fail(ctx, HIMG_ERR_HIP, "tree scratch allocation failed");
+  uint8_t *base = (uint8_t *)ctx->e_dbgtree.p;
+  EncWs w{};
+  w.hist = (uint32_t *)(base + o_hist);
+  w.codes = (uint64_t *)(base + o_codes);
+  w.lens = (uint32_t *)(base + o_lens);
+  w.tree = base + o_tree;
+  w.tree_nbytes = (uint32_t *)(base + o_nb);
+  w.status = (int32_t *)(base + o_status);
+  std::vector<uint32_t> h(slots * kHistStride, 0u);
+  for (size_t s = 0; s < slots; ++s) memcpy(&h[s * kHistStride], hist + (s / 2) * kNumSym, kNumSym * 4);
+  HIP_TRY(ctx, hipMemset(base, 0, total));
+  HIP_TRY(ctx, hipMemcpy(w.hist, h.data(), h.size() * 4, hipMemcpyHostToDevice));
+  himg_dev::launch_debug_trees(w, n, nullptr);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  std::vector<uint64_t> c(slots * kHistStride);
+  std::vector<uint8_t> t(slots * kTreeStride);
+  HIP_TRY(ctx, hipMemcpy(c.data(), w.codes, c.size() * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(h.data(), w.lens, h.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(t.data(), w.tree, t.size(), hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(tree_bytes, w.tree_nbytes, slots * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(status, w.status, (size_t)n * 4, hipMemcpyDeviceToHost));
+  for (size_t s = 0; s < slots; ++s) {
+    memcpy(codes + s * kNumSym, &c[s * kHistStride], kNumSym * 8);
+    memcpy(lens + s * kNumSym, &h[s * kHistStride], kNumSym * 4);
+    memcpy(trees + s * kTreeStride, &t[s * kTreeStride], kTreeStride);
+  }
   return HIMG_OK;
 }
 

@@ -2675,6 +2675,10 @@ static void launch_emit_tok(const Geom &g, const EncWs &ws, uint8_t *d_out, size
   prof_end(prof, stream);
 }
 
+void launch_debug_trees(const EncWs &ws, int n, hipStream_t stream) {
+  hipLaunchKernelGGL(k_tree, dim3(2, n), dim3(kTreeThreads), 0, stream, ws, 0);
+}
+
 void launch_tok_expand(const Geom &g, const EncWs &ws, int frame, uint8_t *dst, hipStream_t stream) {
   (void)hipMemsetAsync(dst, 0, (size_t)g.fres_size, stream);
   hipLaunchKernelGGL(k_tok_expand, dim3((g.rows + 63) / 64), dim3(64), 0, stream, g, ws, frame, dst);

@@ -1382,6 +1382,18 @@ int himg_hip_debug_row_records(himg_hip_ctx *ctx, const void *d_packed, size_t i
                                const uint32_t *h_sizes, int batch, int width, int height,
                                int num_channels, int32_t *d_status, void *stream);
 
+/* The encoder's tree kernel (k_tree) alone, on histograms of the caller's: n token histograms of 261
+ * counts each (host memory, none of them empty, every total at most 2^31 - 1 like the reference's
+ * int counts; 1 <= n <= 16384).  Histogram i is put into BOTH stream slots (0 = LRES, 1 = FRES) of frame
+ * i of a scratch workspace of the call's own -- the last encode's buffers are not touched -- and
+ * the unchanged kernel runs over them.  All outputs are host arrays: codes [n][2][261] (LSB first),
+ * lens [n][2][261], trees [n][2][384] (the serialised tree, zero behind its tree_bytes [n][2] bytes)
+ * and status [n] (0, or 3 where a code is longer than 32 bits: what an encode would answer with
+ * HIMG_ERR_UNSUPPORTED).  For the tests that hold the kernel against the reference's tree on
+ * histograms no picture produces.  Synchronises the device. */
+int himg_hip_debug_trees(himg_hip_ctx *ctx, const uint32_t *hist, int n, uint64_t *codes,
+                         uint32_t *lens, uint8_t *trees, uint32_t *tree_bytes, int32_t *status);
+
 /* Per-stage device timing with hipEvents recorded on the caller's stream.
  * enable != 0 brackets every kernel of the following calls; stage_ms returns
  * the accumulated milliseconds and launch counts since the last reset. */

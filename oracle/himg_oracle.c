@@ -640,6 +640,26 @@ static void make_tree(symtab *st, bitw *w) {
     store_tree(nodes, 0, st, w, 0, 1); /* single symbol: huffman_enc.cpp:231-237 */
 }
 
+/* The tree builder on its own, for tests of the tree alone: the histogram in, the code table and
+ * the serialised tree (byte aligned, at most kMaxTreeDataSize bytes) out.  Exactly what
+ * huffman_compress does with a histogram; codes longer than 64 bits do not fit code[]. */
+void himg_oracle_tree(const uint32_t hist[261], uint64_t code[261], uint8_t bits[261],
+                      uint8_t *tree, int *tree_bytes) {
+  uint8_t buf[kMaxTreeDataSize + 1];
+  bitw w = {buf, buf, 0};
+  symtab st;
+  memset(&st, 0, sizeof(st));
+  memcpy(st.count, hist, sizeof(st.count));
+  memset(buf, 0, sizeof(buf));
+  make_tree(&st, &w);
+  align_to_byte(&w);
+  const int n = bitw_size(&w);
+  memcpy(code, st.code, sizeof(st.code));
+  memcpy(bits, st.bits, sizeof(st.bits));
+  if (tree) memcpy(tree, buf, (size_t)n);
+  if (tree_bytes) *tree_bytes = n;
+}
+
 /* huffman_enc.cpp:246-363.  Returns the packed size.  row_bytes (optional)
  * receives the payload size of every block; tree_bytes the tree size. */
 static int huffman_compress(uint8_t *out, const uint8_t *in, int in_size,

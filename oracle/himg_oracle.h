@@ -77,6 +77,12 @@ uint8_t himg_oracle_map_to_8bit(const int16_t table[128], int x);
 void himg_oracle_hadamard_forward(int16_t *out, const int16_t *in);
 void himg_oracle_hadamard_inverse(int16_t *out, const int16_t *in);
 
+/* The encoder's Huffman tree builder alone (huffman_enc.cpp:148-238): token histogram in; LSB-first
+ * codes, code lengths and the byte-aligned serialised tree (at most 359 bytes) out.  The empty
+ * histogram is not a valid input (the format never produces it). */
+void himg_oracle_tree(const uint32_t hist[261], uint64_t code[261], uint8_t bits[261],
+                      uint8_t *tree, int *tree_bytes);
+
 #ifdef __cplusplus
 }
 #endif

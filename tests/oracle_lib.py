@@ -143,6 +143,30 @@ def oracle_decode_trace(packed):
     return 0, res
 
 
+def oracle_tree(hist):
+    """himg_oracle_tree: the oracle's own tree builder (make_tree / store_tree) on a histogram of 261
+    counts.  Returns (lens uint8[261], codes uint64[261] LSB first, tree bytes, their count)."""
+    h = np.ascontiguousarray(hist, np.uint32)
+    assert h.shape == (261,) and h.any()
+    code, bits = np.zeros(261, np.uint64), np.zeros(261, np.uint8)
+    tree, n = np.zeros(360, np.uint8), C.c_int()
+    oracle().himg_oracle_tree.restype = None
+    oracle().himg_oracle_tree(h.ctypes.data_as(C.c_void_p), code.ctypes.data_as(C.c_void_p),
+                              bits.ctypes.data_as(C.c_void_p), tree.ctypes.data_as(C.c_void_p), C.byref(n))
+    return bits, code, tree[:n.value].tobytes(), n.value
+
+
+def chunk_payloads(packed):
+    """Offsets of the chunk payloads of a stream by tag (the RIFF walk of decoder.cpp:144-200)."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    out, off = {}, 12
+    while off + 8 <= packed.size:
+        size = int.from_bytes(packed[off + 4:off + 8].tobytes(), "little")
+        out[packed[off:off + 4].tobytes().decode("latin1")] = (off + 8, size)
+        off += 8 + size
+    return out
+
+
 def ref_encode(img, quality=50, use_ycbcr=True, channels=None, stride=None):
     img = np.ascontiguousarray(img, np.uint8)
     h, w = img.shape[:2]

@@ -7,80 +7,13 @@ the two lightest nodes and s = count(x1) + count(x2), every node created from no
 least s, so all nodes lighter than s are consumed first, in that order and in consecutive pairs;
 an odd last one is left over for the next batch.  This file states that batching in plain Python
 (same thresholds and the same 64-per-kind cap as the kernel; what a batch does not take goes to
-the serial loop, like there) and compares the sequence of merges with the O(n^2) definition on
-tie-heavy, geometric, heavy-tailed, uniform and all-equal histograms.  The kernel itself is
-checked byte for byte by the GPU parity tests; this pins the reasoning it rests on."""
+the serial loop, like there; the two functions live in tests/tree_model.py) and compares the
+sequence of merges with the O(n^2) definition on tie-heavy, geometric, heavy-tailed, uniform and
+all-equal histograms.  The kernel itself is checked byte for byte by the GPU parity tests and, on
+histograms no picture produces, by tests/test_gpu_trees.py; this pins the reasoning it rests on."""
 import numpy as np
 
-
-def merges_by_definition(counts):
-    cnt = list(counts)
-    alive = list(range(len(cnt)))
-    out = []
-    while len(alive) > 1:
-        alive.sort(key=lambda i: (cnt[i], -i))
-        a, b = alive[0], alive[1]
-        cnt.append(cnt[a] + cnt[b])
-        out.append((a, b))
-        alive = alive[2:] + [len(cnt) - 1]
-    return out
-
-
-def merges_in_batches(counts, cap=64):
-    n = len(counts)
-    cnt = list(counts)
-    leaves = sorted(range(n), key=lambda i: (cnt[i], -i))
-    lh, qh, nxt, y = 0, n, n, None
-    out, rounds, serial = [], 0, 0
-    while (n - lh) + (nxt - qh) + (y is not None) >= 2:
-        heads = ([cnt[y]] if y is not None else []) + [cnt[leaves[k]] for k in range(lh, min(lh + 2, n))] \
-            + [cnt[q] for q in range(qh, min(qh + 2, nxt))]
-        heads.sort()
-        s = heads[0] + heads[1]
-        if lh + cap < n and cnt[leaves[lh + cap]] < s:
-            s = cnt[leaves[lh + cap]]
-        if qh + cap < nxt and cnt[qh + cap] < s:
-            s = cnt[qh + cap]
-        L = [leaves[k] for k in range(lh, min(lh + cap, n)) if cnt[leaves[k]] < s]
-        I = [q for q in range(qh, min(qh + cap, nxt)) if cnt[q] < s]
-        yin = y is not None and cnt[y] < s
-        m = int(yin) + len(L) + len(I)
-        if m < 2:      # the serial loop takes the rest
-            rest = ([y] if y is not None else []) + [leaves[k] for k in range(lh, n)] + list(range(qh, nxt))
-            while len(rest) > 1:
-                rest.sort(key=lambda i: (cnt[i], -i))
-                a, b = rest[0], rest[1]
-                cnt.append(cnt[a] + cnt[b])
-                out.append((a, b))
-                rest = rest[2:] + [len(cnt) - 1]
-                serial += 1
-            return out, rounds, serial
-        # rank inside the batch exactly as the kernel computes it
-        ranked = {}
-        base = int(yin)
-        if yin:
-            ranked[0] = y
-        for a, leaf in enumerate(L):
-            le = sum(1 for q in I if cnt[q] <= cnt[leaf])
-            ranked[base + a + le] = leaf
-        for b, q in enumerate(I):
-            run_b = b
-            while run_b > 0 and cnt[I[run_b - 1]] == cnt[q]:
-                run_b -= 1
-            run_e = b + 1
-            while run_e < len(I) and cnt[I[run_e]] == cnt[q]:
-                run_e += 1
-            kb = run_b + (run_e - 1 - b)
-            lt = sum(1 for leaf in L if cnt[leaf] < cnt[q])
-            ranked[base + kb + lt] = q
-        assert sorted(ranked) == list(range(m)), "ranks are a permutation"
-        B = [ranked[k] for k in range(m)]
-        for k in range(m // 2):
-            cnt.append(cnt[B[2 * k]] + cnt[B[2 * k + 1]])
-            out.append((B[2 * k], B[2 * k + 1]))
-        y = B[m - 1] if m & 1 else None
-        lh, qh, nxt, rounds = lh + len(L), qh + len(I), nxt + m // 2, rounds + 1
-    return out, rounds, serial
+from tree_model import merges_by_definition, merges_in_batches
 
 
 def _hist(kind, n, rng):
