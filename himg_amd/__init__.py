@@ -130,6 +130,8 @@ def lib():
     L.himg_hip_open_stream_host.argtypes = [vp, vp, sz, P(vp)]
     L.himg_hip_opened_regions_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.himg_hip_opened_regions_to.argtypes = [vp, vp, i32, vp, vp, i32, i32, vp, sz, vp, P(i32), P(i32), P(i32)]
+    L.himg_hip_opened_scaled_regions_device.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.himg_hip_opened_scaled_regions_to.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, sz, vp, P(i32), P(i32), P(i32)]
     L.himg_hip_opened_info.argtypes = [vp, P(i32), P(i32), P(i32), P(i32), P(sz), P(C.c_longlong)]
     L.himg_hip_close_streams.argtypes = [vp, vp]
     L.himg_hip_close_streams.restype = None
@@ -1199,6 +1201,42 @@ class OpenedStreams:
                                               C.byref(wo), C.byref(ho), C.byref(co))
         if rc != 0 and (wo.value == 0 or rc == HIMG_ERR_CAPACITY):
             self._eng._check(rc, "opened regions")
+        return out.ravel()[:cap].reshape(n, ho.value, wo.value, co.value), st[:n].copy()
+
+    def scaled_regions_device(self, scale_log2, stream_of, origins, w, h, d_out, d_status, stream=None, engine=None):
+        """himg_hip_opened_scaled_regions_device: window k is the w x h rectangle at origins[k] of stream
+        stream_of[k]'s picture at 1 / 2^scale_log2 (1, 2: bytes and status words as
+        Engine.decode_scaled_regions_device on that stream alone; 3: the crop of Engine.preview_device's output and
+        the stream's head verdict).  engine: as in regions_device."""
+        so = None if stream_of is None else np.ascontiguousarray(np.asarray(stream_of, np.int32).ravel())
+        org = None if origins is None else np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = 0 if so is None else int(so.size)
+        if org is not None and so is not None and org.shape[0] != n:
+            raise ValueError("stream_of and origins differ in length")
+        eng = engine or self._eng
+        rc = lib().himg_hip_opened_scaled_regions_device(
+            eng._ctx if self._h else None, self._h, int(scale_log2), so.ctypes.data if n else None,
+            org.ctypes.data if org is not None and org.size else None, n, int(w), int(h), _ptr(d_out), _ptr(d_status),
+            C.c_void_p(stream or 0))
+        eng._check(rc, "opened scaled_regions_device")
+
+    def scaled_regions(self, scale_log2, origins, w, h, stream_of=None, out=None):
+        """himg_hip_opened_scaled_regions_to: ((n, h, w, C) uint8 array, statuses) as regions(), the windows those
+        of the picture at 1 / 2^scale_log2; stream_of None: every window of stream 0."""
+        org = np.ascontiguousarray(np.asarray(origins, np.int32).reshape(-1, 2))
+        n = org.shape[0]
+        so = None if stream_of is None else np.ascontiguousarray(np.asarray(stream_of, np.int32).ravel())
+        c = self.info()["channels"]
+        cap = n * max(int(w), 0) * max(int(h), 0) * c
+        out = _out_buffer(out, cap)
+        st = np.zeros(max(n, 1), np.int32)
+        wo, ho, co = C.c_int(), C.c_int(), C.c_int()
+        rc = lib().himg_hip_opened_scaled_regions_to(self._ctx(), self._h, int(scale_log2), n,
+                                                     so.ctypes.data if so is not None else None, org.ctypes.data, int(w),
+                                                     int(h), out.ctypes.data, cap, st.ctypes.data, C.byref(wo),
+                                                     C.byref(ho), C.byref(co))
+        if rc != 0 and (wo.value == 0 or rc == HIMG_ERR_CAPACITY):
+            self._eng._check(rc, "opened scaled_regions")
         return out.ravel()[:cap].reshape(n, ho.value, wo.value, co.value), st[:n].copy()
 
     def info(self):

@@ -18,7 +18,7 @@ HIP_SOURCES = ["kernels_enc.hip", "kernels_dec.hip", "himg_hip.hip", "himg_multi
 CXX_SOURCES = ["encoder.cpp", "decoder.cpp"]
 C_SOURCES = ["himg_tables.c", "himg_synth.c"]
 HEADERS = ["himg_dev.h", "search_step.h", "loop_counts.h", "himg_tables.h", "ctx_pool.h", "prefix_walk.h", "opened_plan.h", "dec_body_rowwalk.inc", "dec_body_set_index.inc",
-           "dec_body_row_count.inc", "dec_body_row_count_w.inc", "dec_body_scaled_tile.inc", "dec_body_region.inc", "enc_body_lres_predict.inc", "enc_body_lowres_avg.inc", "enc_body_tile_fwd.inc",
+           "dec_body_row_count.inc", "dec_body_row_count_w.inc", "dec_body_scaled_tile.inc", "dec_body_region.inc", "dec_body_scaled_region.inc", "enc_body_lres_predict.inc", "enc_body_lowres_avg.inc", "enc_body_tile_fwd.inc",
            "enc_body_pix_fwd.inc", "enc_body_front.inc", "../../include/himg_hip.h",
            "../../include/encoder.h", "../../include/decoder.h"]
 

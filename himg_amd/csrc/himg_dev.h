@@ -481,6 +481,18 @@ void launch_opened_regions(const Geom &g, const DecWs &ws, const uint8_t *d_pack
                            const int32_t *d_org, const int32_t *d_list, int n_windows, const int32_t *h_org, int n_list,
                            long long list_rows, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream,
                            Profiler *prof);
+// A scaled call on the handle (himg_hip_opened_scaled_regions_device): window k, w x h samples of stream
+// stream_of[k]'s picture at 1 / 2^scale_log2.  scale_log2 = 1, 2: h_org / d_org hold the origins of the
+// full-resolution rectangles the windows cover, (F x_k, F y_k), as launch_region takes them; k_opened_gate and the
+// counts over d_list run with the height F h -- the list is the handle's, so a row counted by a full-resolution
+// call is not counted again, and the other way round --, then k_dec_opened_scaled_region.  scale_log2 = 3: d_org
+// holds the origins in the ceil(W / 8) x ceil(H / 8) picture; k_opened_preview_region alone crops the kept
+// low-res plane and writes the kept head verdict; d_list, h_org and d_packed are not used.
+void launch_opened_scaled_regions(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
+                                  const uint32_t *d_sizes, const OpenedWalk &walk, int scale_log2,
+                                  const int32_t *d_stream_of, const int32_t *d_org, const int32_t *d_list, int n_windows,
+                                  const int32_t *h_org, int n_list, long long list_rows, int w, int h, uint8_t *d_out,
+                                  int32_t *d_status, hipStream_t stream, Profiler *prof);
 // The decode of stream prefixes (include/himg_hip.h): frame f's first d_words[f] bytes are present.
 // k_span_gate (the head of the stream with every load checked against the bytes present, then the frame's
 // state against what it found), the head phase in its prefix form (k_dec_parse_prefix, the LRES chain

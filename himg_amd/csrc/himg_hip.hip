@@ -195,11 +195,11 @@ struct himg_hip_ctx {
   // into a ctx-owned pinned slot; a slot is reused only after the copy that read it
   // has run (event).
   struct SizeRing {
-    static constexpr int kSlots = 4;
-    uint32_t *h[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    size_t cap[kSlots] = {0, 0, 0, 0};
-    hipEvent_t ev[kSlots] = {nullptr, nullptr, nullptr, nullptr};
-    bool busy[kSlots] = {false, false, false, false};
+    static constexpr int kSlots = 8;   // (a viewer's open, pan and zoom calls queue behind one another without a wait)
+    uint32_t *h[kSlots] = {};
+    size_t cap[kSlots] = {};
+    hipEvent_t ev[kSlots] = {};
+    bool busy[kSlots] = {};
     int next = 0;
   } sizes_ring;
 
@@ -3411,22 +3411,36 @@ extern "C" int himg_hip_open_stream_host(himg_hip_ctx *ctx, const uint8_t *packe
   return rc;
 }
 
-extern "C" int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, const int32_t *h_stream_of,
-                                              const int32_t *h_org, int n_windows, int w, int h, void *d_out,
-                                              int32_t *d_status, void *stream) {
+// A call on a handle, every argument checked before anything is launched.  scale_log2 = 0: the windows of the
+// full-resolution picture.  1, 2, 3: of the picture at that scale -- ow x oh by himg_hip_scaled_size, and
+// ceil(W / 8) x ceil(H / 8) at 3 --, the origins in its coordinates.  At 1 and 2 the planner and the device get the
+// origins of the full-resolution rectangles the windows cover, (F x, F y), and the height F h (region_launch's
+// rule); at 3 no row is touched, so nothing is planned and the origins go up as they are.
+static int opened_launch(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2, const int32_t *h_stream_of,
+                         const int32_t *h_org, int n_windows, int w, int h, void *d_out, int32_t *d_status, void *stream) {
   if (!opened_owned(ctx, o) || !h_stream_of || !h_org || !d_out || !d_status || n_windows < 1 || n_windows > 65535)
     return HIMG_ERR_ARG;
+  if (scale_log2 < 0 || scale_log2 > 3) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1, 2 or 3");
+  const int F = 1 << scale_log2;
+  const int ow = (int)(((long long)o->W + F - 1) / F), oh = (int)(((long long)o->H + F - 1) / F);
   for (int k = 0; k < n_windows; ++k) {
     if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams) return fail(ctx, HIMG_ERR_ARG, "stream_of outside the streams");
-    if (!region_ok(o->W, o->H, h_org[2 * k], h_org[2 * k + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
+    if (!region_ok(ow, oh, h_org[2 * k], h_org[2 * k + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
   }
   Geom g;
   if (int rc = decode_args(ctx, o->W, o->H, o->C, o->n_streams, kWsRegion, o->d_packed, d_out, nullptr, nullptr, &g)) return rc;
   g.fix_t2 = o->fix_t2;
   ctx->head.valid = false;   // (the words below overwrite the sizes a head phase staged)
+  const bool rows_touched = scale_log2 != 3;
+  std::vector<int32_t> up_org;
+  if (scale_log2 == 1 || scale_log2 == 2) {
+    up_org.resize(2 * (size_t)n_windows);
+    for (size_t i = 0; i < up_org.size(); ++i) up_org[i] = F * h_org[i];
+    h_org = up_org.data();
+  }
   // The rows of these windows that no call has counted yet, cut into the count kernels' entries.
   std::vector<himg_dev::OpenedRun> runs;
-  const long long list_rows = o->rows.pending(h_stream_of, h_org, n_windows, h, &runs);
+  const long long list_rows = rows_touched ? o->rows.pending(h_stream_of, h_org, n_windows, F * h, &runs) : 0;
   const size_t o_org = (size_t)n_windows, o_list = o_org + 2 * (size_t)n_windows;
   std::vector<uint32_t> words(o_list);
   memcpy(words.data(), h_stream_of, (size_t)n_windows * 4);
@@ -3440,23 +3454,45 @@ extern "C" int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened
   if (int rc = stage_words(ctx, ctx->d_sizes.p, words.data(), words.size(), nullptr, 0, ctx->last_stream)) return rc;
   o->rows.mark(runs);   // (queued: the stream orders the counts in front of whatever call reads them)
   const int32_t *dw = (const int32_t *)ctx->d_sizes.p;
-  himg_dev::launch_opened_regions(g, o->ws, o->d_packed, o->in_stride, o->d_sizes, o->walk, dw, dw + o_org, dw + o_list,
-                                  n_windows, h_org, (int)n_list, list_rows, w, h, (uint8_t *)d_out, d_status,
-                                  (hipStream_t)stream, &ctx->prof);
+  if (scale_log2)
+    himg_dev::launch_opened_scaled_regions(g, o->ws, o->d_packed, o->in_stride, o->d_sizes, o->walk, scale_log2, dw,
+                                           dw + o_org, dw + o_list, n_windows, h_org, (int)n_list, list_rows, w, h,
+                                           (uint8_t *)d_out, d_status, (hipStream_t)stream, &ctx->prof);
+  else
+    himg_dev::launch_opened_regions(g, o->ws, o->d_packed, o->in_stride, o->d_sizes, o->walk, dw, dw + o_org, dw + o_list,
+                                    n_windows, h_org, (int)n_list, list_rows, w, h, (uint8_t *)d_out, d_status,
+                                    (hipStream_t)stream, &ctx->prof);
   (void)hipEventRecord(o->ev, (hipStream_t)stream);
   HIP_TRY(ctx, hipGetLastError());
   return HIMG_OK;
 }
 
-extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
-                                          const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
-                                          int *statuses, int *width, int *height, int *channels) {
+extern "C" int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, const int32_t *h_stream_of,
+                                              const int32_t *h_org, int n_windows, int w, int h, void *d_out,
+                                              int32_t *d_status, void *stream) {
+  return opened_launch(ctx, o, 0, h_stream_of, h_org, n_windows, w, h, d_out, d_status, stream);
+}
+
+extern "C" int himg_hip_opened_scaled_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2,
+                                                     const int32_t *h_stream_of, const int32_t *h_origins, int n_windows,
+                                                     int w, int h, void *d_out, int32_t *d_status, void *stream) {
+  if (scale_log2 < 1) return opened_owned(ctx, o) ? fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1, 2 or 3") : HIMG_ERR_ARG;
+  return opened_launch(ctx, o, scale_log2, h_stream_of, h_origins, n_windows, w, h, d_out, d_status, stream);
+}
+
+// The host form of opened_launch (scale_log2 as there).
+static int opened_to(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2, int n, const int32_t *h_stream_of,
+                     const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap, int *statuses, int *width,
+                     int *height, int *channels) {
   if (!opened_owned(ctx, o) || !origins || !statuses || !width || !height || !channels || n < 1 || n > 65535)
     return HIMG_ERR_ARG;
+  if (scale_log2 < 0 || scale_log2 > 3) return fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1, 2 or 3");
+  const int F = 1 << scale_log2;
+  const int ow = (int)(((long long)o->W + F - 1) / F), oh = (int)(((long long)o->H + F - 1) / F);
   std::vector<int32_t> map;
   if (!h_stream_of) { map.assign((size_t)n, 0); h_stream_of = map.data(); }
   for (int k = 0; k < n; ++k)
-    if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams || !region_ok(o->W, o->H, origins[2 * k], origins[2 * k + 1], w, h))
+    if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams || !region_ok(ow, oh, origins[2 * k], origins[2 * k + 1], w, h))
       return fail(ctx, HIMG_ERR_ARG, "bad window");
   const size_t out_bytes = (size_t)n * h * w * o->C;
   *width = w; *height = h; *channels = o->C;
@@ -3466,7 +3502,7 @@ extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o,
   if (!ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(round_up((size_t)n * 4, 256)))
     return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   int32_t *d_status = (int32_t *)ctx->h_status.p;
-  if (int rc = himg_hip_opened_regions_device(ctx, o, h_stream_of, origins, n, w, h, ctx->h_out.p, d_status, nullptr))
+  if (int rc = opened_launch(ctx, o, scale_log2, h_stream_of, origins, n, w, h, ctx->h_out.p, d_status, nullptr))
     return launch_refused(rc);
   std::vector<int32_t> st(n);
   HIP_TRY(ctx, hipMemcpy(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -3477,6 +3513,20 @@ extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o,
   }
   HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return first;
+}
+
+extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
+                                          const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
+                                          int *statuses, int *width, int *height, int *channels) {
+  return opened_to(ctx, o, 0, n, h_stream_of, origins, w, h, dst, dst_cap, statuses, width, height, channels);
+}
+
+extern "C" int himg_hip_opened_scaled_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2, int n,
+                                                 const int32_t *h_stream_of, const int32_t *origins, int w, int h,
+                                                 uint8_t *dst, size_t dst_cap, int *statuses, int *width, int *height,
+                                                 int *channels) {
+  if (scale_log2 < 1) return opened_owned(ctx, o) ? fail(ctx, HIMG_ERR_ARG, "scale_log2 must be 1, 2 or 3") : HIMG_ERR_ARG;
+  return opened_to(ctx, o, scale_log2, n, h_stream_of, origins, w, h, dst, dst_cap, statuses, width, height, channels);
 }
 
 extern "C" int himg_hip_opened_info(const himg_hip_opened *o, int *n_streams, int *width, int *height, int *channels,

@@ -5604,98 +5604,67 @@ template <int S>
 __global__ __launch_bounds__(kDecThreads, 8) void k_dec_scaled_region(Geom g, DecWs ws, const uint8_t *packed,
                                                                      size_t in_stride, const uint32_t *sizes,
                                                                      ScaledRegionArgs sa) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  constexpr int LG = S == 4 ? 1 : 2;
-  const RegionLayout L = scaled_layout<S>(g.C, sa.sw);
-  LdsTables &T = *reinterpret_cast<LdsTables *>(smem + L.tab);
-  RegionShared *sh = reinterpret_cast<RegionShared *>(smem + L.sh);
-  const int16_t *s_unmap = reinterpret_cast<const int16_t *>(smem + L.rowtab);   // unmap, shift: contiguous
-  const uint8_t *s_shift = smem + L.rowtab + 512;
-  uint8_t *sym = smem + L.sym;
-  const int tid = threadIdx.x, f = blockIdx.z;
-  // The frame's own window: its rows and tile columns; a workgroup past either has nothing to do.
-  ScaledCrop rr;
-  rr.x = sa.org[2 * f] >> LG; rr.y = sa.org[2 * f + 1] >> LG; rr.w = sa.w; rr.h = sa.h;
-  const int r = rr.y / S + (int)blockIdx.y, u1 = (rr.x + rr.w + S - 1) / S;
-  const int su0 = rr.x / S + (int)blockIdx.x * sa.sw;
-  if (r >= (rr.y + rr.h + S - 1) / S || su0 >= u1) return;
-  const int ww = min(sa.sw, u1 - su0);
-  DecFrame *df = ws.frames + f;
-  if (tid == 0) { sh->flag = df->status; sh->err = 0; sh->endbit = ~0ull; }
-  __syncthreads();
-  if (sh->flag) return;
-  load_dec_tables(ws, df, f, 1, &T);
-  if (tid < kRowTabWords / 4)
-    reinterpret_cast<uint4 *>(smem + L.rowtab)[tid] = reinterpret_cast<const uint4 *>(df->row_tabs)[tid];
-  const uint32_t nsym16 = (L.seg * (uint32_t)(S * S) * (uint32_t)g.C + 15u) / 16u;
-  for (uint32_t k = tid; k < nsym16; k += kDecThreads) reinterpret_cast<uint4 *>(sym)[k] = make_uint4(0, 0, 0, 0);
-  __syncthreads();
-  // A tree with a leaf past the last run symbol: a walk may fail anywhere (every lane walks).
-  const int nn = min(df->s[1].num_nodes, kMaxNodes + 1);
-  const uint32_t nd = tid < nn ? T.nd[tid] : 0u;
-  const bool strict = __syncthreads_or((nn <= 1) || ((nd >> 20) != 0 && (nd >> 20) - 1u > 260u)) != 0;
+  constexpr bool kScaledMap = false;
+  const int32_t *const smap = nullptr;
+  int32_t *const wstat = nullptr;
+#include "dec_body_scaled_region.inc"
+}
 
-  const size_t ri = (size_t)f * g.rows + (size_t)r;
-  const uint32_t pay_off = ws.row_off[ri], pay_len = ws.row_len[ri], out_size = (uint32_t)g.row_block;
-  const uint8_t *p = packed + (size_t)f * in_stride;
-  const uint32_t end = (uint32_t)min((unsigned long long)sizes[f], (unsigned long long)pay_off + pay_len);
-  const GrpTables tb = tables_of(&T);
-  ScaledWin<S> win;
-  win.base = lds_addr(sym); win.cols = (uint32_t)g.cols; win.u0 = (uint32_t)su0; win.ww = (uint32_t)ww;
-  win.seg = L.seg; win.nseg = 64u * (uint32_t)g.C;
-  const uint32_t *ps = ws.lane_start + ri * kDecThreads, *po = ws.lane_off + ri * (kDecThreads + kRecHdr);
-  const uint32_t valid = po[kDecThreads + 2];
-  const bool rec = valid != 0 && pay_len != 0;
-  const unsigned long long P1 = 8ull * pay_len;
-  uint32_t end_bp = ~0u, tot = 0, rel0 = 0;
-  bool ok = true;
-  if (pay_len != 0) {
-    GReader rd;
-    rel0 = rd.attach(p, end, 8ull * pay_off);
-    const uint32_t rel_end = rel0 + (uint32_t)P1;
-    if (rec) {
-      const uint32_t st = ps[tid], off = po[tid], nxt = po[tid + 1];
-      const uint32_t nst = tid + 1 < kDecThreads ? ps[tid + 1] : ~0u;
-      tot = po[kDecThreads];
-      const uint32_t start = rel0 + st, wlim = nst < (uint32_t)P1 ? rel0 + nst : rel_end;
-      const uint32_t cnt = nxt - off;
-      if (off + cnt < out_size) {
-        // The lane's last needed symbol of the window (stop), if its symbols [off, off + cnt) hold one.
-        uint32_t stop = ~0u;
-        bool walk = true;
-        if (!strict) {
-          const long long last = cnt ? scaled_last_needed<S>(off + cnt - 1u, (uint32_t)g.cols, (uint32_t)su0, (uint32_t)ww) : -1;
-          walk = cnt != 0 && last >= (long long)off;
-          stop = walk ? (uint32_t)last : 0u;
-        }
-        if (walk) ok = region_walk<false>(rd, tb, start, wlim, off, stop, out_size, win, &end_bp);
-      } else if (off < out_size) {
-        ok = region_walk<true>(rd, tb, start, wlim, off, ~0u, out_size, win, &end_bp);
-      }
-    } else if (tid == 0) {
-      ok = region_walk<true>(rd, tb, rel0, rel_end, 0u, ~0u, out_size, win, &end_bp);
-    }
-  }
-  if (!ok) sh->err = 1;
-  if (end_bp != ~0u) sh->endbit = (unsigned long long)(end_bp - rel0);
-  __syncthreads();
-  // ---- accept / reject like UncompressStream (huffman_dec.cpp:361-417), decode_row_recorded ----
-  int bad = sh->err || pay_len == 0;
-  if (rec && tot < out_size) bad = 1;   // ran out of payload before the block was full
-  const unsigned long long E = sh->endbit;
-  if (!bad && !(E <= P1 && E + 8 > P1 && E > 0)) bad = 1;   // AtTheEnd (huffman_dec.cpp:140-145)
-  if (bad) {
-    if (tid == 0) atomicMax(&df->status, fmt_err(7, 1));
+// ---------------------------------------------------------------------------
+// OPENED STREAMS, SCALED (himg_hip_opened_scaled_regions_device): window k of the picture of stream s_k at
+// 1/2, 1/4 or 1/8 scale, from the handle's kept products and records and nothing else.
+//   k_dec_opened_scaled_region<S>   k_dec_scaled_region<S>'s body on a grid of (strip, row - r0_k, window)
+//                      under k_opened_gate, as k_dec_stream_region is k_dec_region's: the frame, records,
+//                      tables and low-res plane of stream s_k, read only -- the handle's DecFrame is kept
+//                      state --; the kernel reads head | wstat[k] and raises a rejected row into wstat[k], the
+//                      caller's d_status word the gate has set from R^'s rows (origin (F x, F y), height F h).
+//                      The records are those of the full-resolution windows: a row counted by either serves both.
+//   k_opened_preview_region   the 1/8 level: k_lres_preview's arithmetic over the w x h window of stream s_k's
+//                      kept plane, a lane per pixel.  The status word is the kept head verdict alone; no row is
+//                      touched and the packed streams are not read.
+// ---------------------------------------------------------------------------
+template <int S>
+__global__ __launch_bounds__(kDecThreads, 8) void k_dec_opened_scaled_region(Geom g, DecWs ws, const uint8_t *packed,
+                                                                            size_t in_stride, const uint32_t *sizes,
+                                                                            ScaledRegionArgs sa, const int32_t *smap,
+                                                                            int32_t *wstat) {
+  constexpr bool kScaledMap = true;
+#include "dec_body_scaled_region.inc"
+}
+
+struct PreviewWinArgs {
+  const int32_t *stream_of;   // [n_windows] s_k
+  const int32_t *org;         // [2 n_windows] (x_k, y_k) in the ceil(W / 8) x ceil(H / 8) picture
+  int w, h;
+  uint8_t *out;               // window k's pixels at out + k * h * w * C
+  int32_t *status;            // [n_windows]
+};
+
+__global__ __launch_bounds__(256) void k_opened_preview_region(Geom g, DecWs ws, PreviewWinArgs pa) {
+  const int k = blockIdx.y, s = __builtin_amdgcn_readfirstlane(pa.stream_of[k]);
+  const DecFrame *df = ws.frames + s;
+  const int hd = df->status;
+  if (blockIdx.x == 0 && threadIdx.x == 0) pa.status[k] = hd;
+  if (hd) return;
+  const uint32_t n = (uint32_t)pa.w * (uint32_t)pa.h, i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t y = i / (uint32_t)pa.w, x = i - y * (uint32_t)pa.w;
+  const uint32_t npix = (uint32_t)g.rows * (uint32_t)g.cols;
+  const uint32_t p = ((uint32_t)pa.org[2 * k + 1] + y) * (uint32_t)g.cols + (uint32_t)pa.org[2 * k] + x;
+  const int C = g.C;
+  const uint8_t *plane = ws.low + (size_t)s * ws.plane_stride;
+  uint32_t v[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) v[c] = c < C ? plane[(size_t)c * npix + p] : 0u;
+  if (df->ycbcr) ycc_to_rgb(v[0], v[1], v[2]);
+  uint8_t *dst = pa.out + ((size_t)k * n + i) * (size_t)C;
+  if (C == 4 && ((uintptr_t)dst & 3u) == 0) {
+    *reinterpret_cast<uint32_t *>(dst) = v[0] | (v[1] << 8) | (v[2] << 16) | (v[3] << 24);
     return;
   }
-  // ---- the strip's tiles: a lane per tile, the stores cropped to the window ----
-  const uint8_t *low = ws.low + (size_t)f * ws.plane_stride;
-  uint8_t *img = sa.out + (size_t)f * ((size_t)sa.h * sa.w * g.C);
-  const int ycbcr = df->ycbcr;
-#pragma unroll 1
-  for (int ul = tid; ul < ww; ul += kDecThreads)
-    scaled_tile_store_crop<S>(g, (int)L.seg, S * S * (int)L.seg, sym + 4 + ul, low, s_unmap, s_shift, ycbcr, su0 + ul,
-                              r, rr, img);
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+    if (c < C) dst[c] = (uint8_t)v[c];
 }
 
 #define HIMG_LAUNCH(name, grid, block, ...)                    \
@@ -5727,7 +5696,8 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
       {HIMG_K(k_dec_span<false>), 0},      {HIMG_K(k_dec_span<true>), 0},       {HIMG_K(k_dec_stream_region), 0},
       {HIMG_K(k_dec_scaled<4, true>), 0},  {HIMG_K(k_dec_scaled<2, true>), 0},  {HIMG_K(k_dec_scaled<4, false>), 0},
-      {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0}};
+      {HIMG_K(k_dec_scaled<2, false>), 0}, {HIMG_K(k_dec_scaled_region<4>), 0}, {HIMG_K(k_dec_scaled_region<2>), 0},
+      {HIMG_K(k_dec_opened_scaled_region<4>), 0}, {HIMG_K(k_dec_opened_scaled_region<2>), 0}};
 #undef HIMG_K
   for (const auto &k : kDynLds) {
     uint32_t lds = k.fixed_lds;
@@ -6017,16 +5987,13 @@ void launch_open_streams(const Geom &g, const DecWs &ws_in, int n_streams, const
 }
 
 // A call on the handle: the gate, the counts over the list (n_list = 0: none), the row kernel.  ws: the handle's.
-void launch_opened_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_packed, size_t in_stride,
-                           const uint32_t *d_sizes, const OpenedWalk &walk, const int32_t *d_stream_of,
-                           const int32_t *d_org, const int32_t *d_list, int n_windows, const int32_t *h_org, int n_list,
-                           long long list_rows, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream,
-                           Profiler *prof) {
-  DecWs ws = ws_in;
-  ws.lane_q = nullptr;
-  const WindowExtents e = window_extents(g, n_windows, h_org, 8, w, h);
+// The gate over rectangles of height hf at the full-resolution origins d_org, then the counts.  ws: lane_q cleared.
+static void launch_opened_gate_counts(const Geom &g, const DecWs &ws, const uint8_t *d_packed, size_t in_stride,
+                                      const uint32_t *d_sizes, const OpenedWalk &walk, const int32_t *d_stream_of,
+                                      const int32_t *d_org, const int32_t *d_list, int n_windows, int n_list,
+                                      long long list_rows, int hf, int32_t *d_status, hipStream_t stream, Profiler *prof) {
   HIMG_LAUNCH(k_opened_gate, dim3((n_windows + 63) / 64), dim3(64), g, ws, d_stream_of, d_org, walk.rows, walk.st, d_status,
-              h, n_windows);
+              hf, n_windows);
   if (n_list > 0) {
     StreamWinWords sw = {};
     sw.stream_of = d_stream_of; sw.org = d_org; sw.list = d_list;
@@ -6038,6 +6005,18 @@ void launch_opened_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_p
       HIMG_LAUNCH(k_stream_count, dim3(n_list), dim3(kDecThreads), cr.g, ws, d_packed, in_stride, d_sizes, sw, cr.rpc);
     }
   }
+}
+
+void launch_opened_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_packed, size_t in_stride,
+                           const uint32_t *d_sizes, const OpenedWalk &walk, const int32_t *d_stream_of,
+                           const int32_t *d_org, const int32_t *d_list, int n_windows, const int32_t *h_org, int n_list,
+                           long long list_rows, int w, int h, uint8_t *d_out, int32_t *d_status, hipStream_t stream,
+                           Profiler *prof) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;
+  const WindowExtents e = window_extents(g, n_windows, h_org, 8, w, h);
+  launch_opened_gate_counts(g, ws, d_packed, in_stride, d_sizes, walk, d_stream_of, d_org, d_list, n_windows, n_list,
+                            list_rows, h, d_status, stream, prof);
   const int smax = region_strip_tiles(g);
   const int nstrip = (e.ntiles + smax - 1) / smax, swt = (e.ntiles + nstrip - 1) / nstrip;
   RegionArgs ra;
@@ -6045,6 +6024,43 @@ void launch_opened_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_p
   prof_begin(prof, "k_dec_stream_region", stream);
   hipLaunchKernelGGL(k_dec_stream_region, dim3(nstrip, e.nrows, n_windows), dim3(kDecThreads), region_layout(g.C, swt).total,
                      stream, g, ws, d_packed, in_stride, d_sizes, ra, d_stream_of, d_status);
+  prof_end(prof, stream);
+}
+
+// A scaled call on the handle.  scale_log2 = 1, 2: h_org / d_org are the origins of the full-resolution rectangles
+// the windows cover, (F x_k, F y_k), as in launch_region; the gate and the counts take them with the height F h,
+// then the scaled row kernel runs over (strip, row, window).  scale_log2 = 3: d_org holds the origins in the
+// 1/8-scale picture, and k_opened_preview_region runs alone (d_list, h_org unused).
+void launch_opened_scaled_regions(const Geom &g, const DecWs &ws_in, const uint8_t *d_packed, size_t in_stride,
+                                  const uint32_t *d_sizes, const OpenedWalk &walk, int scale_log2,
+                                  const int32_t *d_stream_of, const int32_t *d_org, const int32_t *d_list, int n_windows,
+                                  const int32_t *h_org, int n_list, long long list_rows, int w, int h, uint8_t *d_out,
+                                  int32_t *d_status, hipStream_t stream, Profiler *prof) {
+  DecWs ws = ws_in;
+  ws.lane_q = nullptr;
+  if (scale_log2 == 3) {
+    PreviewWinArgs pa;
+    pa.stream_of = d_stream_of; pa.org = d_org; pa.w = w; pa.h = h; pa.out = d_out; pa.status = d_status;
+    const uint32_t n = (uint32_t)w * (uint32_t)h;
+    HIMG_LAUNCH(k_opened_preview_region, dim3((n + 255u) / 256u, n_windows), dim3(256), g, ws, pa);
+    return;
+  }
+  const int F = 1 << scale_log2;
+  const WindowExtents e = window_extents(g, n_windows, h_org, 8 / F, w, h);
+  launch_opened_gate_counts(g, ws, d_packed, in_stride, d_sizes, walk, d_stream_of, d_org, d_list, n_windows, n_list,
+                            list_rows, F * h, d_status, stream, prof);
+  const int smax = scaled_strip_tiles(g, scale_log2);
+  const int nstrip = (e.ntiles + smax - 1) / smax, swt = (e.ntiles + nstrip - 1) / nstrip;
+  ScaledRegionArgs sa;
+  sa.org = d_org; sa.sw = swt; sa.w = w; sa.h = h; sa.out = d_out;
+  const dim3 grid(nstrip, e.nrows, n_windows);
+  prof_begin(prof, "k_dec_opened_scaled_region", stream);
+  if (scale_log2 == 1)
+    hipLaunchKernelGGL(k_dec_opened_scaled_region<4>, grid, dim3(kDecThreads), scaled_layout<4>(g.C, swt).total, stream, g,
+                       ws, d_packed, in_stride, d_sizes, sa, d_stream_of, d_status);
+  else
+    hipLaunchKernelGGL(k_dec_opened_scaled_region<2>, grid, dim3(kDecThreads), scaled_layout<2>(g.C, swt).total, stream, g,
+                       ws, d_packed, in_stride, d_sizes, sa, d_stream_of, d_status);
   prof_end(prof, stream);
 }
 

@@ -160,8 +160,8 @@ void himg_hip_host_free(void *p);
 /* Streams.  Every entry point of this section and of the device forms below takes the caller's
  * `stream` and is asynchronous: it queues its work and returns; nothing is synchronised with the host
  * (the exceptions: a context's first call at a larger geometry, which reserves workspace; the first call
- * of the per-quality encode section; and, since four pinned slots carry the host arrays to the device, a
- * call whose slot is still waiting for its copy four calls back waits for that copy -- not for the
+ * of the per-quality encode section; and, since eight pinned slots carry the host arrays to the device, a
+ * call whose slot is still waiting for its copy eight calls back waits for that copy -- not for the
  * kernels behind it).  All of a call's work is ordered on `stream`: it starts
  * behind what the stream held at the call and is complete for whatever the caller queues on the stream
  * afterwards -- the context's own side streams are forked from `stream` and joined back into it before
@@ -637,8 +637,33 @@ int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_t *packed, 
  * The records (8480 bytes per block row) and the low-res planes dominate: 17.4 + 16.8 MB for one 16384^2
  * RGBA stream, 704 MB for 128 x 4096^2.
  *
- * Not in this change: scaled, tensor and pitched store forms; eviction or a cap on a handle's memory;
- * re-opening on a changed stream; a prefix that grows under a handle; the C++ classes and the
+ * Scaled windows (himg_hip_opened_scaled_regions_device / _to): a viewer that pans also zooms, and a tile
+ * server serves every pyramid level.  scale_log2 is 1, 2 or 3 (anything else: HIMG_ERR_ARG); window k is the
+ * w x h rectangle at (x_k, y_k) IN THE COORDINATES OF STREAM stream_of[k]'s PICTURE AT THAT SCALE -- ow x oh by
+ * himg_hip_scaled_size at scales 1 and 2, ceil(W / 8) x ceil(H / 8) at scale 3 --, and must lie inside it.  The
+ * output is n_windows x h x w x C interleaved bytes, window k at k h w C.  Every check and rule of
+ * himg_hip_opened_regions_device above holds: all arguments are checked on the host before anything is
+ * launched, a refusal writes nothing and marks no row as counted, the call is asynchronous on the caller's
+ * stream, nothing outside the output bytes and the n_windows status words is written, and the
+ * HIMG_OPT_FIX_T2 recorded at open applies.  One scale per call.
+ *   scales 1, 2   d_status[k], and the bytes of every window with status 0, are exactly those of
+ *                 himg_hip_decode_scaled_regions_device on stream s_k alone (batch 1) with that origin, w x h
+ *                 and scale: the verdict is the region decode's of the covered full-resolution rectangle R^
+ *                 (see the scaled region decode), so a whole-picture window gets himg_hip_decode's.  The
+ *                 independence rules hold across scales as across calls: a window that meets damage fails
+ *                 alone, in whichever call and at whichever scale it comes, and no call changes what a later
+ *                 call returns, at this scale, another, or full resolution.  The window touches block rows
+ *                 [y / S, ceil((y + h) / S)), S = 8 >> scale_log2 -- R^'s rows.  The records are shared: a
+ *                 block row counted by a full-resolution call serves a scaled call and the other way round,
+ *                 so a row is counted once per handle whatever mix of entry points touches it, and
+ *                 rows_counted (himg_hip_opened_info) counts these rows like any others.
+ *   scale 3       d_status[k] is stream s_k's head verdict, the word open wrote to d_head_status; where it
+ *                 is 0 the bytes are the crop of himg_hip_preview_device's output for that stream, read
+ *                 from the low-res plane the handle holds.  No row is touched: no count runs, rows_counted
+ *                 does not move, and d_packed is not read at all.
+ *
+ * Not in this change: tensor and pitched store forms; mixed scales within one call; a stateless many-windows
+ * scaled decode; eviction or a cap on a handle's memory; re-opening on a changed stream; a prefix that grows under a handle; the C++ classes and the
  * command-line tools; the multi-GPU handle and the row-sharded paths.
  */
 typedef struct himg_hip_opened himg_hip_opened;
@@ -669,6 +694,17 @@ int himg_hip_opened_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, const 
 int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
                                const int32_t *origins, int w, int h, uint8_t *dst, size_t dst_cap,
                                int *statuses, int *width, int *height, int *channels);
+/* Scaled windows against a handle (the section above): scale_log2 = 1, 2, 3; the origins and w x h in the
+ * picture at that scale; everything else as in himg_hip_opened_regions_device. */
+int himg_hip_opened_scaled_regions_device(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2,
+                                          const int32_t *h_stream_of, const int32_t *h_origins, int n_windows,
+                                          int w, int h, void *d_out, int32_t *d_status, void *stream);
+/* The host form, with himg_hip_opened_regions_to's contract: a NULL h_stream_of means stream 0; a NULL or short
+ * dst gives HIMG_ERR_CAPACITY with *width = w, *height = h, *channels = C, nothing decoded and nothing counted;
+ * returns the first error in window order. */
+int himg_hip_opened_scaled_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2, int n,
+                                      const int32_t *h_stream_of, const int32_t *origins, int w, int h, uint8_t *dst,
+                                      size_t dst_cap, int *statuses, int *width, int *height, int *channels);
 /* What a handle holds (any pointer may be NULL); rows_counted: the (stream, block row) pairs a call has
  * queued a count for. */
 int himg_hip_opened_info(const himg_hip_opened *o, int *n_streams, int *width, int *height, int *channels,
