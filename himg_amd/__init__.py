@@ -138,6 +138,10 @@ def lib():
     L.himg_hip_tensor_bytes.argtypes = [vp, i32, i32, i32, P(sz)]
     L.himg_hip_decode_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp]
     L.himg_hip_decode_regions_tensor_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.himg_hip_planes_bytes.argtypes = [i32, C.c_uint32, i32, i32, P(sz)]
+    L.himg_hip_peek_format.argtypes = [vp, sz, P(i32), P(i32), P(i32), P(i32)]
+    L.himg_hip_decode_planes_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, C.c_uint32, vp, vp, vp]
+    L.himg_hip_decode_planes_to.argtypes = [vp, vp, sz, C.c_uint32, vp, sz, P(i32), P(i32), P(i32)]
     L.himg_hip_dst_extent.argtypes = [vp, i32, i32, vp, i32, i32, P(sz)]
     L.himg_hip_decode_into_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     L.himg_hip_decode_regions_into_device.argtypes = [vp, vp, sz, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp]
@@ -1014,6 +1018,35 @@ class Engine:
                                                  _ptr(d_status), C.c_void_p(stream))
         self._check(rc, "decode_tensor_device")
 
+    def decode_planes_device(self, d_packed, in_stride, h_sizes, batch, width, height, channels, plane_mask, d_out,
+                             d_status, stream=0):
+        """himg_hip_decode_planes_device: the contract of decode_device with the stream's own channel
+        planes as the output: d_out holds [batch][P][H][W] bytes, P = popcount(plane_mask), the planes
+        of the wanted channels (bit c of plane_mask) in ascending order, in front of the colour inverse."""
+        hs = np.ascontiguousarray(h_sizes, np.uint32)
+        rc = lib().himg_hip_decode_planes_device(self._ctx, _ptr(d_packed), in_stride, hs.ctypes.data,
+                                                 batch, width, height, channels, int(plane_mask) & 0xFFFFFFFF,
+                                                 _ptr(d_out), _ptr(d_status), C.c_void_p(stream))
+        self._check(rc, "decode_planes_device")
+
+    def decode_planes(self, packed, plane_mask, out=None):
+        """himg_hip_decode_planes_to: the wanted planes of one host stream as a (P, H, W) uint8 array
+        (`out` is reused when it has the right size).  Plane 0 of a colour-space-1 stream is its luma
+        (peek_format says which colour space a stream has)."""
+        packed = _as_u8(packed)
+        mask = int(plane_mask) & 0xFFFFFFFF
+        w, h, c = C.c_int(), C.c_int(), C.c_int()
+        dst, cap = None, 0
+        geom = _peek(packed)
+        if geom:
+            planes = bin(mask & ((1 << geom[2]) - 1)).count("1")
+            out = _out_buffer(out, planes * geom[0] * geom[1])
+            dst, cap = out.ctypes.data, out.nbytes
+        rc = lib().himg_hip_decode_planes_to(self._ctx, packed.ctypes.data, packed.nbytes, mask, dst, cap,
+                                             C.byref(w), C.byref(h), C.byref(c))
+        self._check(rc, "decode_planes")
+        return out.reshape(-1, h.value, w.value)
+
     def decode_rows_device(self, d_packed, packed_size, width, height, channels, row0, row1,
                            d_out_rows, d_status, stream=0):
         """Block rows [row0, row1) of one frame (row-sharded decode, himg_amd/sharded.py)."""
@@ -1469,6 +1502,29 @@ def tensor_bytes(desc, channels, w, h):
     if rc != 0:
         raise HimgError(rc, "tensor_bytes")
     return n.value
+
+
+def planes_bytes(channels, plane_mask, w, h):
+    """himg_hip_planes_bytes (no GPU): bytes per frame of the [P][h][w] planes output for `plane_mask`
+    of a stream of `channels` channels.  Raises HimgError (HIMG_ERR_ARG) for what the decode calls
+    reject: mask 0, a bit at or above channels, channels outside 1..4, a non-positive size."""
+    n = C.c_size_t()
+    rc = lib().himg_hip_planes_bytes(int(channels), int(plane_mask) & 0xFFFFFFFF, int(w), int(h), C.byref(n))
+    if rc != 0:
+        raise HimgError(rc, "planes_bytes")
+    return n.value
+
+
+def peek_format(packed):
+    """himg_hip_peek_format (no GPU): (width, height, channels, colour_space) of a stream; colour
+    space 1: channels 0..2 of a stream of three or four channels are Y, Cb, Cr.  Raises HimgError
+    (HIMG_ERR_FORMAT / HIMG_ERR_UNSUPPORTED)."""
+    a = _as_u8(packed)
+    w, h, c, cs = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    rc = lib().himg_hip_peek_format(a.ctypes.data, a.nbytes, C.byref(w), C.byref(h), C.byref(c), C.byref(cs))
+    if rc != 0:
+        raise HimgError(rc, "peek_format")
+    return w.value, h.value, c.value, cs.value
 
 
 class SrcDesc(C.Structure):

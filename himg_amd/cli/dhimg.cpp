@@ -23,6 +23,10 @@
 // the decoder accepts as the full decode writes them, the rows it rejects or cannot delimit from the
 // low-res plane, and on stderr a line "concealed N of R block rows" followed, when N > 0, by a line with
 // the rows' indices.  Exit status 0 whenever the stream's head is sound.  On its own only, like -m.
+// A sixth: "-g image out.pgm" writes plane 0 of the stream as a PGM (himg_hip_decode_planes_to, mask 1): the
+// codec's own luma for a colour-space-1 stream of three or four channels, else the first channel.  Only
+// that plane is transformed and stored.  The rows go through the same flip as a whole picture.  On its own
+// only, like -m.
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -72,11 +76,19 @@ int main(int argc, const char **argv) {
     printf("Usage: %s image outfile\n", argv[0]);
     return 0;
   }
+  // Plane 0: "-g image outfile" and nothing else.
+  bool grey = false;
+  if (argc >= 4)
+    for (int i = 1; i < argc - 2; ++i) grey = grey || std::strcmp(argv[i], "-g") == 0;
+  if (grey && !(argc == 4 && std::strcmp(argv[1], "-g") == 0)) {
+    printf("Usage: %s image outfile\n", argv[0]);
+    return 0;
+  }
   int scale_log2 = 0;
   if (argc >= 4 && std::strcmp(argv[1], "-s2") == 0) scale_log2 = 1;
   else if (argc >= 4 && std::strcmp(argv[1], "-s4") == 0) scale_log2 = 2;
   const bool prefix = !scale_log2 && argc >= 4 && std::strcmp(argv[1], "-t") == 0;
-  int arg = scale_log2 || prefix || mip || conceal ? 2 : 1;
+  int arg = scale_log2 || prefix || mip || conceal || grey ? 2 : 1;
   bool region = false;
   int rx = 0, ry = 0, rw = 0, rh = 0;
   if (!prefix && argc >= arg + 4 && std::strcmp(argv[arg], "-r") == 0) {
@@ -163,6 +175,30 @@ int main(int argc, const char **argv) {
     pnm::flip_and_swap(pixels.data(), picture.data.data(), w, h, c);
     const bool writable = c == 1 || c == 3 || c == 4;
     if (!writable || !pnm::write(out_path, picture)) return fail("Unable to write file", out_path);
+    return 0;
+  }
+
+  if (grey) {
+    int w = 0, h = 0, c = 0;
+    if (himg_hip_peek(stream.data(), stream.size(), &w, &h, &c) != HIMG_OK) return fail("Unable to decode image.", nullptr);
+    std::vector<uint8_t> plane(static_cast<size_t>(w) * h);
+    himg_hip_ctx *ctx = nullptr;
+    if (himg_hip_create(0, &ctx) != HIMG_OK) return fail("Error: no usable MI355X device (the HIMG engine has no CPU fallback).", nullptr);
+    const int rc = himg_hip_decode_planes_to(ctx, stream.data(), stream.size(), 1u, plane.data(), plane.size(), &w, &h, &c);
+    if (rc != HIMG_OK) {
+      const char *msg = himg_hip_last_error(ctx);
+      printf("%s%s", msg, (*msg && msg[std::strlen(msg) - 1] == '\n') ? "" : "\n");
+      himg_hip_destroy(ctx);
+      return fail("Unable to decode image.", nullptr);
+    }
+    himg_hip_destroy(ctx);
+    pnm::Image picture;
+    picture.width = w;
+    picture.height = h;
+    picture.channels = 1;
+    picture.data.resize(plane.size());
+    pnm::flip_and_swap(plane.data(), picture.data.data(), w, h, 1);
+    if (!pnm::write(out_path, picture)) return fail("Unable to write file", out_path);
     return 0;
   }
 

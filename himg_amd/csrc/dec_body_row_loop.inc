@@ -1,6 +1,6 @@
-// The persistent row loop of k_dec_row_fused and of its tensor, pitched and pyramid forms
-// (k_dec_row_fused_t / _p / _m): one copy, included as each kernel's whole body with KA (the kernel's
-// argument struct), kRowTens / kRowPitch / kRowPyr (the form) and HIMG_ROW_A (the RowArgs inside KA)
+// The persistent row loop of k_dec_row_fused and of its tensor, pitched, pyramid and planes forms
+// (k_dec_row_fused_t / _p / _m / _c): one copy, included as each kernel's whole body with KA (the kernel's
+// argument struct), kRowTens / kRowPitch / kRowPyr / kRowPlanes (the form) and HIMG_ROW_A (the RowArgs inside KA)
 // defined, so that every kernel keeps its code instruction for instruction.  A function template
 // around the loop does not: DESIGN.md 4.12.
   typedef const __attribute__((address_space(4))) KA *KArgs;
@@ -24,10 +24,10 @@
     karg_copy<unsigned long long>(&ws, &HIMG_ROW_A(ka).ws);
     const int gx = HIMG_ROW_A(ka).gx, f = (int)(lin / (uint32_t)gx);
     const uint32_t nd = (uint32_t)HIMG_ROW_A(ka).next_dist;
-    dec_row_fused_body<COLS, kRowTens, kRowPitch, kRowPyr>(
+    dec_row_fused_body<COLS, kRowTens, kRowPitch, kRowPyr, kRowPlanes>(
         g, ws, HIMG_ROW_A(ka).packed, HIMG_ROW_A(ka).in_stride, HIMG_ROW_A(ka).sizes, HIMG_ROW_A(ka).out_frames,
         HIMG_ROW_A(ka).r0, HIMG_ROW_A(ka).r1, HIMG_ROW_A(ka).rpw, (int)(lin % (uint32_t)gx), f, gx, HIMG_ROW_A(ka).gy,
-        nd ? lin + nd : element(i + 1), again, f == f_prev, row_td(ka), row_pd(ka), row_pm(ka));
+        nd ? lin + nd : element(i + 1), again, f == f_prev, row_td(ka), row_pd(ka), row_pm(ka), row_pc(ka));
     again = true;
     f_prev = f;
   }

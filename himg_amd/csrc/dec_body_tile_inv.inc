@@ -1,4 +1,4 @@
-// The front of k_tile_inv and of its tensor, pitched and pyramid forms (k_tile_inv_t / _p / _m): one
+// The front of k_tile_inv and of its tensor, pitched, pyramid and planes forms (k_tile_inv_t / _p / _m / _c): one
 // copy, included behind each kernel's own binding of g, ws and v0 (parameters of k_tile_inv, members of
 // the other kernels' argument structs), so that every kernel keeps its code instruction for instruction.
 // It leaves the block row v, the frame f and its DecFrame df, the tables in LDS and the lane's

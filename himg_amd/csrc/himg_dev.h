@@ -386,9 +386,22 @@ struct PyrDesc {
   uint8_t *level[4];
 };
 
+// The stream's own planes (himg_hip_decode_planes_device): bit c of mask set for each wanted channel c
+// of the stream, P = popcount(mask) planes per frame in ascending channel order, frame f's [P][H][W]
+// bytes at f * P * H * W.  Plane c holds the bytes in front of the colour inverse, which never runs.
+// It travels in the kernel-argument segment of the planes forms of the store kernels
+// (k_dec_row_fused_c, k_tile_inv_c), which read the mask there: in front of the transform -- an
+// unselected channel's tile_plane is not run -- and at the stores.
+struct PlaneDesc {
+  uint32_t mask;
+};
+__host__ __device__ inline int plane_count(uint32_t mask) {
+  return (int)((mask & 1u) + ((mask >> 1) & 1u) + ((mask >> 2) & 1u) + ((mask >> 3) & 1u));
+}
+
 // The form in which the pixel-writing kernels store: interleaved uint8 (no descriptor), or one of the
-// three forms above with its descriptor, which the launch copies into the kernel's arguments.
-enum StoreKind { kStoreU8, kStoreTens, kStorePitch, kStorePyr };
+// four forms above with its descriptor, which the launch copies into the kernel's arguments.
+enum StoreKind { kStoreU8, kStoreTens, kStorePitch, kStorePyr, kStorePlanes };
 struct StoreForm {
   StoreKind kind = kStoreU8;
   const void *desc = nullptr;   // the kind's descriptor
@@ -396,15 +409,18 @@ struct StoreForm {
   StoreForm(const TensDesc *t) : kind(kStoreTens), desc(t) {}
   StoreForm(const DstDesc *d) : kind(kStorePitch), desc(d) {}
   StoreForm(const PyrDesc *m) : kind(kStorePyr), desc(m) {}
+  StoreForm(const PlaneDesc *c) : kind(kStorePlanes), desc(c) {}
   const TensDesc &tens() const { return *static_cast<const TensDesc *>(desc); }
   const DstDesc &dst() const { return *static_cast<const DstDesc *>(desc); }
   const PyrDesc &pyr() const { return *static_cast<const PyrDesc *>(desc); }
+  const PlaneDesc &planes() const { return *static_cast<const PlaneDesc *>(desc); }
 };
 
 // form: kStoreTens, the pixel-writing kernels run in their tensor form (d_out: [batch][co][H][W]
 // elements); kStorePitch: in their pitched form (d_out: the destination pictures); kStorePyr: in their
 // pyramid form (d_out: level[0], which may be nullptr; level 3 is k_lres_preview's, behind the LRES
-// chain).  Everything in front of them is the same launch.
+// chain); kStorePlanes: in their planes form (d_out: [batch][P][H][W] bytes).  Everything in front of
+// them is the same launch.
 void launch_decode(const Geom &g, const DecWs &ws, int batch, const uint8_t *d_packed,
                    size_t in_stride, const uint32_t *d_sizes, uint8_t *d_out,
                    int32_t *d_status, hipStream_t stream, Profiler *prof, const HostOpts &ho,

@@ -1121,8 +1121,8 @@ extern "C" int himg_hip_psnr_to_sse(double psnr_db, int width, int height, int n
 
 // The launch behind the full decodes of a batch in HBM, in the caller's form: the interleaved bytes
 // (himg_hip_decode_device), the planar float output, windows of pitched pictures (with each frame's
-// origin in h_org: the origins ride with the sizes, the descriptor's org is filled in here) or the
-// picture pyramid (d_out its level 0).  bad: what the caller found wrong with its descriptor.
+// origin in h_org: the origins ride with the sizes, the descriptor's org is filled in here), the
+// picture pyramid (d_out its level 0) or the stream's own planes.  bad: what the caller found wrong with its descriptor.
 static int decode_full(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride, const uint32_t *h_sizes, int batch,
                        int width, int height, int num_channels, void *d_out, int32_t *d_status, void *stream,
                        const char *bad = nullptr, himg_dev::StoreForm form = himg_dev::StoreForm(),
@@ -1211,6 +1211,32 @@ extern "C" int himg_hip_decode_tensor_device(himg_hip_ctx *ctx, const void *d_pa
   const char *bad = tensor_desc_ok(t, num_channels, &td) ? nullptr : "bad tensor descriptor";
   return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream, bad,
                      &td);
+}
+
+// ---------------------------------------------------------------------------
+// Planes decode: the stream's own channel planes, in front of the colour inverse (include/himg_hip.h).
+// The mask is checked on the host and rides in the kernel arguments of the store kernels.
+// ---------------------------------------------------------------------------
+static bool plane_mask_ok(int C, uint32_t mask) { return C >= 1 && C <= 4 && mask != 0 && (mask >> C) == 0; }
+
+extern "C" int himg_hip_planes_bytes(int num_channels, uint32_t plane_mask, int w, int h, size_t *bytes_per_frame) {
+  Geom g;
+  if (!bytes_per_frame || !plane_mask_ok(num_channels, plane_mask) || !make_geom(w, h, num_channels, num_channels, 1, &g))
+    return HIMG_ERR_ARG;
+  *bytes_per_frame = (size_t)himg_dev::plane_count(plane_mask) * (size_t)h * (size_t)w;
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_decode_planes_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                             const uint32_t *h_sizes, int batch, int width, int height,
+                                             int num_channels, uint32_t plane_mask, void *d_out,
+                                             int32_t *d_status, void *stream) {
+  if (!ctx || !d_packed || !h_sizes || !d_out || !d_status || batch < 1 || batch > 65535)
+    return HIMG_ERR_ARG;
+  const himg_dev::PlaneDesc pc = {plane_mask};
+  const char *bad = plane_mask_ok(num_channels, plane_mask) ? nullptr : "bad plane mask";
+  return decode_full(ctx, d_packed, in_stride, h_sizes, batch, width, height, num_channels, d_out, d_status, stream, bad,
+                     &pc);
 }
 
 // ---------------------------------------------------------------------------
@@ -1749,7 +1775,7 @@ extern "C" int himg_hip_fetch_last(himg_hip_ctx *ctx, uint8_t *dst, size_t dst_c
 
 // Geometry from the FRMT chunk (decoder.cpp:144-200).  Returns nullptr or the
 // reference's message for the failing check.
-static const char *parse_header(const uint8_t *packed, size_t packed_size, int *W, int *H, int *C) {
+static const char *parse_header(const uint8_t *packed, size_t packed_size, int *W, int *H, int *C, int *cs = nullptr) {
   // decoder.cpp:144-166: the RIFF size field must match the buffer exactly.
   if (packed_size < 12 || packed_size > 0x7fffffffu || memcmp(packed, "RIFF", 4) != 0 ||
       memcmp(packed + 8, "HIMG", 4) != 0 ||
@@ -1768,6 +1794,7 @@ static const char *parse_header(const uint8_t *packed, size_t packed_size, int *
       *W = (int)(packed[idx + 1] | (packed[idx + 2] << 8) | (packed[idx + 3] << 16) | ((uint32_t)packed[idx + 4] << 24));
       *H = (int)(packed[idx + 5] | (packed[idx + 6] << 8) | (packed[idx + 7] << 16) | ((uint32_t)packed[idx + 8] << 24));
       *C = packed[idx + 9];
+      if (cs) *cs = packed[idx + 10];
       return nullptr;
     }
     idx += sz;
@@ -1784,6 +1811,17 @@ extern "C" int himg_hip_peek(const uint8_t *packed, size_t packed_size, int *wid
   Geom g;
   if (!make_geom(W, H, C, C, 1, &g)) return HIMG_ERR_UNSUPPORTED;
   *width = W; *height = H; *num_channels = C;
+  return HIMG_OK;
+}
+
+extern "C" int himg_hip_peek_format(const uint8_t *packed, size_t packed_size, int *width, int *height,
+                                    int *num_channels, int *colour_space) {
+  if (!packed || !width || !height || !num_channels || !colour_space) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0, cs = 0;
+  if (parse_header(packed, packed_size, &W, &H, &C, &cs)) return HIMG_ERR_FORMAT;
+  Geom g;   // (the engine's limits, as in himg_hip_peek)
+  if (!make_geom(W, H, C, C, 1, &g)) return HIMG_ERR_UNSUPPORTED;
+  *width = W; *height = H; *num_channels = C; *colour_space = cs;
   return HIMG_OK;
 }
 
@@ -2832,6 +2870,33 @@ extern "C" int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *pack
   if (st) return status_error(ctx, st);
   for (int k = 0; k < 4; ++k)
     if (bytes[k]) HIP_TRY(ctx, hipMemcpy(dst[k], py.level[k], bytes[k], hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+// The planes of one host stream: the upload of decode_core (the device walks the row headers), one
+// launch, the verdict, then the capacity rule of himg_hip_decode_to and one copy.
+extern "C" int himg_hip_decode_planes_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                                         uint32_t plane_mask, uint8_t *dst, size_t dst_cap, int *width, int *height,
+                                         int *num_channels) {
+  if (!ctx || !packed || !width || !height || !num_channels) return HIMG_ERR_ARG;
+  int W = 0, H = 0, C = 0;
+  Geom g;
+  if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
+  if (!plane_mask_ok(C, plane_mask)) return fail(ctx, HIMG_ERR_ARG, "bad plane mask");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t in_cap = round_up(packed_size + 16, 256);
+  const size_t out_bytes = (size_t)himg_dev::plane_count(plane_mask) * (size_t)W * (size_t)H;
+  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, packed, packed_size)) return rc;
+  const uint32_t sz32 = (uint32_t)packed_size;
+  if (int rc = himg_hip_decode_planes_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, plane_mask, ctx->h_out.p,
+                                             (int32_t *)ctx->h_status.p, nullptr))
+    return launch_refused(rc);
+  int32_t st = 0;
+  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
+  if (st) return status_error(ctx, st);
+  *width = W; *height = H; *num_channels = C;
+  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
   return HIMG_OK;
 }
 

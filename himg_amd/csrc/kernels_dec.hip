@@ -29,6 +29,9 @@
 //                     the pyramid forms of the two row kernels: besides the full picture, the 1/2-
 //                     and 1/4-scale ones from the same symbols (PyrDesc; include/himg_hip.h,
 //                     "picture pyramid"; the 1/8-scale level is k_lres_preview's)
+//   k_dec_row_fused_c, k_tile_inv_c
+//                     their planes forms: the stream's own channel planes in front of the colour
+//                     inverse, the wanted ones alone (PlaneDesc; include/himg_hip.h, "planes decode")
 // One entropy-decode engine serves all of them: see "Entropy decoding" below.
 #include "himg_dev.h"
 #include "prefix_walk.h"
@@ -2743,6 +2746,13 @@ __device__ __forceinline__ uint8_t *dst_frame(uint8_t *out, DstK pd, int f) {
   return out + (size_t)f * pd->frame_pitch + (size_t)org[2 * f + 1] * pd->row_pitch +
          (size_t)org[2 * f] * (size_t)pd->pixel_stride;
 }
+// The wanted planes (PlaneDesc) in the kernel-argument segment.  planes_at_use: the pointer made
+// opaque where the stores begin, so that the mask is read again there and is not live across the transform.
+typedef const __attribute__((address_space(4))) PlaneDesc *PlaneK;
+__device__ __forceinline__ PlaneK planes_at_use(PlaneK pc) {
+  asm volatile("" : "+s"(pc));
+  return pc;
+}
 // FULL4: four channels, whole tiles only (W and H multiples of 8) -- the ragged-edge
 // stores and the channel-count tests are compiled out.
 // SSE (k_sse, the encoder's distortion probe): nothing is stored -- the lane's four pixel rows are
@@ -2764,7 +2774,15 @@ __device__ __forceinline__ uint8_t *dst_frame(uint8_t *out, DstK pd, int f) {
 // a whole tile row at a 16-byte aligned address the two 16-byte stores, otherwise a dword per real
 // pixel (the host checks make every pixel 4-byte aligned); everything else the C channel bytes of
 // every real pixel.  No store covers a byte that is not a channel byte of a pixel of the picture.
-template <int COLS, bool FULL4 = false, bool SSE = false, bool TENS = false, bool PITCH = false>
+// PLANES (the planes forms): the stream's own channel planes -- img is frame f's [P][H][W] bytes, pl
+// the descriptor in the kernel-argument segment.  Of the lane's two channels, step cc of the transform
+// (channel cc for the lower half of the wavefront, 2 + cc for the upper) runs only where the mask wants
+// one of the two: a uniform branch, and tile_plane is not run for a step nobody asked for.  Behind the
+// swap the lane holds its four pixel rows of every channel as packed bytes (ch0..ch3), byte k of a
+// word x = 4h + k: a wanted plane's tile row is stored as it is -- no colour inverse, no interleave --,
+// one 8-byte store where the tile is whole and the address a multiple of 8 (FULL4: always), else a
+// byte per real pixel; rows masked to H.
+template <int COLS, bool FULL4 = false, bool SSE = false, bool TENS = false, bool PITCH = false, bool PLANES = false>
 __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols_rt, const uint8_t *sym,
                                                      const uint8_t *low, const int16_t *s_unmap,
                                                      const uint8_t *s_shift, const uint32_t *s_shiftp,
@@ -2772,18 +2790,24 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
                                                      const uint32_t *pre_lr = nullptr, bool store_ok = true,
                                                      bool touched_on = false, uint32_t touched = 0,
                                                      const uint8_t *src = nullptr, int sstride = 0,
-                                                     TensK td = nullptr, DstK pd = nullptr) {
+                                                     TensK td = nullptr, DstK pd = nullptr, PlaneK pl = nullptr) {
   uint32_t sse = 0;
   const int cols = COLS > 0 ? COLS : cols_rt;
   const int C = FULL4 ? 4 : g.C;
   const int v2 = min(v + 1, g.rows - 1);
     const int u2 = min(u + 1, cols - 1);
+    // (PLANES: which of the two steps are wanted -- uniform, a scalar load)
+    uint32_t want_cc = 3u;
+    if constexpr (PLANES) {
+      const uint32_t m = pl->mask;
+      want_cc = ((m | (m >> 2)) & 3u);
+    }
     uint32_t QA[16], QB[16];
 #pragma unroll
     for (int cc = 0; cc < 2; ++cc) {
       const int c = 2 * s + cc;
       uint32_t O[16];
-      if (FULL4 || c < C) {
+      if ((FULL4 || c < C) && (!PLANES || ((want_cc >> cc) & 1u))) {
         const uint8_t *m = low + (size_t)c * g.rows * cols;
         const int chroma = (ycbcr && (c == 1 || c == 2)) ? 1 : 0;  // decoder.cpp:376
         uint32_t lr0, lr8;
@@ -2836,10 +2860,35 @@ __device__ __forceinline__ uint32_t transform_store_pair(const Geom &g, int cols
       const DstK pk = dst_at_use(pd);
       row_pitch = pk->row_pitch; ps = pk->pixel_stride;
     }
+    // (PLANES: the mask, read again here -- behind the transform, for the four rows)
+    uint32_t pmask = 0;
+    if constexpr (PLANES) pmask = planes_at_use(pl)->mask;
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
       const int y = 4 * s + rr;
-      if constexpr (TENS) {
+      if constexpr (PLANES) {
+        if (store_ok && (FULL4 || y < bh)) {
+          size_t e = (size_t)(8 * v + y) * g.W + (size_t)(8 * u);   // the tile row in the next wanted plane
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            if ((pmask >> c) & 1u) {   // (uniform; the host has refused a bit at or above C)
+              const uint32_t lo = c == 0 ? ch0[rr * 2] : c == 1 ? ch1[rr * 2] : c == 2 ? ch2[rr * 2] : ch3[rr * 2];
+              const uint32_t hi = c == 0 ? ch0[rr * 2 + 1] : c == 1 ? ch1[rr * 2 + 1] : c == 2 ? ch2[rr * 2 + 1] : ch3[rr * 2 + 1];
+              uint8_t *dst = img + e;
+              if (FULL4 || (bw == 8 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0)) {
+                uint2 o;
+                o.x = lo; o.y = hi;
+                *reinterpret_cast<uint2 *>(dst) = o;
+              } else {
+#pragma unroll
+                for (int x = 0; x < 8; ++x)
+                  if (x < bw) dst[x] = (uint8_t)((x < 4 ? lo : hi) >> (8 * (x & 3)));
+              }
+              e += (size_t)g.H * g.W;
+            }
+          }
+        }
+      } else if constexpr (TENS) {
         uint32_t pc[4][2];   // [channel][h]: the bytes of x = 4h..4h+3
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -3040,6 +3089,29 @@ __global__ __launch_bounds__(256) void k_tile_inv_p(TileArgsP a) {
       pair_half(it), v, dst_frame(a.out_frames, pd, f), nullptr, true, false, 0, nullptr, 0, nullptr, pd);
 }
 
+// k_tile_inv_c: k_tile_inv in its planes form (PlaneDesc): frame f's [P][H][W] bytes at
+// out_frames + f * P * H * W.  The arguments in one struct, as in k_tile_inv_t.
+struct TileArgsC {
+  Geom g;
+  DecWs ws;
+  uint8_t *out_frames;
+  int v0;
+  PlaneDesc c;
+};
+template <bool FAST>
+__global__ __launch_bounds__(256) void k_tile_inv_c(TileArgsC a) {
+  const Geom &g = a.g;
+  const DecWs &ws = a.ws;
+  const int v0 = a.v0;
+  const PlaneK pc = &((const __attribute__((address_space(4))) TileArgsC *)__builtin_amdgcn_kernarg_segment_ptr())->c;
+#include "dec_body_tile_inv.inc"
+  const size_t frame_bytes = (size_t)g.W * g.H * (size_t)plane_count(pc->mask);
+  transform_store_pair<(FAST ? -1 : 0), FAST, false, false, false, true>(
+      g, g.cols, ws.fres_sym + (size_t)f * ws.fres_stride + (size_t)v * g.row_block,
+      ws.low + (size_t)f * ws.plane_stride, s_unmap, &s_shift[0][0], s_shiftp, df->ycbcr, pair_tile(it),
+      pair_half(it), v, a.out_frames + (size_t)f * frame_bytes, nullptr, true, false, 0, nullptr, 0, nullptr, nullptr, pc);
+}
+
 // ---------------------------------------------------------------------------
 // k_sse: the encoder's distortion probe (himg_hip_encode_sse_device).  k_tile_inv's transform on
 // the ENCODER's symbol plane (the same [rows][C][64][cols] layout) and its reconstructed low-res
@@ -3099,18 +3171,21 @@ __global__ __launch_bounds__(256) void k_sse(Geom g, const uint8_t *frames, cons
 // the loop above stores when it is wanted; a second loop over the rows' tiles then computes the wanted
 // ones of the 1/2- and 1/4-scale levels from the same symbols in LDS (pyr_tile_part: k_dec_scaled's
 // tile arithmetic at stride cols, channel stride 64 cols).
+// PLANES: the stream's own planes (transform_store_pair's planes form); out_frames is then the
+// [batch][P][H][W] buffer and pc the descriptor in the kernel-argument segment.
 template <int PART>
 __device__ __forceinline__ void pyr_tile_part(const Geom &g, int sstride, int cstride, const uint8_t *sym,
                                               const uint8_t *low, const int16_t *s_unmap, const uint8_t *s_shift,
                                               int ycbcr, int u, int v, int f, uint8_t *level);   // (behind scaled_tile_rows)
 typedef const __attribute__((address_space(4))) PyrDesc *PyrK;
-template <int COLS, bool TENS = false, bool PITCH = false, bool PYR = false>
+template <int COLS, bool TENS = false, bool PITCH = false, bool PYR = false, bool PLANES = false>
 __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &ws, const uint8_t *packed,
                                                    size_t in_stride, const uint32_t *sizes,
                                                    uint8_t *out_frames, int r0, int r1, int rpw,
                                                    const int bx, const int f, const int gx, const int gy,
                                                    const uint32_t next_lin, const bool again, const bool same_tables,
-                                                   TensK td = nullptr, DstK pd = nullptr, PyrK pm = nullptr) {
+                                                   TensK td = nullptr, DstK pd = nullptr, PyrK pm = nullptr,
+                                                   PlaneK pc = nullptr) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   if (COLS == 512) rpw = 1;   // 4096-pixel rows: one row fills the lanes and the LDS (known at compile time)
   const FusedLayout L = fused_layout(g.row_block, rpw);
@@ -3305,6 +3380,7 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
   uint8_t *img;
   if constexpr (TENS) img = out_frames + (size_t)f * ((size_t)g.W * g.H * (size_t)(td->co * tens_elem_size(td->dtype)));
   else if constexpr (PITCH) img = dst_frame(out_frames, pd, f);
+  else if constexpr (PLANES) img = out_frames + (size_t)f * ((size_t)g.W * g.H * (size_t)plane_count(pc->mask));
   else img = out_frames + (size_t)f * ((size_t)g.W * g.H * g.C);
   const int per_row = ((cols + 31) >> 5) * 64;   // whole wavefronts: a lane pair never straddles rows
   // (PYR: level 0 only where it is wanted -- uniform, a scalar load)
@@ -3318,10 +3394,10 @@ __device__ __forceinline__ void dec_row_fused_body(const Geom &g, const DecWs &w
     // transforms the last tile once more and stores nothing: no exec-masked region around
     // the transform (with compile-time strides it cost 50 VGPR spills at 1920 pixels).
     const bool in_row = pair_tile(il) < cols;
-    transform_store_pair<COLS, COLS != 0, false, TENS, PITCH>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
+    transform_store_pair<COLS, COLS != 0, false, TENS, PITCH, PLANES>(g, cols, sym0 + (size_t)i * rb16, low, s_unmap, s_shift, s_shiftp, ycbcr,
                                             in_row ? pair_tile(il) : cols - 1, pair_half(il), rb + i, img,
                                             COLS == 512 ? pre_lr : nullptr, in_row, pf_on && it == tid, pf_a,
-                                            nullptr, 0, td, pd);
+                                            nullptr, 0, td, pd, pc);
   }
   HIMG_SPAN_END("dec.transform");
   if constexpr (PYR) {
@@ -3392,9 +3468,9 @@ struct RowArgs {
 // (The arguments are read from the kernel-argument segment anew for every row, through a pointer
 // the compiler cannot see through: read once in front of the loop they all stay live across the
 // body -- 104 scalar registers spilled instead of 36, the row kernel 9 % slower.)
-// The kernel's four forms share the loop, dec_body_row_loop.inc; a form is its argument struct --
-// RowArgs itself, or RowArgs followed by the form's descriptor --, its three flags and HIMG_ROW_A,
-// the RowArgs inside the struct.  row_td / row_pd / row_pm: the descriptor a form's struct carries.
+// The kernel's five forms share the loop, dec_body_row_loop.inc; a form is its argument struct --
+// RowArgs itself, or RowArgs followed by the form's descriptor --, its four flags and HIMG_ROW_A,
+// the RowArgs inside the struct.  row_td / row_pd / row_pm / row_pc: the descriptor a form's struct carries.
 struct RowArgsT {
   RowArgs a;
   TensDesc t;
@@ -3407,17 +3483,23 @@ struct RowArgsM {
   RowArgs a;
   PyrDesc m;
 };
+struct RowArgsC {
+  RowArgs a;
+  PlaneDesc c;
+};
 template <class K> __device__ __forceinline__ TensK row_td(K) { return nullptr; }
 template <class K> __device__ __forceinline__ DstK row_pd(K) { return nullptr; }
 template <class K> __device__ __forceinline__ PyrK row_pm(K) { return nullptr; }
+template <class K> __device__ __forceinline__ PlaneK row_pc(K) { return nullptr; }
 __device__ __forceinline__ TensK row_td(const __attribute__((address_space(4))) RowArgsT *ka) { return &ka->t; }
 __device__ __forceinline__ DstK row_pd(const __attribute__((address_space(4))) RowArgsP *ka) { return &ka->d; }
 __device__ __forceinline__ PyrK row_pm(const __attribute__((address_space(4))) RowArgsM *ka) { return &ka->m; }
+__device__ __forceinline__ PlaneK row_pc(const __attribute__((address_space(4))) RowArgsC *ka) { return &ka->c; }
 
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused(RowArgs) {
   typedef RowArgs KA;
-  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = false;
+  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = false, kRowPlanes = false;
 #define HIMG_ROW_A(ka) (*(ka))
 #include "dec_body_row_loop.inc"
 #undef HIMG_ROW_A
@@ -3431,7 +3513,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused(RowArgs) {
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_t(RowArgsT) {
   typedef RowArgsT KA;
-  constexpr bool kRowTens = true, kRowPitch = false, kRowPyr = false;
+  constexpr bool kRowTens = true, kRowPitch = false, kRowPyr = false, kRowPlanes = false;
 #include "dec_body_row_loop.inc"
 }
 
@@ -3441,7 +3523,7 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_t(RowArgsT) {
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_p(RowArgsP) {
   typedef RowArgsP KA;
-  constexpr bool kRowTens = false, kRowPitch = true, kRowPyr = false;
+  constexpr bool kRowTens = false, kRowPitch = true, kRowPyr = false, kRowPlanes = false;
 #include "dec_body_row_loop.inc"
 }
 
@@ -3451,7 +3533,17 @@ __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_p(RowArgsP) {
 template <int COLS>
 __global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_m(RowArgsM) {
   typedef RowArgsM KA;
-  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = true;
+  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = true, kRowPlanes = false;
+#include "dec_body_row_loop.inc"
+}
+
+// k_dec_row_fused_c: the same kernel in its planes form.  RowArgs -- unchanged -- followed by the
+// plane mask, which stays in the kernel-argument segment: it is read where the transform phase begins
+// (the frame's size), in front of the transform (which steps run) and at the stores.
+template <int COLS>
+__global__ __launch_bounds__(kDecThreads) void k_dec_row_fused_c(RowArgsC) {
+  typedef RowArgsC KA;
+  constexpr bool kRowTens = false, kRowPitch = false, kRowPyr = false, kRowPlanes = true;
 #include "dec_body_row_loop.inc"
 }
 #undef HIMG_ROW_A
@@ -5692,6 +5784,7 @@ hipError_t dec_set_kernel_attrs() {
       {HIMG_K(k_dec_row_fused_t<512>), 0}, {HIMG_K(k_dec_row_fused_t<-1>), 0},  {HIMG_K(k_dec_row_fused_t<0>), 0},
       {HIMG_K(k_dec_row_fused_p<512>), 0}, {HIMG_K(k_dec_row_fused_p<-1>), 0},  {HIMG_K(k_dec_row_fused_p<0>), 0},
       {HIMG_K(k_dec_row_fused_m<512>), 0}, {HIMG_K(k_dec_row_fused_m<-1>), 0},  {HIMG_K(k_dec_row_fused_m<0>), 0},
+      {HIMG_K(k_dec_row_fused_c<512>), 0}, {HIMG_K(k_dec_row_fused_c<-1>), 0},  {HIMG_K(k_dec_row_fused_c<0>), 0},
       {HIMG_K(k_row_window), kRowWindowLds},
       {HIMG_K(k_dec_region), 0},           {HIMG_K(k_dec_region_t), 0},         {HIMG_K(k_dec_region_p), 0},
       {HIMG_K(k_dec_span<false>), 0},      {HIMG_K(k_dec_span<true>), 0},       {HIMG_K(k_dec_stream_region), 0},
@@ -6234,11 +6327,12 @@ void launch_row_records(const Geom &g, const DecWs &ws, int batch, const uint8_t
 // instantiation in the name: the tests assert which one ran.
 enum StoreInst { kRow512, kRowWhole4, kRowAny, kTileFast, kTileAny };
 static const char *store_stage_name(StoreKind kind, StoreInst inst) {
-  static const char *const kName[4][5] = {
+  static const char *const kName[5][5] = {
       {"k_dec_row_fused", "k_dec_row_fused", "k_dec_row_fused", "k_tile_inv<true>", "k_tile_inv<false>"},
       {"k_dec_row_fused_t<512>", "k_dec_row_fused_t<-1>", "k_dec_row_fused_t<0>", "k_tile_inv_t<true>", "k_tile_inv_t<false>"},
       {"k_dec_row_fused_p<512>", "k_dec_row_fused_p<-1>", "k_dec_row_fused_p<0>", "k_tile_inv_p<true>", "k_tile_inv_p<false>"},
-      {"k_dec_row_fused_m<512>", "k_dec_row_fused_m<-1>", "k_dec_row_fused_m<0>", "k_tile_inv_m<true>", "k_tile_inv_m<false>"}};
+      {"k_dec_row_fused_m<512>", "k_dec_row_fused_m<-1>", "k_dec_row_fused_m<0>", "k_tile_inv_m<true>", "k_tile_inv_m<false>"},
+      {"k_dec_row_fused_c<512>", "k_dec_row_fused_c<-1>", "k_dec_row_fused_c<0>", "k_tile_inv_c<true>", "k_tile_inv_c<false>"}};
   return kName[kind][inst];
 }
 
@@ -6259,6 +6353,9 @@ static void launch_row_fused(const StoreForm &form, const RowArgs &ra, unsigned 
   } else if (form.kind == kStorePyr) {
     const RowArgsM rm = {ra, form.pyr()};
     hipLaunchKernelGGL((k_dec_row_fused_m<FC>), grid, block, lds, stream, rm);
+  } else if (form.kind == kStorePlanes) {
+    const RowArgsC rc = {ra, form.planes()};
+    hipLaunchKernelGGL((k_dec_row_fused_c<FC>), grid, block, lds, stream, rc);
   } else {
     hipLaunchKernelGGL((k_dec_row_fused<COLS>), grid, block, lds, stream, ra);
   }
@@ -6280,6 +6377,9 @@ static void launch_tile_inv(const StoreForm &form, const Geom &g, const DecWs &w
   } else if (form.kind == kStorePyr) {
     const TileArgsM tm = {g, ws, v0, form.pyr()};
     hipLaunchKernelGGL(k_tile_inv_m<FAST>, grid, block, 0, stream, tm);
+  } else if (form.kind == kStorePlanes) {
+    const TileArgsC tc = {g, ws, d_out, v0, form.planes()};
+    hipLaunchKernelGGL(k_tile_inv_c<FAST>, grid, block, 0, stream, tc);
   } else {
     hipLaunchKernelGGL(k_tile_inv<FAST>, grid, block, 0, stream, g, ws, d_out, v0);
   }

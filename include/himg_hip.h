@@ -839,6 +839,57 @@ int himg_hip_decode_regions_tensor_device(himg_hip_ctx *ctx, const void *d_packe
                                           const himg_hip_tensor_desc *t, void *d_out,
                                           int32_t *d_status, void *stream);
 
+/* ---- planes decode: the stream's own channel planes (luma, alpha, planar YCbCr) ---- */
+/*
+ * Every other decode ends in the picture BEHIND the colour inverse.  This one stores the stream's own
+ * channel planes, the representation the reference decoder holds immediately before YCbCrToRGB
+ * (decoder.cpp:372-423): for a colour-space-1 stream of three or four channels plane 0 is the codec's
+ * luma, planes 1 and 2 its Cb and Cr, plane 3 alpha.  A greyscale consumer takes plane 0, a compositor
+ * plane 3, a video or re-encode pipeline planes 0..2 with no round trip through RGB.  (Luma recomputed
+ * from decoded RGB is not the stream's luma: the inverse clamps.)
+ *
+ * plane_mask has bit c set for each wanted channel c of the stream; it must be non-zero and have no bit
+ * at or above num_channels.  P = popcount(plane_mask).  Output: [batch][P][H][W] uint8, tightly packed,
+ * the planes in ascending channel order, frame f at f * P * H * W.  Plane c, pixel (y, x) is the byte
+ * the reference decoder holds for that channel immediately before YCbCrToRGB: the inverse transform,
+ * plus the interpolated low-res plane, clamped to 0..255, dequantised with the chroma shift table
+ * exactly where the reference uses it (decoder.cpp:376: channels 1 and 2 of a colour-space-1 stream of
+ * three or four channels).  No colour inverse is ever applied.  Where the full decode applies no colour
+ * inverse (colour space 0, or C < 3), plane c is channel c of himg_hip_decode_device's output, byte for
+ * byte.  What plane 1 means is the stream's business: himg_hip_peek_format reports its colour space.
+ * Frame f's status word is exactly himg_hip_decode_device's, under either HIMG_OPT_FIX_T2 setting (the
+ * T2 rule included); a failed frame's bytes are unspecified and its neighbours are unaffected.  Only
+ * real pixels are stored: nothing is written at or beyond batch * P * H * W.
+ * An unselected channel's tiles are not transformed and nothing of it is stored: plane 0 alone of an
+ * RGBA stream is a quarter of the output bytes and a quarter of the tile transforms; the entropy
+ * decode is the full decode's.
+ * Not in this form: the region, scaled, pitched, tensor, prefix, concealing, opened-stream and pyramid
+ * decodes, himg::Decoder, the multi-GPU handle and the row-sharded paths; there is no host batch entry.
+ */
+/* Host only, no GPU: validates num_channels (1..4), plane_mask (the rules above) and the geometry
+ * (w, h >= 1, the engine's limits), and sets *bytes_per_frame = P * h * w.  HIMG_ERR_ARG otherwise
+ * (also for a NULL result). */
+int himg_hip_planes_bytes(int num_channels, uint32_t plane_mask, int w, int h, size_t *bytes_per_frame);
+/* Host only, no GPU: himg_hip_peek, and *colour_space = FRMT byte 10 (0: the channels are the picture's
+ * own; 1: channels 0..2 of a stream of three or four channels are Y, Cb, Cr). */
+int himg_hip_peek_format(const uint8_t *packed, size_t packed_size, int *width, int *height,
+                         int *num_channels, int *colour_space);
+/* Streams of a batch in HBM: the argument, alignment (d_out's base 16-byte aligned), asynchrony and
+ * verdict contract of himg_hip_decode_device with the output above.  A bad mask is HIMG_ERR_ARG:
+ * nothing launched, neither d_out nor d_status written.  The mask travels in the kernel arguments: no
+ * host synchronisation, no extra copy. */
+int himg_hip_decode_planes_device(himg_hip_ctx *ctx, const void *d_packed, size_t in_stride,
+                                  const uint32_t *h_sizes, int batch, int width, int height,
+                                  int num_channels, uint32_t plane_mask, void *d_out,
+                                  int32_t *d_status, void *stream);
+/* One stream in host memory, himg_hip_decode_to's rules: the geometry is reported whenever the stream
+ * decodes, and with dst == NULL or dst_cap < P * H * W the call returns HIMG_ERR_CAPACITY with
+ * width, height and num_channels set (the size to allocate: himg_hip_planes_bytes).  A mask that does
+ * not fit the stream's channel count is HIMG_ERR_ARG. */
+int himg_hip_decode_planes_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
+                              uint32_t plane_mask, uint8_t *dst, size_t dst_cap, int *width, int *height,
+                              int *num_channels);
+
 /* ---- scaled decode: the picture at 1/2 and 1/4 scale ----------------------------- */
 /*
  * scale_log2 = 1 or 2: F = 2^scale_log2 pixels per output sample and side, S = 8 / F coefficients
