@@ -187,7 +187,7 @@ struct himg_hip_ctx {
 
   // Staging for the host-buffer API.
   DevBuf h_in, h_out, h_result, h_status, h_index;   // h_result: a HostResult (encode); h_status: status words (decode)
-  uint32_t *hp_index = nullptr;          // pinned staging of the host row index (decode_core)
+  uint32_t *hp_index = nullptr;          // pinned staging of the host row index (stage_reserve)
   size_t hp_index_cap = 0;               // in dwords
 
   // Packed sizes handed to the decoder: the caller's array (or a by-value argument)
@@ -739,7 +739,8 @@ static int status_to_code(int32_t st) {
 }
 
 // A device status as the host API reports it: the reference's message for a format error, else `what`.
-static int status_error(himg_hip_ctx *ctx, int32_t st, const char *what = "device decode reported an error") {
+static const char kDecodeError[] = "device decode reported an error";
+static int status_error(himg_hip_ctx *ctx, int32_t st, const char *what = kDecodeError) {
   const int code = status_to_code(st);
   if (code == HIMG_ERR_FORMAT) ctx->err = format_message(st);
   else fail(ctx, code, what);
@@ -1763,16 +1764,6 @@ extern "C" int himg_hip_encode_target_to(himg_hip_ctx *ctx, const uint8_t *data,
   return encode_to(ctx, data, width, height, pixel_stride, num_channels, use_ycbcr, rq, dst, dst_cap, out_size);
 }
 
-extern "C" int himg_hip_fetch_last(himg_hip_ctx *ctx, uint8_t *dst, size_t dst_cap, size_t *size) {
-  if (!ctx || !size) return HIMG_ERR_ARG;
-  *size = ctx->host_bytes;
-  if (!ctx->host_bytes) return fail(ctx, HIMG_ERR_ARG, "no result to fetch");
-  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
-}
-
 // Geometry from the FRMT chunk (decoder.cpp:144-200).  Returns nullptr or the
 // reference's message for the failing check.
 static const char *parse_header(const uint8_t *packed, size_t packed_size, int *W, int *H, int *C, int *cs = nullptr) {
@@ -1835,12 +1826,28 @@ static int stream_geom(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_s
   return HIMG_OK;
 }
 
-// The pinned staging of host row indices (decode_core, staged_launch), n_idx dwords.
-static int reserve_hp_index(himg_hip_ctx *ctx, size_t n_idx) {
+// ---- The steps the host decodes of one stream share: the staging reserved, the stream and the host's row
+// index up, the verdict behind the launch read, the result delivered.  Everything is ordered on the null
+// stream, which the decode runs on; the one wait of a call is the read of its verdict.  (What each entry
+// point does with them: DESIGN.md, "The host decodes' contract".)
+// The slot of a stream of n bytes in the staging: the row kernels read whole dwords and a few dwords
+// ahead, so a slot ends at least 16 bytes behind its stream.
+static size_t stage_slot(size_t n) { return round_up(n + 16, 256); }
+
+// A call's staging, on the context's device: in_bytes of `in` (h_in, or a buffer that becomes a handle's), out_bytes of h_out,
+// status_bytes of h_status, and n_idx dwords of h_index with the pinned hp_index they go up from (the
+// context keeps it: a call returns only after the decode that reads its copy has finished).  A call that
+// takes h_out leaves nothing there for himg_hip_fetch_last until it says so.
+static int stage_reserve(himg_hip_ctx *ctx, DevBuf &in, size_t in_bytes, size_t out_bytes, size_t status_bytes,
+                         size_t n_idx) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (out_bytes) ctx->host_bytes = 0;
+  if (!in.reserve(in_bytes) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
+      !ctx->h_status.reserve(round_up(status_bytes, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
+    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
   if (ctx->hp_index_cap >= n_idx) return HIMG_OK;
   if (ctx->hp_index) hipHostFree(ctx->hp_index);
-  ctx->hp_index = nullptr;
-  ctx->hp_index_cap = 0;
+  ctx->hp_index = nullptr; ctx->hp_index_cap = 0;
   if (hipHostMalloc((void **)&ctx->hp_index, round_up(n_idx * 4, 4096), hipHostMallocDefault) != hipSuccess)
     return fail(ctx, HIMG_ERR_HIP, "pinned index allocation failed");
   ctx->hp_index_cap = round_up(n_idx * 4, 4096) / 4;
@@ -1849,57 +1856,136 @@ static int reserve_hp_index(himg_hip_ctx *ctx, size_t n_idx) {
 
 // A stream (or its first n bytes) into the staging slot [d, d + slot): the row kernels read whole dwords
 // and a few dwords ahead, so nothing of a stream staged before may lie behind this one -- zeros from
-// the last 16-byte boundary to the end of the slot, then the bytes.  On the null stream.
-static int upload_zero_tail(himg_hip_ctx *ctx, uint8_t *d, size_t slot, const uint8_t *src, size_t n) {
-  HIP_TRY(ctx, hipMemsetAsync(d + (n & ~(size_t)15), 0, slot - (n & ~(size_t)15), nullptr));
-  HIP_TRY(ctx, hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, nullptr));
+// the last 16-byte boundary to the end of the slot, then the bytes.  With ranges (n_ranges pairs of
+// begin, end) only those bytes go up, each at its offset: the head and the rows a plan touches, beside
+// which the kernels, led by the host's index, read nothing.
+static int stage_upload(himg_hip_ctx *ctx, uint8_t *d, size_t slot, const uint8_t *src, size_t n,
+                        const size_t *ranges = nullptr, size_t n_ranges = 0) {
+  if (!ranges) {
+    HIP_TRY(ctx, hipMemsetAsync(d + (n & ~(size_t)15), 0, slot - (n & ~(size_t)15), nullptr));
+    HIP_TRY(ctx, hipMemcpyAsync(d, src, n, hipMemcpyHostToDevice, nullptr));
+  }
+  for (size_t i = 0; i < n_ranges; ++i)
+    if (ranges[2 * i + 1] > ranges[2 * i])
+      HIP_TRY(ctx, hipMemcpyAsync(d + ranges[2 * i], src + ranges[2 * i], ranges[2 * i + 1] - ranges[2 * i],
+                                  hipMemcpyHostToDevice, nullptr));
   return HIMG_OK;
+}
+
+// The host's row index, n_idx dwords that a caller's walk left in hp_index, into h_index.
+static int stage_index(himg_hip_ctx *ctx, size_t n_idx) {
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  return HIMG_OK;
+}
+
+// The two steps of a host form that sends one stream (its first n bytes) up whole, for the device to walk.
+static int stage_whole(himg_hip_ctx *ctx, const uint8_t *packed, size_t n, size_t out_bytes, size_t status_bytes) {
+  if (int rc = stage_reserve(ctx, ctx->h_in, stage_slot(n), out_bytes, status_bytes, 0)) return rc;
+  return stage_upload(ctx, (uint8_t *)ctx->h_in.p, stage_slot(n), packed, n);
+}
+
+// The verdict behind a launch: launch_rc is what the device entry point returned.  A refused launch is
+// waited for, because the uploads may still be reading the caller's and the pinned buffers.  Else the
+// first n words of h_status come down to st.  what == nullptr: a batch's, which its caller judges frame by
+// frame.  statuses == nullptr: st[0] is the call's status word (the words behind it are results of the
+// entry point's own) and `what` the message of a status that has no text of the reference's -- what_arg,
+// where given, for one that blames an argument.  Else the words are n windows': each one's code to
+// statuses, the first failing window's message the call's (the windows' failures are no failure of this
+// step: the call delivers what the others decoded and returns first_code).
+static int stage_verdict(himg_hip_ctx *ctx, int launch_rc, int32_t *st, size_t n, const char *what = kDecodeError,
+                         int *statuses = nullptr, const char *what_arg = nullptr) {
+  if (launch_rc) return (void)hipStreamSynchronize(nullptr), launch_rc;
+  HIP_TRY(ctx, hipMemcpy(st, ctx->h_status.p, n * 4, hipMemcpyDeviceToHost));
+  if (!what) return HIMG_OK;
+  if (!statuses)
+    return st[0] ? status_error(ctx, st[0], what_arg && status_to_code(st[0]) == HIMG_ERR_ARG ? what_arg : what) : HIMG_OK;
+  for (size_t k = n; k-- > 0;) {   // (backwards: the message left is the first failing window's)
+    statuses[k] = status_to_code(st[k]);
+    if (st[k]) (void)status_error(ctx, st[k], what);
+  }
+  return HIMG_OK;
+}
+
+// What a call of n windows returns behind its delivery: the first failing window's code.
+static int first_code(const int *statuses, int n) {
+  for (int k = 0; k < n; ++k)
+    if (statuses[k]) return statuses[k];
+  return HIMG_OK;
+}
+
+// A piece of the output staging and the caller's buffer it goes to.
+struct Piece { size_t at, bytes; uint8_t *dst; size_t cap; };
+
+// The capacity rule: every piece has a buffer that holds it.
+static int pieces_fit(himg_hip_ctx *ctx, const Piece *pc, int n) {
+  for (int i = 0; i < n; ++i)
+    if (!pc[i].dst || pc[i].cap < pc[i].bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+  return HIMG_OK;
+}
+
+static int pieces_copy(himg_hip_ctx *ctx, const Piece *pc, int n) {
+  for (int i = 0; i < n; ++i)
+    if (pc[i].bytes)
+      HIP_TRY(ctx, hipMemcpy(pc[i].dst, (const uint8_t *)ctx->h_out.p + pc[i].at, pc[i].bytes, hipMemcpyDeviceToHost));
+  return HIMG_OK;
+}
+
+// What a call reports before it copies: the dimensions, then the capacity rule -- so a caller whose
+// buffer is too small learns what to allocate.
+static int out_check(himg_hip_ctx *ctx, int W, int H, int C, int *width, int *height, int *channels, const Piece *pc,
+                     int n) {
+  *width = W; *height = H; *channels = C;
+  return pieces_fit(ctx, pc, n);
+}
+
+// The delivery behind a good verdict: `resident` bytes of h_out stay for himg_hip_fetch_last (0: none),
+// out_check, the copies.  (The entry points that check the capacity before they launch call out_check
+// there and pieces_copy here.)
+static int deliver(himg_hip_ctx *ctx, int W, int H, int C, int *width, int *height, int *channels, size_t resident,
+                   const Piece *pc, int n) {
+  ctx->host_bytes = resident;
+  if (int rc = out_check(ctx, W, H, C, width, height, channels, pc, n)) return rc;
+  return pieces_copy(ctx, pc, n);
+}
+
+extern "C" int himg_hip_fetch_last(himg_hip_ctx *ctx, uint8_t *dst, size_t dst_cap, size_t *size) {
+  if (!ctx || !size) return HIMG_ERR_ARG;
+  *size = ctx->host_bytes;
+  if (!ctx->host_bytes) return fail(ctx, HIMG_ERR_ARG, "no result to fetch");
+  const Piece pc = {0, ctx->host_bytes, dst, dst_cap};
+  if (int rc = pieces_fit(ctx, &pc, 1)) return rc;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  return pieces_copy(ctx, &pc, 1);
 }
 
 static int decode_core(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size, int *W, int *H,
                        int *C) {
   Geom g;
   if (int rc = stream_geom(ctx, packed, packed_size, W, H, C, &g)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_cap = round_up(packed_size + 16, 256);
-  const size_t out_bytes = (size_t)*W * *H * *C;
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
-      !ctx->h_status.reserve(256))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;
+  const size_t in_cap = stage_slot(packed_size), out_bytes = (size_t)*W * *H * *C;
+  const size_t n_idx = g.rows >= 2 ? 2 * (size_t)g.rows : 0;
+  if (int rc = stage_reserve(ctx, ctx->h_in, in_cap, out_bytes, 4, n_idx)) return rc;
   // The stream is in host memory: the FRES rows are indexed HERE -- the walk over the row
   // size headers (huffman_dec.cpp:232-248) is a chain of dependent reads, microseconds on
   // a CPU and 0.24 ms of a 0.41 ms decode as k_dec_rowwalk's 512 dependent HBM loads -- and
-  // the index goes up with the stream, from a pinned buffer the context keeps (this call returns
-  // only after the decode that reads its copy has finished).  A stream the host walk does not
-  // accept (damaged headers, a geometry it does not index) takes the device walk, which words the
-  // verdict.
-  const size_t n_idx = 2 * (size_t)g.rows;
-  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
-  // (Everything below is ordered on the null stream, which the decode runs on; the one wait of
-  // this call is the read of the verdict at the end.)
-  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
+  // the index goes up with the stream.  A stream the host walk does not accept (damaged headers, a
+  // geometry it does not index) takes the device walk, which words the verdict.
+  if (int rc = stage_upload(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
   const uint32_t sz32 = (uint32_t)packed_size;
   int rc = -1;
   uint32_t first = 0;
   int w2 = 0, h2 = 0, c2 = 0;
-  if (g.rows >= 2 && ctx->h_index.reserve(round_up(n_idx * 4, 256)) &&
-      himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows, &first) == HIMG_OK) {
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  if (n_idx && himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows, &first) == HIMG_OK) {
+    if (int e = stage_index(ctx, n_idx)) return e;
     rc = himg_hip_decode_rows_indexed_device(ctx, ctx->h_in.p, sz32, *W, *H, *C, 0, g.rows, (const uint32_t *)ctx->h_index.p,
                                              ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
   }
   if (rc == -1)
     rc = himg_hip_decode_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, *W, *H, *C, ctx->h_out.p,
                                 (int32_t *)ctx->h_status.p, nullptr);
-  if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the stream / index uploads may still be reading the caller's and the pinned buffer
-    return rc;
-  }
   int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) return status_error(ctx, st);
-  ctx->host_bytes = out_bytes;
+  if ((rc = stage_verdict(ctx, rc, &st, 1))) return rc;
+  ctx->host_bytes = out_bytes;   // (resident: the three callers copy it down each in their own way)
   return HIMG_OK;
 }
 
@@ -1926,10 +2012,8 @@ extern "C" int himg_hip_decode_to(himg_hip_ctx *ctx, const uint8_t *packed, size
   int W = 0, H = 0, C = 0;
   const int rc = decode_core(ctx, packed, packed_size, &W, &H, &C);
   if (rc) return rc;
-  *width = W; *height = H; *num_channels = C;
-  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  const Piece pc = {0, ctx->host_bytes, dst, dst_cap};
+  return deliver(ctx, W, H, C, width, height, num_channels, ctx->host_bytes, &pc, 1);
 }
 
 // The whole picture of a host stream into a host picture at (x, y): himg_hip_decode_to's decode, then
@@ -2088,12 +2172,8 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
     if (launched[j]) {
       HIP_TRY(ctx, hipEventSynchronize(p.ev_k[slot]));
       const int32_t st = p.h_meta->res[slot].status;
-      int err = HIMG_OK;
-      if (st) {
-        err = status_error(ctx, st);
-      } else if (!dst[j] || dst_cap[j] < out_bytes[j]) {
-        err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-      }
+      const Piece pc = {0, out_bytes[j], dst[j], dst_cap[j]};
+      const int err = st ? status_error(ctx, st) : pieces_fit(ctx, &pc, 1);
       if (!err) HIP_TRY(ctx, hipMemcpyAsync(dst[j], p.out[slot].p, out_bytes[j], hipMemcpyDeviceToHost, p.s_out));
       else { widths[j] = heights[j] = channels[j] = 0; if (!first_err) first_err = err; }
     }
@@ -2110,7 +2190,7 @@ extern "C" int himg_hip_decode_batch(himg_hip_ctx *ctx, const uint8_t *const *pa
     if (msg || !make_geom(W, H, C, C, 1, &g)) {
       if (!first_err) first_err = msg ? fail(ctx, HIMG_ERR_FORMAT, msg) : fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
     } else {
-      const size_t in_cap = round_up(packed_sizes[i] + 16, 256);
+      const size_t in_cap = stage_slot(packed_sizes[i]);
       out_bytes[i] = (size_t)W * H * C;
       if (!p.in[slot].reserve(in_cap) || !p.out[slot].reserve(round_up(out_bytes[i], 256)))
         return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
@@ -2229,6 +2309,8 @@ extern "C" int himg_hip_preview_device(himg_hip_ctx *ctx, const void *d_packed, 
 // Decode of a stream prefix: whole block rows exact, the rest from the low-res plane
 // (kernels_dec.hip, launch_prefix; the walk's rules: prefix_walk.h, shared with the device).
 // ---------------------------------------------------------------------------
+static const char kPrefixShort[] = "the prefix ends before the first block row";
+static const char kPrefixState[] = "the state does not belong to this prefix";
 static uint32_t prefix_avail32(size_t avail) { return avail > 0x80000000u ? 0x80000000u : (uint32_t)avail; }
 
 static_assert(sizeof(himg_hip_prefix_state) == 16 && sizeof(himg_dev::PfxState) == 16, "the state is four words");
@@ -2317,22 +2399,6 @@ extern "C" int himg_hip_decode_prefix_device(himg_hip_ctx *ctx, const void *d_pa
                        d_status, stream);
 }
 
-// The one-stream host forms stage alike: h_in (in_cap bytes), h_out and h_status reserved, nothing resident,
-// and -- `packed` given -- its first n bytes up with a zeroed tail.
-static int stage_stream(himg_hip_ctx *ctx, size_t in_cap, size_t out_bytes, size_t status_bytes, const uint8_t *packed,
-                        size_t n) {
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(status_bytes))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;   // (nothing stays resident until the call says so)
-  return packed ? upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, n) : HIMG_OK;
-}
-
-// A launch refused behind the uploads, which may still be reading the caller's buffers.
-static int launch_refused(int rc) {
-  (void)hipStreamSynchronize(nullptr);
-  return rc;
-}
-
 extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t avail, uint8_t *dst,
                                          size_t dst_cap, int *width, int *height, int *channels, int *rows_complete) {
   if (!ctx || (!packed && avail) || !width || !height || !channels || !rows_complete) return HIMG_ERR_ARG;
@@ -2343,27 +2409,22 @@ extern "C" int himg_hip_decode_prefix_to(himg_hip_ctx *ctx, const uint8_t *packe
   himg_dev::PfxHead h;
   const int hc = himg_dev::pfx_chain(packed, av, ctx->fix_t2, 0, &h);
   if (!h.frmt) {
-    if (hc == himg_dev::kPfxShort) return fail(ctx, HIMG_ERR_CAPACITY, "the prefix ends before the first block row");
+    if (hc == himg_dev::kPfxShort) return fail(ctx, HIMG_ERR_CAPACITY, kPrefixShort);
     return fail(ctx, HIMG_ERR_FORMAT, h.stage == 1 ? "Not a RIFF HIMG file.\n" : "Error decoding header.\n");
   }
   const int W = (int)h.W, H = (int)h.H, C = (int)h.C;
   Geom g;
   if (!make_geom(W, H, C, C, 1, &g)) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_cap = round_up((size_t)av + 16, 256);
   const size_t out_bytes = (size_t)W * H * C;
-  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, packed, av)) return rc;   // (only the bytes present)
-  int32_t *d_st = (int32_t *)ctx->h_status.p;
-  if (int rc = himg_hip_decode_prefix_device(ctx, ctx->h_in.p, in_cap, &av, 1, W, H, C, ctx->h_out.p, d_st + 1, d_st, nullptr))
-    return launch_refused(rc);
+  if (int rc = stage_whole(ctx, packed, av, out_bytes, 8)) return rc;   // (only the bytes present)
+  int32_t *d_st = (int32_t *)ctx->h_status.p;   // the status word, then k
+  int rc = himg_hip_decode_prefix_device(ctx, ctx->h_in.p, stage_slot(av), &av, 1, W, H, C, ctx->h_out.p, d_st + 1, d_st,
+                                         nullptr);
   int32_t st[2] = {0, -1};
-  HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
-  if (st[0]) return status_error(ctx, st[0], "the prefix ends before the first block row");
-  ctx->host_bytes = out_bytes;
-  *width = W; *height = H; *channels = C; *rows_complete = st[1];
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  if ((rc = stage_verdict(ctx, rc, st, 2, kPrefixShort))) return rc;
+  *rows_complete = st[1];
+  const Piece pc = {0, out_bytes, dst, dst_cap};
+  return deliver(ctx, W, H, C, width, height, channels, out_bytes, &pc, 1);
 }
 
 // The prefix decode continued from the rows a caller's picture already holds (kernels_dec.hip,
@@ -2388,48 +2449,38 @@ extern "C" int himg_hip_decode_prefix_more_to(himg_hip_ctx *ctx, const uint8_t *
   const uint32_t av = prefix_avail32(avail);
   himg_hip_prefix_plan plan;
   const int pc = prefix_peek_impl(packed, av, ctx->fix_t2, state, &plan);
-  if (pc == HIMG_ERR_ARG) return fail(ctx, HIMG_ERR_ARG, "the state does not belong to this prefix");
+  if (pc == HIMG_ERR_ARG) return fail(ctx, HIMG_ERR_ARG, kPrefixState);
   if (pc == HIMG_ERR_UNSUPPORTED) return fail(ctx, HIMG_ERR_UNSUPPORTED, "unsupported geometry");
   if (!plan.num_channels) {   // FRMT has not arrived, or the walk failed before it
-    if (pc == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, "the prefix ends before the first block row");
+    if (pc == HIMG_ERR_CAPACITY) return fail(ctx, HIMG_ERR_CAPACITY, kPrefixShort);
     return fail(ctx, HIMG_ERR_FORMAT, plan.packed_size ? "Error decoding header.\n" : "Not a RIFF HIMG file.\n");
   }
   const int W = plan.width, H = plan.height, C = plan.num_channels;
   const size_t row_bytes = (size_t)W * C, out_bytes = (size_t)H * row_bytes;
-  *width = W; *height = H; *channels = C;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_cap = round_up((size_t)av + 16, 256);
+  const Piece whole = {0, out_bytes, dst, dst_cap};
+  if (int rc = out_check(ctx, W, H, C, width, height, channels, &whole, 1)) return rc;
+  const size_t in_cap = stage_slot(av);
   // A resumed state the host's walk accepts: the head and the bytes from the walk's position on, each at its
   // offset (the bytes between them are the rows already decoded: nothing reads them).  Else the whole prefix.
-  // (Nothing stays resident: no fetch_last behind this call.)
+  // h_status: the status word, k, then the state at byte 16.  (Nothing stays resident: no fetch_last behind
+  // this call.)
   const bool partial = state->started && pc == HIMG_OK;
-  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, partial ? nullptr : packed, av)) return rc;
+  const size_t ranges[4] = {0, plan.head_bytes, state->walk_pos, av};
+  if (int rc = stage_reserve(ctx, ctx->h_in, in_cap, out_bytes, 32, 0)) return rc;
   uint8_t *d_in = (uint8_t *)ctx->h_in.p;
-  if (partial) {
-    HIP_TRY(ctx, hipMemcpyAsync(d_in, packed, plan.head_bytes, hipMemcpyHostToDevice, nullptr));
-    if (av > state->walk_pos)
-      HIP_TRY(ctx, hipMemcpyAsync(d_in + state->walk_pos, packed + state->walk_pos, av - state->walk_pos,
-                                  hipMemcpyHostToDevice, nullptr));
-  }
-  // h_status: the status word, k, then the state at byte 16.
+  if (int rc = stage_upload(ctx, d_in, in_cap, packed, av, partial ? ranges : nullptr, partial ? 2 : 0)) return rc;
   int32_t *d_st = (int32_t *)ctx->h_status.p;
   himg_hip_prefix_state *d_state = (himg_hip_prefix_state *)((uint8_t *)ctx->h_status.p + 16);
   HIP_TRY(ctx, hipMemcpyAsync(d_state, state, sizeof(*state), hipMemcpyHostToDevice, nullptr));
-  if (int rc = himg_hip_decode_prefix_more_device(ctx, d_in, in_cap, &av, 1, W, H, C, d_state, ctx->h_out.p, d_st + 1, d_st,
-                                                  nullptr))
-    return launch_refused(rc);
+  int rc = himg_hip_decode_prefix_more_device(ctx, d_in, in_cap, &av, 1, W, H, C, d_state, ctx->h_out.p, d_st + 1, d_st,
+                                              nullptr);
   struct { int32_t st, k, pad[2]; himg_hip_prefix_state s; } back;
-  HIP_TRY(ctx, hipMemcpy(&back, d_st, sizeof(back), hipMemcpyDeviceToHost));
-  if (back.st) return status_error(ctx, back.st, status_to_code(back.st) == HIMG_ERR_ARG
-                                                     ? "the state does not belong to this prefix"
-                                                     : "the prefix ends before the first block row");
+  if ((rc = stage_verdict(ctx, rc, &back.st, sizeof(back) / 4, kPrefixShort, nullptr, kPrefixState))) return rc;
   // A fresh state: the whole picture; else the pixel rows of block rows [k_prev, k_new) alone.
   const size_t y0 = state->started ? 8 * (size_t)state->rows_done : 0;
   const size_t y1 = state->started ? (8 * (size_t)back.k < (size_t)H ? 8 * (size_t)back.k : (size_t)H) : (size_t)H;
-  if (y1 > y0)
-    HIP_TRY(ctx, hipMemcpy(dst + y0 * row_bytes, (const uint8_t *)ctx->h_out.p + y0 * row_bytes, (y1 - y0) * row_bytes,
-                           hipMemcpyDeviceToHost));
+  const Piece rows = {y0 * row_bytes, y1 > y0 ? (y1 - y0) * row_bytes : 0, dst + y0 * row_bytes, dst_cap};
+  if ((rc = pieces_copy(ctx, &rows, 1))) return rc;
   *state = back.s;
   *rows_complete = back.k;
   return HIMG_OK;
@@ -2473,27 +2524,21 @@ extern "C" int himg_hip_decode_conceal_to(himg_hip_ctx *ctx, const uint8_t *pack
   Geom g;
   if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
   if (rowmap && rowmap_cap < (size_t)g.rows) return fail(ctx, HIMG_ERR_CAPACITY, "row map buffer too small");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   // The whole stream goes up and the device walks it: the host index cannot be built over a bad header.
-  const size_t in_cap = round_up(packed_size + 16, 256);
   const size_t out_bytes = (size_t)W * H * C;
   const size_t map_at = 256;   // (h_status: the status word, the count, then the row map)
-  if (int rc = stage_stream(ctx, in_cap, out_bytes, map_at + round_up((size_t)g.rows, 256), packed, packed_size)) return rc;
+  if (int rc = stage_whole(ctx, packed, packed_size, out_bytes, map_at + (size_t)g.rows)) return rc;
   const uint32_t sz32 = (uint32_t)packed_size;
   int32_t *d_st = (int32_t *)ctx->h_status.p;
   uint8_t *d_map = (uint8_t *)ctx->h_status.p + map_at;
-  if (int rc = himg_hip_decode_conceal_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, ctx->h_out.p, d_st + 1, d_map, d_st,
-                                              nullptr))
-    return launch_refused(rc);
+  int rc = himg_hip_decode_conceal_device(ctx, ctx->h_in.p, stage_slot(packed_size), &sz32, 1, W, H, C, ctx->h_out.p,
+                                          d_st + 1, d_map, d_st, nullptr);
   int32_t st[2] = {0, -1};
-  HIP_TRY(ctx, hipMemcpy(st, d_st, 8, hipMemcpyDeviceToHost));
-  if (st[0]) return status_error(ctx, st[0]);
-  ctx->host_bytes = out_bytes;
-  *width = W; *height = H; *channels = C; *concealed = st[1];
+  if ((rc = stage_verdict(ctx, rc, st, 2))) return rc;
+  *concealed = st[1];
   if (rowmap) HIP_TRY(ctx, hipMemcpy(rowmap, d_map, (size_t)g.rows, hipMemcpyDeviceToHost));
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  const Piece pc = {0, out_bytes, dst, dst_cap};
+  return deliver(ctx, W, H, C, width, height, channels, out_bytes, &pc, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -2825,9 +2870,9 @@ extern "C" int himg_hip_decode_pyramid_device(himg_hip_ctx *ctx, const void *d_p
                      bad, only0 ? himg_dev::StoreForm() : himg_dev::StoreForm(&pm));
 }
 
-// One host stream: the upload of decode_core (the device walks the row headers), one launch, the
-// verdict, then a copy per wanted level.  The levels lie one behind the other in the output staging,
-// each at a multiple of 256 bytes.
+// One host stream: stage_whole (the device walks the row headers), one launch, stage_verdict, then a
+// piece per wanted level.  The levels lie one behind the other in the output staging, each at a
+// multiple of 256 bytes.
 extern "C" int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
                                           uint8_t *const dst[4], const size_t dst_cap[4], int *width, int *height,
                                           int *channels) {
@@ -2835,46 +2880,34 @@ extern "C" int himg_hip_decode_pyramid_to(himg_hip_ctx *ctx, const uint8_t *pack
   int W = 0, H = 0, C = 0;
   Geom g;
   if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
-  *width = W; *height = H; *channels = C;
-  size_t bytes[4] = {0, 0, 0, 0}, at[4] = {0, 0, 0, 0}, total = 0;
-  int wanted = 0;
-  bool small = false;
+  Piece pc[4];
+  int wanted = 0, level[4];
+  size_t total = 0;
   for (int k = 0; k < 4; ++k) {
     if (!dst[k] && !dst_cap[k]) continue;
     int ow = 0, oh = 0;
     (void)himg_hip_pyramid_size(W, H, k, &ow, &oh);
-    bytes[k] = (size_t)ow * oh * C;
-    at[k] = total;
-    total += round_up(bytes[k], 256);
-    ++wanted;
-    if (!dst[k] || dst_cap[k] < bytes[k]) small = true;
+    pc[wanted] = {total, (size_t)ow * oh * C, dst[k], dst_cap[k]};
+    total += round_up(pc[wanted].bytes, 256);
+    level[wanted++] = k;
   }
+  // (the dimensions and the capacity rule in front of the launch; no level wanted: the dimensions alone)
+  if (int rc = out_check(ctx, W, H, C, width, height, channels, pc, wanted)) return rc;
   if (!wanted) return fail(ctx, HIMG_ERR_ARG, "no pyramid level wanted");
-  if (small) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_cap = round_up(packed_size + 16, 256);
-  if (!ctx->h_in.reserve(in_cap) || !ctx->h_out.reserve(total) || !ctx->h_status.reserve(256))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  ctx->host_bytes = 0;   // (nothing stays resident: no fetch_last behind this call)
-  if (int rc = upload_zero_tail(ctx, (uint8_t *)ctx->h_in.p, in_cap, packed, packed_size)) return rc;
-  himg_hip_pyramid py;
-  for (int k = 0; k < 4; ++k) py.level[k] = bytes[k] ? (uint8_t *)ctx->h_out.p + at[k] : nullptr;
+  // (nothing stays resident: no fetch_last behind this call)
+  if (int rc = stage_whole(ctx, packed, packed_size, total, 4)) return rc;
+  himg_hip_pyramid py = himg_hip_pyramid();
+  for (int i = 0; i < wanted; ++i) py.level[level[i]] = (uint8_t *)ctx->h_out.p + pc[i].at;
   const uint32_t sz32 = (uint32_t)packed_size;
-  if (int rc = himg_hip_decode_pyramid_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, &py, (int32_t *)ctx->h_status.p,
-                                              nullptr)) {
-    (void)hipStreamSynchronize(nullptr);   // the upload may still be reading the caller's buffer
-    return rc;
-  }
+  int rc = himg_hip_decode_pyramid_device(ctx, ctx->h_in.p, stage_slot(packed_size), &sz32, 1, W, H, C, &py,
+                                          (int32_t *)ctx->h_status.p, nullptr);
   int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) return status_error(ctx, st);
-  for (int k = 0; k < 4; ++k)
-    if (bytes[k]) HIP_TRY(ctx, hipMemcpy(dst[k], py.level[k], bytes[k], hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  if ((rc = stage_verdict(ctx, rc, &st, 1))) return rc;
+  return pieces_copy(ctx, pc, wanted);
 }
 
-// The planes of one host stream: the upload of decode_core (the device walks the row headers), one
-// launch, the verdict, then the capacity rule of himg_hip_decode_to and one copy.
+// The planes of one host stream: stage_whole (the device walks the row headers), one launch,
+// stage_verdict, then deliver's capacity rule and one copy.
 extern "C" int himg_hip_decode_planes_to(himg_hip_ctx *ctx, const uint8_t *packed, size_t packed_size,
                                          uint32_t plane_mask, uint8_t *dst, size_t dst_cap, int *width, int *height,
                                          int *num_channels) {
@@ -2883,21 +2916,15 @@ extern "C" int himg_hip_decode_planes_to(himg_hip_ctx *ctx, const uint8_t *packe
   Geom g;
   if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
   if (!plane_mask_ok(C, plane_mask)) return fail(ctx, HIMG_ERR_ARG, "bad plane mask");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t in_cap = round_up(packed_size + 16, 256);
   const size_t out_bytes = (size_t)himg_dev::plane_count(plane_mask) * (size_t)W * (size_t)H;
-  if (int rc = stage_stream(ctx, in_cap, out_bytes, 256, packed, packed_size)) return rc;
+  if (int rc = stage_whole(ctx, packed, packed_size, out_bytes, 4)) return rc;
   const uint32_t sz32 = (uint32_t)packed_size;
-  if (int rc = himg_hip_decode_planes_device(ctx, ctx->h_in.p, in_cap, &sz32, 1, W, H, C, plane_mask, ctx->h_out.p,
-                                             (int32_t *)ctx->h_status.p, nullptr))
-    return launch_refused(rc);
+  int rc = himg_hip_decode_planes_device(ctx, ctx->h_in.p, stage_slot(packed_size), &sz32, 1, W, H, C, plane_mask,
+                                         ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
   int32_t st = 0;
-  HIP_TRY(ctx, hipMemcpy(&st, ctx->h_status.p, 4, hipMemcpyDeviceToHost));
-  if (st) return status_error(ctx, st);
-  *width = W; *height = H; *num_channels = C;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  if ((rc = stage_verdict(ctx, rc, &st, 1))) return rc;
+  const Piece pc = {0, out_bytes, dst, dst_cap};
+  return deliver(ctx, W, H, C, width, height, num_channels, 0, &pc, 1);   // (not resident: no fetch_last)
 }
 
 // ---------------------------------------------------------------------------
@@ -2931,17 +2958,18 @@ static void staged_dims(const Staged &c, int W, int H, int i, int *ow, int *oh) 
   else { *ow = (W + 7) / 8; *oh = (H + 7) / 8; }
 }
 
-static int staged_error(himg_hip_ctx *ctx, const Staged &c, int32_t st) {
-  return status_error(ctx, st, c.kind == Staged::kPreview ? "device preview reported an error"
-                                                          : "device decode reported an error");
+static const char *staged_what(const Staged &c) {
+  return c.kind == Staged::kPreview ? "device preview reported an error" : kDecodeError;
 }
 
 // Frames grp[0 .. m) -- one geometry, for kRegion one window size, every rectangle checked -- into the
-// staging at a stride, one device launch, their statuses to st.  A stream goes up to its head (kPreview)
+// staging at a stride, one device launch, their statuses to st (what: stage_verdict's, the message of a
+// call of one stream or nullptr for a batch).  A stream goes up to its head (kPreview)
 // or whole, the rest of its slot zeroed; with the host's index a region's stream only as its plan (the
 // head and the touched rows, each at its offset).  A stream the host does not index (a call of its own:
 // the batches plan their frames first) goes up whole and takes the device walk, which words the verdict.
-static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C, const int *grp, int m, int32_t *st) {
+static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C, const int *grp, int m, int32_t *st,
+                         const char *what) {
   const int rows = (H + 7) / 8;
   int ow = 0, oh = 0;
   staged_dims(c, W, H, grp[0], &ow, &oh);
@@ -2950,19 +2978,15 @@ static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C
     const size_t n = c.heads ? c.heads[grp[k]] : c.packed_sizes[grp[k]];
     stride = n > stride ? n : stride;
   }
-  stride = round_up(stride + 16, 256);
+  stride = stage_slot(stride);
   const size_t n_idx = c.index ? 2 * (size_t)rows * m : 0, out_bytes = (size_t)ow * oh * C;
-  if (!ctx->h_in.reserve(stride * m) || !ctx->h_out.reserve(round_up(out_bytes * m, 256)) ||
-      !ctx->h_status.reserve(round_up((size_t)m * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  if (int rc = stage_reserve(ctx, ctx->h_in, stride * m, out_bytes * m, (size_t)m * 4, n_idx)) return rc;
   uint8_t *in = (uint8_t *)ctx->h_in.p;
   std::vector<uint32_t> sz(m);
   std::vector<int32_t> org(2 * (size_t)m);
   bool indexed = c.index && rows >= 2;
   for (int k = 0; k < m; ++k) {
     const int i = grp[k];
-    uint8_t *d = in + (size_t)k * stride;
     sz[k] = (uint32_t)c.packed_sizes[i];
     int up[4] = {0, 0, W, H};   // (kScaled: every row, the whole frame as a rectangle)
     if (c.rects) {
@@ -2974,15 +2998,14 @@ static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C
     himg_hip_region_plan plan = himg_hip_region_plan();
     indexed = indexed && region_index(c.packed[i], c.packed_sizes[i], ctx->fix_t2, up[0], up[1], up[2], up[3], &plan,
                                       ctx->hp_index + (size_t)k * 2 * rows) == HIMG_OK;
-    if (indexed && c.kind == Staged::kRegion) {
-      HIP_TRY(ctx, hipMemcpyAsync(d, c.packed[i], plan.head_bytes, hipMemcpyHostToDevice, nullptr));
-      HIP_TRY(ctx, hipMemcpyAsync(d + plan.rows_begin, c.packed[i] + plan.rows_begin, plan.rows_end - plan.rows_begin,
-                                  hipMemcpyHostToDevice, nullptr));
-    } else if (int rc = upload_zero_tail(ctx, d, stride, c.packed[i], c.heads ? c.heads[i] : c.packed_sizes[i])) {
+    const bool planned = indexed && c.kind == Staged::kRegion;
+    const size_t ranges[4] = {0, plan.head_bytes, plan.rows_begin, plan.rows_end};
+    if (int rc = stage_upload(ctx, in + (size_t)k * stride, stride, c.packed[i], c.heads ? c.heads[i] : c.packed_sizes[i],
+                              planned ? ranges : nullptr, planned ? 2 : 0))
       return rc;
-    }
   }
-  if (indexed) HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
+  if (indexed)
+    if (int rc = stage_index(ctx, n_idx)) return rc;
   const uint32_t *d_index = indexed ? (const uint32_t *)ctx->h_index.p : nullptr;
   int32_t *d_status = (int32_t *)ctx->h_status.p;
   int rc;
@@ -2993,30 +3016,20 @@ static int staged_launch(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C
   else
     rc = region_launch(ctx, in, stride, sz.data(), m, W, H, C, org.data(), ow, oh, d_index, ctx->h_out.p, d_status, nullptr,
                        c.scale_log2);
-  if (rc) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
-    return rc;
-  }
-  HIP_TRY(ctx, hipMemcpy(st, d_status, (size_t)m * 4, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  return stage_verdict(ctx, rc, st, (size_t)m, what);
 }
 
 // A *_to call is a launch of one stream (the arrays of c hold that one) whose result stays resident for
 // himg_hip_fetch_last; the dimensions are reported even where dst is too small.
 static int staged_to(himg_hip_ctx *ctx, const Staged &c, int W, int H, int C, uint8_t *dst, size_t dst_cap, int *width,
                      int *height, int *channels) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
   const int frame = 0;
   int32_t st = 0;
-  if (int rc = staged_launch(ctx, c, W, H, C, &frame, 1, &st)) return rc;
-  if (st) return staged_error(ctx, c, st);
-  staged_dims(c, W, H, 0, width, height);
-  *channels = C;
-  ctx->host_bytes = (size_t)*width * *height * C;
-  if (!dst || dst_cap < ctx->host_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, ctx->host_bytes, hipMemcpyDeviceToHost));
-  return HIMG_OK;
+  if (int rc = staged_launch(ctx, c, W, H, C, &frame, 1, &st, staged_what(c))) return rc;
+  int ow = 0, oh = 0;
+  staged_dims(c, W, H, 0, &ow, &oh);
+  const Piece pc = {0, (size_t)ow * oh * C, dst, dst_cap};
+  return deliver(ctx, ow, oh, C, width, height, channels, pc.bytes, &pc, 1);
 }
 
 // The launches of a batch call.  Frames not yet done that share (W, H, C) -- for kRegion the window size
@@ -3037,7 +3050,7 @@ static int staged_batch(himg_hip_ctx *ctx, const Staged &c, int n, const int *W,
       int wi = ow, hi = oh;
       if (c.rects) staged_dims(c, W[i], H[i], i, &wi, &hi);
       if (done[i] || W[i] != W[i0] || H[i] != H[i0] || C[i] != C[i0] || wi != ow || hi != oh) continue;
-      const size_t si = round_up(c.packed_sizes[i] + 16, 256), s2 = si > stride ? si : stride;
+      const size_t si = stage_slot(c.packed_sizes[i]), s2 = si > stride ? si : stride;
       if (byte_cap && !grp.empty() && s2 * (grp.size() + 1) > byte_cap) break;
       stride = s2;
       grp.push_back(i);
@@ -3046,12 +3059,11 @@ static int staged_batch(himg_hip_ctx *ctx, const Staged &c, int n, const int *W,
     const int m = (int)grp.size();
     const size_t out_bytes = (size_t)ow * oh * C[i0];
     std::vector<int32_t> st(m);
-    if (int rc = staged_launch(ctx, c, W[i0], H[i0], C[i0], grp.data(), m, st.data())) return rc;
+    if (int rc = staged_launch(ctx, c, W[i0], H[i0], C[i0], grp.data(), m, st.data(), nullptr)) return rc;
     for (int k = 0; k < m; ++k) {
       const int i = grp[k];
-      int err = HIMG_OK;
-      if (st[k]) err = staged_error(ctx, c, st[k]);
-      else if (!dst[i] || dst_cap[i] < out_bytes) err = fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
+      const Piece pc = {(size_t)k * out_bytes, out_bytes, dst[i], dst_cap[i]};
+      const int err = st[k] ? status_error(ctx, st[k], staged_what(c)) : pieces_fit(ctx, &pc, 1);
       if (err) { if (!*first_err) *first_err = err; continue; }
       HIP_TRY(ctx, hipMemcpyAsync(dst[i], (uint8_t *)ctx->h_out.p + (size_t)k * out_bytes, out_bytes,
                                   hipMemcpyDeviceToHost, nullptr));
@@ -3273,13 +3285,8 @@ extern "C" int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_
   if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
   for (int k = 0; k < n; ++k)
     if (!region_ok(W, H, origins[2 * k], origins[2 * k + 1], w, h)) return fail(ctx, HIMG_ERR_ARG, "bad rectangle");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  const size_t stride = round_up(packed_size + 16, 256), out_bytes = (size_t)n * h * w * C, n_idx = 2 * (size_t)g.rows;
-  if (!ctx->h_in.reserve(stride) || !ctx->h_out.reserve(round_up(out_bytes, 256)) ||
-      !ctx->h_status.reserve(round_up((size_t)n * 4, 256)) || !ctx->h_index.reserve(round_up(n_idx * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  if (int rc = reserve_hp_index(ctx, n_idx)) return rc;
+  const size_t stride = stage_slot(packed_size), out_bytes = (size_t)n * h * w * C, n_idx = 2 * (size_t)g.rows;
+  if (int rc = stage_reserve(ctx, ctx->h_in, stride, out_bytes, (size_t)n * 4, n_idx)) return rc;
   std::vector<himg_hip_region_plan> plans(n);
   std::vector<int> codes(n);
   std::vector<size_t> ranges;
@@ -3294,33 +3301,20 @@ extern "C" int himg_hip_decode_stream_regions_to(himg_hip_ctx *ctx, const uint8_
   const bool indexed = g.rows >= 2 && stream_regions_plan(packed, packed_size, ctx->fix_t2, n, origins, w, h, plans.data(),
                                                           codes.data(), &ranges, ctx->hp_index) == HIMG_OK;
   uint8_t *in = (uint8_t *)ctx->h_in.p;
-  if (indexed) {
-    for (size_t i = 0; i + 1 < ranges.size(); i += 2)
-      HIP_TRY(ctx, hipMemcpyAsync(in + ranges[i], packed + ranges[i], ranges[i + 1] - ranges[i], hipMemcpyHostToDevice, nullptr));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr));
-  } else if (int rc = upload_zero_tail(ctx, in, stride, packed, packed_size)) {
+  if (int rc = stage_upload(ctx, in, stride, packed, packed_size, indexed ? ranges.data() : nullptr,
+                            indexed ? ranges.size() / 2 : 0))
     return rc;
-  }
+  if (indexed)
+    if (int rc = stage_index(ctx, n_idx)) return rc;
   const uint32_t sz = (uint32_t)packed_size;
-  int32_t *d_status = (int32_t *)ctx->h_status.p;
-  if (int rc = stream_regions_launch(ctx, in, stride, &sz, 1, W, H, C, map.data(), origins, n, w, h,
-                                     indexed ? (const uint32_t *)ctx->h_index.p : nullptr, indexed ? index_rows : nullptr,
-                                     ctx->h_out.p, d_status, nullptr)) {
-    (void)hipStreamSynchronize(nullptr);   // the uploads may still read the caller's and the pinned buffers
-    return rc;
-  }
+  int rc = stream_regions_launch(ctx, in, stride, &sz, 1, W, H, C, map.data(), origins, n, w, h,
+                                 indexed ? (const uint32_t *)ctx->h_index.p : nullptr, indexed ? index_rows : nullptr,
+                                 ctx->h_out.p, (int32_t *)ctx->h_status.p, nullptr);
   std::vector<int32_t> st(n);
-  HIP_TRY(ctx, hipMemcpy(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
-  int first = HIMG_OK;
-  for (int k = n - 1; k >= 0; --k) {   // (backwards: the message left is the first failing window's)
-    statuses[k] = status_to_code(st[k]);
-    if (st[k]) first = status_error(ctx, st[k]);
-  }
-  *width = w; *height = h; *channels = C;
-  ctx->host_bytes = out_bytes;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return first;
+  if ((rc = stage_verdict(ctx, rc, st.data(), (size_t)n, kDecodeError, statuses))) return rc;
+  const Piece pc = {0, out_bytes, dst, dst_cap};
+  rc = deliver(ctx, w, h, C, width, height, channels, out_bytes, &pc, 1);
+  return rc ? rc : first_code(statuses, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -3451,22 +3445,17 @@ extern "C" int himg_hip_open_stream_host(himg_hip_ctx *ctx, const uint8_t *packe
   int W = 0, H = 0, C = 0;
   Geom g;
   if (int rc = stream_geom(ctx, packed, packed_size, &W, &H, &C, &g)) return rc;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t stride = round_up(packed_size + 16, 256), n_idx = 2 * (size_t)g.rows;
+  // (the stream's buffer becomes the handle's; the context's h_out and what himg_hip_fetch_last serves stay)
+  const size_t stride = stage_slot(packed_size), n_idx = 2 * (size_t)g.rows;
   DevBuf in;
-  if (!in.reserve(stride) || !ctx->h_index.reserve(round_up(n_idx * 4, 256))) {
-    in.release();
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  }
-  int rc = reserve_hp_index(ctx, n_idx);
-  if (!rc) rc = upload_zero_tail(ctx, (uint8_t *)in.p, stride, packed, packed_size);
+  int rc = stage_reserve(ctx, in, stride, 0, 0, n_idx);
+  if (!rc) rc = stage_upload(ctx, (uint8_t *)in.p, stride, packed, packed_size);
   uint32_t first = 0;
   int w2 = 0, h2 = 0, c2 = 0;
   const bool indexed = !rc && g.rows >= 2 &&
                        himg_hip_index_host(packed, packed_size, ctx->fix_t2, &w2, &h2, &c2, ctx->hp_index, (size_t)g.rows,
                                            &first) == HIMG_OK;
-  if (indexed && hipMemcpyAsync(ctx->h_index.p, ctx->hp_index, n_idx * 4, hipMemcpyHostToDevice, nullptr) != hipSuccess)
-    rc = fail(ctx, HIMG_ERR_HIP, "index upload failed");
+  if (indexed) rc = stage_index(ctx, n_idx);
   const uint32_t sz = (uint32_t)packed_size;
   if (!rc)
     rc = open_streams(ctx, in.p, stride, &sz, 1, W, H, C, indexed ? (const uint32_t *)ctx->h_index.p : nullptr, nullptr, &in,
@@ -3560,24 +3549,16 @@ static int opened_to(himg_hip_ctx *ctx, himg_hip_opened *o, int scale_log2, int 
     if (h_stream_of[k] < 0 || h_stream_of[k] >= o->n_streams || !region_ok(ow, oh, origins[2 * k], origins[2 * k + 1], w, h))
       return fail(ctx, HIMG_ERR_ARG, "bad window");
   const size_t out_bytes = (size_t)n * h * w * o->C;
-  *width = w; *height = h; *channels = o->C;
-  if (!dst || dst_cap < out_bytes) return fail(ctx, HIMG_ERR_CAPACITY, "output buffer too small");
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->host_bytes = 0;
-  if (!ctx->h_out.reserve(round_up(out_bytes, 256)) || !ctx->h_status.reserve(round_up((size_t)n * 4, 256)))
-    return fail(ctx, HIMG_ERR_HIP, "staging allocation failed");
-  int32_t *d_status = (int32_t *)ctx->h_status.p;
-  if (int rc = opened_launch(ctx, o, scale_log2, h_stream_of, origins, n, w, h, ctx->h_out.p, d_status, nullptr))
-    return launch_refused(rc);
+  const Piece pc = {0, out_bytes, dst, dst_cap};
+  if (int rc = out_check(ctx, w, h, o->C, width, height, channels, &pc, 1)) return rc;
+  // (no stream goes up: the handle holds it.  Nothing stays resident: no fetch_last behind this call.)
+  if (int rc = stage_reserve(ctx, ctx->h_in, 0, out_bytes, (size_t)n * 4, 0)) return rc;
+  int rc = opened_launch(ctx, o, scale_log2, h_stream_of, origins, n, w, h, ctx->h_out.p, (int32_t *)ctx->h_status.p,
+                         nullptr);
   std::vector<int32_t> st(n);
-  HIP_TRY(ctx, hipMemcpy(st.data(), d_status, (size_t)n * 4, hipMemcpyDeviceToHost));
-  int first = HIMG_OK;
-  for (int k = n - 1; k >= 0; --k) {   // (backwards: the message left is the first failing window's)
-    statuses[k] = status_to_code(st[k]);
-    if (st[k]) first = status_error(ctx, st[k]);
-  }
-  HIP_TRY(ctx, hipMemcpy(dst, ctx->h_out.p, out_bytes, hipMemcpyDeviceToHost));
-  return first;
+  if ((rc = stage_verdict(ctx, rc, st.data(), (size_t)n, kDecodeError, statuses))) return rc;
+  rc = pieces_copy(ctx, &pc, 1);
+  return rc ? rc : first_code(statuses, n);
 }
 
 extern "C" int himg_hip_opened_regions_to(himg_hip_ctx *ctx, himg_hip_opened *o, int n, const int32_t *h_stream_of,
